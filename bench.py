@@ -15,18 +15,28 @@ in HBM (no dataloader on either side), fp32.  One "step" = one forward+loss+back
 N>1: one process per GPU, every rank fine-tunes on its own frames (weak scaling) and the flat
 gradient buffer is all-reduced (RCCL over xGMI via torch.distributed 'nccl') once per optimizer step.
 
-Prints ONE JSON line on rank 0 with the contract fields plus `roofline` (dominant kernel family:
-the conv3x3 implicit-GEMM MFMA kernel; achieved = algorithmic FLOPs / summed launch durations
-measured with HIP events on the launch stream inside the timed region) and `cpu_baseline` (the
-torch-CPU restatement of the reference loop from oracle/torch_ref.py on this node's host cores).
+Prints ONE JSON line on rank 0 with the contract fields.  A plain run does only what the headline
+needs: set-up (including the settle phase, see measure()), --warmup steps, EXACTLY --steps timed steps
+(driver contract: `value`, `ms_per_step`), the outputs of the last timed step when --dump-outputs DIR
+is given, and the line.
 
-The headline `value` times EXACTLY --steps steps (driver contract).  Because that region is only
-~0.16 s at the driver's --steps 20, the same loop is then run again for at least --min-seconds
-(default 2 s) and reported as `sustained` next to it.  With the default workload on one GPU the line
-also carries, under `extra_configs`, the other two single-GPU configurations of BASELINE.json --
-configs[2] (854x480 batch 12 parent loop, bf16 MFMA) and configs[4] (1920x1080 batch 4 inference from
-a captured hipGraph) -- and `with_loss_item_sync`, the headline loop with the reference's
-`loss.item()` every iteration (train_online.py:128) left in.  `--no-extra` skips them.
+--full adds everything else the benchmark measures or checks, as before: the parity gate (one
+micro-batch against the CPU oracle), `roofline` (dominant kernel family: the conv3x3 implicit-GEMM
+MFMA kernel; achieved = algorithmic FLOPs / summed launch durations measured with HIP events on the
+launch stream inside the timed region), `cpu_baseline` (the torch-CPU restatement of the reference
+loop from oracle/torch_ref.py on this node's host cores) and `sustained`: because the headline region
+is only ~0.16 s at the driver's --steps 20, the same loop is then run again for at least
+--min-seconds (default 2 s).  With the default workload on one GPU the full line also carries, under
+`extra_configs`, the other two single-GPU configurations of BASELINE.json -- configs[2] (854x480
+batch 12 parent loop, bf16 MFMA) and configs[4] (1920x1080 batch 4 inference from a captured
+hipGraph) -- and `with_loss_item_sync`, the headline loop with the reference's `loss.item()` every
+iteration (train_online.py:128) left in.  `--no-extra` skips them.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy
+(float32, losses float64): the five logit maps, the per-head losses and, in the training modes, the
+input gradient; a fixed seeded sample of each array when all of them together exceed 64 MB.  The
+inputs (frames, labels, weights) depend only on the arguments, so two builds can be compared output
+for output.
 """
 import argparse
 from collections import OrderedDict
@@ -325,9 +335,10 @@ def parity_gate(wl):
 
 class Workload(object):
     """One benchmark configuration: builds the net + synthetic batch, exposes step()."""
+    keep_last = False       # --dump-outputs: hold on to what each step returns (inputs, outputs, losses) for last_step_outputs()
 
     def __init__(self, mode, precision, height, width, batch, graph, n_ave, item_sync, device, rank, dist, force_dist, graph_train=0, comm=None,
-                 window=0):
+                 window=0, keep_last=False):
         from layers.osvos_layers import class_balanced_cross_entropy_loss as cbce
         from osvos_pytorch_amd.layers.osvos_layers import class_balanced_cross_entropy_loss_step as cbce_step
         from osvos_pytorch_amd.layers.osvos_layers import class_balanced_cross_entropy_loss_step_multi as cbce_step_multi
@@ -358,6 +369,7 @@ class Workload(object):
         self.running = torch.zeros((), device=device)
         self.ave, self.epoch, self.nsteps = 0, 0, 0
         self.keep = {}
+        self.keep_last = keep_last
         self.step = self._window_step if self.window else self._train_step
         self.graph_train = bool(graph_train) and mode != "infer" and not self.window
         if self.graph_train:
@@ -388,6 +400,8 @@ class Workload(object):
         else:
             losses = [self.cbce(o, self.gt, size_average=False) for o in outputs]
             loss = self.side_w * sum(losses[:-1]) + losses[-1]
+        if self.keep_last:      # (captured: every replay rewrites these tensors)
+            self.keep["last"] = (inputs, [o.detach() for o in outputs], [l.detach().clone() for l in ([loss] if self.mode == "online" else losses)])
         self.running.add_(loss.detach())
         loss /= self.n_ave
         loss.backward()
@@ -487,6 +501,8 @@ class Workload(object):
             if arm:
                 self.reducer.arm()
             loss.backward()
+        if self.keep_last:
+            self.keep["last"] = (inputs, [o.detach() for o in outputs], losses)
         return outputs, losses
 
     def _window_step(self):
@@ -503,6 +519,8 @@ class Workload(object):
         if self.reducer is not None:
             self.reducer.arm()
         torch.autograd.backward(heads, grads)
+        if self.keep_last:
+            self.keep["last"] = (inputs, [o.detach() for o in outputs], losses)
         self.nsteps += 1
         self.net.join_backward()
         if self.reducer is not None:
@@ -521,6 +539,74 @@ class Workload(object):
                 % (self.w, self.h, self.batch, self.mode, self.mode, "" if self.mode == "online" else "+4 side", self.n_ave,
                    8 if self.mode == "online" else 10, self.precision,
                    ", micro-batch (fwd+loss+bwd) replayed from a captured hipGraph" if self.graph_train else ""))
+
+
+def save_train_state(wl):
+    """Parameters and momentum buffers of a training workload, copied: the settle phase runs a number of steps that depends on the box's speed,
+    restore_train_state() puts the weights back afterwards so that the warm-up and timed steps see the same inputs on every run."""
+    params = list(wl.net.parameters())
+    bufs = {}
+    for p in params:
+        b = wl.opt.state[p].get("momentum_buffer") if p in wl.opt.state else None
+        if b is not None:
+            bufs[p] = b.clone()
+    return params, [p.detach().clone() for p in params], bufs
+
+
+def restore_train_state(wl, saved):
+    params, values, bufs = saved
+    with torch.no_grad():
+        for p, v in zip(params, values):
+            p.copy_(v)                                  # (bumps p._version: the packed weights are rebuilt at the next forward)
+        for p in params:
+            st = wl.opt.state[p] if p in wl.opt.state else None
+            if st is None:
+                continue
+            if p in bufs:
+                st["momentum_buffer"].copy_(bufs[p])
+            else:
+                st.pop("momentum_buffer", None)
+    wl.net.invalidate_packed_weights()
+    wl.running.zero_()
+    wl.nsteps = 0
+
+
+HEAD_NAMES = ["logits_side1", "logits_side2", "logits_side3", "logits_side4", "logits_fused"]
+DUMP_LIMIT_BYTES = 64 * 10 ** 6       # --dump-outputs: all files together
+
+
+def last_step_outputs(wl):
+    """What the caller of the timed step received from its LAST call, as numpy arrays: the five logit maps (float32), in the training modes
+    the per-head losses (float64) and the gradient of the input frames (float32)."""
+    if wl.mode == "infer":
+        outs, inputs, losses = wl.keep["outs"], None, None
+    else:
+        wl.net.join_backward()
+        inputs, outs, losses = wl.keep["last"]
+    torch.cuda.synchronize()
+    arrays = OrderedDict((name, o.detach().float().cpu().numpy()) for name, o in zip(HEAD_NAMES, outs))
+    if losses is not None:
+        ls = list(losses) if not torch.is_tensor(losses) else [losses]
+        arrays["loss"] = np.concatenate([np.asarray(l.detach().double().cpu().numpy() if torch.is_tensor(l) else l, dtype=np.float64).reshape(-1)
+                                         for l in ls])
+    if inputs is not None and inputs.grad is not None:
+        arrays["input_grad"] = inputs.grad.detach().float().cpu().numpy()
+    return arrays
+
+
+def write_outputs(arrays, out_dir):
+    """DIR/<name>.npy per array.  When they exceed DUMP_LIMIT_BYTES together, every array larger than an equal share of the limit is replaced by
+    the flat elements at a fixed, seeded set of indices (the same for every run with the same shapes)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays)) - 4096          # (room for the .npy header)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if total > DUMP_LIMIT_BYTES and a.nbytes > share:
+            k = share // a.itemsize
+            idx = np.sort(np.random.default_rng(1234).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def pipe_sustained_tflops(device):
@@ -688,8 +774,9 @@ def timed_region(wl, steps, ctl, device, prof_lib=None):
     return elapsed, (list(ms), list(fl), list(cnt)), (n_prof if prof_lib is not None else 0)
 
 
-def measure(wl, steps, warmup, min_seconds, world, ctl, device, use_prof=True, settle_seconds=0.0):
-    """Device settle (setup), W warm-up steps, EXACTLY `steps` timed steps (headline), then a sustained region of >= min_seconds."""
+def measure(wl, steps, warmup, min_seconds, world, ctl, device, use_prof=True, settle_seconds=0.0, roofline=True, after_timed=None):
+    """Device settle (setup), W warm-up steps, EXACTLY `steps` timed steps (headline), after_timed() (outside any timed region), then a
+    sustained region of >= min_seconds and, with `roofline`, the roofline figures."""
     from osvos_pytorch_amd import _lib
     lib = _lib.lib()
     # setup, before the W warm-up steps: bring the device out of its idle power state.  A process that starts stepping on an idle MI355X runs
@@ -701,6 +788,7 @@ def measure(wl, steps, warmup, min_seconds, world, ctl, device, use_prof=True, s
     prepare_region(steps, lib if prof else None)      # (host-side preparation of the timed region: before ANY of the steps below)
     settle_done = 0
     if settle_seconds > 0:
+        saved = save_train_state(wl) if wl.mode != "infer" else None
         unit = wl.steps_per_opt                               # whole optimizer steps
         for _ in range(unit):                                  # (first launches: packs, workspaces, kernel attributes)
             wl.step()
@@ -716,6 +804,8 @@ def measure(wl, steps, warmup, min_seconds, world, ctl, device, use_prof=True, s
         for _ in range(n):
             wl.step()
         settle_done = n + 2 * unit
+        if saved is not None:                                  # (whole optimizer steps: no gradient window is open here)
+            restore_train_state(wl, saved)
     res_settle = settle_done
     for _ in range(warmup):
         wl.step()
@@ -723,12 +813,17 @@ def measure(wl, steps, warmup, min_seconds, world, ctl, device, use_prof=True, s
     frames = steps * wl.batch * world
     res = {"value": frames / elapsed, "ms_per_step": elapsed / steps * 1e3, "elapsed": elapsed, "timing_detail": dict(TIMING_DETAIL),
            "settle_steps": res_settle}
+    if after_timed is not None:
+        after_timed()
     if min_seconds > 0:
         n2 = max(steps, int(math.ceil(min_seconds / max(elapsed / steps, 1e-6))))
         n2 = -(-n2 // wl.steps_per_opt) * wl.steps_per_opt     # whole optimizer steps
         e2, _, _ = timed_region(wl, n2, ctl, device, None)
         res["sustained"] = {"seconds": round(e2, 3), "steps": n2, "value": round(n2 * wl.batch * world / e2, 3),
                             "ms_per_step": round(e2 / n2 * 1e3, 4)}
+    if not roofline:
+        res["roofline"] = None
+        return res
     gf_fwd = conv_gflop_forward(wl.h, wl.w) * wl.batch
     passes = 1 if wl.mode == "infer" else 3
     # f32x3: fp32 results from the bf16 matrix pipe -- every algorithmic FLOP is executed as SIX bf16 MFMA FLOPs.  The roofline that
@@ -1057,7 +1152,12 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--n-ave-grad", type=int, default=0, help="0 = reference value (5 online, 10 parent)")
     ap.add_argument("--item-sync", type=int, default=0, help="1 = loss.item() every iteration like the reference's logging")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="length of the additional `sustained` timed region (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="besides the headline, run everything else the benchmark measures or checks: the parity "
+                    "gate, the roofline, the `sustained` region, the CPU baseline and (default workload, one GPU) the extra configurations; "
+                    "--no-parity / --no-prof / --min-seconds / --no-cpu-baseline / --no-extra apply to these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned (logit maps, "
+                    "losses, input gradient) as DIR/<name>.npy, at most 64 MB in all")
+    ap.add_argument("--min-seconds", type=float, default=2.0, help="--full: length of the additional `sustained` timed region (0 = skip)")
     ap.add_argument("--force-dist", action="store_true", help="initialise the nccl (RCCL) process group and run the gradient "
                     "all-reduce even with one rank (single-GPU check of the multi-GPU path)")
     ap.add_argument("--settle-seconds", type=float, default=1.0, help="untimed SETUP before the --warmup steps: run the workload this long (whole "
@@ -1109,10 +1209,11 @@ def main():
         torch.cuda.synchronize()
         world = ctl.world                       # n_gpus of the JSON line = the communicator's size, not an environment variable
         ranks_seen = int(t.item())              # = number of ranks RCCL actually reaches
+    dump = args.dump_outputs is not None and rank == 0
     wl = Workload(args.mode, args.precision, args.height, args.width, args.batch, args.graph, args.n_ave_grad, args.item_sync,
-                  device, rank, ctl, args.force_dist, graph_train=args.graph_train, comm=comm, window=args.window_fused)
+                  device, rank, ctl, args.force_dist, graph_train=args.graph_train, comm=comm, window=args.window_fused, keep_last=dump)
     parity = None
-    if rank == 0 and world == 1 and ctl is None and not args.no_parity and not args.window_fused and not args.graph_train:
+    if args.full and rank == 0 and world == 1 and ctl is None and not args.no_parity and not args.window_fused and not args.graph_train:
         try:
             parity = parity_gate(wl)
         except Exception as e:      # the timing must still be reported; a missing gate shows in the line
@@ -1120,12 +1221,18 @@ def main():
         if not (parity.get("within_bars", False) or parity.get("within_autocast_bars", False) or parity.get("within_x2_bars", False)):      # the line carries it; say it where a person running the script looks, too
             print("bench.py: PARITY GATE OUTSIDE ITS BARS (or not run): %s" % json.dumps({k: parity.get(k) for k in
                   ("max_dlogit_over_std", "loss_rel", "iou", "bars", "error")}), file=sys.stderr, flush=True)
-    res = measure(wl, args.steps, args.warmup, args.min_seconds, world, ctl, device, use_prof=not args.no_prof, settle_seconds=args.settle_seconds)
+
+    def dump_last_step():
+        write_outputs(last_step_outputs(wl), args.dump_outputs)
+        wl.keep_last = False
+        wl.keep.pop("last", None)
+    res = measure(wl, args.steps, args.warmup, args.min_seconds if args.full else 0.0, world, ctl, device, use_prof=args.full and not args.no_prof,
+                  settle_seconds=args.settle_seconds, roofline=args.full, after_timed=dump_last_step if dump else None)
     settle = res["settle_steps"]
     frames_per_step = wl.batch
     default_workload = (args.mode, args.precision, args.height, args.width, args.batch, args.item_sync, args.window_fused) == ("online", "fp32x3", 480, 854, 1, 0, 0)
     extras, item_line, no_settle = None, None, None
-    if world == 1 and ctl is None and default_workload and not args.no_extra:
+    if args.full and world == 1 and ctl is None and default_workload and not args.no_extra:
         # the headline loop with the reference's per-iteration loss.item() left in (train_online.py:128)
         wl.item_sync = 1
         r = measure(wl, args.steps, 2, 0.0, 1, None, device, use_prof=False)
@@ -1165,7 +1272,7 @@ def main():
                 ("configs[4]/fp32-exact", "configs[4] on the EXACT fp32 MFMA kernels",
                  ["--mode", "infer", "--height", "1080", "--width", "1920", "--batch", "4", "--graph", "1", "--precision", "fp32", "--no-parity"])]:
             cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(max(10, min(args.steps, 30))),
-                   "--warmup", str(max(3, min(args.warmup, 5))), "--min-seconds", str(args.min_seconds), "--no-extra", "--no-cpu-baseline", "--full-line"] + extra_args
+                   "--warmup", str(max(3, min(args.warmup, 5))), "--min-seconds", str(args.min_seconds), "--full", "--no-extra", "--no-cpu-baseline", "--full-line"] + extra_args
             try:
                 env = dict(os.environ)
                 for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
@@ -1183,7 +1290,7 @@ def main():
         no_settle = None
         try:
             cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--min-seconds", "0",
-                   "--settle-seconds", "0", "--no-extra", "--no-cpu-baseline", "--no-prof", "--full-line"]
+                   "--settle-seconds", "0", "--full", "--no-extra", "--no-cpu-baseline", "--no-prof", "--full-line"]
             env = dict(os.environ)
             for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
                 env.pop(k, None)
@@ -1200,7 +1307,7 @@ def main():
     if rank == 0:
         n_ave = args.n_ave_grad or (5 if args.mode == "online" else 10)
         base = None
-        if not args.no_cpu_baseline and world == 1 and args.mode != "infer":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.mode != "infer":
             try:
                 base = cpu_baseline(args.height, args.width, args.mode, n_ave)
             except Exception as e:  # the GPU result must still be reported

@@ -147,3 +147,25 @@ def test_parity_gate_is_in_the_line(line):
     assert c2["dtype"] == "bf16" and isinstance(c2["within_bars"], bool) and c2["iou"] >= 0.985 and 1.0 < c2["traffic_ratio"] < 2.0
     assert c4["within_bars"] is True and c4["iou"] >= 1 - 1e-3 and c4["algorithmic_hbm_GBps"] > 100
     assert extras["configs[1]/fp32-exact"]["within_bars"] is True
+
+
+def test_dump_outputs_stay_under_the_limit_and_sample_the_same_indices(bench, tmp_path):
+    """--dump-outputs: DIR/<name>.npy in float32 / float64, at most 64 MB together; an output set larger than that (configs[4]: five 1920x1080
+    batch-4 logit maps) is cut to a fixed seeded sample, the same elements in every run, so two runs can be compared array for array."""
+    import numpy as np
+    rng = np.random.default_rng(0)
+    arrays = {n: rng.standard_normal((4, 1, 1080, 1920)).astype(np.float32) for n in bench.HEAD_NAMES}
+    arrays["loss"] = np.arange(5, dtype=np.float64)
+    small = {"logits_fused": arrays["logits_fused"][:1, :, :48, :64], "loss": arrays["loss"]}
+    for tag in ("a", "b"):
+        bench.write_outputs(arrays, str(tmp_path / tag))
+        bench.write_outputs(small, str(tmp_path / ("small_" + tag)))
+    for tag in ("a", "b"):
+        files = sorted(os.listdir(str(tmp_path / tag)))
+        assert files == sorted(n + ".npy" for n in arrays)
+        assert sum(os.path.getsize(str(tmp_path / tag / f)) for f in files) <= bench.DUMP_LIMIT_BYTES <= 64 * 10 ** 6
+    for n in arrays:
+        a, b = np.load(str(tmp_path / "a" / (n + ".npy"))), np.load(str(tmp_path / "b" / (n + ".npy")))
+        assert a.dtype == arrays[n].dtype and np.array_equal(a, b)
+        assert np.isin(a, arrays[n]).all()                        # a sample of the array's own elements
+    assert np.array_equal(np.load(str(tmp_path / "small_a" / "logits_fused.npy")), small["logits_fused"])      # under the limit: whole, shape kept

@@ -89,3 +89,31 @@ def test_train_parent_through_both_rccl_backends_on_one_rank_is_bit_identical(tm
         for k, v in runs["plain"][0].items():
             assert torch.equal(v, runs[tag][0][k]), (tag, k)
         assert runs[tag][1] == runs["plain"][1], tag
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_repeatable_outputs(tmp_path):
+    """bench.py without --full: the headline line only (no parity gate, roofline, CPU baseline or extra configurations), exactly --steps timed
+    steps, and --dump-outputs writes what the last timed step returned.  The settle phase runs a speed-dependent number of steps; the weights
+    are put back after it, so two runs with the same arguments compute the same outputs (up to the order of atomic sums)."""
+    import json
+    import numpy as np
+    dirs = []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        out = _run(["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1", "--height", "120", "--width", "214", "--settle-seconds", "0.3",
+                    "--dump-outputs", str(d)], tmp_path)
+        line = json.loads(out.strip().splitlines()[-1])
+        assert line["steps"] == 4 and line["warmup"] == 1 and line["unit"] == "frames/s" and line["higher_is_better"] is True
+        assert line["ms_per_step"] > 0 and abs(line["value"] - 1e3 / line["ms_per_step"]) <= 1e-2 * line["value"]
+        assert line["parity"] is None and line["roofline"] is None and line["cpu_baseline"] is None and line["extra_configs"] is None
+        assert line["sustained_value"] is None and line["setup_settle_steps"] > 0
+        dirs.append(d)
+    names = sorted(os.listdir(str(dirs[0])))
+    assert names == sorted(["logits_side1.npy", "logits_side2.npy", "logits_side3.npy", "logits_side4.npy", "logits_fused.npy", "loss.npy",
+                            "input_grad.npy"])
+    for n in names:
+        a, b = np.load(str(dirs[0] / n)), np.load(str(dirs[1] / n))
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and np.isfinite(a).all(), n
+        if n.startswith("logits"):
+            assert a.shape == (1, 1, 120, 214), (n, a.shape)
+        assert float(np.abs(a - b).max()) <= 1e-4 * float(np.abs(a).max()), (n, float(np.abs(a - b).max()))

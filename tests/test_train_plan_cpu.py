@@ -185,6 +185,7 @@ def test_step_schedule_closes_every_epoch_once_and_in_collective_order():
 
 def _main_worker(rank, world, port, out, argv):
     sys.path.insert(0, REPO)
+    torch.cuda.is_available = lambda: False      # the gloo / CPU path of init_distributed on any box (a visible GPU would give rank r cuda:r)
     os.environ.update({"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "RANK": str(rank), "WORLD_SIZE": str(world), "LOCAL_RANK": str(rank)})
     os.environ["OSVOS_SAVE_ROOT"] = os.path.dirname(out)
     torch.set_num_threads(2)
@@ -356,6 +357,7 @@ def test_train_parent_main_eight_ranks(tmp_path, n_ave):
 
 def _split_root_worker(rank, world, port, roots, argv, out):
     sys.path.insert(0, REPO)
+    torch.cuda.is_available = lambda: False      # the gloo / CPU path of init_distributed on any box (a visible GPU would give rank r cuda:r)
     os.environ.update({"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "RANK": str(rank), "WORLD_SIZE": str(world), "LOCAL_RANK": str(rank)})
     os.environ["OSVOS_SAVE_ROOT"] = roots[rank]
     torch.set_num_threads(2)

@@ -7,6 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 for rnd in $(seq 1 $R); do
   for T in $A $B; do
     X=""; grep -q -- "--no-parity" $ROOT/$T/bench.py && X="--no-parity"      # (trees older than round 5 have no parity gate)
+    grep -q -- '"--full"' $ROOT/$T/bench.py && X="$X --full"                 # (the sustained region runs under --full where the tree has it)
     v=$(cd $ROOT/$T && OSVOS_AUTOBUILD=0 python bench.py --no-extra --no-cpu-baseline $X --min-seconds 2 "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])

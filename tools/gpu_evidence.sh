@@ -3,7 +3,7 @@
 # and configs[2] (what profiles/r04_bench_default.json, r04_bench_*_kernel_stats.txt and r04_step_timeline*.txt are).  usage: gpu_evidence.sh <tag>
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; export TMPDIR=/tmp; O=$R/gpurun_out/${1:-evidence}; mkdir -p $O
 t0=$(date +%s)
-[ -z "$NOBENCH" ] && { timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $? $(( $(date +%s) - t0 )) s" > $O/times.txt; }
+[ -z "$NOBENCH" ] && { timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $? $(( $(date +%s) - t0 )) s" > $O/times.txt; }
 prof() { # tag, bench args...
   T=$1; shift
   A="--no-extra --no-cpu-baseline --no-parity --no-prof --min-seconds 0 --settle-seconds 1.0 --steps 20 --warmup 5 $*"

@@ -27,7 +27,7 @@ mkdir -p $O/profiles; cp profiles/${TAG}_pmc_traffic_*.json $O/profiles/ 2>/dev/
 # the line the driver reads (its exact command) FIRST; bench.py prints the compact line and leaves the full record in gpurun_out/bench_detail.json
 timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; echo "bench (driver's command: --gpus 1 --steps 20 --warmup 5) exit $? $(( $(date +%s) - t0 )) s, line $(wc -c < $O/bench_driver_cmd.json) bytes" >> $O/summary.txt
 cp gpurun_out/bench_detail.json $O/bench_detail_driver_cmd.json 2>/dev/null
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench exit $? $(( $(date +%s) - t0 )) s" >> $O/summary.txt
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench exit $? $(( $(date +%s) - t0 )) s" >> $O/summary.txt
 cp gpurun_out/bench_detail.json $O/bench_detail_default.json 2>/dev/null
 NOBENCH=1 bash tools/gpu_evidence.sh ${TAG}_final > /dev/null 2>&1
 # round 6 extras: per-layer tables, the Cin = 64 tile sweep, per-tensor gradient errors of the precisions, the seam of the two-piece backward

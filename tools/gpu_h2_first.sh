@@ -6,7 +6,7 @@ timeout 120 tools/native/bin/mfma_f16_probe > $O/probe.txt 2>&1
 timeout 900 python -m pytest tests/test_gpu_ops.py -q -k "fp16_pairs or two_pieces" -s > $O/ops.txt 2>&1; tail -3 $O/ops.txt
 timeout 900 python -m pytest tests/test_gpu_net.py -q -k "h2" > $O/net.txt 2>&1; tail -3 $O/net.txt
 for p in fp32x3 fp32x3b2 fp32h2 fp32x3h2; do
-  timeout 300 python bench.py --precision $p --no-extra --no-cpu-baseline --steps 30 --warmup 5 --full-line > $O/bench_$p.txt 2>&1
+  timeout 300 python bench.py --full --precision $p --no-extra --no-cpu-baseline --steps 30 --warmup 5 --full-line > $O/bench_$p.txt 2>&1
   python - <<PY
 import json
 try:
@@ -17,7 +17,7 @@ except Exception as e:
 PY
 done
 for p in fp32x3 fp32h2; do
-  timeout 300 python bench.py --mode infer --height 1080 --width 1920 --batch 4 --graph 1 --precision $p --no-extra --no-cpu-baseline --steps 20 --warmup 5 --full-line > $O/bench4_$p.txt 2>&1
+  timeout 300 python bench.py --full --mode infer --height 1080 --width 1920 --batch 4 --graph 1 --precision $p --no-extra --no-cpu-baseline --steps 20 --warmup 5 --full-line > $O/bench4_$p.txt 2>&1
   python - <<PY
 import json
 try:

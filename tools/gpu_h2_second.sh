@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out/h2; mkdir -p $O
 timeout 600 python tools/h2_flip_probe.py > $O/flips.txt 2>&1; tail -25 $O/flips.txt
 timeout 900 python tools/grad_error_table.py > $O/grad_table.txt 2>&1; tail -8 $O/grad_table.txt
-b() { timeout 300 env $1 python bench.py --precision $2 --no-extra --no-cpu-baseline --no-parity --steps 30 --warmup 5 --full-line 2>/dev/null | tail -1 | python -c "import json,sys; l=json.loads(sys.stdin.read()); print('$1 $2', l['value'], l['ms_per_step'], l.get('sustained',{}).get('value'))"; }
+b() { timeout 300 env $1 python bench.py --full --precision $2 --no-extra --no-cpu-baseline --no-parity --steps 30 --warmup 5 --full-line 2>/dev/null | tail -1 | python -c "import json,sys; l=json.loads(sys.stdin.read()); print('$1 $2', l['value'], l['ms_per_step'], l.get('sustained',{}).get('value'))"; }
 for r in 1 2; do
   b OSVOS_X3_WIDE_TILE=10 fp32h2; b OSVOS_X3_WIDE_TILE=12 fp32h2; b OSVOS_X3_WIDE_TILE=16 fp32h2
   b OSVOS_X3_WIDE_TILE=10 fp32x3b2; b OSVOS_X3_WIDE_TILE=12 fp32x3b2
