@@ -17,7 +17,7 @@
 //     pixel), re-used by all 9 taps (a tap is an LDS address offset); weights of the chunk (9 taps x 16 ci x BN co)
 //     staged from the fp32 pack [tap][Cin/4][CoutP][4] and split the same way
 //   * one LDS buffer, the NEXT chunk waits in registers (raw fp32, loaded with branch-free buffer loads while the
-//     MFMAs of the current chunk run)
+//     MFMAs of the current chunk run); the production tiles 10 / 12 / 14 run the pipelined form of the loop instead (PIPE, at the kernel)
 //   * per (tap, M block): 3 A fragments + (per tap) 3 x WN B fragments -> 6 WN MFMAs; fragment reads are issued one
 //     step ahead and pinned with sched_barrier (hipcc otherwise sinks every ds_read to its first use)
 //   * epilogue identical to conv3x3_f32.hip (cout-major accumulators -> 16-byte buffer stores, bias / ReLU / ReLU-mask
@@ -96,6 +96,9 @@ struct CfgX {
   static constexpr int A_U4_2 = 4 * PLANE, B_U4_2 = 2 * B_ITEMS;
   static constexpr size_t LDS_BYTES_2 = (size_t)(A_U4_2 + B_U4_2 + 2 + 4) * 16;
   static constexpr int SK_SLOT_F4 = NT * WM * WN * 4;       // float4 per stream-K partial slot
+  // pipelined K loop (PIPE = 1): two activation buffers + a ring of two weight slots of one tap row each ([piece 3][tap 3][group 2][BN])
+  static constexpr int ROW_U4 = 18 * BN;
+  static constexpr size_t LDS_BYTES_PIPE = (size_t)(2 * A_U4 + 2 * ROW_U4 + 2) * 16;
   static_assert(WGM * WGN == 4 || WGM * WGN == 8, "4 or 8 waves per workgroup");
   static_assert(MB % WGM == 0 && NB % WGN == 0, "wave grid must divide the tile");
   static_assert(LDS_BYTES <= 160 * 1024, "tile does not fit the 160 KB LDS of a gfx950 CU");
@@ -151,10 +154,20 @@ __device__ inline void split8_hm(const u32x4& lo, const u32x4& hi, uint4& p0, ui
 // magnitude of the chunk's raw values through LDS (no extra barrier: written before the barrier that opens the staging phase, read after it);
 // the running exponent only ever decreases, and when it does the accumulators are multiplied by the (exact) power of two that separates the
 // old scale from the new one.  The epilogue un-scales once.
-template <class C, int PS, int SK, int NP = 3, int HP = 0>
+//
+// PIPE = 1 (the production tiles 10, 12, 14 with the pre-split three-piece pack; OSVOS_X3_PIPE=0 selects the loop above instead): the K loop
+// is pipelined so that no staging phase sits between two barriers with the matrix pipe empty.  The weights travel by LDS-DMA straight from
+// the pre-split pack (every (piece, tap, group) run of BN couts is contiguous in the pack and in LDS) into a ring of two TAP-ROW slots (3 taps
+// x 16 channels x BN x 3 pieces: 36.9 KB at BN = 128); the DMA of tap row j + 1 is issued at the start of row j.  The activations have two
+// buffers: chunk k + 1's raw values (loaded during chunk k - 1) are split and written into the idle buffer between the MFMAs of chunk k's
+// first tap row, then chunk k + 2's loads are issued.  One raw s_barrier per tap row (three per chunk) with counted vmcnt / lgkmcnt, never
+// __syncthreads() (its fence would drain the DMA in flight).  The MFMA sequence of every accumulator is the one above (chunk, tap, piece
+// products small-first), so the results are bit-identical.
+template <class C, int PS, int SK, int NP = 3, int HP = 0, int PIPE = 0>
 __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_f32x3_kernel(ConvArgsX a) {
   static_assert(NP == 2 || NP == 3, "two or three bf16 pieces per operand");
   static_assert(HP == 0 || (NP == 2 && PS == 1 && SK == 0), "h2: two pieces, pre-split pack, plain grid");
+  static_assert(PIPE == 0 || (PS == 1 && NP == 3 && HP == 0 && C::ILV != 0 && C::NT == 512), "pipelined loop: pre-split three-piece eight-wave tiles");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint4* As = reinterpret_cast<uint4*>(smem);
   uint4* Bs = As + (NP == 3 ? C::A_U4 : C::A_U4_2);
@@ -325,6 +338,7 @@ __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_f32x3_kernel(ConvArgsX 
 
   // probe builds (tools/native/build.sh, -DOSVOS_X3_ABL=n; wrong results, timing only): 1 no MFMA, 2 no fragment reads after the first step,
   // 3 no global loads inside the K loop, 4 tiles stored once (no split / ds_write per chunk), 5 no barriers
+  if constexpr (PIPE == 0) {
   load_chunk(kc_begin);
   // (s_setprio was measured in round 5 -- static priority 1 for the second wave of every SIMD, and priority 1 during a chunk's MFMAs / 0 during
   //  its split + store phase: both within +-0.3 % of no priority at step level, profiles/r05_ab_setprio.txt -- and is not in the kernel)
@@ -424,6 +438,149 @@ __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_f32x3_kernel(ConvArgsX 
       }
     }
   }
+  } else {
+    // ---- pipelined K loop (PIPE = 1, header): tap row j = 3 (kc - kc_begin) + r of this segment reads weight slot j & 1
+    static_assert(C::NA == 2 && 3 * C::WM >= 4, "pipelined loop: two activation items per thread, four staging steps in a tap row");
+    constexpr int NW = C::NT / 64;
+    constexpr int NRI = C::ROW_U4 / 64;                 // DMA instructions per tap row (64 lanes x 16 B each)
+    constexpr int NRW = cdivx(NRI, NW);                 // ... per wave (the last round only on waves wv < NRI % NW)
+    static_assert(C::BN % 64 == 0, "pipelined loop: whole 64-slot DMA runs");
+    uint4* const Bring = As + 2 * C::A_U4;
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    const int CG = a.Cin >> 3;
+    const unsigned long long wp = reinterpret_cast<unsigned long long>(a.wpk3);
+    const i32x4 w3dma = {(int)(unsigned)wp, (int)(unsigned)(wp >> 32), (int)((size_t)27 * CG * a.CoutP * 16), 0x00020000};
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    const unsigned lds_ring = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)Bring;
+    // instruction d of this wave moves run i = wv + NW d: (piece, tap in row, group) = ((i / (BN / 64)) / 6, (i / (BN / 64)) / 2 % 3,
+    // (i / (BN / 64)) % 2), couts co0 + 64 (i % (BN / 64)) + lane; LDS slot i * 64 of the row slot (the image is [piece][tap][group][BN])
+    unsigned w_off[NRW];
+#pragma unroll
+    for (int d = 0; d < NRW; ++d) {
+      const int i = wv + NW * d, run = i / (C::BN / 64), nn = (i % (C::BN / 64)) * 64 + lane;
+      const int p = run / 6, s = (run >> 1) % 3, g = run & 1;
+      w_off[d] = (i < NRI && co0 + nn < a.CoutP) ? (unsigned)((((p * 9 + s) * CG + g) * a.CoutP + co0 + nn) * 16) : OOB;
+    }
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+    auto dma_row = [&](int j) {                         // weights of tap row j -> slot j & 1
+      const int kc = kc_begin + j / 3, r = j % 3;
+      const int soff = (3 * r * CG + 2 * kc) * a.CoutP * 16;
+      const unsigned base = lds_ring + (unsigned)((j & 1) * C::ROW_U4 * 16);
+#pragma unroll
+      for (int d = 0; d < NRW; ++d)
+        if (NRI % NW == 0 || d + 1 < NRW || wv + NW * d < NRI)
+          asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
+                       : : "s"(base + (unsigned)((wv + NW * d) * 1024)), "v"(w_off[d]), "s"(w3dma), "s"(soff) : "m0", "memory");
+    };
+#pragma clang diagnostic pop
+    // the counted waits: at the barrier that opens row j the newest DMA of this wave is row j's; behind it at most this segment's
+    // activation loads (2 NA, issued in row j - 1 or the prologue), which may stay in flight
+#if defined(OSVOS_X3_ABL) && OSVOS_X3_ABL == 5
+#define X3P_BARRIER(ra_behind) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory")
+#else
+#define X3P_BARRIER(ra_behind) do { if (ra_behind) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
+                                    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); } while (0)
+#endif
+    auto ld_a = [&](int kc) {
+#pragma unroll
+      for (int i = 0; i < C::NA; ++i) {
+        ra[i][0] = __builtin_amdgcn_raw_buffer_load_b128(xrs, a_off[i], kc * 64, 0);
+        ra[i][1] = __builtin_amdgcn_raw_buffer_load_b128(xrs, a_off[i] + 16u, kc * 64, 0);
+      }
+    };
+    auto put_a = [&](int i, uint4* Ab) {
+      uint4 p0, p1, p2;
+      split8(ra[i][0], ra[i][1], p0, p1, p2);
+      if (C::A_ITEMS % C::NT == 0 || a_dst[i] >= 0) {
+        Ab[a_dst[i]] = p0;
+        Ab[a_dst[i] + 2 * C::PLANE] = p1;
+        Ab[a_dst[i] + 4 * C::PLANE] = p2;
+      }
+    };
+    const int nrows = 3 * (kc_end - kc_begin);
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // (stream-K) every wave is done with the previous segment's LDS
+    ld_a(kc_begin);
+    put_a(0, As);
+    put_a(1, As);
+    dma_row(0);
+    bool ra_behind = kc_begin + 1 < kc_end;
+    if (ra_behind) ld_a(kc_begin + 1);
+    for (int kc = kc_begin; kc < kc_end; ++kc) {
+      const int buf = (kc - kc_begin) & 1;
+      const uint4* const Acur = As + buf * C::A_U4;
+      uint4* const Anext = As + (buf ^ 1) * C::A_U4;
+      const bool more = kc + 1 < kc_end, more2 = kc + 2 < kc_end;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const int j = 3 * (kc - kc_begin) + r;
+        X3P_BARRIER(ra_behind);          // row j's weights (and, r = 0, chunk kc's activations) are in LDS; every wave has left row j - 1
+        ra_behind = false;
+        const uint4* const Bcur = Bring + (j & 1) * C::ROW_U4;
+        const bool dma_next = j + 1 < nrows;
+        uint4 fb[2][3][C::WN], fa[2][3];
+        auto ldB = [&](int s, int set) {
+#if defined(OSVOS_X3_ABL) && OSVOS_X3_ABL == 2
+          if (r + s > 0) return;
+#endif
+#pragma unroll
+          for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int ni = 0; ni < C::WN; ++ni) fb[set][p][ni] = Bcur[b_idx + (p * 3 + s) * 2 * C::BN + ni * 32];
+        };
+        auto ldA = [&](int s, int mi, int set) {
+#if defined(OSVOS_X3_ABL) && OSVOS_X3_ABL == 2
+          if (r + s > 0 || mi > 1) return;
+#endif
+#pragma unroll
+          for (int p = 0; p < 3; ++p) fa[set][p] = Acur[a_idx[mi] + p * 2 * C::PLANE + r * C::PITCH + s];
+        };
+        ldB(0, 0);
+        ldA(0, 0, 0);
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+#pragma unroll
+          for (int mi = 0; mi < C::WM; ++mi) {
+            const int step = s * C::WM + mi;
+            if (mi + 1 < C::WM) ldA(s, mi + 1, (step + 1) & 1);
+            else if (s + 1 < 3) ldA(s + 1, 0, (step + 1) & 1);
+            if (mi == 0 && s + 1 < 3) ldB(s + 1, (s + 1) & 1);
+            // staging, one item per step behind the fragment reads: row 0 -- split + write chunk kc + 1's activations (2 steps), the DMA
+            // of row j + 1, chunk kc + 2's loads (after the DMA: the barrier of row j + 1 lets them stay in flight); rows 1, 2 -- the DMA
+            if (r == 0) {
+#if !(defined(OSVOS_X3_ABL) && OSVOS_X3_ABL == 4)
+              if (step < 2 && more) put_a(step, Anext);
+#endif
+#if !(defined(OSVOS_X3_ABL) && OSVOS_X3_ABL == 3)
+              if (step == 2 && dma_next) dma_row(j + 1);
+              if (step == 3 && more2) { ld_a(kc + 2); ra_behind = true; }
+#endif
+            } else {
+#if !(defined(OSVOS_X3_ABL) && OSVOS_X3_ABL == 3)
+              if (step == 0 && dma_next) dma_row(j + 1);
+#endif
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const int sa = step & 1, sb = s & 1;
+            constexpr int PB[6] = {2, 0, 1, 1, 0, 0};      // (piece of B, piece of A) per product, small first, hi x hi last (as above)
+            constexpr int PA[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+            for (int t = 0; t < 6; ++t)
+#pragma unroll
+              for (int ni = 0; ni < C::WN; ++ni)
+#if defined(OSVOS_X3_ABL) && OSVOS_X3_ABL == 1
+                acc[mi][ni][t] += __uint_as_float(fb[sb][PB[t]][ni].x ^ fb[sb][PB[t]][ni].w ^ fa[sa][PA[t]].x ^ fa[sa][PA[t]].w);
+#else
+                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fb[sb][PB[t]][ni]),
+                                                                      __builtin_bit_cast(bf16x8_t, fa[sa][PA[t]]), acc[mi][ni], 0, 0, 0);
+#endif
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+      }
+    }
+#undef X3P_BARRIER
+  }
 
   if constexpr (HP != 0) {      // un-scale: the pack's exponent (word 0 of its third plane) + the tile's
     const unsigned wbits = reinterpret_cast<const unsigned*>(a.wpk3 + (size_t)2 * 9 * (a.Cin >> 3) * a.CoutP)[0];
@@ -448,7 +605,7 @@ __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_f32x3_kernel(ConvArgsX 
       // every fence flushed an L2 full of other workgroups' freshly written output tiles).
       constexpr int SC1 = 16;
       const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(a.sk_part, 0, (int)((size_t)G * 2 * C::SK_SLOT_F4 * 16), 0x00020000);
-      unsigned* const flag = reinterpret_cast<unsigned*>(As + C::BUF_U4 + 1);
+      unsigned* const flag = reinterpret_cast<unsigned*>(As + (PIPE ? 2 * C::A_U4 + 2 * C::ROW_U4 : C::BUF_U4) + 1);
       // If every other contributor has already arrived, this workgroup is the last one whatever it does: it keeps its part in registers and
       // skips the publish (the usual case for the workgroup that holds a tile's LAST K range as the first segment of its share).
       if (tid == 0) *flag = __hip_atomic_load(a.sk_tickets + tile_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -615,13 +772,14 @@ constexpr size_t kSkSlotBytes = 128 * 1024;               // the largest tile's 
 constexpr size_t kSkTicketBytes = (size_t)kSkMaxTiles * 4;
 
 // sk_grid > 0: the stream-K kernel with that many persistent workgroups (the caller has checked that the tile order has >= sk_grid units)
-template <class C, int PS, int SK, int NP = 3, int HP = 0>
+template <class C, int PS, int SK, int NP = 3, int HP = 0, int PIPE = 0>
 int launch_x2(const ConvArgsX& a0, int sk_grid, hipStream_t stream) {
   static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};      // hipFuncSetAttribute is per device
   bool& attr_set = attr_set_dev[osvos_current_device()];
-  constexpr size_t lds_bytes = NP == 3 ? C::LDS_BYTES : C::LDS_BYTES_2;
+  constexpr size_t lds_bytes = PIPE ? C::LDS_BYTES_PIPE : (NP == 3 ? C::LDS_BYTES : C::LDS_BYTES_2);
+  static_assert(lds_bytes <= 160 * 1024, "tile does not fit the 160 KB LDS of a gfx950 CU");
   if (!attr_set) {
-    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_f32x3_kernel<C, PS, SK, NP, HP>),
+    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_f32x3_kernel<C, PS, SK, NP, HP, PIPE>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     attr_set = true;
   }
@@ -635,18 +793,18 @@ int launch_x2(const ConvArgsX& a0, int sk_grid, hipStream_t stream) {
     const long ntiles = (long)a.nct * a.nsp, units = ntiles * (a.Cin >> 4);
     OSVOS_ARG_CHECK(sk_grid > 0 && sk_grid <= kSkMaxGrid && ntiles <= kSkMaxTiles && units >= sk_grid && a.sk_tickets && a.sk_part && a.ksplit == 1,
                     "conv3x3 f32x3 stream-K: %ld tiles, %ld units on %d workgroups", ntiles, units, sk_grid);
-    hipLaunchKernelGGL((conv3x3_f32x3_kernel<C, PS, SK, NP, HP>), dim3((unsigned)sk_grid), dim3(C::NT), lds_bytes, stream, a);
+    hipLaunchKernelGGL((conv3x3_f32x3_kernel<C, PS, SK, NP, HP, PIPE>), dim3((unsigned)sk_grid), dim3(C::NT), lds_bytes, stream, a);
   } else {
     const long blocks = a.map == 0 ? (long)a.nct * a.nsp : (long)a.nct * ((a.nsp + 7) / 8) * 8;
     OSVOS_ARG_CHECK(blocks > 0 && blocks < (1L << 31), "conv3x3 f32x3: grid of %ld blocks", blocks);
-    hipLaunchKernelGGL((conv3x3_f32x3_kernel<C, PS, SK, NP, HP>), dim3((unsigned)blocks, (unsigned)a.ksplit), dim3(C::NT), lds_bytes, stream, a);
+    hipLaunchKernelGGL((conv3x3_f32x3_kernel<C, PS, SK, NP, HP, PIPE>), dim3((unsigned)blocks, (unsigned)a.ksplit), dim3(C::NT), lds_bytes, stream, a);
   }
   OSVOS_LAUNCH_CHECK();
   return 0;
 }
 // the pre-split form is built for the production tiles (eight waves, in-loop staging); the others take the fp32 pack.  Stream-K: the
-// pre-split production tiles of the wide layers (SKT)
-template <class C, bool SKT = false>
+// pre-split production tiles of the wide layers (SKT).  PIPE: the tile has the pipelined K loop (10, 12, 14), taken unless OSVOS_X3_PIPE=0
+template <class C, bool SKT = false, bool PIPE = false>
 int launch_x(const ConvArgsX& a, int sk_grid, hipStream_t stream) {
   if (osvos_x3_pieces() == 22) {     // two fp16 pieces with block exponents (precision 'fp32h2'): the pre-split production tiles only
     if constexpr (C::ILV != 0 && (C::NT == 512 || C::NT == 256)) {
@@ -663,6 +821,15 @@ int launch_x(const ConvArgsX& a, int sk_grid, hipStream_t stream) {
     return launch_x2<C, 0, 0, 2>(a, 0, stream);
   }
   if constexpr (C::ILV != 0 && C::NT == 512) {
+    if constexpr (PIPE) {
+      OSVOS_ENV_INT(env_pipe, "OSVOS_X3_PIPE", 1);       // 0: the single-buffered loop (A/B comparisons)
+      if (env_pipe != 0) {
+        if constexpr (SKT) {
+          if (a.wpk3 != nullptr && sk_grid > 0) return launch_x2<C, 1, 1, 3, 0, 1>(a, sk_grid, stream);
+        }
+        if (a.wpk3 != nullptr) return launch_x2<C, 1, 0, 3, 0, 1>(a, 0, stream);
+      }
+    }
     if constexpr (SKT) {
       if (a.wpk3 != nullptr && sk_grid > 0) return launch_x2<C, 1, 1>(a, sk_grid, stream);
     }
@@ -979,11 +1146,11 @@ int osvos_conv3x3_f32x3_epi(const float* x, const float* wpk, const void* wpk3, 
     case 7: rc = launch_x<X7>(a, 0, stream); break;
     case 8: rc = launch_x<X8>(a, 0, stream); break;
     case 9: rc = launch_x<X9>(a, 0, stream); break;
-    case 10: rc = launch_x<X10, true>(a, sk_grid, stream); break;
+    case 10: rc = launch_x<X10, true, true>(a, sk_grid, stream); break;
     case 11: rc = launch_x<X11>(a, 0, stream); break;
-    case 12: rc = launch_x<X12, true>(a, sk_grid, stream); break;
+    case 12: rc = launch_x<X12, true, true>(a, sk_grid, stream); break;
     case 13: rc = launch_x<X13>(a, 0, stream); break;
-    case 14: rc = launch_x<X14, true>(a, sk_grid, stream); break;
+    case 14: rc = launch_x<X14, true, true>(a, sk_grid, stream); break;
     case 15: rc = launch_x<X15>(a, 0, stream); break;
     case 16: rc = launch_x<X16>(a, 0, stream); break;
     case 17: rc = launch_x<X17>(a, 0, stream); break;
