@@ -55,6 +55,16 @@ extern "C" {
                                             with it, a backward with the flag needs data-gradient packs with OSVOS_FLAG_X3_HALF_PIECES_BWD). */
 #define OSVOS_FLAG_X3_HALF_PIECES_BWD 0x2000 /* osvos_net_pack only: the DATA-GRADIENT packs are written in the FP16-pair format (for backward calls that
                                             carry OSVOS_FLAG_X3_HALF_PIECES) */
+#define OSVOS_FLAG_BF16_W2 0x4000        /* OR-ed into the dtype OSVOS_F32_BF16MFMA only (any other dtype: argument error): precision 'bf16w2' -- bf16 activations
+                                            times TWO-PIECE weights.  w_hi = RNE_bf16(w), w_lo = RNE_bf16(w - w_hi) (|w - w_hi - w_lo| <= 2^-16 |w|); every
+                                            forward 3x3 convolution (13 trunk + 4 side_prep) forms sum a*w_hi + sum a*w_lo on v_mfma_f32_32x32x16_bf16 into one
+                                            fp32 accumulator, a = the bf16 activation of the bf16 mode.  Backward, head, loss: those of the bf16 mode.
+                                              osvos_wpack_bytes / osvos_pack_conv3x3_fwd: the two-piece forward pack [plane][9][CinP/8][CoutP][8]: plane 0 is
+                                            the single-piece pack byte for byte, plane 1 (the lo pieces) follows at + osvos_wpack_bytes(.., OSVOS_F32_BF16MFMA).
+                                              osvos_net_wbuf_bytes / osvos_net_pack: the single-piece layout plus the 17 forward lo planes appended behind it in
+                                            layer order (13 trunk, then the 4 side_prep filters; each a multiple of 256 bytes); osvos_net_forward (also with
+                                            OSVOS_FLAG_INFERENCE): reads them -- a forward with the flag needs a pack with it.  osvos_net_backward accepts the
+                                            flag and ignores it (its packs are the single-piece ones at the same offsets). */
 #define OSVOS_F32_X3 3        /* fp32 tensors, fp32 parameters and fp32 weight packs exactly as OSVOS_F32; the wide 3x3 convolutions
                                  (forward, data gradient) run on the bf16 matrix pipe with three-way split operands (six bf16
                                  products per fp32 product, fp32 accumulate): fp32-grade results, see osvos_conv3x3 below */
@@ -169,6 +179,16 @@ int osvos_maxpool2x2_bwd_bf16act_code(const void* code, const void* dy_bf16, con
 int osvos_conv3x3_bf16act_fused(const void* x_bf16, const void* wpk, const float* bias, const void* mask_bits, void* y_bf16, void* y_bits,
                                 void* pooled_bf16, void* pool_code, int N, int H, int W, int Cin, int Cout, int relu, int tile, void* stream);
 int osvos_conv3x3_bf16io_tiles(int* tiles, int max);
+/* precision 'bf16w2' (OSVOS_FLAG_BF16_W2) at op level: the FORWARD convolution of osvos_conv3x3_bf16act_fused (same arguments and fused epilogues,
+ * vgg_osvos.py:136-145 conv -> ReLU [-> MaxPool2d(2, stride=2, ceil_mode=True)]) with a two-piece pack (osvos_pack_conv3x3_fwd(.., OSVOS_F32_BF16MFMA |
+ * OSVOS_FLAG_BF16_W2, ..)) -- two MFMA products per product.  x_is_f32 != 0: x is fp32 NHWC (channel stride Cin), rounded to bf16 (RNE) while staged
+ * (conv1_1's input).  mask_bits must be NULL (the data gradients stay single-piece).  tile: osvos_conv3x3_bf16w2_tiles() ids (+100: XCD-local block
+ * order) or -1 = automatic; a single-piece tile id is an argument error, as is a two-piece id in osvos_conv3x3_bf16act_fused.  y_f32 (optional): the
+ * fp32 result before its bf16 rounding (then y_bf16 may be NULL unless pooled_bf16 is given) -- what the accuracy tests compare. */
+int osvos_conv3x3_bf16w2_fused(const void* x, const void* wpk_w2, const float* bias, const void* mask_bits, void* y_bf16, void* y_bits,
+                               void* pooled_bf16, void* pool_code, int N, int H, int W, int Cin, int Cout, int relu, int x_is_f32, float* y_f32, int tile,
+                               void* stream);
+int osvos_conv3x3_bf16w2_tiles(int* tiles, int max);
 /* pieces per operand of the OSVOS_F32_X3 kernels called from THIS host thread through the op-level entry points (osvos_conv3x3,
  * osvos_conv3x3_x3*, osvos_conv3x3_wgrad, osvos_pack_conv3x3_x3 with that dtype): 3 (default: three bf16 pieces, six products, fp32-grade),
  * 2 (two bf16 pieces, three products; what OSVOS_FLAG_X3_TWO_PIECES selects for the osvos_net_* calls, which set and restore it themselves)

@@ -22,6 +22,7 @@ DEFER_JOIN = 0x200         # OSVOS_FLAG_DEFER_JOIN: osvos_net_backward leaves th
 X3_TWO_PIECES = 0x800       # OSVOS_FLAG_X3_TWO_PIECES: precision 'fp32x2' (two bf16 pieces per operand, three products)
 X3_HALF_PIECES = 0x1000     # OSVOS_FLAG_X3_HALF_PIECES: precision 'fp32h2' (two FP16 pieces under block exponents, three products); on net_pack: forward packs
 X3_HALF_PIECES_BWD = 0x2000 # OSVOS_FLAG_X3_HALF_PIECES_BWD: net_pack only -- data-gradient packs in the FP16-pair format
+BF16_W2 = 0x4000            # OSVOS_FLAG_BF16_W2: precision 'bf16w2' (dtype F32_BF16MFMA only) -- two-piece forward weight packs, two products per product
 INFERENCE = 0x400           # OSVOS_FLAG_INFERENCE: osvos_net_forward writes nothing only a backward would read (sign bits, pool codes)
 GENERIC_DECONV = 0x100      # OSVOS_FLAG_GENERIC_DECONV: OR-ed into the dtype of the osvos_net_* calls
 NPARAMS = 52
@@ -57,6 +58,8 @@ PROTOTYPES = {
     "osvos_maxpool2x2_bwd_bf16act_code": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "osvos_conv3x3_bf16act_fused": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "osvos_conv3x3_bf16io_tiles": (_i, [_vp, _i]),
+    "osvos_conv3x3_bf16w2_fused": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "osvos_conv3x3_bf16w2_tiles": (_i, [_vp, _i]),
     "osvos_set_x3_pieces": (_i, [_i]),
     "osvos_nchw_to_nhwc_bf16copy": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "osvos_maxpool2x2_bf16copy": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),

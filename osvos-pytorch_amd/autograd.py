@@ -8,16 +8,19 @@ import os
 
 import torch
 
-from ._lib import DEFER_JOIN, F32, F32_BF16MFMA, F32_X3, GENERIC_DECONV, INFERENCE, NPARAMS, X3_HALF_PIECES, X3_HALF_PIECES_BWD, X3_TWO_PIECES, check, lib, ptr_array
+from ._lib import (BF16_W2, DEFER_JOIN, F32, F32_BF16MFMA, F32_X3, GENERIC_DECONV, INFERENCE, NPARAMS, X3_HALF_PIECES, X3_HALF_PIECES_BWD, X3_TWO_PIECES, check,
+                   lib, ptr_array)
 
 # indices (state_dict order) of the frozen transposed-conv weights: lr 0 in both reference
 # scripts (train_online.py:84-85, train_parent.py:99-100); their gradients are never formed
 _FROZEN = set(range(8))
 # precision name -> (library dtype, pieces per operand of the f32x3 kernels in the forward, ... in the backward); see OSVOS.set_precision.
 # Pieces: 3 = three bf16 (six products, the default), 2 = two bf16 (three products), 22 = two FP16 under block exponents (three products; csrc/h2split.h)
+# 'bf16w2': the bf16 mode with TWO-PIECE weights in the forward (w_hi + w_lo, two products per product; OSVOS_FLAG_BF16_W2) -- the bf16 dtype with the
+# forward pieces marked 'w2' (the f32x3 piece counts do not apply to it); its backward is the bf16 mode's
 PRECISIONS = {"fp32": (F32, 3, 3), "bf16": (F32_BF16MFMA, 3, 3), "fp32x3": (F32_X3, 3, 3), "fp32x2": (F32_X3, 2, 2), "fp32x3b2": (F32_X3, 3, 2),
-              "fp32h2": (F32_X3, 22, 22), "fp32x3h2": (F32_X3, 3, 22)}
-_PIECE_FLAG = {3: 0, 2: X3_TWO_PIECES, 22: X3_HALF_PIECES}
+              "fp32h2": (F32_X3, 22, 22), "fp32x3h2": (F32_X3, 3, 22), "bf16w2": (F32_BF16MFMA, "w2", 3)}
+_PIECE_FLAG = {3: 0, 2: X3_TWO_PIECES, 22: X3_HALF_PIECES, "w2": BF16_W2}
 
 
 def _stream():
@@ -105,30 +108,39 @@ class NetRuntime:
         # on the network calls: 'fp32x2' in both passes, 'fp32x3b2' in the BACKWARD only (forward = 'fp32x3' bit for bit)
         # 'fp32h2': TWO FP16 pieces under block exponents in both passes (fp32-grade at three products: the packs change format, hence the re-pack);
         # 'fp32x3h2': the forward of 'fp32x3' bit for bit, the backward on FP16 pairs
+        # 'bf16w2': the bf16 mode's forward on two-piece weight packs (OSVOS_FLAG_BF16_W2) -- a larger buffer, hence re-allocation and re-pack
         dt, pf, pb = PRECISIONS[name]
-        if (pf == 22) != (self.pieces_fwd == 22) or (pb == 22) != (self.pieces_bwd == 22):
-            self.key = None
+        fmt_before = self.pack_format()
         self.pieces_fwd, self.pieces_bwd = pf, pb
-        if dt != self.dtype:
+        if dt != self.dtype or (pf == "w2") != (fmt_before[1] == "w2"):
             self.dtype, self.wbuf, self.key = dt, None, None
+        elif self.pack_format() != fmt_before:
+            self.key = None
+
+    def pack_format(self):
+        """What the packs in wbuf are: (dtype, forward format, data-gradient format) -- 'w2' two-piece bf16, 'h2' FP16 pairs, '' the dtype's plain
+        packs.  Part of the pack key: a graph recorded under one format must not run its backward on packs of another (the backward raises)."""
+        fwd = "w2" if self.pieces_fwd == "w2" else ("h2" if self.pieces_fwd == 22 else "")
+        return (self.dtype, fwd, "h2" if self.pieces_bwd == 22 else "")
 
     def ensure_packed(self, params):
         dev = params[0].device
-        key = tuple((p.data_ptr(), p._version) for p in params)
+        key = (self.pack_format(), tuple((p.data_ptr(), p._version) for p in params))
         if self.wbuf is not None and key == self.key and self.wbuf.device == dev:
             return
         l = lib()
         if self.wbuf is None or self.wbuf.device != dev:
-            self.wbuf = torch.empty(l.osvos_net_wbuf_bytes(self.dtype), device=dev, dtype=torch.uint8)
+            self.wbuf = torch.empty(l.osvos_net_wbuf_bytes(self.dtype | (BF16_W2 if self.pieces_fwd == "w2" else 0)), device=dev, dtype=torch.uint8)
             self.deconv_key = None
-        dkey = key[:4]
+        dkey = key[1][:4]
         if dkey != self.deconv_key:
             # (round 6: the generic head runs on the bf16 trunk too -- the head is fp32 in every precision, its backward now also writes the bf16
             #  copy of the side_prep output gradient the bf16-store mode's convolutions read)
             self.generic_head = not self._deconv_is_diagonal(params[:4])
             self.deconv_key = dkey
         check(l.osvos_net_pack(ptr_array([p.data_ptr() for p in params]), C.c_void_p(self.wbuf.data_ptr()),
-                               self.cdtype() | (X3_HALF_PIECES if self.pieces_fwd == 22 else 0) | (X3_HALF_PIECES_BWD if self.pieces_bwd == 22 else 0),
+                               self.cdtype() | (X3_HALF_PIECES if self.pieces_fwd == 22 else 0) | (X3_HALF_PIECES_BWD if self.pieces_bwd == 22 else 0) |
+                               (BF16_W2 if self.pieces_fwd == "w2" else 0),
                                1, _stream()), "net_pack")
         self.key = key
 
@@ -202,6 +214,10 @@ class OSVOSNetFunction(torch.autograd.Function):
         (ws,) = ctx.saved_tensors      # (freed by a previous backward without retain_graph=True: autograd raises its usual error here)
         n, h, w = ctx.shape
         if rt.key != ctx.pack_key:
+            if rt.key is not None and rt.key[0] != ctx.pack_key[0]:
+                raise RuntimeError("the weight packs changed format between forward and backward of the same graph (forward under %r, packs now %r: "
+                                   "set_precision was called in between); run the backward before switching precision"
+                                   % (ctx.pack_key[0], rt.key[0]))
             raise RuntimeError("parameters changed between forward and backward of the same graph")
         l = lib()
         dev = ws.device

@@ -21,8 +21,20 @@ int osvos_nhwc_to_nchw(const void* src, float* dst, int N, int C, int H, int W, 
   return osvos_nhwc_to_nchw_f32((const float*)src, dst, N, C, H, W, cs, (hipStream_t)stream);
 }
 
+// OSVOS_FLAG_BF16_W2 on the op-level pack entries: two-piece forward pack (hi plane, then lo plane), dtype OSVOS_F32_BF16MFMA only
+static bool w2_pack_flag(int& dtype, const char* what, bool* bad) {
+  const bool w2 = (dtype & OSVOS_FLAG_BF16_W2) != 0;
+  dtype &= ~OSVOS_FLAG_BF16_W2;
+  *bad = w2 && dtype != OSVOS_F32_BF16MFMA;
+  if (*bad) osvos_set_error("%s: OSVOS_FLAG_BF16_W2 needs dtype OSVOS_F32_BF16MFMA (got dtype %d)", what, dtype);
+  return w2;
+}
+
 size_t osvos_wpack_bytes(int Cout, int Cin, int dtype) {
-  if (dtype == OSVOS_F32_BF16MFMA) return (size_t)9 * ((Cin + 31) / 32 * 32) * osvos_cout_pad(Cout) * 2;
+  bool bad;
+  const bool w2 = w2_pack_flag(dtype, "wpack_bytes", &bad);
+  if (bad) return 0;
+  if (dtype == OSVOS_F32_BF16MFMA) return (size_t)9 * ((Cin + 31) / 32 * 32) * osvos_cout_pad(Cout) * 2 * (w2 ? 2 : 1);
   return (size_t)9 * osvos_cin_pad(Cin, dtype) * osvos_cout_pad(Cout) * osvos_elem(dtype);
 }
 size_t osvos_wpack_dgrad_bytes(int Cout, int Cin, int dtype) {
@@ -30,6 +42,16 @@ size_t osvos_wpack_dgrad_bytes(int Cout, int Cin, int dtype) {
   return (size_t)9 * osvos_cin_pad(Cout, dtype) * osvos_cout_pad(Cin) * osvos_elem(dtype);
 }
 int osvos_pack_conv3x3_fwd(const float* w, void* wpk, int Cout, int Cin, int dtype, void* stream) {
+  bool bad;
+  if (w2_pack_flag(dtype, "pack_conv3x3_fwd", &bad)) {
+    if (bad) return -1;
+    OSVOS_ARG_CHECK(w && wpk && Cout > 0 && Cin > 0, "pack_conv3x3_fwd w2: bad arguments");
+    const float* ws[1] = {w};
+    void* dsts[1] = {wpk};
+    void* los[1] = {reinterpret_cast<char*>(wpk) + osvos_wpack_bytes(Cout, Cin, OSVOS_F32_BF16MFMA)};
+    const int co[1] = {Cout}, ci[1] = {Cin}, dg[1] = {0};
+    return osvos_pack_bf16_multi_lo(ws, dsts, co, ci, dg, los, 1, (hipStream_t)stream);
+  }
   NEED_F32(dtype, "pack_conv3x3_fwd");
   if (dtype == OSVOS_F32_BF16MFMA) return osvos_pack_fwd_bf16(w, wpk, Cout, Cin, (hipStream_t)stream);
   return osvos_pack_fwd_f32(w, (float*)wpk, Cout, Cin, (hipStream_t)stream);
@@ -113,6 +135,17 @@ int osvos_conv3x3_bf16act_fused(const void* x_bf16, const void* wpk, const float
                                      reinterpret_cast<unsigned*>(y_bits), pooled_bf16, N, H, W, Cin, Cout, Cout, relu, tile, (hipStream_t)stream, pool_code);
 }
 int osvos_conv3x3_bf16io_tiles(int* tiles, int max) { return osvos_conv3x3_bf16mfma_xb_tiles(tiles, max); }
+int osvos_conv3x3_bf16w2_fused(const void* x, const void* wpk_w2, const float* bias, const void* mask_bits, void* y_bf16, void* y_bits,
+                               void* pooled_bf16, void* pool_code, int N, int H, int W, int Cin, int Cout, int relu, int x_is_f32, float* y_f32, int tile,
+                               void* stream) {
+  OSVOS_ARG_CHECK(y_bf16 != nullptr || (y_f32 != nullptr && pooled_bf16 == nullptr), "conv3x3_bf16w2_fused: y_bf16 (or y_f32 without a pool) is required");
+  OSVOS_ARG_CHECK(mask_bits == nullptr, "conv3x3_bf16w2_fused: forward only (the data gradients of 'bf16w2' are single-piece)");
+  OSVOS_ARG_CHECK(Cout > 0 && Cin > 0, "conv3x3_bf16w2_fused: bad shape");
+  return osvos_conv3x3_bf16mfma_bits(x, x_is_f32 ? 0 : 1, wpk_w2, bias, nullptr, 0, nullptr, y_f32, y_bf16, reinterpret_cast<unsigned*>(y_bits), pooled_bf16,
+                                     N, H, W, Cin, Cout, Cout, relu, tile, (hipStream_t)stream, pool_code, 2,
+                                     osvos_wpack_bytes(Cout, Cin, OSVOS_F32_BF16MFMA));
+}
+int osvos_conv3x3_bf16w2_tiles(int* tiles, int max) { return osvos_conv3x3_bf16w2_tiles_impl(tiles, max); }
 
 size_t osvos_conv3x3_splitk_ws_bytes(int N, int H, int W, int Cout, int dtype) {
   (void)dtype;

@@ -34,6 +34,7 @@ struct ConvArgsB {
   bf16_t* pooled;              // optional: maxpool2x2 (ceil mode) of the bf16 result, [N][ceil(H/2)][ceil(W/2)][y_cs] (last convolution of a stage; needs ReLU)
   unsigned char* pool_code;    // optional, with pooled: one byte per pooled element for the pool's backward (pool.hip: first-max position + 4 "input > 0" bits)
   unsigned long long* prof;   // phase cycle counters (only read by builds with -DOSVOS_CONV_PROF; tools/conv_phase_probe.py)
+  unsigned w_lo;               // two-piece weights (WP = 2) only: byte offset of the lo plane from wpk (laid out like the hi plane at wpk)
 };
 
 constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
@@ -76,8 +77,15 @@ __device__ inline uint4 pack_bf16x8(const f32x4& a, const f32x4& b) {
   return __builtin_bit_cast(uint4, v);
 }
 
-template <class C, int XB>      // XB = 1: the input tensor is already bf16 (half the bytes, no conversion while staging)
+// XB = 1: the input tensor is already bf16 (half the bytes, no conversion while staging)
+// WP = 2: two-piece weights (precision 'bf16w2'): the filter arrives as w_hi + w_lo (two bf16 planes, the lo plane at wpk + w_lo bytes), both are
+//         staged into LDS behind each other and every (A fragment, B fragment) pair issues two MFMAs into the same accumulator
+template <class C, int XB, int WP = 1>
 __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_bf16_kernel(ConvArgsB a) {
+  static_assert(WP == 1 || WP == 2, "one or two weight pieces");
+  constexpr int BW_U4 = WP * C::B_U4;             // B tile of all weight planes (plane p at Bs + p * B_U4)
+  constexpr int NBLW = cdiv(BW_U4, C::NT);
+  constexpr int SPARE = C::A_U4 + BW_U4;          // slot of the lanes that stage nothing
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint4* lds = reinterpret_cast<uint4*>(smem);
   uint4* As = lds;
@@ -111,7 +119,8 @@ __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_bf16_kernel(ConvArgsB a
   // branch pair: 36 of them per chunk before).  The chunk advance rides in the scalar offset.
   constexpr unsigned OOB = 0x80000000u;
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(ximg), 0, (int)((size_t)a.H * a.W * a.Cin * XE), 0x00020000);
-  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(a.wpk), 0, (int)((size_t)9 * CG * a.CoutP * 16), 0x00020000);
+  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(a.wpk), 0,
+                                                                       (int)((WP == 2 ? (size_t)a.w_lo : 0) + (size_t)9 * CG * a.CoutP * 16), 0x00020000);
   // (A measured alternative -- consecutive lanes on consecutive 16-byte pieces, 8-byte LDS stores -- was no faster:
   // the cost of the activation loads is their L2 miss rate, not their lane pattern.)
   unsigned a_off[C::NA];                         // byte offset of the slot's 8 channels in chunk 0
@@ -125,29 +134,30 @@ __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_bf16_kernel(ConvArgsB a
     const int hy = pix / C::HWD, hx = pix % C::HWD;
     const int gy = y0 + hy - 1, gx = x0 + hx - 1;
     const bool slot = e < C::A_LOAD;
-    a_dst[i] = slot ? g * C::PLANE + hy * C::PITCH + hx : C::BUF_U4;      // lanes without a slot write the spare slot
+    a_dst[i] = slot ? g * C::PLANE + hy * C::PITCH + hx : SPARE;      // lanes without a slot write the spare slot
     a_off[i] = (slot && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) ? (unsigned)(((gy * a.W + gx) * a.Cin + 8 * g) * XE) : OOB;
   }
-  unsigned b_off[C::NBL];
+  unsigned b_off[NBLW];
 #pragma unroll
-  for (int i = 0; i < C::NBL; ++i) {
+  for (int i = 0; i < NBLW; ++i) {
     const int e = tid + i * C::NT;
-    const int tap = e / (C::KG * C::BN), rem = e % (C::KG * C::BN);
+    const int pl = WP == 1 ? 0 : e / C::B_U4, ep = WP == 1 ? e : e % C::B_U4;      // weight plane, slot inside it
+    const int tap = ep / (C::KG * C::BN), rem = ep % (C::KG * C::BN);
     const int g = rem / C::BN, nn = rem % C::BN;
-    b_off[i] = (e < C::B_U4 && co0 + nn < a.CoutP) ? (unsigned)(((tap * CG + g) * a.CoutP + co0 + nn) * 16) : OOB;
+    b_off[i] = (e < BW_U4 && co0 + nn < a.CoutP) ? (pl ? a.w_lo : 0u) + (unsigned)(((tap * CG + g) * a.CoutP + co0 + nn) * 16) : OOB;
   }
   const int cin_groups = a.Cin >> 3;             // 8-channel groups that exist in x (the pack is zero padded to CinP)
 
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   u32x4 ra[C::NA][2];
-  u32x4 rb[C::NBL];
+  u32x4 rb[NBLW];
 #ifdef OSVOS_PROF_NO_A       // probe builds only: out-of-range offsets = zero fill without memory traffic
 #pragma unroll
   for (int i = 0; i < C::NA; ++i) a_off[i] = OOB;
 #endif
 #ifdef OSVOS_PROF_NO_B
 #pragma unroll
-  for (int i = 0; i < C::NBL; ++i) b_off[i] = OOB;
+  for (int i = 0; i < NBLW; ++i) b_off[i] = OOB;
 #endif
   auto load_chunk = [&](int kc) {
 #pragma unroll
@@ -157,15 +167,15 @@ __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_bf16_kernel(ConvArgsB a
       if (!XB) ra[i][1] = __builtin_amdgcn_raw_buffer_load_b128(xrs, off + 16, kc * (8 * C::KG * XE), 0);
     }
 #pragma unroll
-    for (int i = 0; i < C::NBL; ++i) rb[i] = __builtin_amdgcn_raw_buffer_load_b128(wrs, b_off[i], kc * C::KG * a.CoutP * 16, 0);
+    for (int i = 0; i < NBLW; ++i) rb[i] = __builtin_amdgcn_raw_buffer_load_b128(wrs, b_off[i], kc * C::KG * a.CoutP * 16, 0);
   };
   auto store_chunk = [&]() {
 #pragma unroll
     for (int i = 0; i < C::NA; ++i)
       As[a_dst[i]] = XB ? __builtin_bit_cast(uint4, ra[i][0]) : pack_bf16x8(__builtin_bit_cast(f32x4, ra[i][0]), __builtin_bit_cast(f32x4, ra[i][1]));
 #pragma unroll
-    for (int i = 0; i < C::NBL; ++i)
-      if (C::B_U4 % C::NT == 0 || tid + i * C::NT < C::B_U4) Bs[tid + i * C::NT] = __builtin_bit_cast(uint4, rb[i]);
+    for (int i = 0; i < NBLW; ++i)
+      if (BW_U4 % C::NT == 0 || tid + i * C::NT < BW_U4) Bs[tid + i * C::NT] = __builtin_bit_cast(uint4, rb[i]);
   };
 
   int a_idx[C::WM];
@@ -216,7 +226,7 @@ __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_bf16_kernel(ConvArgsB a
     // 9 x KS (tap, k-step) stages, software pipelined: operands of stage s+1 are requested before the MFMAs of stage s issue;
     // sched_barrier pins that order.  (Measured and removed, see DESIGN.md 3.4: re-using A fragments across tap rows -- 40 % fewer
     // LDS reads -- and issuing the next chunk's loads one per MFMA inside this loop were both no faster.)
-    uint4 fa[1 + C::PIPE][C::WM], fb[1 + C::PIPE][C::WN];
+    uint4 fa[1 + C::PIPE][C::WM], fb[1 + C::PIPE][C::WN], fl[1 + C::PIPE][C::WN];      // (fl: lo plane, WP = 2 only)
     auto ldfrag = [&](int st, int set) {
       const int tap = st / C::KS, ks = st % C::KS;
       const int r = tap / 3, s = tap % 3;
@@ -224,6 +234,10 @@ __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_bf16_kernel(ConvArgsB a
       for (int mi = 0; mi < C::WM; ++mi) fa[set][mi] = As[a_idx[mi] + 2 * ks * C::PLANE + r * C::PITCH + s];
 #pragma unroll
       for (int ni = 0; ni < C::WN; ++ni) fb[set][ni] = Bs[b_idx + (tap * C::KG + 2 * ks) * C::BN + ni * 32];
+      if constexpr (WP == 2) {
+#pragma unroll
+        for (int ni = 0; ni < C::WN; ++ni) fl[set][ni] = Bs[C::B_U4 + b_idx + (tap * C::KG + 2 * ks) * C::BN + ni * 32];
+      }
     };
     if (C::PIPE) ldfrag(0, 0);
 #pragma unroll
@@ -241,6 +255,14 @@ __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_bf16_kernel(ConvArgsB a
         for (int ni = 0; ni < C::WN; ++ni)
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fb[cur][ni]),
                                                                 __builtin_bit_cast(bf16x8_t, fa[cur][mi]), acc[mi][ni], 0, 0, 0);
+      if constexpr (WP == 2) {      // the lo products after all hi ones: WM x WN independent MFMAs between the two writes of an accumulator
+#pragma unroll
+        for (int mi = 0; mi < C::WM; ++mi)
+#pragma unroll
+          for (int ni = 0; ni < C::WN; ++ni)
+            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fl[cur][ni]),
+                                                                  __builtin_bit_cast(bf16x8_t, fa[cur][mi]), acc[mi][ni], 0, 0, 0);
+      }
       if (C::PIPE) __builtin_amdgcn_sched_barrier(0);
     }
     PROF_MARK(6);
@@ -435,13 +457,18 @@ __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_bf16_kernel(ConvArgsB a
 #endif
 }
 
-template <class C, int XB = 0>
+template <class C, int WP>
+constexpr size_t lds_bytes() { return (size_t)(C::A_U4 + WP * C::B_U4 + 1) * 16; }      // (WP = 1: C::LDS_BYTES)
+
+template <class C, int XB = 0, int WP = 1>
 int launch_cfg(const ConvArgsB& a0, hipStream_t stream) {
+  static_assert(lds_bytes<C, WP>() <= 160 * 1024, "LDS budget of a CU");
+  constexpr size_t LDS = lds_bytes<C, WP>();
   static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};      // hipFuncSetAttribute is per device
   bool& attr_set = attr_set_dev[osvos_current_device()];
   if (!attr_set) {
-    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_bf16_kernel<C, XB>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES));
+    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_bf16_kernel<C, XB, WP>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
     attr_set = true;
   }
   ConvArgsB a = a0;
@@ -451,7 +478,7 @@ int launch_cfg(const ConvArgsB& a0, hipStream_t stream) {
   a.nsp = a.tiles_x * a.tiles_y * a.N;
   const long blocks = a.map == 0 ? (long)a.nct * a.nsp : (long)a.nct * ((a.nsp + 7) / 8) * 8;
   OSVOS_ARG_CHECK(blocks > 0 && blocks < (1L << 31), "conv3x3 bf16: grid of %ld blocks", blocks);
-  hipLaunchKernelGGL((conv3x3_bf16_kernel<C, XB>), dim3((unsigned)blocks), dim3(C::NT), C::LDS_BYTES, stream, a);
+  hipLaunchKernelGGL((conv3x3_bf16_kernel<C, XB, WP>), dim3((unsigned)blocks), dim3(C::NT), LDS, stream, a);
   OSVOS_LAUNCH_CHECK();
   return 0;
 }
@@ -516,6 +543,42 @@ int pick_tile_b(int N, int H, int W, int CoutP, int Cin) {
   return 7;
 }
 
+// Two-piece weight tiles (precision 'bf16w2', WP = 2; ids 40-45).  Every tile stages BOTH weight planes, so the B tile is twice the single-piece one;
+// all of them run 16-channel K chunks (KG = 2) to keep that inside the 160 KB of LDS a CU has:
+//   40: 256 px x 128 co, 4 waves of 4x2 accumulators:  A 10.9 KB + B 2 x 36.9 KB = 84.6 KB -> ONE workgroup per CU (B8's form; B8 itself fits two)
+//   41: 256 px x 128 co, 8 waves of 2x2:               the same 84.6 KB, two waves per SIMD
+//   42: 256 px x  64 co, 4 waves of 4x1 (B9's form):   10.9 + 36.9 = 47.8 KB -> three per CU (conv1_x, conv2_1, the 64-cout layers)
+//   43: 256 px x  32 co, 4 waves of 2x1 (side_prep):   10.9 + 18.4 = 29.3 KB
+//   44: 16x8 px x 64 co, 4 waves of 1x1 (small frames): 10.0 + 36.9 = 46.9 KB
+//   45:  8x8 px x 64 co, 4 waves of 1x1 (tiny frames):   3.2 + 36.9 = 40.1 KB; its waves hold no whole pooling windows (separate pool launch)
+//                  RBW TBX TBY NB WGM WGN PIPE OCC KG
+using W0 = CfgB<32, 1, 8, 4, 2, 2, 1, 1, 2>;
+using W1 = CfgB<32, 1, 8, 4, 4, 2, 1, 2, 2>;
+using W2 = CfgB<32, 1, 8, 2, 2, 2, 1, 2, 2>;
+using W3 = CfgB<32, 1, 8, 1, 4, 1, 1, 2, 2>;
+using W4 = CfgB<16, 1, 4, 2, 2, 2, 1, 2, 2>;
+using W5 = CfgB<8, 1, 2, 2, 2, 2, 1, 2, 2>;
+constexpr int kW2First = 40, kNumTilesW2 = 6;
+const TileInfoB kTilesW2[kNumTilesW2] = {infoB<W0>(), infoB<W1>(), infoB<W2>(), infoB<W3>(), infoB<W4>(), infoB<W5>()};
+inline bool is_w2_tile(int t) { return t >= kW2First && t < kW2First + kNumTilesW2; }
+
+// the single-piece rule's shape classes with the two-piece tiles: B9 / B1 / B8 -> 42, B6 -> 43, B5 -> 44, B7 -> 45.  Measured at batch 12, 854x480
+// (tools/precision_ab.py, profiles/bf16w2_ab.txt): the 256 px x 64 co tile beats both 128-cout tiles on EVERY 128- and 512-cout layer (conv2_2 0.694 ms
+// against 0.833 / 0.757 for 40 / 41, conv4_2 0.694 against 0.739 / 0.704): at 84.6 KB a 128-cout workgroup has its CU alone, and four or eight waves
+// cannot hide the K loop's LDS and MFMA latencies the way two 47.8 KB workgroups do.  40 / 41 stay built for forced-tile tests and measurements.
+int pick_tile_w2(int N, int H, int W, int CoutP, int Cin) {
+  auto tiles = [&](int t) { const TileInfoB& i = kTilesW2[t - kW2First]; return (long)N * ceil_div(H, i.th) * ceil_div(W, i.tw) * ceil_div(CoutP, i.bn); };
+  if (CoutP <= 32) return 43;
+  if (Cin <= 16) return 42;
+  if (Cin <= 64 && CoutP <= 128 && tiles(42) >= 400 && (long)ceil_div(H, 8) * 8 * ceil_div(W, 32) * 32 * 100 <= (long)H * W * 115) return 42;
+  const int order[] = {42, 44, 45};
+  for (int k = 0; k < 3; ++k) {
+    if (kTilesW2[order[k] - kW2First].bn > CoutP) continue;
+    if (tiles(order[k]) >= 400 || k == 2) return order[k];
+  }
+  return 45;
+}
+
 // wpk[((tap*CG + cg)*CoutP + co)*8 + e] = bf16(W[co][8cg+e][tap])   (zero padded)
 // every layer's bf16 packs, forward and data-gradient form, in ONE launch (round 5 prep; the f32x3 twin is pack_x3_multi_kernel): osvos_net_pack
 // re-packs 17 filters x 2 forms after every optimizer step -- 34 launches of ~8 us each, one float per thread at a 36-byte stride.  A unit =
@@ -526,6 +589,8 @@ struct PackB16Table {
   const float* w[OSVOS_PACK_MAX];
   bf16_t* dst[OSVOS_PACK_MAX];
   int Cout[OSVOS_PACK_MAX], Cin[OSVOS_PACK_MAX], dgrad[OSVOS_PACK_MAX];
+  int pieces[OSVOS_PACK_MAX];          // 2: also the lo plane RNE(w - hi) at dst + lo[k] elements (forward packs of precision 'bf16w2')
+  long lo[OSVOS_PACK_MAX];
   long start[OSVOS_PACK_MAX + 1];      // in (cg, 32-channel) units
   int n;
 };
@@ -566,8 +631,16 @@ __global__ __launch_bounds__(256) void pack_bf16_multi_kernel(PackB16Table t) {
     __syncthreads();
     const int ml = (int)threadIdx.x >> 3, e = (int)threadIdx.x & 7;
     bf16_t* d = t.dst[k];
+    const bool two = t.pieces[k] == 2;
+    const long lo = t.lo[k];
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) d[(((long)tap * CG + cg) * MP + m0 + ml) * 8 + e] = f32_to_bf16(tile[ml * ROW + e * 9 + tap]);
+    for (int tap = 0; tap < 9; ++tap) {
+      const float v = tile[ml * ROW + e * 9 + tap];
+      const bf16_t hi = f32_to_bf16(v);
+      const long o = (((long)tap * CG + cg) * MP + m0 + ml) * 8 + e;
+      d[o] = hi;
+      if (two) d[o + lo] = f32_to_bf16(v - bf16_to_f32(hi));      // (exact difference; w - hi - lo <= 2^-16 |w|)
+    }
   }
 }
 
@@ -594,6 +667,13 @@ int osvos_pack_dgrad_bf16(const float* w, void* wpk, int Cout, int Cin, hipStrea
 // n bf16 packs (n <= OSVOS_PACK_MAX) in one launch: ws[k] OIHW fp32 [Couts[k]][Cins[k]][3][3] -> dsts[k] (osvos_pack_fwd_bf16 layout; dgrads[k] != 0:
 // osvos_pack_dgrad_bf16 layout)
 int osvos_pack_bf16_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, int n, hipStream_t stream) {
+  return osvos_pack_bf16_multi_lo(ws, dsts, Couts, Cins, dgrads, nullptr, n, stream);
+}
+
+// the same with two-piece entries: lo_dsts (NULL = none) [k] != NULL writes the lo plane of entry k there (forward packs only; the hi plane, at
+// dsts[k], is the single-piece pack byte for byte)
+int osvos_pack_bf16_multi_lo(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, void* const* lo_dsts, int n,
+                             hipStream_t stream) {
   OSVOS_ARG_CHECK(ws && dsts && Couts && Cins && dgrads && n >= 0 && n <= OSVOS_PACK_MAX, "pack_bf16_multi: bad table (n = %d)", n);
   if (n == 0) return 0;
   PackB16Table t;
@@ -604,6 +684,15 @@ int osvos_pack_bf16_multi(const float* const* ws, void* const* dsts, const int* 
     OSVOS_ARG_CHECK(ws[k] && dsts[k] && K > 0 && M > 0, "pack_bf16_multi: entry %d (K = %d, M = %d)", k, K, M);
     t.w[k] = ws[k]; t.dst[k] = reinterpret_cast<bf16_t*>(dsts[k]); t.Cout[k] = Couts[k]; t.Cin[k] = Cins[k]; t.dgrad[k] = dgrads[k] ? 1 : 0;
     t.start[k + 1] = t.start[k] + (long)(((K + 31) / 32 * 32) / 8) * (osvos_cout_pad(M) / 32);
+    t.pieces[k] = 1;
+    t.lo[k] = 0;
+    if (lo_dsts != nullptr && lo_dsts[k] != nullptr) {
+      OSVOS_ARG_CHECK(!dgrads[k], "pack_bf16_multi: entry %d: two-piece packs are forward packs only", k);
+      const long d = reinterpret_cast<const bf16_t*>(lo_dsts[k]) - t.dst[k];
+      OSVOS_ARG_CHECK(reinterpret_cast<const char*>(lo_dsts[k]) == reinterpret_cast<const char*>(t.dst[k] + d), "pack_bf16_multi: entry %d: misaligned lo plane", k);
+      t.pieces[k] = 2;
+      t.lo[k] = d;
+    }
   }
   const long blocks = t.start[n] < 8192 ? t.start[n] : 8192;
   hipLaunchKernelGGL(pack_bf16_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, t);
@@ -634,8 +723,9 @@ int osvos_conv3x3_bf16mfma_io(const void* x, int xb, const void* wpk, const floa
 // pool_code (optional, with pooled_bf16): [N][ceil(H/2)][ceil(W/2)][Cout] bytes for osvos_maxpool2x2_bwd_bf16_code; written whichever kernel runs
 int osvos_conv3x3_bf16mfma_bits(const void* x, int xb, const void* wpk, const float* bias, const void* mask, int mask_bf16, const unsigned* mask_bits,
                                 float* y, void* ybf, unsigned* y_bits, void* pooled_bf16, int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile,
-                                hipStream_t stream, void* pool_code) {
+                                hipStream_t stream, void* pool_code, int wp, size_t w_lo) {
   OSVOS_ARG_CHECK(pool_code == nullptr || pooled_bf16 != nullptr, "conv3x3 bf16: pool code bytes without a pooled result");
+  OSVOS_ARG_CHECK(wp == 1 || wp == 2, "conv3x3 bf16: %d weight pieces (1 or 2)", wp);
   OSVOS_ARG_CHECK(pooled_bf16 == nullptr || (ybf != nullptr && relu && mask == nullptr && mask_bits == nullptr && Cout % 8 == 0 && y_cs == Cout),
                   "conv3x3 bf16: the fused forward pool needs a bf16 result, ReLU, no mask and a dense Cout %% 8 == 0 (Cout %d, stride %d)", Cout, y_cs);
   OSVOS_ARG_CHECK(x && wpk && (y || ybf), "conv3x3 bf16: null pointer");
@@ -656,6 +746,46 @@ int osvos_conv3x3_bf16mfma_bits(const void* x, int xb, const void* wpk, const fl
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.CinP = (Cin + 31) / 32 * 32; a.Cout = Cout; a.CoutP = osvos_cout_pad(Cout); a.y_cs = y_cs;
   a.relu = relu;
   a.prof = OSVOS_CONV_PROF_PTR;
+  a.w_lo = 0;
+  // A pack and the kernel that reads it must agree on the number of weight pieces: the two-piece tiles (40-45) exist for two-piece packs only, and no
+  // other tile (register-staged 0-11, LDS-DMA 30-37, persistent 38) may be handed one -- they would read the hi plane and silently drop the lo one.
+  if (wp == 2) {
+    const size_t plane = (size_t)9 * a.CinP * a.CoutP * 2;
+    OSVOS_ARG_CHECK(w_lo >= plane && w_lo + plane < (1UL << 31), "conv3x3 bf16w2: lo plane offset %zu (plane %zu bytes, 31-bit offsets)", w_lo, plane);
+    a.w_lo = (unsigned)w_lo;
+    if (tile < 0) {
+      OSVOS_ENV_INT(env_tile_w2, "OSVOS_CONV_TILE_W2", -1);
+      tile = env_tile_w2 >= 0 ? env_tile_w2 : pick_tile_w2(N, H, W, a.CoutP, Cin);
+      if (env_tile_w2 < 0 && (double)H * W * Cin * 4 > 9.0 * Cin * a.CoutP * 2 * 2) tile += 100;      // (the single-piece map rule, both planes)
+    }
+    a.map = tile >= 100 ? 1 : 0;
+    tile %= 100;
+    OSVOS_ARG_CHECK(is_w2_tile(tile), "conv3x3 bf16w2: tile %d is a single-piece kernel; two-piece packs need tiles %d-%d", tile, kW2First, kW2First + kNumTilesW2 - 1);
+    if (a.pooled != nullptr && !(xb && tile != 45)) {      // waves without whole windows / fp32 staging: separate pooling launch, as single-piece
+      const int rc = osvos_conv3x3_bf16mfma_bits(x, xb, wpk, bias, mask, mask_bf16, mask_bits, y, ybf, y_bits, nullptr, N, H, W, Cin, Cout, y_cs, relu, tile + 100 * a.map,
+                                                 stream, nullptr, wp, w_lo);
+      return rc ? rc : osvos_maxpool2x2_bf16_code(ybf, pooled_bf16, pool_code, N, H, W, Cout, stream);
+    }
+    if (xb) {
+      switch (tile) {
+        case 40: return launch_cfg<W0, 1, 2>(a, stream);
+        case 41: return launch_cfg<W1, 1, 2>(a, stream);
+        case 42: return launch_cfg<W2, 1, 2>(a, stream);
+        case 43: return launch_cfg<W3, 1, 2>(a, stream);
+        case 44: return launch_cfg<W4, 1, 2>(a, stream);
+        default: return launch_cfg<W5, 1, 2>(a, stream);
+      }
+    }
+    switch (tile) {
+      case 40: return launch_cfg<W0, 0, 2>(a, stream);
+      case 41: return launch_cfg<W1, 0, 2>(a, stream);
+      case 42: return launch_cfg<W2, 0, 2>(a, stream);
+      case 43: return launch_cfg<W3, 0, 2>(a, stream);
+      case 44: return launch_cfg<W4, 0, 2>(a, stream);
+      default: return launch_cfg<W5, 0, 2>(a, stream);
+    }
+  }
+  OSVOS_ARG_CHECK(!is_w2_tile(tile % 100), "conv3x3 bf16: tile %d needs a two-piece (bf16w2) pack", tile % 100);
   if (tile < 0) {
     OSVOS_ENV_INT(env_tile, "OSVOS_CONV_TILE_BF16", -1);
     const bool env = env_tile >= 0;
@@ -733,6 +863,12 @@ int osvos_conv3x3_bf16mfma_bits(const void* x, int xb, const void* wpk, const fl
     case 11: return launch_cfg<B11>(a, stream);
     default: osvos_set_error("conv3x3 bf16: unknown tile config %d", tile); return -1;
   }
+}
+
+int osvos_conv3x3_bf16w2_tiles_impl(int* tiles, int max) {      // tile ids built for two-piece weights (bf16 or fp32 activations)
+  int n = 0;
+  for (; n < kNumTilesW2 && n < max; ++n) tiles[n] = kW2First + n;
+  return n;
 }
 
 int osvos_conv3x3_bf16mfma_xb_tiles(int* tiles, int max) {      // tile ids built for bf16 activations

@@ -27,6 +27,8 @@ int osvos_conv3x3_wgrad_f32x3(const float* x, const float* dy, void* ws, float* 
 size_t osvos_wpack_x3_bytes(int M, int K);
 #define OSVOS_PACK_MAX 40
 int osvos_pack_bf16_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, int n, hipStream_t stream);
+int osvos_pack_bf16_multi_lo(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, void* const* lo_dsts, int n,
+                             hipStream_t stream);
 int osvos_pack_x3_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, int n, hipStream_t stream);
 int osvos_pack_x3_multi_fmt(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, const int* halfs, int n,
                             hipStream_t stream);
@@ -83,7 +85,10 @@ int osvos_conv3x3_bf16mfma_num_tiles(void);
 // xb = 1: x is bf16 NHWC; ybf (optional): bf16 copy of y
 int osvos_conv3x3_bf16mfma_bits(const void* x, int xb, const void* wpk, const float* bias, const void* mask, int mask_bf16, const unsigned* mask_bits,
                                 float* y, void* ybf, unsigned* y_bits, void* pooled_bf16, int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile,
-                                hipStream_t stream, void* pool_code = nullptr);
+                                hipStream_t stream, void* pool_code = nullptr, int wp = 1, size_t w_lo = 0);
+// wp = 2: two-piece weights (precision 'bf16w2'): wpk is the hi plane (= the single-piece pack), the lo plane lies w_lo bytes behind it; only the
+// two-piece tiles 40-45 read such packs (osvos_conv3x3_bf16w2_tiles), and they read nothing else
+int osvos_conv3x3_bf16w2_tiles_impl(int* tiles, int max);
 int osvos_conv3x3_bf16mfma_io(const void* x, int xb, const void* wpk, const float* bias, const void* mask, int mask_bf16, float* y, void* ybf,
                               int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, hipStream_t stream);
 int osvos_conv3x3_bf16mfma_xb_tiles(int* tiles, int max);

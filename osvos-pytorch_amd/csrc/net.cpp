@@ -41,13 +41,17 @@ int last_of_stage(int si) {
 struct WbufLayout {
   size_t fwd[kNumConv], dgrad[kNumConv], bias[kNumConv];
   size_t fwd3[kNumConv], dgrad3[kNumConv];      // OSVOS_F32_X3: pre-split bf16x3 packs of the layers the f32x3 kernels take ((size_t)-1: none)
+  size_t fwd_lo[kNumConv];   // OSVOS_FLAG_BF16_W2: lo planes of the forward packs, BEHIND everything else ((size_t)-1: none)
   size_t wd[4], bd[4], wf, bf, f1[4], f16[4];
   size_t weff[4];            // generic head only: Weff_i[16][k*k] (head_generic.hip)
   size_t wup[4];             // generic head only: copy of upscale[i].weight [16][16][k][k] (the backward forms fuse / upscale gradients from it)
   size_t total;
 };
 
-WbufLayout wbuf_layout(int dtype) {
+// dtype: with OSVOS_FLAG_BF16_W2 the layout is the single-piece one plus the 17 forward lo planes appended in layer order (trunk 0-12, side_prep
+// 13-16): every other offset is unchanged, so the hi planes ARE the bf16 packs and a backward needs no flag to find its packs
+WbufLayout wbuf_layout(int dtype_) {
+  const int dtype = dtype_ & 0xff;
   WbufLayout L;
   ConvDesc d[kNumConv];
   conv_table(d);
@@ -69,6 +73,7 @@ WbufLayout wbuf_layout(int dtype) {
   for (int i = 0; i < 4; ++i) { const int k = 4 << i; L.f1[i] = take(sizeof(float) * k * k); L.f16[i] = take(sizeof(float) * k * k); }
   for (int i = 0; i < 4; ++i) { const int k = 4 << i; L.weff[i] = take(sizeof(float) * 16 * k * k); }
   for (int i = 0; i < 4; ++i) { const int k = 4 << i; L.wup[i] = take(sizeof(float) * 256 * k * k); }
+  for (int l = 0; l < kNumConv; ++l) L.fwd_lo[l] = (dtype_ & OSVOS_FLAG_BF16_W2) ? take(osvos_wpack_bytes(d[l].cout, d[l].cin_s, dtype)) : (size_t)-1;
   L.total = off;
   return L;
 }
@@ -241,10 +246,11 @@ inline bool use_presplit() {
 // (x_b: bf16 copy of x, preferred when present; y_b: where the bf16 copy of y goes, NULL = none)
 // (mask_b: bf16 mask, takes precedence over the fp32 `mask`; y may be NULL in the bf16 modes when y_b is given)
 // (epi: fused pooling epilogues, f32x3 only -- fuse_pool() says when the caller may ask for them)
+// (w_lo: precision 'bf16w2' -- the byte distance from the hi plane wpk to the lo plane of a two-piece forward pack; 0 = single-piece pack)
 inline int conv_main(const void* x, const void* x_b, const void* wpk, const float* bias, const void* mask, const void* mask_b, void* y, void* y_b,
                      int N, int h, int w, int cin, int cout, int y_cs, int relu, int dtype, void* part, hipStream_t stream, const void* wpk3 = nullptr,
                      const ConvEpi* epi = nullptr, const void* mask_bits = nullptr, void* y_bits = nullptr, void* pooled_b = nullptr, void* sk_ws = nullptr,
-                     void* pool_code = nullptr) {
+                     void* pool_code = nullptr, size_t w_lo = 0) {
   if (dtype == OSVOS_F32_X3 && osvos_conv3x3_f32x3_applicable(cin, cout, y_cs)) {    // three-way bf16 split on the bf16 matrix pipe
     ConvEpi e2;
     if (epi != nullptr) e2 = *epi;
@@ -260,7 +266,7 @@ inline int conv_main(const void* x, const void* x_b, const void* wpk, const floa
     return osvos_conv3x3_f32_ws((const float*)x, (const float*)wpk, bias, (const float*)mask, (float*)y, N, h, w, cin, cout, y_cs,
                                 relu, -1, part, stream);
   return osvos_conv3x3_bf16mfma_bits(x_b ? x_b : x, x_b ? 1 : 0, wpk, bias, mask_b ? mask_b : mask, mask_b ? 1 : 0, (const unsigned*)mask_bits, (float*)y, y_b,
-                                     (unsigned*)y_bits, pooled_b, N, h, w, cin, cout, y_cs, relu, -1, stream, pooled_b ? pool_code : nullptr);
+                                     (unsigned*)y_bits, pooled_b, N, h, w, cin, cout, y_cs, relu, -1, stream, pooled_b ? pool_code : nullptr, w_lo ? 2 : 1, w_lo);
 }
 
 // f32x3 and the bf16-store mode: the forward max-pool of a stage boundary runs as an epilogue of the stage's last convolution (epi.h).
@@ -329,7 +335,14 @@ int osvos_head_grads_finalize(const double* const* part, const int* nblk, const 
 
 extern "C" {
 
-size_t osvos_net_wbuf_bytes(int dtype) { return wbuf_layout(dtype & 0xff).total; }
+// OSVOS_FLAG_BF16_W2 is defined for dtype OSVOS_F32_BF16MFMA only (osvos_hip.h)
+static bool w2_flag_ok(int dtype_, const char* what) {
+  if (!(dtype_ & OSVOS_FLAG_BF16_W2) || (dtype_ & 0xff) == OSVOS_F32_BF16MFMA) return true;
+  osvos_set_error("%s: OSVOS_FLAG_BF16_W2 needs dtype OSVOS_F32_BF16MFMA (got dtype %d)", what, dtype_ & 0xff);
+  return false;
+}
+
+size_t osvos_net_wbuf_bytes(int dtype) { return w2_flag_ok(dtype, "net_wbuf_bytes") ? wbuf_layout(dtype).total : 0; }
 size_t osvos_net_ws_bytes(int N, int H, int W, int dtype) { return ws_layout(N, H, W, dtype & 0xff).total; }
 size_t osvos_net_ws_bytes_infer(int N, int H, int W, int dtype) { return ws_layout(N, H, W, dtype & 0xff).fwd_total; }
 
@@ -361,8 +374,9 @@ int osvos_net_pack(const float* const* params, void* wbuf, int dtype_, int with_
   const bool generic = (dtype_ & OSVOS_FLAG_GENERIC_DECONV) != 0;
   OSVOS_ARG_CHECK(params && wbuf, "net_pack: null pointer");
   OSVOS_ARG_CHECK(osvos_dtype_built(dtype), "net_pack: dtype %d not built", dtype);
+  if (!w2_flag_ok(dtype_, "net_pack")) return -1;
   for (int i = 0; i < OSVOS_NPARAMS; ++i) OSVOS_ARG_CHECK(params[i] != nullptr, "net_pack: params[%d] is null", i);
-  WbufLayout L = wbuf_layout(dtype);
+  WbufLayout L = wbuf_layout(dtype_);
   ConvDesc d[kNumConv];
   conv_table(d);
   const float* srcs[64];
@@ -373,6 +387,7 @@ int osvos_net_pack(const float* const* params, void* wbuf, int dtype_, int with_
   // the input-gradient kernel (layer 0's data-gradient pack); all pre-split packs are formed by ONE launch
   const bool x3ps = dtype == OSVOS_F32_X3 && use_presplit();
   const float* xw[OSVOS_PACK_MAX]; void* xd[OSVOS_PACK_MAX]; int xco[OSVOS_PACK_MAX], xci[OSVOS_PACK_MAX], xdg[OSVOS_PACK_MAX], xhalf[OSVOS_PACK_MAX];
+  void* xlo[OSVOS_PACK_MAX];      // precision 'bf16w2': lo planes of the forward packs (NULL: single-piece entry)
   int nx = 0;
   // precision 'fp32h2': forward and / or data-gradient packs in the FP16-pair format (h2split.h) -- same buffers, other contents
   const int half_fwd = (dtype_ & OSVOS_FLAG_X3_HALF_PIECES) ? 1 : 0, half_bwd = (dtype_ & OSVOS_FLAG_X3_HALF_PIECES_BWD) ? 1 : 0;
@@ -381,8 +396,9 @@ int osvos_net_pack(const float* const* params, void* wbuf, int dtype_, int with_
   for (int l = 0; l < kNumConv; ++l) {
     int rc;
     if (b16) {
-      xw[nx] = params[d[l].w_param]; xd[nx] = at(wbuf, L.fwd[l]); xco[nx] = d[l].cout; xci[nx] = d[l].cin; xdg[nx] = 0; ++nx;
-      if (with_dgrad) { xw[nx] = params[d[l].w_param]; xd[nx] = at(wbuf, L.dgrad[l]); xco[nx] = d[l].cout; xci[nx] = d[l].cin; xdg[nx] = 1; ++nx; }
+      xw[nx] = params[d[l].w_param]; xd[nx] = at(wbuf, L.fwd[l]); xco[nx] = d[l].cout; xci[nx] = d[l].cin; xdg[nx] = 0;
+      xlo[nx] = L.fwd_lo[l] != (size_t)-1 ? at(wbuf, L.fwd_lo[l]) : nullptr; ++nx;
+      if (with_dgrad) { xw[nx] = params[d[l].w_param]; xd[nx] = at(wbuf, L.dgrad[l]); xco[nx] = d[l].cout; xci[nx] = d[l].cin; xdg[nx] = 1; xlo[nx] = nullptr; ++nx; }
       srcs[ns] = params[d[l].b_param]; dsts[ns] = L.bias[l]; counts[ns] = d[l].cout; ++ns;
       continue;
     }
@@ -394,7 +410,7 @@ int osvos_net_pack(const float* const* params, void* wbuf, int dtype_, int with_
     srcs[ns] = params[d[l].b_param]; dsts[ns] = L.bias[l]; counts[ns] = d[l].cout; ++ns;
   }
   if (nx > 0) {
-    const int rc = b16 ? osvos_pack_bf16_multi(xw, xd, xco, xci, xdg, nx, stream) : osvos_pack_x3_multi_fmt(xw, xd, xco, xci, xdg, xhalf, nx, stream);
+    const int rc = b16 ? osvos_pack_bf16_multi_lo(xw, xd, xco, xci, xdg, xlo, nx, stream) : osvos_pack_x3_multi_fmt(xw, xd, xco, xci, xdg, xhalf, nx, stream);
     if (rc) return rc;
   }
 
@@ -432,7 +448,10 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
   OSVOS_ARG_CHECK(osvos_dtype_built(dtype), "net_forward: dtype %d not built", dtype);
   OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0, "net_forward: bad shape %dx%dx%d", N, H, W);
   for (int i = 0; i < 5; ++i) OSVOS_ARG_CHECK(outs[i] != nullptr, "net_forward: outs[%d] is null", i);
-  const WbufLayout P = wbuf_layout(dtype);
+  if (!w2_flag_ok(dtype_, "net_forward")) return -1;
+  // precision 'bf16w2': all 17 forward convolutions read two-piece packs (osvos_net_pack with the same flag); w_lo(l) = hi -> lo plane distance
+  const WbufLayout P = wbuf_layout(dtype_);
+  auto w_lo = [&](int l) -> size_t { return P.fwd_lo[l] != (size_t)-1 ? P.fwd_lo[l] - P.fwd[l] : 0; };
   const WsLayout L = ws_layout(N, H, W, dtype);
   ConvDesc d[kNumConv];
   conv_table(d);
@@ -475,7 +494,7 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
                        f32(L.act[l]), sh(L.act_b[l]), N, h, w, d[l].cin_s, d[l].cout, d[l].cout, 1, dtype, at(ws, L.conv_part), stream,
                        P.fwd3[l] != (size_t)-1 ? at(wbuf, P.fwd3[l]) : nullptr, (pool_here && !store) ? &epi : nullptr, nullptr,
                        (L.bits[l] != (size_t)-1 && !infer) ? at(ws, L.bits[l]) : nullptr, (pool_here && store) ? at(ws, L.pooled_b[si + 1]) : nullptr, sk_ws,
-                       (pool_here && store && L.pool_code[si + 1] != (size_t)-1 && !infer) ? at(ws, L.pool_code[si + 1]) : nullptr);
+                       (pool_here && store && L.pool_code[si + 1] != (size_t)-1 && !infer) ? at(ws, L.pool_code[si + 1]) : nullptr, w_lo(l));
       }
       if (rc) return rc;
       cur = at(ws, L.act[l]);
@@ -497,7 +516,7 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
         ProfScope ps(OSVOS_PROF_OTHER, conv_flops(N, h, w, d[sl].cin, 16), aux);
         rc = conv_main(cur, cur_b, at(wbuf, P.fwd[sl]), reinterpret_cast<const float*>(at(wbuf, P.bias[sl])), nullptr, nullptr,
                        at(ws, L.prep[i]), nullptr, N, h, w, d[sl].cin_s, 16, 16, 0, dtype, L.side_part[i] != (size_t)-1 ? at(ws, L.side_part[i]) : nullptr, aux,
-                       P.fwd3[sl] != (size_t)-1 ? at(wbuf, P.fwd3[sl]) : nullptr);
+                       P.fwd3[sl] != (size_t)-1 ? at(wbuf, P.fwd3[sl]) : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, w_lo(sl));
       }
       if (rc) return rc;
       float* sc = reinterpret_cast<float*>(at(ws, L.score[i]));
@@ -568,6 +587,7 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
   const bool three = aux2 != aux;
   OSVOS_ARG_CHECK(wbuf && ws && douts && grads, "net_backward: null pointer");
   OSVOS_ARG_CHECK(osvos_dtype_built(dtype), "net_backward: dtype %d not built", dtype);
+  if (!w2_flag_ok(dtype_, "net_backward")) return -1;      // (accepted and ignored: the backward of 'bf16w2' is that of 'bf16', on the same packs)
   const WbufLayout P = wbuf_layout(dtype);
   const WsLayout L = ws_layout(N, H, W, dtype);
   ConvDesc d[kNumConv];

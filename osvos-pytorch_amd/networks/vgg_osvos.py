@@ -82,6 +82,8 @@ class OSVOS(nn.Module):
         'fp32x3b2' / 'fp32x3h2': the forward of 'fp32x3' bit for bit, the BACKWARD convolutions on two bf16 pieces / on two FP16 pieces under block
         exponents (22-23-bit operands) -- three products, every parity number of 'fp32x3' unchanged, 1.2-1.3x its step rate.  'fp32h2': FP16 pairs in
         both passes (activations closer to float64 than 'fp32x3''s; see DESIGN.md 3.1a for what that does and does not buy in training).
+        'bf16w2': the 'bf16' mode with TWO-PIECE weights in every forward convolution (w = w_hi + w_lo, two bf16 MFMA products per product;
+        DESIGN.md 3.3) -- the backward is 'bf16''s.  Switching format re-packs; a backward of a graph recorded under another pack format raises.
         Not part of the reference's API."""
         self._runtime.set_precision(name)
         return self

@@ -117,6 +117,30 @@ def conv3x3_bf16act_fused(x, wpk, bias, cout, relu=False, mask_bits=None, want_b
     return y, bits, pooled, code
 
 
+def conv3x3_bf16w2_fused(x, wpk_w2, bias, cout, relu=False, want_bits=False, want_pool=False, tile=-1, want_f32=False):
+    """Precision 'bf16w2''s forward convolution (osvos_conv3x3_bf16w2_fused): x torch.bfloat16 [N,H,W,Cin], or float32 (rounded to bf16 while
+    staged: conv1_1's input), wpk_w2 = pack_fwd(w, F32_BF16MFMA | BF16_W2); returns (y bf16, y_bits | None, pooled bf16 | None, pool_code | None),
+    with want_f32 (y fp32 before its bf16 rounding, y bf16, bits, pooled, code)."""
+    _need_cuda(x, wpk_w2, bias)
+    assert x.dtype in (torch.bfloat16, torch.float32)
+    n, h, w, cin = x.shape
+    y = torch.zeros((n, h, w, cout), device=x.device, dtype=torch.bfloat16)
+    bits = torch.zeros((n, h, w, cout // 32), device=x.device, dtype=torch.int32) if want_bits else None
+    pooled = torch.zeros((n, (h + 1) // 2, (w + 1) // 2, cout), device=x.device, dtype=torch.bfloat16) if want_pool else None
+    code = torch.zeros((n, (h + 1) // 2, (w + 1) // 2, cout), device=x.device, dtype=torch.uint8) if want_pool else None
+    yf = torch.zeros((n, h, w, cout), device=x.device, dtype=torch.float32) if want_f32 else None
+    check(lib().osvos_conv3x3_bf16w2_fused(_p(x), _p(wpk_w2), _p(bias), None, _p(y), _p(bits), _p(pooled), _p(code), n, h, w, cin, cout, int(relu),
+                                           int(x.dtype == torch.float32), _p(yf), tile, _stream()), "conv3x3_bf16w2_fused")
+    return (yf, y, bits, pooled, code) if want_f32 else (y, bits, pooled, code)
+
+
+def conv3x3_bf16w2_tiles():
+    import ctypes
+    buf = (ctypes.c_int * 64)()
+    n = lib().osvos_conv3x3_bf16w2_tiles(buf, 64)
+    return [buf[i] for i in range(n)]
+
+
 def conv3x3_wgrad_bf16act(x, dy, cin, cout, want_bias=True):
     """x, dy torch.bfloat16 NHWC (wide layers) -> (dW fp32 [cout,cin,3,3], db fp32)"""
     _need_cuda(x, dy)
