@@ -50,7 +50,7 @@ int osvos_pack_conv3x3_fwd(const float* w, void* wpk, int Cout, int Cin, int dty
     void* dsts[1] = {wpk};
     void* los[1] = {reinterpret_cast<char*>(wpk) + osvos_wpack_bytes(Cout, Cin, OSVOS_F32_BF16MFMA)};
     const int co[1] = {Cout}, ci[1] = {Cin}, dg[1] = {0};
-    return osvos_pack_bf16_multi_lo(ws, dsts, co, ci, dg, los, 1, (hipStream_t)stream);
+    return osvos_pack_bf16_multi(ws, dsts, co, ci, dg, los, 1, (hipStream_t)stream);
   }
   NEED_F32(dtype, "pack_conv3x3_fwd");
   if (dtype == OSVOS_F32_BF16MFMA) return osvos_pack_fwd_bf16(w, wpk, Cout, Cin, (hipStream_t)stream);
@@ -62,17 +62,23 @@ int osvos_pack_conv3x3_dgrad(const float* w, void* wpk, int Cout, int Cin, int d
   return osvos_pack_dgrad_f32(w, (float*)wpk, Cout, Cin, (hipStream_t)stream);
 }
 
+// what every op-level convolution entry passes: fp32 tensors, one pack in `wpk` (the entries below add what they have beyond that)
+static ConvCall conv_call(const void* x, const void* wpk, const float* bias, const void* mask, void* y, int N, int H, int W, int Cin, int Cout, int y_cs,
+                          int relu, int tile, void* stream) {
+  ConvCall c;
+  c.x = x; c.wpk = wpk; c.bias = bias; c.mask = mask; c.y = (float*)y;
+  c.N = N; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.y_cs = y_cs; c.relu = relu; c.tile = tile;
+  c.stream = (hipStream_t)stream;
+  return c;
+}
+
 int osvos_conv3x3(const void* x, const void* wpk, const float* bias, const void* mask, void* y,
                   int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int dtype, int tile, void* stream) {
   NEED_F32(dtype, "conv3x3");
-  if (dtype == OSVOS_F32_BF16MFMA)
-    return osvos_conv3x3_bf16mfma((const float*)x, wpk, bias, (const float*)mask, (float*)y, N, H, W, Cin, Cout, y_cs, relu, tile,
-                                  (hipStream_t)stream);
-  if (dtype == OSVOS_F32_X3 && tile < 0 && osvos_conv3x3_f32x3_applicable(Cin, Cout, y_cs))
-    return osvos_conv3x3_f32x3((const float*)x, (const float*)wpk, bias, (const float*)mask, (float*)y, N, H, W, Cin, Cout, y_cs, relu, -1, 0,
-                               nullptr, (hipStream_t)stream);
-  return osvos_conv3x3_f32((const float*)x, (const float*)wpk, bias, (const float*)mask, (float*)y,
-                           N, H, W, Cin, Cout, y_cs, relu, tile, (hipStream_t)stream);
+  const ConvCall c = conv_call(x, wpk, bias, mask, y, N, H, W, Cin, Cout, y_cs, relu, tile, stream);
+  if (dtype == OSVOS_F32_BF16MFMA) return osvos_conv3x3_bf16mfma(c);
+  if (dtype == OSVOS_F32_X3 && tile < 0 && osvos_conv3x3_f32x3_applicable(Cin, Cout, y_cs)) return osvos_conv3x3_f32x3(c);
+  return osvos_conv3x3_f32(c);
 }
 
 int osvos_conv3x3_f32x3_tiles(void) { return osvos_conv3x3_f32x3_num_tiles(); }
@@ -83,8 +89,9 @@ int osvos_pack_conv3x3_x3(const float* w, void* wpk3, int Cout, int Cin, int dgr
 int osvos_conv3x3_x3(const void* x, const void* wpk3, const float* bias, const void* mask, void* y,
                      int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, void* stream) {
   OSVOS_ARG_CHECK(wpk3 != nullptr, "conv3x3_x3: null pack");
-  return osvos_conv3x3_f32x3_ps((const float*)x, nullptr, wpk3, bias, (const float*)mask, (float*)y, N, H, W, Cin, Cout, y_cs, relu,
-                                tile >= 200 ? tile - 200 : tile, 0, nullptr, (hipStream_t)stream);
+  ConvCall c = conv_call(x, nullptr, bias, mask, y, N, H, W, Cin, Cout, y_cs, relu, tile >= 200 ? tile - 200 : tile, stream);
+  c.wpk3 = wpk3;
+  return osvos_conv3x3_f32x3(c);
 }
 
 // stream-K form of osvos_conv3x3_x3 (conv3x3_f32x3.hip): sk_ws of osvos_conv3x3_x3_streamk_ws_bytes() with its first
@@ -94,25 +101,23 @@ size_t osvos_conv3x3_x3_streamk_ticket_bytes(void) { return osvos_conv3x3_f32x3_
 int osvos_conv3x3_x3_streamk(const void* x, const void* wpk3, const float* bias, const void* mask, void* y, void* pooled, int N, int H, int W, int Cin,
                              int Cout, int y_cs, int relu, int tile, int grid, void* sk_ws, void* stream) {
   OSVOS_ARG_CHECK(wpk3 != nullptr && sk_ws != nullptr && grid >= 0, "conv3x3_x3_streamk: null pack / workspace");
-  ConvEpi epi;
-  epi.sk_ws = sk_ws;
-  epi.sk_grid = grid;
-  epi.pooled = reinterpret_cast<float*>(pooled);
-  return osvos_conv3x3_f32x3_epi((const float*)x, nullptr, wpk3, bias, (const float*)mask, (float*)y, N, H, W, Cin, Cout, y_cs, relu,
-                                 tile >= 200 ? tile - 200 : tile, 1, nullptr, &epi, (hipStream_t)stream);
+  ConvCall c = conv_call(x, nullptr, bias, mask, y, N, H, W, Cin, Cout, y_cs, relu, tile >= 200 ? tile - 200 : tile, stream);
+  c.wpk3 = wpk3; c.ksplit = 1; c.sk_ws = sk_ws; c.sk_grid = grid; c.pooled = reinterpret_cast<float*>(pooled);
+  return osvos_conv3x3_f32x3(c);
 }
 
 // bf16-MFMA convolution with explicit operand / result formats: x fp32 (x_is_bf16 = 0) or bf16 NHWC; y fp32 and,
 // when y_bf16 != NULL, a bf16 copy of y with the same channel stride (the operand of the next convolution)
 int osvos_conv3x3_bf16io(const void* x, int x_is_bf16, const void* wpk, const float* bias, const void* mask, int mask_is_bf16, float* y,
                          void* y_bf16, int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, void* stream) {
-  return osvos_conv3x3_bf16mfma_io(x, x_is_bf16 ? 1 : 0, wpk, bias, mask, mask_is_bf16, y, y_bf16, N, H, W, Cin, Cout, y_cs, relu, tile,
-                                   (hipStream_t)stream);
+  ConvCall c = conv_call(x, wpk, bias, mask, y, N, H, W, Cin, Cout, y_cs, relu, tile, stream);
+  c.x_bf16 = x_is_bf16 ? 1 : 0; c.mask_bf16 = mask_is_bf16; c.y_bf16 = y_bf16;
+  return osvos_conv3x3_bf16mfma(c);
 }
 // weight gradient of the wide layers (Cin_s, Cout multiples of 64) from bf16 x AND dy; dw/db fp32 as osvos_conv3x3_wgrad
 int osvos_conv3x3_wgrad_bf16act(const void* x_bf16, const void* dy_bf16, void* ws, float* dw, float* db, int N, int H, int W, int Cin, int Cin_s,
                                 int Cout, int Cout_s, int accumulate, void* stream) {
-  return osvos_conv3x3_wgrad_bf16mfma_io(x_bf16, dy_bf16, 1, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s, accumulate, (hipStream_t)stream);
+  return osvos_conv3x3_wgrad_bf16mfma(x_bf16, dy_bf16, 1, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s, accumulate, (hipStream_t)stream);
 }
 int osvos_maxpool2x2_bf16act(const void* x_bf16, void* y_bf16, int N, int H, int W, int C, void* stream) {
   return osvos_maxpool2x2_bf16(x_bf16, y_bf16, N, H, W, C, (hipStream_t)stream);
@@ -131,8 +136,10 @@ int osvos_maxpool2x2_bwd_bf16act_code(const void* code, const void* dy_bf16, con
 int osvos_conv3x3_bf16act_fused(const void* x_bf16, const void* wpk, const float* bias, const void* mask_bits, void* y_bf16, void* y_bits,
                                 void* pooled_bf16, void* pool_code, int N, int H, int W, int Cin, int Cout, int relu, int tile, void* stream) {
   OSVOS_ARG_CHECK(y_bf16 != nullptr, "conv3x3_bf16act_fused: y_bf16 is required");
-  return osvos_conv3x3_bf16mfma_bits(x_bf16, 1, wpk, bias, nullptr, 0, reinterpret_cast<const unsigned*>(mask_bits), nullptr, y_bf16,
-                                     reinterpret_cast<unsigned*>(y_bits), pooled_bf16, N, H, W, Cin, Cout, Cout, relu, tile, (hipStream_t)stream, pool_code);
+  ConvCall c = conv_call(x_bf16, wpk, bias, nullptr, nullptr, N, H, W, Cin, Cout, Cout, relu, tile, stream);
+  c.x_bf16 = 1; c.mask_bits = reinterpret_cast<const unsigned*>(mask_bits);
+  c.y_bf16 = y_bf16; c.y_bits = reinterpret_cast<unsigned*>(y_bits); c.pooled_bf16 = pooled_bf16; c.pool_code = pool_code;
+  return osvos_conv3x3_bf16mfma(c);
 }
 int osvos_conv3x3_bf16io_tiles(int* tiles, int max) { return osvos_conv3x3_bf16mfma_xb_tiles(tiles, max); }
 int osvos_conv3x3_bf16w2_fused(const void* x, const void* wpk_w2, const float* bias, const void* mask_bits, void* y_bf16, void* y_bits,
@@ -141,9 +148,10 @@ int osvos_conv3x3_bf16w2_fused(const void* x, const void* wpk_w2, const float* b
   OSVOS_ARG_CHECK(y_bf16 != nullptr || (y_f32 != nullptr && pooled_bf16 == nullptr), "conv3x3_bf16w2_fused: y_bf16 (or y_f32 without a pool) is required");
   OSVOS_ARG_CHECK(mask_bits == nullptr, "conv3x3_bf16w2_fused: forward only (the data gradients of 'bf16w2' are single-piece)");
   OSVOS_ARG_CHECK(Cout > 0 && Cin > 0, "conv3x3_bf16w2_fused: bad shape");
-  return osvos_conv3x3_bf16mfma_bits(x, x_is_f32 ? 0 : 1, wpk_w2, bias, nullptr, 0, nullptr, y_f32, y_bf16, reinterpret_cast<unsigned*>(y_bits), pooled_bf16,
-                                     N, H, W, Cin, Cout, Cout, relu, tile, (hipStream_t)stream, pool_code, 2,
-                                     osvos_wpack_bytes(Cout, Cin, OSVOS_F32_BF16MFMA));
+  ConvCall c = conv_call(x, wpk_w2, bias, nullptr, y_f32, N, H, W, Cin, Cout, Cout, relu, tile, stream);
+  c.x_bf16 = x_is_f32 ? 0 : 1; c.w_pieces = 2; c.w_lo = osvos_wpack_bytes(Cout, Cin, OSVOS_F32_BF16MFMA);
+  c.y_bf16 = y_bf16; c.y_bits = reinterpret_cast<unsigned*>(y_bits); c.pooled_bf16 = pooled_bf16; c.pool_code = pool_code;
+  return osvos_conv3x3_bf16mfma(c);
 }
 int osvos_conv3x3_bf16w2_tiles(int* tiles, int max) { return osvos_conv3x3_bf16w2_tiles_impl(tiles, max); }
 
@@ -156,11 +164,9 @@ int osvos_conv3x3_splitk(const void* x, const void* wpk, const float* bias, cons
                          void* part_ws, void* stream) {
   OSVOS_ARG_CHECK(dtype == OSVOS_F32 || dtype == OSVOS_F32_X3, "conv3x3_splitk: fp32 only (dtype %d)", dtype);
   OSVOS_ARG_CHECK(part_ws != nullptr && ksplit >= 0 && ksplit <= 8, "conv3x3_splitk: bad ksplit / workspace");
-  osvos_conv3x3_force_ksplit(ksplit);
-  const int rc = osvos_conv3x3_f32_ws((const float*)x, (const float*)wpk, bias, (const float*)mask, (float*)y, N, H, W, Cin, Cout,
-                                      y_cs, relu, (dtype == OSVOS_F32_X3 && tile < 0) ? -2 : tile, part_ws, (hipStream_t)stream);
-  osvos_conv3x3_force_ksplit(0);
-  return rc;
+  ConvCall c = conv_call(x, wpk, bias, mask, y, N, H, W, Cin, Cout, y_cs, relu, (dtype == OSVOS_F32_X3 && tile < 0) ? -2 : tile, stream);
+  c.ksplit = ksplit; c.part_ws = part_ws;
+  return osvos_conv3x3_f32(c);
 }
 
 size_t osvos_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int dtype) {
@@ -175,8 +181,7 @@ int osvos_conv3x3_wgrad(const void* x, const void* dy, void* ws, float* dw, floa
   // the wide trunk layers go through the bf16 MFMA kernel; conv1_1 (Cin 3) and side_prep (Cout 16) keep
   // their exact-fp32 skinny kernels (5 % of the weight-gradient FLOPs)
   if (dtype == OSVOS_F32_BF16MFMA && Cin == Cin_s && Cout % 64 == 0 && osvos_wgrad_bf16_applicable(Cin_s, Cout))
-    return osvos_conv3x3_wgrad_bf16mfma((const float*)x, (const float*)dy, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s,
-                                        accumulate, (hipStream_t)stream);
+    return osvos_conv3x3_wgrad_bf16mfma(x, dy, 0, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s, accumulate, (hipStream_t)stream);
   // f32x3 (dtype OSVOS_F32_X3): the wide trunk layers on the bf16 matrix pipe with three-way split operands; conv1_1 and side_prep keep
   // their exact skinny kernels
   if (dtype == OSVOS_F32_X3 &&

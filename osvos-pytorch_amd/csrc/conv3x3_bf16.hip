@@ -653,7 +653,7 @@ int osvos_pack_fwd_bf16(const float* w, void* wpk, int Cout, int Cin, hipStream_
   const float* ws[1] = {w};
   void* dsts[1] = {wpk};
   const int co[1] = {Cout}, ci[1] = {Cin}, dg[1] = {0};
-  return osvos_pack_bf16_multi(ws, dsts, co, ci, dg, 1, stream);
+  return osvos_pack_bf16_multi(ws, dsts, co, ci, dg, nullptr, 1, stream);
 }
 
 int osvos_pack_dgrad_bf16(const float* w, void* wpk, int Cout, int Cin, hipStream_t stream) {
@@ -661,19 +661,11 @@ int osvos_pack_dgrad_bf16(const float* w, void* wpk, int Cout, int Cin, hipStrea
   const float* ws[1] = {w};
   void* dsts[1] = {wpk};
   const int co[1] = {Cout}, ci[1] = {Cin}, dg[1] = {1};
-  return osvos_pack_bf16_multi(ws, dsts, co, ci, dg, 1, stream);
+  return osvos_pack_bf16_multi(ws, dsts, co, ci, dg, nullptr, 1, stream);
 }
 
-// n bf16 packs (n <= OSVOS_PACK_MAX) in one launch: ws[k] OIHW fp32 [Couts[k]][Cins[k]][3][3] -> dsts[k] (osvos_pack_fwd_bf16 layout; dgrads[k] != 0:
-// osvos_pack_dgrad_bf16 layout)
-int osvos_pack_bf16_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, int n, hipStream_t stream) {
-  return osvos_pack_bf16_multi_lo(ws, dsts, Couts, Cins, dgrads, nullptr, n, stream);
-}
-
-// the same with two-piece entries: lo_dsts (NULL = none) [k] != NULL writes the lo plane of entry k there (forward packs only; the hi plane, at
-// dsts[k], is the single-piece pack byte for byte)
-int osvos_pack_bf16_multi_lo(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, void* const* lo_dsts, int n,
-                             hipStream_t stream) {
+int osvos_pack_bf16_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, void* const* lo_dsts, int n,
+                          hipStream_t stream) {
   OSVOS_ARG_CHECK(ws && dsts && Couts && Cins && dgrads && n >= 0 && n <= OSVOS_PACK_MAX, "pack_bf16_multi: bad table (n = %d)", n);
   if (n == 0) return 0;
   PackB16Table t;
@@ -710,20 +702,25 @@ extern "C" void osvos_debug_set_conv_prof(void* p) { g_conv_prof = (unsigned lon
 #define OSVOS_CONV_PROF_PTR nullptr
 #endif
 
-// x fp32 NHWC (stride Cin, multiple of 8), wpk from osvos_pack_{fwd,dgrad}_bf16 with the same Cin/Cout roles
-// xb = 0: x fp32, xb = 1: x bf16; ybf (optional) receives a bf16 copy of y
-int osvos_conv3x3_bf16mfma_io(const void* x, int xb, const void* wpk, const float* bias, const void* mask, int mask_bf16, float* y, void* ybf,
-                              int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, hipStream_t stream) {
-  return osvos_conv3x3_bf16mfma_bits(x, xb, wpk, bias, mask, mask_bf16, nullptr, y, ybf, nullptr, nullptr, N, H, W, Cin, Cout, y_cs, relu, tile, stream, nullptr);
+// the convolution on the chosen tile without its fused pool, then the pooling kernel
+static int conv_then_pool(const ConvCall& c, int tile) {
+  ConvCall cc = c;
+  cc.pooled_bf16 = nullptr; cc.pool_code = nullptr; cc.tile = tile;
+  const int rc = osvos_conv3x3_bf16mfma(cc);
+  return rc ? rc : osvos_maxpool2x2_bf16_code(c.y_bf16, c.pooled_bf16, c.pool_code, c.N, c.H, c.W, c.Cout, c.stream);
 }
 
-// mask_bits: the ReLU mask as one bit per element (maskbits.h; takes precedence over `mask`); y_bits: sign bits of the result, written beside it
-// pooled_bf16 (optional; needs ybf, ReLU, a dense result with Cout % 8 == 0): maxpool2x2 (ceil mode) of the bf16 result, written by the same launch
-// ([N][ceil(H/2)][ceil(W/2)][Cout]; the 8 x 8-pixel tile cannot hold whole windows per wave: there the pooling kernel is launched behind the convolution)
-// pool_code (optional, with pooled_bf16): [N][ceil(H/2)][ceil(W/2)][Cout] bytes for osvos_maxpool2x2_bwd_bf16_code; written whichever kernel runs
-int osvos_conv3x3_bf16mfma_bits(const void* x, int xb, const void* wpk, const float* bias, const void* mask, int mask_bf16, const unsigned* mask_bits,
-                                float* y, void* ybf, unsigned* y_bits, void* pooled_bf16, int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile,
-                                hipStream_t stream, void* pool_code, int wp, size_t w_lo) {
+int osvos_conv3x3_bf16mfma(const ConvCall& c) {
+  const void *x = c.x, *wpk = c.wpk, *mask = c.mask;
+  const float* const bias = c.bias;
+  const unsigned* const mask_bits = c.mask_bits;
+  float* const y = c.y;
+  void *ybf = c.y_bf16, *pooled_bf16 = c.pooled_bf16, *pool_code = c.pool_code;
+  unsigned* const y_bits = c.y_bits;
+  const int xb = c.x_bf16, mask_bf16 = c.mask_bf16, wp = c.w_pieces, N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cout = c.Cout, y_cs = c.y_cs, relu = c.relu;
+  const size_t w_lo = c.w_lo;
+  int tile = c.tile;
+  hipStream_t stream = c.stream;
   OSVOS_ARG_CHECK(pool_code == nullptr || pooled_bf16 != nullptr, "conv3x3 bf16: pool code bytes without a pooled result");
   OSVOS_ARG_CHECK(wp == 1 || wp == 2, "conv3x3 bf16: %d weight pieces (1 or 2)", wp);
   OSVOS_ARG_CHECK(pooled_bf16 == nullptr || (ybf != nullptr && relu && mask == nullptr && mask_bits == nullptr && Cout % 8 == 0 && y_cs == Cout),
@@ -762,9 +759,7 @@ int osvos_conv3x3_bf16mfma_bits(const void* x, int xb, const void* wpk, const fl
     tile %= 100;
     OSVOS_ARG_CHECK(is_w2_tile(tile), "conv3x3 bf16w2: tile %d is a single-piece kernel; two-piece packs need tiles %d-%d", tile, kW2First, kW2First + kNumTilesW2 - 1);
     if (a.pooled != nullptr && !(xb && tile != 45)) {      // waves without whole windows / fp32 staging: separate pooling launch, as single-piece
-      const int rc = osvos_conv3x3_bf16mfma_bits(x, xb, wpk, bias, mask, mask_bf16, mask_bits, y, ybf, y_bits, nullptr, N, H, W, Cin, Cout, y_cs, relu, tile + 100 * a.map,
-                                                 stream, nullptr, wp, w_lo);
-      return rc ? rc : osvos_maxpool2x2_bf16_code(ybf, pooled_bf16, pool_code, N, H, W, Cout, stream);
+      return conv_then_pool(c, tile + 100 * a.map);
     }
     if (xb) {
       switch (tile) {
@@ -818,18 +813,15 @@ int osvos_conv3x3_bf16mfma_bits(const void* x, int xb, const void* wpk, const fl
   if (xb && tile == 38) {      // Cin = 64: persistent, resident filter, deferred + skewed packed epilogue (conv3x3_bf16_p64.hip)
     OSVOS_ARG_CHECK(osvos_conv3x3_bf16_p64_applicable(Cin, Cout, y_cs, y != nullptr, mask != nullptr, mask_bits != nullptr, y_bits != nullptr, pooled_bf16 != nullptr, relu),
                     "conv3x3 bf16: tile 38 needs Cin = 64, bf16 in / out only, no full-tensor mask, sign bits only with ReLU (Cin %d, Cout %d)", Cin, Cout);
-    return osvos_conv3x3_bf16_p64(x, wpk, bias, mask_bits, ybf, y_bits, pooled_bf16, pool_code, N, H, W, Cout, y_cs, relu, a.map, stream);
+    return osvos_conv3x3_bf16_p64(c, a.map);
   }
   if (xb && tile >= 30 && tile <= 37) {      // LDS-DMA staged kernel (its fused pool writes the code bytes too: round 6)
     OSVOS_ARG_CHECK(osvos_conv3x3_bf16_dma_applicable(Cin, Cout, y_cs), "conv3x3 bf16: tile %d (DMA staging) needs Cin %% 16 == 0, Cout, y_cs %% 8 == 0", tile);
     OSVOS_ARG_CHECK(tile < 36 || Cin == 64, "conv3x3 bf16: tile %d (resident filter) is built for Cin = 64 (got %d)", tile, Cin);
-    return osvos_conv3x3_bf16_dma(x, wpk, bias, mask, mask_bf16, mask_bits, y, ybf, y_bits, pooled_bf16, N, H, W, Cin, Cout, y_cs, relu, tile - 30, a.map, stream, pool_code);
+    return osvos_conv3x3_bf16_dma(c, tile - 30, a.map);
   }
   if (a.pooled != nullptr && !(xb && tile != 7 && tile >= 0 && tile < kNumTilesB)) {      // a tile whose waves do not hold whole windows: separate pooling launch
-    a.pooled = nullptr;
-    const int rc = osvos_conv3x3_bf16mfma_bits(x, xb, wpk, bias, mask, mask_bf16, mask_bits, y, ybf, y_bits, nullptr, N, H, W, Cin, Cout, y_cs, relu, tile + 100 * a.map, stream,
-                                               nullptr);
-    return rc ? rc : osvos_maxpool2x2_bf16_code(ybf, pooled_bf16, pool_code, N, H, W, Cout, stream);
+    return conv_then_pool(c, tile + 100 * a.map);
   }
   if (xb) {
     switch (tile) {
@@ -878,15 +870,12 @@ int osvos_conv3x3_bf16mfma_xb_tiles(int* tiles, int max) {      // tile ids buil
   return n;
 }
 
-// x fp32 NHWC (stride Cin, multiple of 8), wpk from osvos_pack_{fwd,dgrad}_bf16 with the same Cin/Cout roles
-int osvos_conv3x3_bf16mfma(const float* x, const void* wpk, const float* bias, const float* mask, float* y,
-                           int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, hipStream_t stream) {
-  return osvos_conv3x3_bf16mfma_io(x, 0, wpk, bias, mask, 0, y, nullptr, N, H, W, Cin, Cout, y_cs, relu, tile, stream);
-}
-
 #ifdef OSVOS_CONV_PROF   // C entry points of the scratch library tools/conv_phase_probe.py builds from this file alone
 extern "C" int osvos_prof_pack_fwd_bf16(const float* w, void* wpk, int Cout, int Cin) { return osvos_pack_fwd_bf16(w, wpk, Cout, Cin, nullptr); }
 extern "C" int osvos_prof_conv3x3_bf16mfma(const float* x, const void* wpk, float* y, int N, int H, int W, int Cin, int Cout, int tile) {
-  return osvos_conv3x3_bf16mfma(x, wpk, nullptr, nullptr, y, N, H, W, Cin, Cout, Cout, 1, tile, nullptr);
+  ConvCall c;
+  c.x = x; c.wpk = wpk; c.y = y;
+  c.N = N; c.H = H; c.W = W; c.Cin = Cin; c.Cout = c.y_cs = Cout; c.relu = 1; c.tile = tile;
+  return osvos_conv3x3_bf16mfma(c);
 }
 #endif

@@ -21,6 +21,7 @@
 // ahead, crossing tile boundaries), and the next tile's first chunks are in flight while the epilogue stores drain.
 #include "common.h"
 #include "maskbits.h"
+#include "kernels.h"
 
 namespace {
 
@@ -465,20 +466,23 @@ bool osvos_conv3x3_bf16_dma_applicable(int Cin, int Cout, int y_cs) { return Cin
 // 4 / 5: variants 0 / 2 as persistent workgroups (one per CU, tiles pipelined back to back);
 // map = 1: XCD-local spatial block order
 // 6 / 7: RESIDENT-FILTER persistent forms for Cin = 64 (512 px / 256 px x 64 couts): see the head of this file
-int osvos_conv3x3_bf16_dma(const void* x, const void* wpk, const float* bias, const void* mask, int mask_bf16, const unsigned* mask_bits, float* y, void* ybf,
-                           unsigned* y_bits, void* pooled_bf16, int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int variant, int map, hipStream_t stream,
-                           void* pool_code) {
+int osvos_conv3x3_bf16_dma(const ConvCall& c, int variant, int map) {
+  const void *x = c.x, *wpk = c.wpk;
+  float* const y = c.y;
+  void* const ybf = c.y_bf16;
+  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cout = c.Cout, y_cs = c.y_cs;
+  hipStream_t stream = c.stream;
   OSVOS_ARG_CHECK(x && wpk && (y || ybf), "conv3x3 bf16 dma: null pointer");
   OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && osvos_conv3x3_bf16_dma_applicable(Cin, Cout, y_cs) && y_cs >= Cout,
                   "conv3x3 bf16 dma: needs Cin %% 16 == 0, Cout %% 8 == 0, y_cs %% 8 == 0 (got %d, %d, %d)", Cin, Cout, y_cs);
   OSVOS_ARG_CHECK((long)H * W * Cin < (1L << 29) && (long)H * W * y_cs < (1L << 29), "conv3x3 bf16 dma: image too large for 31-bit byte offsets");
   DmaArgs a;
-  a.x = reinterpret_cast<const bf16_t*>(x); a.wpk = reinterpret_cast<const uint4*>(wpk); a.bias = bias; a.mask = mask; a.mask_bf16 = mask_bf16 ? 1 : 0;
+  a.x = reinterpret_cast<const bf16_t*>(x); a.wpk = reinterpret_cast<const uint4*>(wpk); a.bias = c.bias; a.mask = c.mask; a.mask_bf16 = c.mask_bf16 ? 1 : 0;
   a.y = y; a.ybf = reinterpret_cast<bf16_t*>(ybf);
-  a.mask_bits = mask_bits; a.y_bits = y_bits; a.pooled = reinterpret_cast<bf16_t*>(pooled_bf16);
-  a.pool_code = reinterpret_cast<unsigned char*>(pool_code);
+  a.mask_bits = c.mask_bits; a.y_bits = c.y_bits; a.pooled = reinterpret_cast<bf16_t*>(c.pooled_bf16);
+  a.pool_code = reinterpret_cast<unsigned char*>(c.pool_code);
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.CinP = (Cin + 31) / 32 * 32; a.Cout = Cout; a.CoutP = osvos_cout_pad(Cout); a.y_cs = y_cs;
-  a.relu = relu; a.map = map ? 1 : 0;
+  a.relu = c.relu; a.map = map ? 1 : 0;
   switch (variant) {
     case 0: return launch<4, 2>(a, 0, stream);
     case 1: return launch<2, 2>(a, 0, stream);

@@ -590,8 +590,13 @@ bool osvos_conv3x3_bf16_p64_applicable(int Cin, int Cout, int y_cs, bool has_y_f
   return true;
 }
 
-int osvos_conv3x3_bf16_p64(const void* x, const void* wpk, const float* bias, const unsigned* mask_bits, void* ybf, unsigned* y_bits, void* pooled_bf16,
-                           void* pool_code, int N, int H, int W, int Cout, int y_cs, int relu, int map, hipStream_t stream) {
+int osvos_conv3x3_bf16_p64(const ConvCall& c, int map) {
+  const void *x = c.x, *wpk = c.wpk;
+  const unsigned* const mask_bits = c.mask_bits;
+  void *ybf = c.y_bf16, *pooled_bf16 = c.pooled_bf16, *pool_code = c.pool_code;
+  unsigned* const y_bits = c.y_bits;
+  const int N = c.N, H = c.H, W = c.W, Cout = c.Cout, y_cs = c.y_cs, relu = c.relu;
+  hipStream_t stream = c.stream;
   OSVOS_ARG_CHECK(x && wpk && ybf, "conv3x3 bf16 p64: null pointer");
   OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && y_cs >= Cout, "conv3x3 bf16 p64: bad shape");
   OSVOS_ARG_CHECK(osvos_conv3x3_bf16_p64_applicable(64, Cout, y_cs, false, false, mask_bits != nullptr, y_bits != nullptr, pooled_bf16 != nullptr, relu),
@@ -599,7 +604,7 @@ int osvos_conv3x3_bf16_p64(const void* x, const void* wpk, const float* bias, co
   OSVOS_ARG_CHECK(pool_code == nullptr || pooled_bf16 != nullptr, "conv3x3 bf16 p64: pool code bytes without a pooled result");
   OSVOS_ARG_CHECK((long)H * W * 64 < (1L << 29) && (long)H * W * y_cs < (1L << 29), "conv3x3 bf16 p64: image too large for 31-bit byte offsets");
   P64Args a;
-  a.x = reinterpret_cast<const bf16_t*>(x); a.wpk = reinterpret_cast<const uint4*>(wpk); a.bias = bias; a.ybf = reinterpret_cast<bf16_t*>(ybf);
+  a.x = reinterpret_cast<const bf16_t*>(x); a.wpk = reinterpret_cast<const uint4*>(wpk); a.bias = c.bias; a.ybf = reinterpret_cast<bf16_t*>(ybf);
   a.N = N; a.H = H; a.W = W; a.Cout = Cout; a.CoutP = osvos_cout_pad(Cout); a.y_cs = y_cs;
   OSVOS_ENV_INT(band, "OSVOS_P64_BAND", 1);      // 0: XCD-local requests keep the interleaved map 1
   a.relu = relu; a.map = map ? (band ? 2 : 1) : 0;

@@ -408,7 +408,6 @@ size_t osvos_conv3x3_splitk_ws_bytes_f32(int N, int H, int W, int Cout) {
   return align_up((size_t)8 * N * H * W * Cout * sizeof(float), 256);      // up to 8 K parts
 }
 
-// part_ws: NULL (never split) or a buffer of osvos_conv3x3_splitk_ws_bytes_f32() for the split-K partial sums
 // phase-counter hook of tools/conv_phase_probe.py: exists only in probe builds (make EXTRA=-DOSVOS_CONV_PROF); the shipped library has no
 // process-global device pointer behind its re-entrant ABI
 #ifdef OSVOS_CONV_PROF
@@ -418,16 +417,13 @@ extern "C" void osvos_debug_set_conv_prof_f32(void* p) { g_conv_prof_f32 = (unsi
 #else
 #define OSVOS_CONV_PROF_PTR nullptr
 #endif
-static thread_local int g_force_ksplit = 0;      // tests / tuning: osvos_conv3x3_splitk(..., ksplit > 0, ...)
-void osvos_conv3x3_force_ksplit(int k) { g_force_ksplit = k; }
-
-int osvos_conv3x3_f32(const float* x, const float* wpk, const float* bias, const float* mask, float* y,
-                      int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, hipStream_t stream) {
-  return osvos_conv3x3_f32_ws(x, wpk, bias, mask, y, N, H, W, Cin, Cout, y_cs, relu, tile, nullptr, stream);
-}
-
-int osvos_conv3x3_f32_ws(const float* x, const float* wpk, const float* bias, const float* mask, float* y,
-                         int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, void* part_ws, hipStream_t stream) {
+int osvos_conv3x3_f32(const ConvCall& c) {
+  const float *x = (const float*)c.x, *wpk = (const float*)c.wpk, *bias = c.bias, *mask = (const float*)c.mask;
+  float* const y = c.y;
+  void* const part_ws = c.part_ws;
+  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cout = c.Cout, y_cs = c.y_cs, relu = c.relu;
+  int tile = c.tile;
+  hipStream_t stream = c.stream;
   OSVOS_ARG_CHECK(x && wpk && y, "conv3x3: null pointer");
   OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3: bad shape");
   OSVOS_ARG_CHECK(Cin % 8 == 0, "conv3x3 f32: Cin (%d) must be a multiple of 8 (pad the input)", Cin);
@@ -436,8 +432,11 @@ int osvos_conv3x3_f32_ws(const float* x, const float* wpk, const float* bias, co
   // f32x3: the same fp32 problem on the bf16 matrix pipe with three-way split operands (conv3x3_f32x3.hip).  Tile ids
   // 200.. force it (tests, tuning); tile -2 = "automatic, in the f32x3 arithmetic where it applies" (what the callers that were handed
   // dtype OSVOS_F32_X3 pass; round 4: this replaces a process-wide mutable mode -- the arithmetic is a per-call argument of the ABI).
-  if ((tile >= 200 || (tile == -2 && osvos_conv3x3_f32x3_applicable(Cin, Cout, y_cs))))
-    return osvos_conv3x3_f32x3(x, wpk, bias, mask, y, N, H, W, Cin, Cout, y_cs, relu, tile >= 200 ? tile - 200 : -1, g_force_ksplit, part_ws, stream);
+  if ((tile >= 200 || (tile == -2 && osvos_conv3x3_f32x3_applicable(Cin, Cout, y_cs)))) {
+    ConvCall cx = c;
+    cx.tile = tile >= 200 ? tile - 200 : -1;
+    return osvos_conv3x3_f32x3(cx);
+  }
   ConvArgs a;
   a.x = x; a.wpk = wpk; a.bias = bias; a.mask = mask; a.y = y;
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.CoutP = osvos_cout_pad(Cout); a.y_cs = y_cs;
@@ -458,8 +457,7 @@ int osvos_conv3x3_f32_ws(const float* x, const float* wpk, const float* bias, co
     // OSVOS_CONV_KSPLIT overrides the automatic choice, but only where the automatic choice could split as well (Cin >= 256):
     // the caller sizes `part_ws` for those layers only (net.cpp ws_layout), a forced split of a shallow layer would overrun it
     OSVOS_ENV_INT(env_ks, "OSVOS_CONV_KSPLIT", 0);
-    a.ksplit = g_force_ksplit > 0 ? g_force_ksplit
-                                  : ((env_ks > 0 && Cin >= 256) ? env_ks : pick_ksplit(kTiles[tile], N, H, W, Cin, Cout, a.CoutP, y_cs));
+    a.ksplit = c.ksplit > 0 ? c.ksplit : ((env_ks > 0 && Cin >= 256) ? env_ks : pick_ksplit(kTiles[tile], N, H, W, Cin, Cout, a.CoutP, y_cs));
     if (a.ksplit < 1 || a.ksplit > 8 || Cout % 4 != 0 || y_cs % 4 != 0 || a.ksplit > (Cin >> 3)) a.ksplit = 1;
   }
   int rc;
@@ -514,6 +512,9 @@ extern "C" int osvos_prof_pack_fwd_f32(const float* w, float* wpk, int Cout, int
   return (int)hipGetLastError();
 }
 extern "C" int osvos_prof_conv3x3_f32(const float* x, const float* wpk, float* y, int N, int H, int W, int Cin, int Cout, int tile) {
-  return osvos_conv3x3_f32(x, wpk, nullptr, nullptr, y, N, H, W, Cin, Cout, Cout, 1, tile, nullptr);
+  ConvCall c;
+  c.x = x; c.wpk = wpk; c.y = y;
+  c.N = N; c.H = H; c.W = W; c.Cin = Cin; c.Cout = c.y_cs = Cout; c.relu = 1; c.tile = tile;
+  return osvos_conv3x3_f32(c);
 }
 #endif

@@ -988,14 +988,8 @@ __global__ __launch_bounds__(256) void pack_x3_multi_kernel(PackX3Table t) {
 
 }  // namespace
 
-// n packs (n <= OSVOS_PACK_MAX) in one launch: ws[k] OIHW fp32 [Couts[k]][Cins[k]][3][3] -> dsts[k] (osvos_pack_x3 layout; dgrads[k] != 0: data-gradient form)
-int osvos_pack_x3_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, int n, hipStream_t stream) {
-  return osvos_pack_x3_multi_fmt(ws, dsts, Couts, Cins, dgrads, nullptr, n, stream);
-}
-// halfs[k] != 0: entry k in the two-piece FP16 format (h2split.h; three launches instead of one: zero + largest magnitude + pack); NULL: every
-// entry in the format of this thread's osvos_x3_pieces() (22 = FP16 pairs, else three bf16 planes)
-int osvos_pack_x3_multi_fmt(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, const int* halfs, int n,
-                            hipStream_t stream) {
+int osvos_pack_x3_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, const int* halfs, int n,
+                        hipStream_t stream) {
   OSVOS_ARG_CHECK(ws && dsts && Couts && Cins && dgrads && n >= 0 && n <= OSVOS_PACK_MAX, "pack_x3_multi: bad table (n = %d)", n);
   if (n == 0) return 0;
   PackX3Table t;
@@ -1031,7 +1025,7 @@ int osvos_pack_x3(const float* w, void* wpk3, int Cout, int Cin, int dgrad, hipS
   const float* ws[1] = {w};
   void* dsts[1] = {wpk3};
   const int co[1] = {Cout}, ci[1] = {Cin}, dg[1] = {dgrad};
-  return osvos_pack_x3_multi(ws, dsts, co, ci, dg, 1, stream);
+  return osvos_pack_x3_multi(ws, dsts, co, ci, dg, nullptr, 1, stream);
 }
 
 int osvos_conv3x3_f32x3_num_tiles(void) { return kNumTilesX; }
@@ -1041,28 +1035,17 @@ int osvos_conv3x3_f32x3_num_tiles(void) { return kNumTilesX; }
 size_t osvos_conv3x3_f32x3_streamk_ws_bytes(void) { return kSkTicketBytes + (size_t)kSkMaxGrid * 2 * kSkSlotBytes; }
 size_t osvos_conv3x3_f32x3_streamk_ticket_bytes(void) { return kSkTicketBytes; }
 
-// Cout may be ragged (the 3-channel input gradient) as long as the output has room for the rounded-up channel quad: the pack's
-// padded couts carry zero weights, so the extra channel is written as 0
 bool osvos_conv3x3_f32x3_applicable(int Cin, int Cout, int y_cs) { return Cin % 16 == 0 && y_cs % 4 == 0 && ((Cout + 3) & ~3) <= y_cs; }
 
-// same contract as osvos_conv3x3_f32_ws (conv3x3_f32.hip); tile: -1 = automatic, 0..kNumTilesX-1 (+100: XCD-local halo map)
-int osvos_conv3x3_f32x3(const float* x, const float* wpk, const float* bias, const float* mask, float* y,
-                        int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, int ksplit, void* part_ws, hipStream_t stream) {
-  return osvos_conv3x3_f32x3_ps(x, wpk, nullptr, bias, mask, y, N, H, W, Cin, Cout, y_cs, relu, tile, ksplit, part_ws, stream);
-}
-
-// wpk3 != NULL: pre-split pack (osvos_pack_x3) -- wpk (the fp32 pack) is then not read and may be NULL
-int osvos_conv3x3_f32x3_ps(const float* x, const float* wpk, const void* wpk3, const float* bias, const float* mask, float* y,
-                           int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, int ksplit, void* part_ws, hipStream_t stream) {
-  return osvos_conv3x3_f32x3_epi(x, wpk, wpk3, bias, mask, y, N, H, W, Cin, Cout, y_cs, relu, tile, ksplit, part_ws, nullptr, stream);
-}
-
-// epi (may be NULL): fused epilogues (epi.h).  epi->pooled: the launch needs one of the eight-wave tiles whose waves hold whole 2 x 2
-// windows (10, 12, 14) and is never cut along K by partial-sum launches (the stream-K form keeps whole tiles in one workgroup's registers)
-int osvos_conv3x3_f32x3_epi(const float* x, const float* wpk, const void* wpk3, const float* bias, const float* mask, float* y,
-                            int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, int ksplit, void* part_ws, const ConvEpi* epi,
-                            hipStream_t stream) {
-  const bool pool_fwd = epi != nullptr && epi->pooled != nullptr;
+int osvos_conv3x3_f32x3(const ConvCall& c) {
+  const float *x = (const float*)c.x, *wpk = (const float*)c.wpk, *bias = c.bias, *mask = (const float*)c.mask;
+  const void* const wpk3 = c.wpk3;
+  float* const y = c.y;
+  void* const part_ws = c.part_ws;
+  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cout = c.Cout, y_cs = c.y_cs, relu = c.relu, ksplit = c.ksplit;
+  int tile = c.tile;
+  hipStream_t stream = c.stream;
+  const bool pool_fwd = c.pooled != nullptr;
   OSVOS_ARG_CHECK(x && (wpk || wpk3) && y, "conv3x3 f32x3: null pointer");
   OSVOS_ARG_CHECK(!pool_fwd || (relu && Cout % 4 == 0 && y_cs == Cout), "conv3x3 f32x3: fused pool forward needs ReLU and a dense Cout %% 4 == 0 result");
   OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3 f32x3: bad shape");
@@ -1075,7 +1058,7 @@ int osvos_conv3x3_f32x3_epi(const float* x, const float* wpk, const void* wpk3, 
   a.x = x; a.wpk = wpk; a.wpk3 = reinterpret_cast<const uint4*>(wpk3); a.bias = bias; a.mask = mask; a.y = y;
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = (Cout + 3) & ~3; a.CoutP = osvos_cout_pad(Cout); a.y_cs = y_cs;
   a.relu = relu;
-  if (epi != nullptr) a.epi = *epi;
+  a.epi.pooled = c.pooled; a.epi.mask_bits = c.mask_bits; a.epi.y_bits = c.y_bits; a.epi.sk_ws = c.sk_ws; a.epi.sk_grid = c.sk_grid;
   if (tile < 0) {
     OSVOS_ENV_INT(env_tile, "OSVOS_X3_TILE", -1);
     tile = env_tile >= 0 ? env_tile : pick_tile_x(N, H, W, a.CoutP);
@@ -1100,9 +1083,9 @@ int osvos_conv3x3_f32x3_epi(const float* x, const float* wpk, const void* wpk3, 
     a.ksplit = ksplit > 0 ? ksplit : (env_ks > 0 && Cin >= 256 ? env_ks : pick_ksplit_x(kTilesX[tile], N, H, W, Cin, Cout, a.CoutP));
     if (a.ksplit < 1 || a.ksplit > 8 || a.ksplit > (Cin >> 4) || Cout % 4 != 0) a.ksplit = 1;
   }
-  if (epi != nullptr && (epi->mask_bits != nullptr || epi->y_bits != nullptr))
+  if (c.mask_bits != nullptr || c.y_bits != nullptr)
     OSVOS_ARG_CHECK(Cout % 32 == 0 && y_cs == Cout, "conv3x3 f32x3: one-bit masks need a dense result with Cout %% 32 == 0 (Cout %d, stride %d)", Cout, y_cs);
-  if (epi != nullptr && epi->y_bits != nullptr) a.ksplit = 1;
+  if (c.y_bits != nullptr) a.ksplit = 1;
   if (pool_fwd) {
     a.ksplit = 1;
     OSVOS_ARG_CHECK(tile == 10 || tile == 12 || tile == 14, "conv3x3 f32x3: fused pool forward is built for tiles 10, 12 and 14 (got %d)", tile);
@@ -1112,11 +1095,11 @@ int osvos_conv3x3_f32x3_epi(const float* x, const float* wpk, const void* wpk3, 
   // (conv3_x at 854x480 batch 1: 210 tiles, 18 %) -- or would need partial-sum launches + a finalize kernel to fill it (conv5_x)
   int sk_grid = 0;
   a.sk_order = 0; a.sk_tickets = nullptr; a.sk_part = nullptr;
-  if (epi != nullptr && epi->sk_ws != nullptr && wpk3 != nullptr && (tile == 10 || tile == 12 || tile == 14) && Cout % 4 == 0) {
+  if (c.sk_ws != nullptr && wpk3 != nullptr && (tile == 10 || tile == 12 || tile == 14) && Cout % 4 == 0) {
     const long ntiles = tiles_of(kTilesX[tile], N, H, W, a.CoutP), units = ntiles * (Cin >> 4);
     OSVOS_ENV_INT(env_grid, "OSVOS_X3_STREAMK_GRID", 0);            // tuning: persistent workgroups (default: the CU count)
     OSVOS_ENV_INT(env_loss, "OSVOS_X3_STREAMK_MIN_LOSS", 6);        // tuning: percent of the chip a plain grid must leave idle
-    int g = epi->sk_grid > 0 ? epi->sk_grid : (env_grid > 0 ? env_grid : osvos_cu_count());
+    int g = c.sk_grid > 0 ? c.sk_grid : (env_grid > 0 ? env_grid : osvos_cu_count());
     if (g > kSkMaxGrid) g = kSkMaxGrid;
     const long rounds = (ntiles * a.ksplit + g - 1) / g;
     // Measured per layer at 854x480 batch 1 (profiles/r04_tune_streamk.txt, three boxes): the 64-cout tiles (12, 14: 64 KB partial slots) WIN --
@@ -1124,14 +1107,14 @@ int osvos_conv3x3_f32x3_epi(const float* x, const float* wpk, const void* wpk3, 
     // 128-cout tile (10: conv2_x / conv3_x, 128 KB slots, short K ranges on conv2_x / conv3_1) LOSES 1-12 % although every workgroup issues a
     // fifth fewer MFMAs.  The automatic choice therefore covers tiles 12 and 14 only; tile 10 runs stream-K when forced (tests, tuning).
     const bool lossy = (tile == 12 || tile == 14) && (a.ksplit > 1 || (rounds * g - ntiles) * 100 >= (long)env_loss * rounds * g);
-    if (ntiles <= kSkMaxTiles && units >= g && (epi->sk_grid > 0 || lossy)) {
+    if (ntiles <= kSkMaxTiles && units >= g && (c.sk_grid > 0 || lossy)) {
       sk_grid = g;
       a.ksplit = 1;
       a.sk_order = a.map ? 0 : 1;      // activations > weights: Cout tiles of one halo back to back; else one weight slice per XCD
       OSVOS_ENV_INT(env_order, "OSVOS_X3_STREAMK_ORDER", -1);
       if (env_order == 0 || env_order == 1) a.sk_order = env_order;
-      a.sk_tickets = reinterpret_cast<unsigned*>(epi->sk_ws);
-      a.sk_part = reinterpret_cast<float*>(reinterpret_cast<char*>(epi->sk_ws) + kSkTicketBytes);
+      a.sk_tickets = reinterpret_cast<unsigned*>(c.sk_ws);
+      a.sk_part = reinterpret_cast<float*>(reinterpret_cast<char*>(c.sk_ws) + kSkTicketBytes);
     }
   }
   int rc;

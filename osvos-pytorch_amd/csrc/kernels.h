@@ -3,21 +3,60 @@
 #include "common.h"
 #include "epi.h"
 
-int osvos_conv3x3_f32(const float* x, const float* wpk, const float* bias, const float* mask, float* y,
-                      int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, hipStream_t stream);
+// One 3x3 convolution launch (stride 1, zero padding 1, NHWC), as every launcher below takes it.  Host only: each launcher translates it
+// into the argument struct of its kernels.  A launcher reads the fields its family has and ignores the others (the exact fp32 kernels
+// have no fused epilogue, the bf16 ones no K split); a caller fills, by name, only what it uses.
+struct ConvCall {
+  const void* x = nullptr;             // input, channel stride Cin: fp32, or bf16 when x_bf16 (bf16 family only)
+  int x_bf16 = 0;
+  // weights, one form per family: fp32 pack (osvos_pack_{fwd,dgrad}_f32) / bf16 pack (osvos_pack_bf16_multi) in wpk; f32x3 also takes the
+  // pre-split pack (osvos_pack_x3) in wpk3 -- wpk is then not read and may be NULL
+  const void* wpk = nullptr;
+  const void* wpk3 = nullptr;
+  int w_pieces = 1;                    // bf16 family: 2 = two-piece weights (precision 'bf16w2'): wpk is the hi plane (= the single-piece pack), the lo
+  size_t w_lo = 0;                     // plane lies w_lo bytes behind it; only the two-piece tiles 40-45 read such packs, and they read nothing else
+  const float* bias = nullptr;
+  // ReLU mask of a data gradient (y = 0 where mask <= 0), laid out like y: fp32, or bf16 when mask_bf16 (bf16 family only); mask_bits: the same as
+  // one bit per element (maskbits.h; dense results with Cout % 32 == 0), takes precedence -- except in the finalize kernel of a launch cut along
+  // K, which reads `mask`: the fp32 families take both
+  const void* mask = nullptr;
+  int mask_bf16 = 0;
+  const unsigned* mask_bits = nullptr;
+  float* y = nullptr;                  // fp32 result, channel stride y_cs (bf16 family: may be NULL when y_bf16 is given)
+  void* y_bf16 = nullptr;              // bf16 family: bf16 result / copy of y with the same stride
+  unsigned* y_bits = nullptr;          // sign bits of the result, written next to it (maskbits.h; f32x3: the launch is then never cut along K)
+  int y_cs = 0;
+  // max-pool 2x2 (ceil mode) of the result by the same call, [N][ceil(H/2)][ceil(W/2)][Cout]; needs ReLU and a dense result.  f32x3: `pooled`
+  // (fp32; tiles 10, 12, 14 only, never cut along K by partial-sum launches).  bf16 family: pooled_bf16 (needs y_bf16, no mask, Cout % 8 == 0; a
+  // tile whose waves do not hold whole windows launches the pooling kernel behind the convolution) and, optionally with it, pool_code: one byte
+  // per pooled element for osvos_maxpool2x2_bwd_bf16_code, written whichever kernel runs
+  float* pooled = nullptr;
+  void* pooled_bf16 = nullptr;
+  void* pool_code = nullptr;
+  int N = 0, H = 0, W = 0, Cin = 0, Cout = 0, relu = 0;
+  int tile = -1;                       // -1: automatic; else the family's tile id (+100: XCD-local block map).  Exact fp32 launcher: 200 + t = f32x3
+                                       // tile t, -2 = "automatic, in the f32x3 arithmetic where it applies"
+  int ksplit = 0;                      // fp32 families: K parts (<= 8) of a launch cut along K; 0 = automatic.  Taken only with part_ws
+  void* part_ws = nullptr;             // NULL (never cut) or osvos_conv3x3_splitk_ws_bytes_f32() bytes for the partial sums
+  // f32x3 stream-K: workspace of osvos_conv3x3_f32x3_streamk_ws_bytes(), tickets zeroed once by the caller (NULL = plain grids only); sk_grid 0 =
+  // automatic (taken when the plain grid would idle CUs), > 0 = forced, that many workgroups (tests)
+  void* sk_ws = nullptr;
+  int sk_grid = 0;
+  hipStream_t stream = nullptr;
+};
+
+// exact fp32 (conv3x3_f32.hip): fp32 tensors and fp32 pack, Cin % 8 == 0
+int osvos_conv3x3_f32(const ConvCall& c);
 size_t osvos_conv3x3_splitk_ws_bytes_f32(int N, int H, int W, int Cout);
-void osvos_conv3x3_force_ksplit(int k);
-int osvos_conv3x3_f32_ws(const float* x, const float* wpk, const float* bias, const float* mask, float* y,
-                         int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, void* part_ws, hipStream_t stream);
 int osvos_conv3x3_splitk_finalize_f32(const float* part, const float* bias, const float* mask, float* y, long npix, int Cout, int y_cs,
                                       int ksplit, int relu, hipStream_t stream);
-// f32x3 (conv3x3_f32x3.hip): fp32 tensors and fp32 packs, three-way bf16 split operands on the bf16 matrix pipe
+// f32x3 (conv3x3_f32x3.hip): fp32 tensors, three-way bf16 split operands on the bf16 matrix pipe; tile ids 0..num_tiles-1.  Cout may be ragged
+// (the 3-channel input gradient) as long as y has room for the rounded-up channel quad
 bool osvos_conv3x3_f32x3_applicable(int Cin, int Cout, int y_cs);
 int osvos_conv3x3_f32x3_num_tiles(void);
 size_t osvos_conv3x3_f32x3_streamk_ws_bytes(void);
 size_t osvos_conv3x3_f32x3_streamk_ticket_bytes(void);
-int osvos_conv3x3_f32x3(const float* x, const float* wpk, const float* bias, const float* mask, float* y,
-                        int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, int ksplit, void* part_ws, hipStream_t stream);
+int osvos_conv3x3_f32x3(const ConvCall& c);
 // f32x3 weight gradient (wgrad_f32x3.hip): fp32 x / dy, three-way bf16 split, fp32 slabs + the shared reduce
 bool osvos_wgrad_f32x3_applicable(int Cin, int Cin_s, int Cout, int Cout_s);
 bool osvos_wgrad_f32x3_skinny_applicable(int Cin, int Cin_s, int Cout, int Cout_s);
@@ -26,18 +65,16 @@ int osvos_conv3x3_wgrad_f32x3(const float* x, const float* dy, void* ws, float* 
                               int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s, int accumulate, hipStream_t stream);
 size_t osvos_wpack_x3_bytes(int M, int K);
 #define OSVOS_PACK_MAX 40
-int osvos_pack_bf16_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, int n, hipStream_t stream);
-int osvos_pack_bf16_multi_lo(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, void* const* lo_dsts, int n,
-                             hipStream_t stream);
-int osvos_pack_x3_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, int n, hipStream_t stream);
-int osvos_pack_x3_multi_fmt(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, const int* halfs, int n,
-                            hipStream_t stream);
+// n packs (n <= OSVOS_PACK_MAX) in one launch: ws[k] OIHW fp32 [Couts[k]][Cins[k]][3][3] -> dsts[k]; dgrads[k] != 0: data-gradient form.
+// bf16: lo_dsts (NULL = none) [k] != NULL also writes the lo plane of a two-piece forward pack there (the hi plane, at dsts[k], is the
+// single-piece pack byte for byte)
+int osvos_pack_bf16_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, void* const* lo_dsts, int n,
+                          hipStream_t stream);
+// pre-split f32x3 packs: halfs[k] != 0: entry k in the two-piece FP16 format (h2split.h; three launches instead of one); NULL: every entry in
+// the format of this thread's osvos_x3_pieces() (22 = FP16 pairs, else three bf16 planes)
+int osvos_pack_x3_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, const int* halfs, int n,
+                        hipStream_t stream);
 int osvos_pack_x3(const float* w, void* wpk3, int Cout, int Cin, int dgrad, hipStream_t stream);
-int osvos_conv3x3_f32x3_ps(const float* x, const float* wpk, const void* wpk3, const float* bias, const float* mask, float* y,
-                           int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, int ksplit, void* part_ws, hipStream_t stream);
-int osvos_conv3x3_f32x3_epi(const float* x, const float* wpk, const void* wpk3, const float* bias, const float* mask, float* y,
-                            int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, int ksplit, void* part_ws, const ConvEpi* epi,
-                            hipStream_t stream);
 bool osvos_dgrad_c3_applicable(int Cin, int Cout);
 int osvos_conv3x3_dgrad_c3_f32(const float* dy, const float* wpk_dgrad, float* dx_nchw, int N, int H, int W, int Cout, hipStream_t stream);
 int osvos_conv3x3_dgrad_c3_bf16mfma(const void* dy_bf16, const void* wpk_bf16_dgrad, float* dx_nchw, int N, int H, int W, int Cout, hipStream_t stream);
@@ -76,44 +113,31 @@ int osvos_head_tapsum(const float* P, int channels, const float* d, double* G, i
 int osvos_head_generic_param_grads(const float* wup, const float* wf16, const double* G, float* dwf16, float* dwup, int k, int accumulate, hipStream_t stream);
 int osvos_head_dw1(const double* G1, float* dw, int k, int accumulate, hipStream_t stream);
 
-// bf16-operand MFMA variant of the convolution (fp32 tensors): conv3x3_bf16.hip
+// bf16-operand MFMA convolution (conv3x3_bf16.hip): x fp32 or bf16, bf16 pack, fp32 and / or bf16 result.  Tile ids: 0-11 register-staged,
+// 30-37 LDS-DMA staged and 38 persistent (bf16 x only; handed on to the two launchers below), 40-45 two-piece weights
 int osvos_pack_fwd_bf16(const float* w, void* wpk, int Cout, int Cin, hipStream_t stream);
 int osvos_pack_dgrad_bf16(const float* w, void* wpk, int Cout, int Cin, hipStream_t stream);
-int osvos_conv3x3_bf16mfma(const float* x, const void* wpk, const float* bias, const float* mask, float* y,
-                           int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, hipStream_t stream);
+int osvos_conv3x3_bf16mfma(const ConvCall& c);
 int osvos_conv3x3_bf16mfma_num_tiles(void);
-// xb = 1: x is bf16 NHWC; ybf (optional): bf16 copy of y
-int osvos_conv3x3_bf16mfma_bits(const void* x, int xb, const void* wpk, const float* bias, const void* mask, int mask_bf16, const unsigned* mask_bits,
-                                float* y, void* ybf, unsigned* y_bits, void* pooled_bf16, int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile,
-                                hipStream_t stream, void* pool_code = nullptr, int wp = 1, size_t w_lo = 0);
-// wp = 2: two-piece weights (precision 'bf16w2'): wpk is the hi plane (= the single-piece pack), the lo plane lies w_lo bytes behind it; only the
-// two-piece tiles 40-45 read such packs (osvos_conv3x3_bf16w2_tiles), and they read nothing else
 int osvos_conv3x3_bf16w2_tiles_impl(int* tiles, int max);
-int osvos_conv3x3_bf16mfma_io(const void* x, int xb, const void* wpk, const float* bias, const void* mask, int mask_bf16, float* y, void* ybf,
-                              int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, hipStream_t stream);
 int osvos_conv3x3_bf16mfma_xb_tiles(int* tiles, int max);
-// LDS-DMA staged variant (bf16 activations only): conv3x3_bf16_dma.hip; reached through tile ids 30..37 (30-33: 256 px x 128 / 64 co with 4 waves, 512 px x 128 / 64 co with 8 waves; 34, 35: persistent forms; 36, 37: resident-filter persistent forms for Cin = 64)
+// LDS-DMA staged variant (conv3x3_bf16_dma.hip; bf16 x, single-piece pack): variant = tile id - 30 (0-3: 256 px x 128 / 64 co with 4 waves,
+// 512 px x 128 / 64 co with 8 waves; 4, 5: persistent forms; 6, 7: resident-filter persistent forms for Cin = 64); map: XCD-local block map
 bool osvos_conv3x3_bf16_dma_applicable(int Cin, int Cout, int y_cs);
+int osvos_conv3x3_bf16_dma(const ConvCall& c, int variant, int map);
 // Cin = 64, bf16 in / out: persistent, resident filter, deferred + skewed packed epilogue (conv3x3_bf16_p64.hip; tile id 38)
 bool osvos_conv3x3_bf16_p64_applicable(int Cin, int Cout, int y_cs, bool has_y_f32, bool has_tensor_mask, bool has_mask_bits, bool has_y_bits, bool has_pool,
                                        int relu);
-int osvos_conv3x3_bf16_p64(const void* x, const void* wpk, const float* bias, const unsigned* mask_bits, void* ybf, unsigned* y_bits, void* pooled_bf16,
-                           void* pool_code, int N, int H, int W, int Cout, int y_cs, int relu, int map, hipStream_t stream);
-int osvos_conv3x3_bf16_dma(const void* x, const void* wpk, const float* bias, const void* mask, int mask_bf16, const unsigned* mask_bits, float* y, void* ybf,
-                           unsigned* y_bits, void* pooled_bf16, int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int variant, int map, hipStream_t stream,
-                           void* pool_code = nullptr);
+int osvos_conv3x3_bf16_p64(const ConvCall& c, int map);
 
 // bf16-operand weight gradient (fp32 tensors): wgrad_bf16.hip
 bool osvos_wgrad_bf16_applicable(int Cin_s, int Cout);
 size_t osvos_wgrad_bf16_ws_bytes(int N, int H, int W, int Cin_s, int Cout);
 // bf16-store mode of the network: the trunk tensors are bf16.  xb: x AND dy are bf16 (wide layers); the skinny fp32 kernels take
 // their WIDE operand (dy of conv1_1, x of side_prep) as bf16 and the narrow one as fp32
-int osvos_conv3x3_wgrad_bf16mfma_io(const void* x, const void* dy, int xb, void* ws, float* dw, float* db,
-                                    int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
-                                    int accumulate, hipStream_t stream);
+int osvos_conv3x3_wgrad_bf16mfma(const void* x, const void* dy, int xb, void* ws, float* dw, float* db,
+                                 int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
+                                 int accumulate, hipStream_t stream);
 int osvos_conv3x3_wgrad_small_f32(const void* x, const void* dy, int wide_bf16, void* ws, float* dw, float* db,
                                   int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
                                   int accumulate, hipStream_t stream);
-int osvos_conv3x3_wgrad_bf16mfma(const float* x, const float* dy, void* ws, float* dw, float* db,
-                                 int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
-                                 int accumulate, hipStream_t stream);

@@ -87,6 +87,15 @@ inline bool use_store(int dtype) {
   return dtype == OSVOS_F32_BF16MFMA && on;
 }
 
+inline char* at(void* base, size_t off) { return reinterpret_cast<char*>(base) + off; }
+inline const char* at(const void* base, size_t off) { return reinterpret_cast<const char*>(base) + off; }
+
+// the two views a workspace tensor can have (WsLayout::view); NULL = the tensor does not exist in that format
+struct Tensor {
+  void* f;      // fp32
+  void* b;      // bf16
+};
+
 struct WsLayout {
   int hs[5], ws[5];
   size_t xin, act[kNumTrunk], pooled[5], prep[4], score[4], fpart[4];
@@ -95,16 +104,21 @@ struct WsLayout {
   size_t side_part[4];       // the same for the side_prep convolutions, which run on the aux stream beside the trunk (own buffers)
   size_t dy[kNumTrunk], dpool[5], dside[4], dprep[4], wgrad[kNumConv], acc, dxin;
   size_t gbuf[4];            // generic head only: tap-indexed reductions G_i[16][k*k] + G1_i[k*k], doubles
-  // the bf16 trunk tensors of the bf16-store mode (dtype OSVOS_F32_BF16MFMA, OSVOS_BF16_STORE=1): the SAME offsets as the fp32 names above
-  // (nothing fp32 is written for them); 0 / unused otherwise.  (Rounds 1-3 could also keep bf16 COPIES next to fp32 tensors --
-  // OSVOS_BF16_SHADOW, measured a net loss at batch 12 -- removed in round 4.)
-  size_t xin_b, act_b[kNumTrunk], pooled_b[5], dy_b[kNumTrunk], dpool_b[5], dside_b[4], dprep_b[4];
+  // bf16-store mode (dtype OSVOS_F32_BF16MFMA, OSVOS_BF16_STORE=1): the trunk tensors (act, pooled, dy, dpool, dside) ARE bf16, at the offsets
+  // above, and nothing fp32 is written for them; xin and dprep stay fp32 and get a bf16 copy here (0 / unused otherwise)
+  bool store;
+  size_t xin_b, dprep_b[4];
   // sign bits of the activations that later serve as ReLU masks (maskbits.h; (size_t)-1 = none): [N][h][w][cout / 32] words
   size_t bits[kNumTrunk];
   // bf16-store mode: one code byte per pooled element, written by the forward's pooling (fused epilogue or kernel), read by maxpool_bwd
   // instead of the pool's input (pool.hip; (size_t)-1 = none)
   size_t pool_code[5];
   size_t fwd_total, total;
+
+  // a tensor of the workspace `ws` as a launcher takes it: trunk tensors have ONE view (bf16 in the store mode, else fp32); with `off_b` (xin,
+  // dprep) the fp32 view always and the bf16 copy in the store mode
+  Tensor view(void* ws, size_t off) const { return store ? Tensor{nullptr, at(ws, off)} : Tensor{at(ws, off), nullptr}; }
+  Tensor view(void* ws, size_t off, size_t off_b) const { return Tensor{at(ws, off), store ? at(ws, off_b) : nullptr}; }
 };
 
 // One-bit ReLU masks (maskbits.h): the forward writes the sign bits of every activation a data gradient is later masked with, the data
@@ -140,7 +154,7 @@ WsLayout ws_layout(int N, int H, int W, int dtype) {
   auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
   ConvDesc d[kNumConv];
   conv_table(d);
-  const bool store = use_store(dtype);
+  const bool store = L.store = use_store(dtype);
   const size_t te = store ? 2 : es;          // element size of the trunk tensors
   L.xin = take(es * N * H * W * kInPad);
   if (store) L.xin_b = take((size_t)2 * N * H * W * kInPad);
@@ -148,13 +162,11 @@ WsLayout ws_layout(int N, int H, int W, int dtype) {
     const int si = d[l].stage;
     const size_t e = (size_t)N * L.hs[si] * L.ws[si] * d[l].cout;
     L.act[l] = take(te * e);
-    L.act_b[l] = store ? L.act[l] : 0;
     L.bits[l] = (use_mask_bits(dtype) && act_is_a_mask(d, l, dtype)) ? take(e / 8) : (size_t)-1;
   }
   for (int si = 1; si < 5; ++si) {
     const size_t e = (size_t)N * L.hs[si] * L.ws[si] * kStageC[si - 1];
     L.pooled[si] = take(te * e);
-    L.pooled_b[si] = store ? L.pooled[si] : 0;
     L.pool_code[si] = (store && use_pool_code()) ? take(e) : (size_t)-1;
   }
   for (int i = 0; i < 4; ++i) {
@@ -184,7 +196,6 @@ WsLayout ws_layout(int N, int H, int W, int dtype) {
     L.dprep[i] = take(es * npix * 16);
     L.dprep_b[i] = store ? take((size_t)2 * npix * 16) : 0;
     L.dside[i] = take(te * npix * kStageC[i + 1]);
-    L.dside_b[i] = store ? L.dside[i] : 0;
   }
   // one gradient buffer per trunk conv output (dLoss/d act[l], ReLU mask applied) and per pooled
   // tensor: no buffer is ever rewritten inside one backward, so the weight-gradient stream can trail
@@ -192,12 +203,8 @@ WsLayout ws_layout(int N, int H, int W, int dtype) {
   for (int l = 0; l < kNumTrunk; ++l) {
     const size_t e = (size_t)N * L.hs[d[l].stage] * L.ws[d[l].stage] * d[l].cout;
     L.dy[l] = take(te * e);
-    L.dy_b[l] = store ? L.dy[l] : 0;
   }
-  for (int si = 1; si < 5; ++si) {
-    L.dpool[si] = take(te * N * L.hs[si] * L.ws[si] * kStageC[si - 1]);
-    L.dpool_b[si] = store ? L.dpool[si] : 0;
-  }
+  for (int si = 1; si < 5; ++si) L.dpool[si] = take(te * N * L.hs[si] * L.ws[si] * kStageC[si - 1]);
   // one slab workspace per layer: the slab reduce of layer l runs on its own stream while the partial
   // kernel of the next layer already refills another buffer
   for (int l = 0; l < kNumConv; ++l) {
@@ -235,38 +242,52 @@ EventPool& event_pool() {
   return p;
 }
 
+// `waiter` waits for everything enqueued on `on` so far
+int stream_wait(hipStream_t waiter, hipStream_t on) {
+  hipEvent_t e = event_pool().next();
+  if (!e) return -1;
+  OSVOS_HIP_CHECK(hipEventRecord(e, on));
+  OSVOS_HIP_CHECK(hipStreamWaitEvent(waiter, e, 0));
+  return 0;
+}
+
 // f32x3: weights pre-split once per pack (default) or re-split by every workgroup from the fp32 pack (OSVOS_X3_PRESPLIT=0; bit-identical)
 inline bool use_presplit() {
   static const bool on = [] { const char* e = getenv("OSVOS_X3_PRESPLIT"); return !(e && e[0] == '0'); }();
   return on;
 }
 
-// 3x3 conv on the main stream: fp32 launches may be cut along K (split-K, partial sums in `part`) when the layer
-// is too small to balance across 256 CUs; the bf16-MFMA dtype goes through the public entry point
-// (x_b: bf16 copy of x, preferred when present; y_b: where the bf16 copy of y goes, NULL = none)
-// (mask_b: bf16 mask, takes precedence over the fp32 `mask`; y may be NULL in the bf16 modes when y_b is given)
-// (epi: fused pooling epilogues, f32x3 only -- fuse_pool() says when the caller may ask for them)
-// (w_lo: precision 'bf16w2' -- the byte distance from the hi plane wpk to the lo plane of a two-piece forward pack; 0 = single-piece pack)
-inline int conv_main(const void* x, const void* x_b, const void* wpk, const float* bias, const void* mask, const void* mask_b, void* y, void* y_b,
-                     int N, int h, int w, int cin, int cout, int y_cs, int relu, int dtype, void* part, hipStream_t stream, const void* wpk3 = nullptr,
-                     const ConvEpi* epi = nullptr, const void* mask_bits = nullptr, void* y_bits = nullptr, void* pooled_b = nullptr, void* sk_ws = nullptr,
-                     void* pool_code = nullptr, size_t w_lo = 0) {
-  if (dtype == OSVOS_F32_X3 && osvos_conv3x3_f32x3_applicable(cin, cout, y_cs)) {    // three-way bf16 split on the bf16 matrix pipe
-    ConvEpi e2;
-    if (epi != nullptr) e2 = *epi;
-    e2.mask_bits = reinterpret_cast<const unsigned*>(mask_bits);
-    e2.y_bits = reinterpret_cast<unsigned*>(y_bits);
-    e2.sk_ws = sk_ws;
-    const bool any = epi != nullptr || mask_bits != nullptr || y_bits != nullptr || sk_ws != nullptr;
+// The convolution of layer l (forward) or its data gradient (dgrad: Cin and Cout swap roles) on an h x w map, as far as the layer table and the
+// packed parameters decide it; the caller adds operands, results and workspaces by name.  Precision 'bf16w2': forward packs have two pieces
+ConvCall conv_of(const ConvDesc& dl, int l, bool dgrad, const void* wbuf, const WbufLayout& P, int N, int h, int w, hipStream_t stream) {
+  ConvCall c;
+  const size_t w3 = dgrad ? P.dgrad3[l] : P.fwd3[l];
+  c.wpk = at(wbuf, dgrad ? P.dgrad[l] : P.fwd[l]);
+  if (w3 != (size_t)-1) c.wpk3 = at(wbuf, w3);
+  if (!dgrad) c.bias = reinterpret_cast<const float*>(at(wbuf, P.bias[l]));
+  if (!dgrad && P.fwd_lo[l] != (size_t)-1) { c.w_pieces = 2; c.w_lo = P.fwd_lo[l] - P.fwd[l]; }
+  c.N = N; c.H = h; c.W = w;
+  c.Cin = dgrad ? dl.cout : dl.cin_s;
+  c.Cout = c.y_cs = dgrad ? dl.cin : dl.cout;
+  c.stream = stream;
+  return c;
+}
+inline void set_x(ConvCall& c, Tensor t) { c.x = t.b ? t.b : t.f; c.x_bf16 = t.b != nullptr; }                // (the bf16 view is preferred when present)
+inline void set_mask(ConvCall& c, Tensor t) { c.mask = t.b ? t.b : t.f; c.mask_bf16 = t.b != nullptr; }
+inline void set_y(ConvCall& c, Tensor t) { c.y = reinterpret_cast<float*>(t.f); c.y_bf16 = t.b; }
+
+// dtype dispatch of a network convolution: fp32 launches may be cut along K (split-K, partial sums in c.part_ws) when the layer is too small to
+// balance across 256 CUs; fused epilogues, bits and stream-K exist in the f32x3 / bf16 families only (fuse_pool() etc. say when the caller may
+// ask for them) and the exact kernels ignore them
+inline int conv_main(ConvCall c, int dtype) {
+  if (dtype == OSVOS_F32_X3 && osvos_conv3x3_f32x3_applicable(c.Cin, c.Cout, c.y_cs)) {    // three-way bf16 split on the bf16 matrix pipe
     // (with a pre-split pack the fp32 pack of the layer is not even built -- osvos_net_pack -- so it is not handed over either)
-    return osvos_conv3x3_f32x3_epi((const float*)x, (use_presplit() && wpk3) ? nullptr : (const float*)wpk, use_presplit() ? wpk3 : nullptr, bias,
-                                   (const float*)mask, (float*)y, N, h, w, cin, cout, y_cs, relu, -1, 0, part, any ? &e2 : nullptr, stream);
+    if (!use_presplit()) c.wpk3 = nullptr;
+    if (c.wpk3 != nullptr) c.wpk = nullptr;
+    return osvos_conv3x3_f32x3(c);
   }
-  if (dtype == OSVOS_F32 || dtype == OSVOS_F32_X3)
-    return osvos_conv3x3_f32_ws((const float*)x, (const float*)wpk, bias, (const float*)mask, (float*)y, N, h, w, cin, cout, y_cs,
-                                relu, -1, part, stream);
-  return osvos_conv3x3_bf16mfma_bits(x_b ? x_b : x, x_b ? 1 : 0, wpk, bias, mask_b ? mask_b : mask, mask_b ? 1 : 0, (const unsigned*)mask_bits, (float*)y, y_b,
-                                     (unsigned*)y_bits, pooled_b, N, h, w, cin, cout, y_cs, relu, -1, stream, pooled_b ? pool_code : nullptr, w_lo ? 2 : 1, w_lo);
+  if (dtype == OSVOS_F32 || dtype == OSVOS_F32_X3) return osvos_conv3x3_f32(c);
+  return osvos_conv3x3_bf16mfma(c);
 }
 
 // f32x3 and the bf16-store mode: the forward max-pool of a stage boundary runs as an epilogue of the stage's last convolution (epi.h).
@@ -322,9 +343,6 @@ GradEvents& grad_events() {
 }
 
 inline double conv_flops(int N, int h, int w, int cin, int cout) { return 2.0 * N * h * w * (double)cout * 9.0 * cin; }
-
-__attribute__((unused)) inline char* at(void* base, size_t off) { return reinterpret_cast<char*>(base) + off; }
-inline const char* at(const void* base, size_t off) { return reinterpret_cast<const char*>(base) + off; }
 
 }  // namespace
 
@@ -410,7 +428,7 @@ int osvos_net_pack(const float* const* params, void* wbuf, int dtype_, int with_
     srcs[ns] = params[d[l].b_param]; dsts[ns] = L.bias[l]; counts[ns] = d[l].cout; ++ns;
   }
   if (nx > 0) {
-    const int rc = b16 ? osvos_pack_bf16_multi_lo(xw, xd, xco, xci, xdg, xlo, nx, stream) : osvos_pack_x3_multi_fmt(xw, xd, xco, xci, xdg, xhalf, nx, stream);
+    const int rc = b16 ? osvos_pack_bf16_multi(xw, xd, xco, xci, xdg, xlo, nx, stream) : osvos_pack_x3_multi(xw, xd, xco, xci, xdg, xhalf, nx, stream);
     if (rc) return rc;
   }
 
@@ -443,62 +461,62 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
   PiecesScope pieces_scope(dtype_);
   hipStream_t aux_all = aux_stream_ ? (hipStream_t)aux_stream_ : stream;
   const bool two = aux_all != stream;
-  EventPool& evp = event_pool();
   OSVOS_ARG_CHECK(x_nchw && wbuf && ws && outs, "net_forward: null pointer");
   OSVOS_ARG_CHECK(osvos_dtype_built(dtype), "net_forward: dtype %d not built", dtype);
   OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0, "net_forward: bad shape %dx%dx%d", N, H, W);
   for (int i = 0; i < 5; ++i) OSVOS_ARG_CHECK(outs[i] != nullptr, "net_forward: outs[%d] is null", i);
   if (!w2_flag_ok(dtype_, "net_forward")) return -1;
-  // precision 'bf16w2': all 17 forward convolutions read two-piece packs (osvos_net_pack with the same flag); w_lo(l) = hi -> lo plane distance
+  // precision 'bf16w2': all 17 forward convolutions read two-piece packs (osvos_net_pack with the same flag)
   const WbufLayout P = wbuf_layout(dtype_);
-  auto w_lo = [&](int l) -> size_t { return P.fwd_lo[l] != (size_t)-1 ? P.fwd_lo[l] - P.fwd[l] : 0; };
   const WsLayout L = ws_layout(N, H, W, dtype);
   ConvDesc d[kNumConv];
   conv_table(d);
-  const bool store = use_store(dtype);
-  auto sh = [&](size_t off) -> void* { return store ? at(ws, off) : nullptr; };      // bf16 tensor (copy, or the only one)
-  auto f32 = [&](size_t off) -> void* { return store ? nullptr : at(ws, off); };                  // fp32 trunk tensor (absent in store mode)
-  int rc = osvos_nchw_to_nhwc_f32(x_nchw, reinterpret_cast<float*>(at(ws, L.xin)), sh(L.xin_b), N, 3, H, W, kInPad, stream);
+  const bool store = L.store;
+  Tensor cur = L.view(ws, L.xin, L.xin_b);
+  int rc = osvos_nchw_to_nhwc_f32(x_nchw, reinterpret_cast<float*>(cur.f), cur.b, N, 3, H, W, kInPad, stream);
   if (rc) return rc;
   // stream-K workspace of the main-stream convolutions: the tickets must be zero before the first launch (every launch leaves them zero; the
   // workspace itself arrives uninitialised from the caller, so they are cleared once per forward -- a 32 KB memset node, capturable)
   void* const sk_ws = (L.sk_ws != (size_t)-1 && streamk_mode() >= 1) ? at(ws, L.sk_ws) : nullptr;
   if (sk_ws != nullptr) OSVOS_HIP_CHECK(hipMemsetAsync(sk_ws, 0, osvos_conv3x3_f32x3_streamk_ticket_bytes(), stream));
-  const void* cur = at(ws, L.xin);
-  const void* cur_b = sh(L.xin_b);
   int l = 0;
   const float* score[4]; const float* fpart[4]; const float* f1[4]; const float* f16[4];
   for (int si = 0; si < 5; ++si) {
     const int h = L.hs[si], w = L.ws[si];
-    if (si > 0 && fuse_pool(dtype)) {      // pooled[si] was written by the previous stage's last convolution
-      cur = at(ws, L.pooled[si]);
-      cur_b = store ? at(ws, L.pooled_b[si]) : nullptr;
-    } else if (si > 0) {
-      if (store)
-        rc = osvos_maxpool2x2_bf16_code(cur_b, at(ws, L.pooled_b[si]), (L.pool_code[si] != (size_t)-1 && !infer) ? at(ws, L.pool_code[si]) : nullptr, N, L.hs[si - 1],
-                                        L.ws[si - 1], kStageC[si - 1], stream);
-      else
-        rc = osvos_maxpool2x2_f32(reinterpret_cast<const float*>(cur), reinterpret_cast<float*>(at(ws, L.pooled[si])), sh(L.pooled_b[si]), N,
-                                  L.hs[si - 1], L.ws[si - 1], kStageC[si - 1], stream);
-      if (rc) return rc;
-      cur = at(ws, L.pooled[si]);
-      cur_b = sh(L.pooled_b[si]);
+    if (si > 0) {
+      const Tensor pooled = L.view(ws, L.pooled[si]);
+      if (!fuse_pool(dtype)) {      // (else pooled[si] was written by the previous stage's last convolution)
+        if (store)
+          rc = osvos_maxpool2x2_bf16_code(cur.b, pooled.b, (L.pool_code[si] != (size_t)-1 && !infer) ? at(ws, L.pool_code[si]) : nullptr, N, L.hs[si - 1],
+                                          L.ws[si - 1], kStageC[si - 1], stream);
+        else
+          rc = osvos_maxpool2x2_f32(reinterpret_cast<const float*>(cur.f), reinterpret_cast<float*>(pooled.f), nullptr, N, L.hs[si - 1], L.ws[si - 1],
+                                    kStageC[si - 1], stream);
+        if (rc) return rc;
+      }
+      cur = pooled;
     }
     for (int j = 0; j < kStageN[si]; ++j, ++l) {
       {
         ProfScope ps(OSVOS_PROF_CONV_FWD, conv_flops(N, h, w, d[l].cin, d[l].cout), stream);
-        ConvEpi epi;
-        const bool pool_here = fuse_pool(dtype) && si < 4 && j == kStageN[si] - 1;      // last convolution of stages 0-3: + the pooled tensor
-        if (pool_here && !store) epi.pooled = reinterpret_cast<float*>(at(ws, L.pooled[si + 1]));
-        rc = conv_main(cur, cur_b, at(wbuf, P.fwd[l]), reinterpret_cast<const float*>(at(wbuf, P.bias[l])), nullptr, nullptr,
-                       f32(L.act[l]), sh(L.act_b[l]), N, h, w, d[l].cin_s, d[l].cout, d[l].cout, 1, dtype, at(ws, L.conv_part), stream,
-                       P.fwd3[l] != (size_t)-1 ? at(wbuf, P.fwd3[l]) : nullptr, (pool_here && !store) ? &epi : nullptr, nullptr,
-                       (L.bits[l] != (size_t)-1 && !infer) ? at(ws, L.bits[l]) : nullptr, (pool_here && store) ? at(ws, L.pooled_b[si + 1]) : nullptr, sk_ws,
-                       (pool_here && store && L.pool_code[si + 1] != (size_t)-1 && !infer) ? at(ws, L.pool_code[si + 1]) : nullptr, w_lo(l));
+        ConvCall c = conv_of(d[l], l, false, wbuf, P, N, h, w, stream);
+        c.relu = 1;
+        const Tensor act = L.view(ws, L.act[l]);
+        set_x(c, cur);
+        set_y(c, act);
+        if (L.bits[l] != (size_t)-1 && !infer) c.y_bits = reinterpret_cast<unsigned*>(at(ws, L.bits[l]));
+        if (fuse_pool(dtype) && si < 4 && j == kStageN[si] - 1) {      // last convolution of stages 0-3: + the pooled tensor
+          const Tensor pooled = L.view(ws, L.pooled[si + 1]);
+          c.pooled = reinterpret_cast<float*>(pooled.f);
+          c.pooled_bf16 = pooled.b;
+          if (L.pool_code[si + 1] != (size_t)-1 && !infer) c.pool_code = at(ws, L.pool_code[si + 1]);
+        }
+        c.part_ws = at(ws, L.conv_part);
+        c.sk_ws = sk_ws;
+        rc = conv_main(c, dtype);
+        cur = act;
       }
       if (rc) return rc;
-      cur = at(ws, L.act[l]);
-      cur_b = sh(L.act_b[l]);
     }
     if (si > 0) {
       // side branch of this stage (skinny Cout=16 conv + the two 1x1 dots): latency-bound launches
@@ -506,17 +524,14 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
       const int i = si - 1, sl = kNumTrunk + i;
       // the LAST stage's side branch has nothing left to hide behind: on the main stream it saves two cross-stream event hops (~12-25 us each)
       hipStream_t aux = (si == 4) ? stream : aux_all;
-      if (two && aux != stream) {
-        hipEvent_t e = evp.next();
-        if (!e) return -1;
-        OSVOS_HIP_CHECK(hipEventRecord(e, stream));
-        OSVOS_HIP_CHECK(hipStreamWaitEvent(aux, e, 0));
-      }
+      if (two && aux != stream && (rc = stream_wait(aux, stream))) return rc;
       {
         ProfScope ps(OSVOS_PROF_OTHER, conv_flops(N, h, w, d[sl].cin, 16), aux);
-        rc = conv_main(cur, cur_b, at(wbuf, P.fwd[sl]), reinterpret_cast<const float*>(at(wbuf, P.bias[sl])), nullptr, nullptr,
-                       at(ws, L.prep[i]), nullptr, N, h, w, d[sl].cin_s, 16, 16, 0, dtype, L.side_part[i] != (size_t)-1 ? at(ws, L.side_part[i]) : nullptr, aux,
-                       P.fwd3[sl] != (size_t)-1 ? at(wbuf, P.fwd3[sl]) : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, w_lo(sl));
+        ConvCall c = conv_of(d[sl], sl, false, wbuf, P, N, h, w, aux);
+        set_x(c, cur);
+        c.y = reinterpret_cast<float*>(at(ws, L.prep[i]));
+        if (L.side_part[i] != (size_t)-1) c.part_ws = at(ws, L.side_part[i]);
+        rc = conv_main(c, dtype);
       }
       if (rc) return rc;
       float* sc = reinterpret_cast<float*>(at(ws, L.score[i]));
@@ -530,12 +545,7 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
       f16[i] = reinterpret_cast<const float*>(at(wbuf, P.f16[i]));
     }
   }
-  if (two) {
-    hipEvent_t e = evp.next();
-    if (!e) return -1;
-    OSVOS_HIP_CHECK(hipEventRecord(e, aux_all));
-    OSVOS_HIP_CHECK(hipStreamWaitEvent(stream, e, 0));
-  }
+  if (two && (rc = stream_wait(stream, aux_all))) return rc;
   if (generic) {      // non-diagonal upscale weights: fused head from the 16-channel side_prep outputs and Weff (head_generic.hip)
     const float* prep[4]; const float* weff[4];
     for (int i = 0; i < 4; ++i) { prep[i] = reinterpret_cast<const float*>(at(ws, L.prep[i])); weff[i] = reinterpret_cast<const float*>(at(wbuf, P.weff[i])); }
@@ -547,13 +557,9 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
 
 int osvos_net_join(void* stream_, void* aux_, void* aux2_) {
   hipStream_t stream = (hipStream_t)stream_;
-  EventPool& evp = event_pool();
   for (void* a : {aux_, aux2_}) {
     if (a == nullptr || a == stream_) continue;
-    hipEvent_t e = evp.next();
-    if (!e) return -1;
-    OSVOS_HIP_CHECK(hipEventRecord(e, (hipStream_t)a));
-    OSVOS_HIP_CHECK(hipStreamWaitEvent(stream, e, 0));
+    if (const int rc = stream_wait(stream, (hipStream_t)a)) return rc;
   }
   return 0;
 }
@@ -592,31 +598,16 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
   const WsLayout L = ws_layout(N, H, W, dtype);
   ConvDesc d[kNumConv];
   conv_table(d);
-  const bool store = use_store(dtype);
-  auto sh = [&](size_t off) -> void* { return store ? at(ws, off) : nullptr; };
-  auto f32 = [&](size_t off) -> void* { return store ? nullptr : at(ws, off); };
-  auto mk32 = [&](size_t off) -> const void* { return store ? nullptr : at(ws, off); };           // ReLU mask operand: fp32 ...
-  auto mk16 = [&](size_t off) -> const void* { return store ? at(ws, off) : nullptr; };           // ... or bf16
+  const bool store = L.store;
   // fork: aux waits for everything enqueued on `stream` so far; join: `stream` waits for aux.
   // The weight-gradient kernels run on aux concurrently with the data-gradient kernel of the same
   // layer: both are MFMA kernels with independent stalls (barriers, LDS latency, tails), and
   // together they keep the matrix pipes busier than either does alone.
-  EventPool& evp = event_pool();
   auto join = [&]() -> int {
     if (defer_join) return 0;            // the caller joins (osvos_net_join) before it touches a parameter gradient
-    if (two) {
-      hipEvent_t e = evp.next();
-      if (!e) return -1;
-      OSVOS_HIP_CHECK(hipEventRecord(e, aux));
-      OSVOS_HIP_CHECK(hipStreamWaitEvent(stream, e, 0));
-    }
-    if (three) {
-      hipEvent_t e = evp.next();
-      if (!e) return -1;
-      OSVOS_HIP_CHECK(hipEventRecord(e, aux2));
-      OSVOS_HIP_CHECK(hipStreamWaitEvent(stream, e, 0));
-    }
-    return 0;
+    int r = two ? stream_wait(stream, aux) : 0;
+    if (r == 0 && three) r = stream_wait(stream, aux2);
+    return r;
   };
   // weight gradient of one layer: partial slabs on aux (MFMA kernel), slab reduce on aux2 (bandwidth kernel)
   // (store mode: the wide layers read both operands as bf16; conv1_1 and side_prep keep their exact-fp32 skinny kernels, fed
@@ -624,8 +615,8 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
   auto wgrad_launch = [&](const void* xin, const void* g, int l, int h, int w, hipStream_t st) -> int {
     if (store) {
       if (osvos_wgrad_bf16_applicable(d[l].cin_s, d[l].cout) && d[l].cin == d[l].cin_s)
-        return osvos_conv3x3_wgrad_bf16mfma_io(xin, g, 1, at(ws, L.wgrad[l]), grads[d[l].w_param], grads[d[l].b_param], N, h, w,
-                                               d[l].cin, d[l].cin_s, d[l].cout, d[l].cout, accumulate, st);
+        return osvos_conv3x3_wgrad_bf16mfma(xin, g, 1, at(ws, L.wgrad[l]), grads[d[l].w_param], grads[d[l].b_param], N, h, w,
+                                            d[l].cin, d[l].cin_s, d[l].cout, d[l].cout, accumulate, st);
       const int r = osvos_conv3x3_wgrad_small_f32(xin, g, 1, at(ws, L.wgrad[l]), grads[d[l].w_param], grads[d[l].b_param], N, h, w,
                                                   d[l].cin, d[l].cin_s, d[l].cout, d[l].cout, accumulate, st);
       if (r == 1) osvos_set_error("net_backward: no bf16-store weight-gradient kernel for layer %d", l);
@@ -642,10 +633,7 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
     osvos_wgrad_set_phase(0);
     if (r) return r;
     if (dbg_skip() & 1) return 0;
-    hipEvent_t e = evp.next();
-    if (!e) return -1;
-    OSVOS_HIP_CHECK(hipEventRecord(e, aux));
-    OSVOS_HIP_CHECK(hipStreamWaitEvent(aux2, e, 0));
+    if ((r = stream_wait(aux2, aux))) return r;
     osvos_wgrad_set_phase(2);
     r = wgrad_launch(xin, g, l, h, w, aux2);
     osvos_wgrad_set_phase(0);
@@ -670,8 +658,9 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
       f1_4[i] = reinterpret_cast<const float*>(at(wbuf, P.f1[i]));
       f16_4[i] = reinterpret_cast<const float*>(at(wbuf, P.f16[i]));
       wd4[i] = reinterpret_cast<const float*>(at(wbuf, P.wd[i]));
-      dprep4[i] = reinterpret_cast<float*>(at(ws, L.dprep[i]));
-      dprepb4[i] = store ? at(ws, L.dprep_b[i]) : nullptr;
+      const Tensor dprep = L.view(ws, L.dprep[i], L.dprep_b[i]);
+      dprep4[i] = reinterpret_cast<float*>(dprep.f);
+      dprepb4[i] = dprep.b;
       acc4[i] = acc + (size_t)i * OSVOS_HEAD_MAX_BLOCKS * 34;
       part[i] = acc4[i];
       nblk[i] = osvos_head_bwd_blocks(N, L.hs[i + 1], L.ws[i + 1], i);
@@ -682,16 +671,17 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
   } else
   for (int i = 0; i < 4; ++i) {
     const int si = i + 1;
+    const Tensor dprep = L.view(ws, L.dprep[i], L.dprep_b[i]);
     if (generic)
       rc = osvos_head_bwd_generic(reinterpret_cast<const float*>(at(ws, L.prep[i])), douts[i], dfused, reinterpret_cast<const float*>(at(wbuf, P.f1[i])),
                                   reinterpret_cast<const float*>(at(wbuf, P.weff[i])), reinterpret_cast<const float*>(at(wbuf, P.wd[i])),
-                                  reinterpret_cast<float*>(at(ws, L.dprep[i])), store ? at(ws, L.dprep_b[i]) : nullptr, acc + (size_t)i * OSVOS_HEAD_MAX_BLOCKS * 34,
+                                  reinterpret_cast<float*>(dprep.f), dprep.b, acc + (size_t)i * OSVOS_HEAD_MAX_BLOCKS * 34,
                                   N, H, W, L.hs[si], L.ws[si], i, stream);
     else
       rc = osvos_head_bwd_f32(reinterpret_cast<const float*>(at(ws, L.prep[i])), douts[i], dfused, reinterpret_cast<const float*>(at(wbuf, P.f1[i])),
                         reinterpret_cast<const float*>(at(wbuf, P.f16[i])), reinterpret_cast<const float*>(at(wbuf, P.wd[i])),
-                        reinterpret_cast<const float*>(at(wbuf, P.wf)) + 16 * i, reinterpret_cast<float*>(at(ws, L.dprep[i])),
-                        store ? at(ws, L.dprep_b[i]) : nullptr, acc + (size_t)i * OSVOS_HEAD_MAX_BLOCKS * 34,
+                        reinterpret_cast<const float*>(at(wbuf, P.wf)) + 16 * i, reinterpret_cast<float*>(dprep.f),
+                        dprep.b, acc + (size_t)i * OSVOS_HEAD_MAX_BLOCKS * 34,
                         N, H, W, L.hs[si], L.ws[si], i, stream);
     if (rc) return rc;
     part[i] = acc + (size_t)i * OSVOS_HEAD_MAX_BLOCKS * 34;
@@ -707,12 +697,7 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
   // is read off `stream`).  The generic head's extra reductions stay on `stream`.
   OSVOS_ENV_INT(fin_side, "OSVOS_FINALIZE_SIDE", 1);      // A/B switch (0: on `stream`, as rounds 1-5)
   hipStream_t fin = (!generic && two && fin_side) ? aux2 : stream;
-  if (fin != stream) {
-    hipEvent_t e = evp.next();
-    if (!e) return -1;
-    OSVOS_HIP_CHECK(hipEventRecord(e, stream));
-    OSVOS_HIP_CHECK(hipStreamWaitEvent(fin, e, 0));
-  }
+  if (fin != stream && (rc = stream_wait(fin, stream))) return rc;
   rc = osvos_head_grads_finalize(part, nblk, fb_part, fb_nblk, grads, accumulate, have_side ? 1 : 0, fin);
   if (rc) return rc;
   if (generic) {
@@ -751,14 +736,7 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
   for (int l = 0; l < kNumConv; ++l) bwd_flops += 2.0 * conv_flops(N, L.hs[d[l].stage], L.ws[d[l].stage], d[l].cin, d[l].cout);
   if (dx_nchw == nullptr) bwd_flops -= conv_flops(N, H, W, 3, d[0].cout);
   ProfScope ps(OSVOS_PROF_CONV_BWD, bwd_flops, stream);
-  auto signal = [&]() -> int {          // aux may consume everything `stream` has produced so far
-    if (!two) return 0;
-    hipEvent_t e = evp.next();
-    if (!e) return -1;
-    OSVOS_HIP_CHECK(hipEventRecord(e, stream));
-    OSVOS_HIP_CHECK(hipStreamWaitEvent(aux, e, 0));
-    return 0;
-  };
+  auto signal = [&]() -> int { return two ? stream_wait(aux, stream) : 0; };      // aux may consume everything `stream` has produced so far
   if ((rc = signal())) return rc;       // dprep[0..3] ready
   // the four skinny side_prep weight gradients head the weight-gradient stream (on the third stream beside the first trunk gradients they
   // measured +0.1-0.25 %, inside the noise: round 3)
@@ -766,8 +744,8 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
     const int si = i + 1, sl = kNumTrunk + i, h = L.hs[si], w = L.ws[si];
     const int lx = last_of_stage(si);
     if (grads[d[sl].w_param] != nullptr && !(dbg_skip() & 16)) {
-      const void* dp = store ? at(ws, L.dprep_b[i]) : at(ws, L.dprep[i]);      // (store mode: bf16 x and bf16 dprep)
-      rc = wgrad(at(ws, L.act[lx]), dp, sl, h, w);
+      const Tensor dprep = L.view(ws, L.dprep[i], L.dprep_b[i]);
+      rc = wgrad(at(ws, L.act[lx]), dprep.b ? dprep.b : dprep.f, sl, h, w);      // (store mode: bf16 x and bf16 dprep)
       if (rc) return rc;
     }
   }
@@ -780,29 +758,26 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
   // configs[2] and 300 vs 306 with the two-piece backward (both slightly worse): same-box alternating rounds, tools/ab_env.sh.
   OSVOS_ENV_INT(side_aside, "OSVOS_SIDE_DGRAD_ASIDE", 0);
   hipStream_t sds = (two && side_aside) ? aux2 : stream;
-  hipEvent_t side_ev[3] = {nullptr, nullptr, nullptr};
-  if (sds != stream) {
-    hipEvent_t e = evp.next();
-    if (!e) return -1;
-    OSVOS_HIP_CHECK(hipEventRecord(e, stream));      // dprep[0..3] ready
-    OSVOS_HIP_CHECK(hipStreamWaitEvent(sds, e, 0));
-  }
+  hipEvent_t side_ev[3] = {};
+  if (sds != stream && (rc = stream_wait(sds, stream))) return rc;      // dprep[0..3] ready
   for (int i = 3; i >= 0; --i) {
     const int si = i + 1, sl = kNumTrunk + i, h = L.hs[si], w = L.ws[si];
     const int lx = last_of_stage(si);
     // stage 4 has no pool after it: its ReLU mask is applied right here and the result is the
     // upstream gradient of conv5_3; stages 1-3 are merged in maxpool2x2_bwd below
-    void* dst = (i == 3) ? f32(L.dy[lx]) : f32(L.dside[i]);
-    void* dst_b = (i == 3) ? sh(L.dy_b[lx]) : (store ? at(ws, L.dside_b[i]) : nullptr);
     if (dbg_skip() & 8) continue;
     hipStream_t st = (i == 3) ? stream : sds;
-    rc = conv_main(at(ws, L.dprep[i]), store ? at(ws, L.dprep_b[i]) : nullptr, at(wbuf, P.dgrad[sl]), nullptr, (i == 3) ? mk32(L.act[lx]) : nullptr,
-                   (i == 3) ? mk16(L.act_b[lx]) : nullptr, dst, dst_b, N, h, w, 16, d[sl].cin, d[sl].cin, 0, dtype, nullptr, st,
-                   P.dgrad3[sl] != (size_t)-1 ? at(wbuf, P.dgrad3[sl]) : nullptr, nullptr,
-                   (i == 3 && L.bits[lx] != (size_t)-1) ? at(ws, L.bits[lx]) : nullptr);
+    ConvCall c = conv_of(d[sl], sl, true, wbuf, P, N, h, w, st);
+    set_x(c, L.view(ws, L.dprep[i], L.dprep_b[i]));
+    set_y(c, L.view(ws, (i == 3) ? L.dy[lx] : L.dside[i]));
+    if (i == 3) {
+      set_mask(c, L.view(ws, L.act[lx]));
+      if (L.bits[lx] != (size_t)-1) c.mask_bits = reinterpret_cast<const unsigned*>(at(ws, L.bits[lx]));
+    }
+    rc = conv_main(c, dtype);
     if (rc) return rc;
     if (st != stream) {
-      side_ev[i] = evp.next();
+      side_ev[i] = event_pool().next();
       if (!side_ev[i]) return -1;
       OSVOS_HIP_CHECK(hipEventRecord(side_ev[i], st));
     }
@@ -816,7 +791,7 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
     const bool first_of_stage = (l == 0) || d[l - 1].stage != si;
     const void* xin = first_of_stage ? (si == 0 ? at(ws, L.xin) : at(ws, L.pooled[si])) : at(ws, L.act[l - 1]);
     const void* g = at(ws, L.dy[l]);
-    const void* g_b = sh(L.dy_b[l]);
+    const Tensor dy = L.view(ws, L.dy[l]);
     // (Measured twice in round 3: conv1_1's weight gradient on the third stream BESIDE the input gradient instead of behind it is neutral at
     //  batch 1 (f32x3) and 0.5-1 % slower at batch 12 (bf16) -- not built in.)
     // conv1_1's weight gradient is the LAST piece of work of the step and the weight-gradient stream is the one that finishes last (conv1_2's
@@ -833,15 +808,18 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
       } else if (dx_nchw != nullptr && (dtype == OSVOS_F32 || dtype == OSVOS_F32_X3)) {
         rc = osvos_conv3x3_dgrad_c3_f32(reinterpret_cast<const float*>(g), reinterpret_cast<const float*>(at(wbuf, P.dgrad[0])), dx_nchw, N, h, w, d[0].cout, stream);
         if (rc) return rc;
-      } else if (dx_nchw != nullptr && g_b != nullptr && d[0].cout == 64) {
+      } else if (dx_nchw != nullptr && dy.b != nullptr && d[0].cout == 64) {
         // bf16 trunk tensors: the whole 64-channel halo tile once through LDS, filter rows on the matrix pipe, straight into NCHW (dgrad_c3.hip;
         // same-box A/B at batch 12, two alternating rounds: 1118.7 / 1114.1 frames/s against 1099.1 / 1106.4 with the 32-cout tile + layout
         // kernel below; the fp32-FMA kernel fed with bf16, a first attempt of the round, read 1073-1081 and is gone)
-        rc = osvos_conv3x3_dgrad_c3_bf16mfma(g_b, at(wbuf, P.dgrad[0]), dx_nchw, N, h, w, d[0].cout, stream);
+        rc = osvos_conv3x3_dgrad_c3_bf16mfma(dy.b, at(wbuf, P.dgrad[0]), dx_nchw, N, h, w, d[0].cout, stream);
         if (rc) return rc;
       } else if (dx_nchw != nullptr) {
-        rc = conv_main(g, g_b, at(wbuf, P.dgrad[0]), nullptr, nullptr, nullptr, at(ws, L.dxin), nullptr, N, h, w, d[0].cout, 3, 4, 0, dtype,
-                       nullptr, stream, P.dgrad3[0] != (size_t)-1 ? at(wbuf, P.dgrad3[0]) : nullptr);
+        ConvCall c = conv_of(d[0], 0, true, wbuf, P, N, h, w, stream);
+        set_x(c, dy);
+        c.y = reinterpret_cast<float*>(at(ws, L.dxin));
+        c.y_cs = 4;
+        rc = conv_main(c, dtype);
         if (rc) return rc;
         rc = osvos_nhwc_to_nchw(at(ws, L.dxin), dx_nchw, N, 3, H, W, 4, dtype, stream);
         if (rc) return rc;
@@ -853,32 +831,34 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
       }
       break;
     }
+    ConvCall c = conv_of(d[l], l, true, wbuf, P, N, h, w, stream);      // the data gradient of layer l; below: where it goes and what masks it
+    set_x(c, dy);
+    c.part_ws = at(ws, L.conv_part);
+    c.sk_ws = sk_bwd;
     if (first_of_stage) {
       // through the pool into the previous stage's output (+ that stage's side branch, + ReLU mask)
-      rc = conv_main(g, g_b, at(wbuf, P.dgrad[l]), nullptr, nullptr, nullptr, f32(L.dpool[si]), store ? at(ws, L.dpool_b[si]) : nullptr, N, h, w,
-                     d[l].cout, d[l].cin, d[l].cin, 0, dtype, at(ws, L.conv_part), stream, P.dgrad3[l] != (size_t)-1 ? at(wbuf, P.dgrad3[l]) : nullptr,
-                     nullptr, nullptr, nullptr, nullptr, sk_bwd);
-      if (rc) return rc;
+      set_y(c, L.view(ws, L.dpool[si]));
+      if ((rc = conv_main(c, dtype))) return rc;
       const int ps2 = si - 1;
       const void* dside = ps2 >= 1 ? at(ws, L.dside[ps2 - 1]) : nullptr;
       if (dbg_skip() & 2) continue;
       if (ps2 >= 1 && side_ev[ps2 - 1] != nullptr) OSVOS_HIP_CHECK(hipStreamWaitEvent(stream, side_ev[ps2 - 1], 0));      // dside written on the reduce stream
       if (store && L.pool_code[si] != (size_t)-1)      // one code byte per pooled element instead of the pool's four inputs
-        rc = osvos_maxpool2x2_bwd_bf16_code(at(ws, L.pool_code[si]), at(ws, L.dpool_b[si]), dside, at(ws, L.dy_b[l - 1]), N, L.hs[ps2], L.ws[ps2],
+        rc = osvos_maxpool2x2_bwd_bf16_code(at(ws, L.pool_code[si]), at(ws, L.dpool[si]), dside, at(ws, L.dy[l - 1]), N, L.hs[ps2], L.ws[ps2],
                                             kStageC[ps2], stream);
       else if (store)
-        rc = osvos_maxpool2x2_bwd_bf16(at(ws, L.act_b[l - 1]), at(ws, L.dpool_b[si]), dside, at(ws, L.dy_b[l - 1]), N, L.hs[ps2], L.ws[ps2],
+        rc = osvos_maxpool2x2_bwd_bf16(at(ws, L.act[l - 1]), at(ws, L.dpool[si]), dside, at(ws, L.dy[l - 1]), N, L.hs[ps2], L.ws[ps2],
                                        kStageC[ps2], stream);
       else
         rc = osvos_maxpool2x2_bwd_f32(reinterpret_cast<const float*>(at(ws, L.act[l - 1])), reinterpret_cast<const float*>(at(ws, L.dpool[si])),
-                                      reinterpret_cast<const float*>(dside), reinterpret_cast<float*>(at(ws, L.dy[l - 1])), sh(L.dy_b[l - 1]), N,
+                                      reinterpret_cast<const float*>(dside), reinterpret_cast<float*>(at(ws, L.dy[l - 1])), nullptr, N,
                                       L.hs[ps2], L.ws[ps2], kStageC[ps2], stream);
       if (rc) return rc;
     } else {
-      rc = conv_main(g, g_b, at(wbuf, P.dgrad[l]), nullptr, mk32(L.act[l - 1]), mk16(L.act_b[l - 1]), f32(L.dy[l - 1]), sh(L.dy_b[l - 1]), N, h, w,
-                     d[l].cout, d[l].cin, d[l].cin, 0, dtype, at(ws, L.conv_part), stream, P.dgrad3[l] != (size_t)-1 ? at(wbuf, P.dgrad3[l]) : nullptr,
-                     nullptr, L.bits[l - 1] != (size_t)-1 ? at(ws, L.bits[l - 1]) : nullptr, nullptr, nullptr, sk_bwd);
-      if (rc) return rc;
+      set_y(c, L.view(ws, L.dy[l - 1]));
+      set_mask(c, L.view(ws, L.act[l - 1]));
+      if (L.bits[l - 1] != (size_t)-1) c.mask_bits = reinterpret_cast<const unsigned*>(at(ws, L.bits[l - 1]));
+      if ((rc = conv_main(c, dtype))) return rc;
     }
   }
   if ((rc = join())) return rc;         // everything is back on `stream` when the call returns

@@ -625,9 +625,9 @@ size_t osvos_wgrad_bf16_ws_bytes(int N, int H, int W, int Cin_s, int Cout) {
 }
 
 // xb = 0: x and dy fp32; xb = 1: both bf16
-int osvos_conv3x3_wgrad_bf16mfma_io(const void* x, const void* dy, int xb, void* ws, float* dw, float* db,
-                                    int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
-                                    int accumulate, hipStream_t stream) {
+int osvos_conv3x3_wgrad_bf16mfma(const void* x, const void* dy, int xb, void* ws, float* dw, float* db,
+                                 int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
+                                 int accumulate, hipStream_t stream) {
   OSVOS_ARG_CHECK(x && dy && ws && dw, "wgrad bf16: null pointer");
   OSVOS_ARG_CHECK(osvos_wgrad_bf16_applicable(Cin_s, Cout) && Cin == Cin_s && Cout_s % 4 == 0, "wgrad bf16: unsupported shape");
   OSVOS_ARG_CHECK((long)H * W * Cin_s < (1L << 29) && (long)H * W * Cout_s < (1L << 29), "wgrad bf16: image too large for 31-bit byte offsets");
@@ -714,9 +714,3 @@ int osvos_conv3x3_wgrad_bf16mfma_io(const void* x, const void* dy, int xb, void*
 #ifdef OSVOS_WGRAD_PROF
 extern "C" void osvos_debug_set_wgrad_prof_bf16(unsigned long long* p) { g_wgrad_prof = p; }
 #endif
-
-int osvos_conv3x3_wgrad_bf16mfma(const float* x, const float* dy, void* ws, float* dw, float* db,
-                                 int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
-                                 int accumulate, hipStream_t stream) {
-  return osvos_conv3x3_wgrad_bf16mfma_io(x, dy, 0, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s, accumulate, stream);
-}

@@ -1,6 +1,6 @@
 // Native (no Python) timing + spot check of the 3x3 convolution kernels: seconds of GPU time per run.
 //   conv_probe bf16|f32|x3ps N H W Cin Cout tile[,tile...]      (tile -1 = the library's choice; x3ps: f32x3 tile ids (+100: XCD-local block map) on the PRE-SPLIT pack)
-// bf16: bf16 NHWC in, bf16 NHWC out (what the network's bf16 mode runs: osvos_conv3x3_bf16mfma_io); f32: osvos_conv3x3_f32_ws.
+// bf16: bf16 NHWC in, bf16 NHWC out (what the network's bf16 mode runs: osvos_conv3x3_bf16mfma); f32: osvos_conv3x3_f32.
 // Prints per tile the average of 20 launches and the largest relative error of 256 output samples against a double-precision
 // restatement on the host (operands rounded the way the kernel rounds them), so a variant that is fast but wrong shows up here.
 #include <hip/hip_runtime.h>
@@ -50,9 +50,14 @@ int main(int argc, char** argv) {
   }
   const int ks_env = getenv("PROBE_KSPLIT") ? atoi(getenv("PROBE_KSPLIT")) : 0;
   auto launch = [&](int tile) {
-    if (x3ps) return osvos_conv3x3_f32x3_ps((const float*)dx, nullptr, dwp3, db, nullptr, (float*)dy, N, H, W, Cin, Cout, Cout, 1, tile, ks_env, dpart, 0);
-    return bf ? osvos_conv3x3_bf16mfma_io(dx, 1, dwp, db, nullptr, 0, nullptr, dy, N, H, W, Cin, Cout, Cout, 1, tile, 0)
-              : osvos_conv3x3_f32_ws((const float*)dx, (const float*)dwp, db, nullptr, (float*)dy, N, H, W, Cin, Cout, Cout, 1, tile, dpart, 0);
+    ConvCall c;
+    c.x = dx; c.x_bf16 = bf ? 1 : 0; c.bias = db;
+    c.N = N; c.H = H; c.W = W; c.Cin = Cin; c.Cout = c.y_cs = Cout; c.relu = 1; c.tile = tile;
+    if (bf) { c.wpk = dwp; c.y_bf16 = dy; return osvos_conv3x3_bf16mfma(c); }
+    c.y = (float*)dy; c.part_ws = dpart;
+    if (x3ps) { c.wpk3 = dwp3; c.ksplit = ks_env; return osvos_conv3x3_f32x3(c); }
+    c.wpk = dwp;
+    return osvos_conv3x3_f32(c);
   };
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   const double fl = 2.0 * N * H * W * (double)Cout * Cin * 9;

@@ -41,11 +41,11 @@ static void run(int N, int H, int W, int Cin, int Cout) {
   for (int phase = 1; phase >= 0; --phase) {        // 1: the MFMA kernel alone, 0: kernel + slab reduce
     osvos_wgrad_set_phase(phase);
     for (int i = 0; i < 3; ++i)
-      if (osvos_conv3x3_wgrad_bf16mfma_io(dx, ddy, 1, ws, dw, db, N, H, W, Cin, Cin, Cout, Cout, 0, 0)) { fprintf(stderr, "launch failed: %s\n", osvos_last_error()); exit(1); }
+      if (osvos_conv3x3_wgrad_bf16mfma(dx, ddy, 1, ws, dw, db, N, H, W, Cin, Cin, Cout, Cout, 0, 0)) { fprintf(stderr, "launch failed: %s\n", osvos_last_error()); exit(1); }
     CK(hipDeviceSynchronize());
     const int reps = getenv("PROBE_REPS") ? atoi(getenv("PROBE_REPS")) : 10;
     CK(hipEventRecord(e0, 0));
-    for (int i = 0; i < reps; ++i) osvos_conv3x3_wgrad_bf16mfma_io(dx, ddy, 1, ws, dw, db, N, H, W, Cin, Cin, Cout, Cout, 0, 0);
+    for (int i = 0; i < reps; ++i) osvos_conv3x3_wgrad_bf16mfma(dx, ddy, 1, ws, dw, db, N, H, W, Cin, Cin, Cout, Cout, 0, 0);
     CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
     float ms; CK(hipEventElapsedTime(&ms, e0, e1));
     const double fl = 2.0 * N * H * W * (double)Cout * Cin * 9;
