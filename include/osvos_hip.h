@@ -362,6 +362,18 @@ int osvos_augment_frame(const unsigned char* img_bgr, const unsigned char* label
  *   counts = 2 N unsigned long long. */
 int osvos_mask_to_bytes(const float* logits, unsigned char* out, void* scratch, long count, int N, void* stream);
 int osvos_mask_iou_counts(const float* logits, const float* gt, void* counts, long count, int N, float logit_threshold, void* stream);
+/* DAVIS J and F in one call (train_online.py:181-189 writes PNGs and leaves both measures to the external DAVIS toolkit; this stands in
+ * for its db_eval_iou + db_eval_boundary).  logits, gt: N frames of H x W floats, read once; P = logit > logit_threshold, G = gt > 0.5.
+ * Boundary map B(M): a pixel is set when M differs from its right, lower or lower-right neighbour (last row: right only, last column:
+ * lower only, corner never); a pixel of one boundary map is matched when the other has a pixel with dy*dy + dx*dx <= radius*radius.
+ * counts: 6 unsigned long long per frame {|P & G|, |P | G|, |B(P)|, |B(G)|, matched of B(P), matched of B(G)} -- the first two are
+ *   osvos_mask_iou_counts' -- accumulate == 0: overwritten; != 0: added to (the caller zeroed it once).
+ * ws: osvos_boundary_ws_bytes(N, H, W) bytes (two one-bit-per-pixel maps per frame), contents irrelevant on entry.  ws and counts 8-byte
+ *   aligned.  radius: 1..OSVOS_BOUNDARY_MAX_RADIUS pixels (DAVIS: ceil(0.008 * image diagonal); 8 at 854x480, 36 at 3840x2160); N <= 65535. */
+#define OSVOS_BOUNDARY_MAX_RADIUS 64
+size_t osvos_boundary_ws_bytes(int N, int H, int W);
+int osvos_mask_jf_counts(const float* logits, const float* gt, void* ws, void* counts, int N, int H, int W, float logit_threshold, int radius,
+                         int accumulate, void* stream);
 
 /* ---- fused SGD (torch.optim.SGD semantics, train_online.py:79-88,147) ----------------------
  * for each i: d = g + wd*p; buf = first ? d : momentum*buf + d; p -= lr*buf      (flat tensors) */

@@ -99,6 +99,8 @@ PROTOTYPES = {
     "osvos_augment_frame": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "osvos_mask_to_bytes": (_i, [_vp, _vp, _vp, _l, _i, _vp]),
     "osvos_mask_iou_counts": (_i, [_vp, _vp, _vp, _l, _i, _f, _vp]),
+    "osvos_boundary_ws_bytes": (_sz, [_i, _i, _i]),
+    "osvos_mask_jf_counts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp]),
     "osvos_sgd_step": (_i, [_vp, _vp, _vp, _l, _f, _f, _f, _i, _vp]),
     "osvos_sgd_step_multi": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp]),
     "osvos_prof_start": (_i, [_i]),

@@ -34,7 +34,7 @@ import torch
 
 import networks.vgg_osvos as vo
 from layers.osvos_layers import sigmoid_np  # noqa: F401  (kept importable like the reference)
-from osvos_pytorch_amd.results import davis_statistics, jaccard, save_masks
+from osvos_pytorch_amd.results import SequenceEvaluator, save_masks
 from mypath import Path
 from osvos_pytorch_amd.parallel import shard_indices
 from osvos_pytorch_amd.train_common import TrainLoop, init_distributed, make_sgd
@@ -194,7 +194,7 @@ def main():
         save_dir_res = os.path.join(save_dir, 'Results', seq_name)
         os.makedirs(save_dir_res, exist_ok=True)
         print('Testing Network')
-        js = []
+        evaluator = SequenceEvaluator()      # J and F counts stay on the device: one read-back after the last frame
         if args.test_precision:
             net.set_precision(args.test_precision)      # (re-packs the weights once: the FP16-pair packs are another format)
         with torch.no_grad():
@@ -204,10 +204,14 @@ def main():
                 # sigmoid + scipy<=1.1 imsave byte scaling on the device, PNG written by osvos_pytorch_amd.results (reference :181-187)
                 save_masks(outputs[-1], [os.path.join(save_dir_res, os.path.basename(fname[jj]) + '.png') for jj in range(int(img.size()[0]))])
                 if 'gt' in sample:
-                    js.extend(jaccard(outputs[-1], sample['gt'].to(device)))
-        if js:
-            st = davis_statistics(js)
-            print('J (region similarity) on %s: mean %.4f recall %.4f decay %.4f over %d frames' % (seq_name, st['mean'], st['recall'], st['decay'], len(js)))
+                    evaluator.add(outputs[-1], sample['gt'].to(device))
+        if evaluator.frames:
+            res = evaluator.summary()
+            st = res['J']
+            print('J (region similarity) on %s: mean %.4f recall %.4f decay %.4f over %d frames' % (seq_name, st['mean'], st['recall'], st['decay'], res['frames']))
+            st = res['F']
+            print('F (contour accuracy) on %s: mean %.4f recall %.4f decay %.4f over %d frames' % (seq_name, st['mean'], st['recall'], st['decay'], res['frames']))
+            print('J&F on %s: %.4f' % (seq_name, res['J&F']))
 
 
 if __name__ == '__main__':
