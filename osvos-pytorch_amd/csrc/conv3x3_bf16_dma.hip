@@ -19,6 +19,8 @@
 // tensor traffic itself).  Here the workgroups are PERSISTENT (one per CU, tiles b, b + G, ... all of ONE cout tile), the filter is loaded ONCE
 // into its own LDS region (9 x Cin/8 x 64 slots = 73.7 KB), only the 16-channel activation chunks rotate (3 buffers of 21.5 KB, DMA two chunks
 // ahead, crossing tile boundaries), and the next tile's first chunks are in flight while the epilogue stores drain.
+#include <algorithm>
+
 #include "common.h"
 #include "maskbits.h"
 #include "kernels.h"
@@ -418,6 +420,11 @@ __global__ __launch_bounds__(64 * 2 * WGM, WGM == 4 ? 2 : 1) void conv3x3_bf16_d
   }
 }
 
+int dma_env_grid() {      // (outside the template: read once per process, not once per variant)
+  OSVOS_ENV_INT(g, "OSVOS_DMA_GRID", 0);
+  return g;
+}
+
 template <int NB, int WGM, int CINR = 0>
 int launch(const DmaArgs& a0, int persist, hipStream_t stream) {
   using C = DmaCfg<NB, WGM, CINR>;
@@ -452,7 +459,11 @@ int launch(const DmaArgs& a0, int persist, hipStream_t stream) {
   const int gmul = 8 * (CINR > 0 ? a.nct : 1);
   const long gmax = (long)n_cu / gmul * gmul;
   OSVOS_ARG_CHECK(gmax > 0, "conv3x3 bf16 dma: %d cout tiles do not fit a persistent grid of %d workgroups", a.nct, n_cu);
-  const long grid = persist && blocks > gmax ? gmax : blocks;
+  // OSVOS_DMA_GRID (tests; persistent forms only): 0 = one workgroup per CU, n > 0 = about n workgroups with many tiles each, -1 = one tile per workgroup
+  const int env_grid = persist ? dma_env_grid() : 0;
+  long grid = persist && blocks > gmax ? gmax : blocks;
+  if (env_grid > 0) grid = std::min(blocks, std::max((long)gmul, (long)env_grid / gmul * gmul));
+  else if (env_grid < 0) grid = blocks;
   hipLaunchKernelGGL((conv3x3_bf16_dma_kernel<NB, WGM, CINR>), dim3((unsigned)grid), dim3(C::NT), C::LDS_BYTES, stream, a);
   OSVOS_LAUNCH_CHECK();
   return 0;

@@ -20,6 +20,8 @@
 //   * counts `s_waitcnt vmcnt` EXACTLY (stores of the epilogue pieces may stay in flight across barriers; only the activation chunk that is
 //     needed next has to have landed).
 // Results are bit-identical to the other tiles' epilogues (same fp32 bias add, same RNE rounding; ReLU and rounding commute).
+// Everything from a workgroup's second tile on (pending set, wait budgets of phases 1 / 2, cursor carries, dead tiles) is pinned by tests/test_gpu_persistent_tiles.py.
+#include <algorithm>
 #include <type_traits>
 
 #include "common.h"
@@ -541,6 +543,11 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_bf16_p64_kernel(P64Args a) {
 #endif
 }
 
+int p64_env_grid() {      // (outside the template: read once per process, not once per mode)
+  OSVOS_ENV_INT(g, "OSVOS_P64_GRID", 0);
+  return g;
+}
+
 template <int MODE>
 int launch(const P64Args& a0, hipStream_t stream) {
   static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};
@@ -563,7 +570,12 @@ int launch(const P64Args& a0, hipStream_t stream) {
   const int gmul = 8 * a.nct;
   const long gmax = (long)n_cu / gmul * gmul;
   OSVOS_ARG_CHECK(gmax > 0, "conv3x3 bf16 p64: %d cout tiles do not fit a persistent grid of %d workgroups", a.nct, n_cu);
-  const long grid = blocks > gmax ? gmax : blocks;
+  // OSVOS_P64_GRID (tests): 0 = one workgroup per CU, n > 0 = about n workgroups with many tiles each, -1 = one tile per workgroup (nothing persistent;
+  // legal because no workgroup waits for another)
+  const int env_grid = p64_env_grid();
+  long grid = blocks > gmax ? gmax : blocks;
+  if (env_grid > 0) grid = std::min(blocks, std::max((long)gmul, (long)env_grid / gmul * gmul));
+  else if (env_grid < 0) grid = blocks;
   hipLaunchKernelGGL((conv3x3_bf16_p64_kernel<MODE>), dim3((unsigned)grid), dim3(NT), LDS_BYTES, stream, a);
   OSVOS_LAUNCH_CHECK();
   return 0;
