@@ -375,6 +375,20 @@ size_t osvos_boundary_ws_bytes(int N, int H, int W);
 int osvos_mask_jf_counts(const float* logits, const float* gt, void* ws, void* counts, int N, int H, int W, float logit_threshold, int radius,
                          int accumulate, void* stream);
 
+/* ---- multi-object results (DAVIS 2017: one network per object, one indexed label map per frame, J and F per object) ----------
+ * osvos_merge_objects: logits [K][N][H][W] fp32 (the fused outputs of K per-object networks for N frames) -> labels [N][H][W] uint8.
+ *   Per pixel m = max_k logits[k] (fmax: a NaN logit never wins); label = 0 when `m > logit_threshold` is false (all NaN included), else
+ *   1 + the lowest k with logits[k] == m.  Decided on the logits, never on a sigmoid.  Every logit is read once; no workspace.
+ * osvos_labels_jf_counts: pred, gt [N][H][W] uint8 label maps, read once.  For frame n and object id k = 1..K row n K + (k - 1) of counts
+ *   [N][K][6] unsigned long long receives the six counts of osvos_mask_jf_counts with P = (pred == k), G = (gt == k); label 0 and labels
+ *   above K belong to no object.  accumulate, radius, alignment: as osvos_mask_jf_counts.  ws: osvos_labels_jf_ws_bytes(N, K, H, W) bytes
+ *   (two one-bit-per-pixel maps per frame and object), contents irrelevant on entry.  1 <= K <= OSVOS_MAX_OBJECTS, N K <= 65535. */
+#define OSVOS_MAX_OBJECTS 16
+int osvos_merge_objects(const float* logits, unsigned char* labels, int N, int K, int H, int W, float logit_threshold, void* stream);
+size_t osvos_labels_jf_ws_bytes(int N, int K, int H, int W);
+int osvos_labels_jf_counts(const unsigned char* pred, const unsigned char* gt, void* ws, void* counts, int N, int K, int H, int W, int radius,
+                           int accumulate, void* stream);
+
 /* ---- fused SGD (torch.optim.SGD semantics, train_online.py:79-88,147) ----------------------
  * for each i: d = g + wd*p; buf = first ? d : momentum*buf + d; p -= lr*buf      (flat tensors) */
 int osvos_sgd_step(float* p, const float* g, float* buf, long count, float lr, float momentum,

@@ -24,6 +24,7 @@ X3_HALF_PIECES = 0x1000     # OSVOS_FLAG_X3_HALF_PIECES: precision 'fp32h2' (two
 X3_HALF_PIECES_BWD = 0x2000 # OSVOS_FLAG_X3_HALF_PIECES_BWD: net_pack only -- data-gradient packs in the FP16-pair format
 BF16_W2 = 0x4000            # OSVOS_FLAG_BF16_W2: precision 'bf16w2' (dtype F32_BF16MFMA only) -- two-piece forward weight packs, two products per product
 INFERENCE = 0x400           # OSVOS_FLAG_INFERENCE: osvos_net_forward writes nothing only a backward would read (sign bits, pool codes)
+MAX_OBJECTS = 16            # OSVOS_MAX_OBJECTS: object ids per label map (osvos_merge_objects, osvos_labels_jf_counts)
 GENERIC_DECONV = 0x100      # OSVOS_FLAG_GENERIC_DECONV: OR-ed into the dtype of the osvos_net_* calls
 NPARAMS = 52
 
@@ -101,6 +102,9 @@ PROTOTYPES = {
     "osvos_mask_iou_counts": (_i, [_vp, _vp, _vp, _l, _i, _f, _vp]),
     "osvos_boundary_ws_bytes": (_sz, [_i, _i, _i]),
     "osvos_mask_jf_counts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp]),
+    "osvos_merge_objects": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "osvos_labels_jf_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "osvos_labels_jf_counts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "osvos_sgd_step": (_i, [_vp, _vp, _vp, _l, _f, _f, _f, _i, _vp]),
     "osvos_sgd_step_multi": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp]),
     "osvos_prof_start": (_i, [_i]),

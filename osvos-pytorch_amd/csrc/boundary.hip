@@ -16,6 +16,7 @@
 // soon as every pixel of the word has its match (a good mask matches at dy = 0).  Counts are wave-uniform popcounts, summed per workgroup,
 // one 64-bit atomic add per workgroup and count: integer sums, so the result does not depend on the order.
 #include "common.h"
+#include "boundary.h"
 
 namespace {
 
@@ -162,6 +163,19 @@ __global__ __launch_bounds__(64 * kMatchWaves) void jf_match_kernel(const u64* _
 
 }  // namespace
 
+// the match launch on `frames` bitmap pairs (boundary.h); the callers have checked frames <= 65535 and the radius
+int osvos_jf_match(const char* who, const unsigned long long* bits, unsigned long long* counts, int frames, int H, int W, int radius, hipStream_t stream) {
+  const int wpr = (W + 63) / 64;
+  const int col_tiles = ceil_div(wpr, kTileWords);
+  const long tiles = (long)ceil_div(H, kTileRows) * col_tiles;
+  OSVOS_ARG_CHECK(tiles <= 0x7fffffffL, "%s: %d x %d is too large", who, H, W);
+  const size_t lds = sizeof(u64) * 2 * (kTileRows + 2 * radius) * kWinWords;             // 7 KB at r = 8, 39 KB at r = 64
+  hipLaunchKernelGGL(jf_match_kernel, dim3((unsigned)tiles, (unsigned)frames), dim3(64 * kMatchWaves), lds, stream, bits, H, W, wpr, radius, col_tiles,
+                     counts);
+  OSVOS_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" size_t osvos_boundary_ws_bytes(int N, int H, int W) {
   if (N < 1 || H < 1 || W < 1) return 0;
   return (size_t)2 * N * H * ((W + 63) / 64) * sizeof(u64);
@@ -176,9 +190,6 @@ extern "C" int osvos_mask_jf_counts(const float* logits, const float* gt, void* 
   OSVOS_ARG_CHECK(radius >= 1 && radius <= kMaxRadius, "mask_jf_counts: radius %d (1..%d pixels)", radius, kMaxRadius);
   const int wpr = (W + 63) / 64;
   const long words = (long)H * wpr;
-  const int col_tiles = ceil_div(wpr, kTileWords);
-  const long tiles = (long)ceil_div(H, kTileRows) * col_tiles;
-  OSVOS_ARG_CHECK(tiles <= 0x7fffffffL, "mask_jf_counts: %d x %d is too large", H, W);
   u64* c = reinterpret_cast<u64*>(counts);
   u64* bits = reinterpret_cast<u64*>(ws);
   if (!accumulate) OSVOS_HIP_CHECK(hipMemsetAsync(c, 0, sizeof(u64) * 6 * N, stream));
@@ -186,8 +197,5 @@ extern "C" int osvos_mask_jf_counts(const float* logits, const float* gt, void* 
   g = g > 1024 ? 1024 : g;
   hipLaunchKernelGGL(jf_pack_kernel, dim3((unsigned)g, (unsigned)N), dim3(256), 0, stream, logits, gt, H, W, wpr, logit_threshold, bits, c);
   OSVOS_LAUNCH_CHECK();
-  const size_t lds = sizeof(u64) * 2 * (kTileRows + 2 * radius) * kWinWords;             // 7 KB at r = 8, 39 KB at r = 64
-  hipLaunchKernelGGL(jf_match_kernel, dim3((unsigned)tiles, (unsigned)N), dim3(64 * kMatchWaves), lds, stream, bits, H, W, wpr, radius, col_tiles, c);
-  OSVOS_LAUNCH_CHECK();
-  return 0;
+  return osvos_jf_match("mask_jf_counts", bits, c, N, H, W, radius, stream);
 }

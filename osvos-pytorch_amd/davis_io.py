@@ -20,10 +20,14 @@ import torch
 
 class DavisFrames(object):
     """File lists of reference dataloaders/davis_2016.py:36-63 (``train_seqs.txt`` / ``val_seqs.txt`` under db_root_dir, or one
-    sequence: first frame only when ``train``, every frame with the first annotation when not)."""
+    sequence: first frame only when ``train``, every frame with the first annotation when not).
 
-    def __init__(self, train=True, db_root_dir=None, seq_name=None):
-        self.train, self.db_root_dir, self.seq_name = train, db_root_dir, seq_name
+    ``indexed=True`` is the DAVIS 2017 reading: a palette ('P' mode) annotation comes back as its raw palette indices -- the object ids --
+    instead of the palette's grey values, and a test-mode sequence carries every annotation file that is on disk (matched to the frames by
+    file stem), so the whole sequence can be scored, not only frame 0."""
+
+    def __init__(self, train=True, db_root_dir=None, seq_name=None, indexed=False):
+        self.train, self.db_root_dir, self.seq_name, self.indexed = train, db_root_dir, seq_name, bool(indexed)
         if seq_name is None:
             img_list, labels = [], []
             with open(os.path.join(db_root_dir, ('train_seqs' if train else 'val_seqs') + '.txt')) as f:
@@ -38,6 +42,10 @@ class DavisFrames(object):
             img_list = [os.path.join('JPEGImages/480p/', str(seq_name), x) for x in names_img]
             name_label = sorted(os.listdir(os.path.join(db_root_dir, 'Annotations/480p/', str(seq_name))))
             labels = [os.path.join('Annotations/480p/', str(seq_name), name_label[0])] + [None] * (len(names_img) - 1)
+            if self.indexed and not train:
+                by_stem = dict((os.path.splitext(x)[0], x) for x in name_label)
+                rest = [by_stem.get(os.path.splitext(x)[0]) for x in names_img[1:]]
+                labels = labels[:1] + [os.path.join('Annotations/480p/', str(seq_name), x) if x else None for x in rest]
             if train:
                 img_list, labels = [img_list[0]], [labels[0]]
         if len(labels) != len(img_list):
@@ -58,8 +66,13 @@ class DavisFrames(object):
         lab = None
         if self.labels[idx] is not None:
             with Image.open(os.path.join(self.db_root_dir, self.labels[idx])) as im:
-                lab = np.ascontiguousarray(np.asarray(im.convert('L')))
+                lab = np.ascontiguousarray(np.asarray(im if self.indexed and im.mode == 'P' else im.convert('L')), dtype=np.uint8)
         return img, lab
+
+
+def n_objects(label):
+    """Number of objects of a sequence: the largest index in its first (indexed) annotation."""
+    return int(np.asarray(label).max()) if np.asarray(label).size else 0
 
 
 class ArrayFrames(object):

@@ -8,6 +8,10 @@ the PNG is written by a small zlib encoder (no PIL / scipy dependency), and the 
 image diagonal) -- with their mean / recall / decay statistics and the headline J&F are computed from device-side integer
 counts (``osvos_mask_iou_counts``, ``osvos_mask_jf_counts``); ``SequenceEvaluator`` keeps the counts of a whole sequence on
 the device and reads them back once.
+
+Multi-object sequences (DAVIS 2017: one fine-tuned network per object) end in the second half of this file: ``merge_objects`` turns the K
+logit stacks into one uint8 label map per frame on the device (``osvos_merge_objects``), ``save_label_maps`` writes them as indexed PNGs with
+the DAVIS palette, and ``MultiObjectEvaluator`` keeps J and F counts per frame AND object on the device (``osvos_labels_jf_counts``).
 """
 import ctypes as C
 import math
@@ -17,7 +21,7 @@ import zlib
 import numpy as np
 import torch
 
-from ._lib import check, lib
+from ._lib import MAX_OBJECTS, check, lib
 
 
 def _stream():
@@ -40,9 +44,14 @@ def mask_bytes(logits):
 
 def write_png(path, img):
     """8-bit grayscale PNG of a [H,W] uint8 array (what PIL writes for mode 'L'; any decoder reads the same pixels)."""
+    _write_png8(path, img, 0, [], "write_png")
+
+
+def _write_png8(path, img, colour_type, extra_chunks, who):
+    """one 8-bit sample per pixel (grayscale or palette index), filter type 0, one IDAT; extra_chunks: (tag, data) between IHDR and IDAT"""
     a = np.ascontiguousarray(img, dtype=np.uint8)
     if a.ndim != 2:
-        raise ValueError("write_png expects a 2-D uint8 array, got shape %r" % (a.shape,))
+        raise ValueError("%s expects a 2-D uint8 array, got shape %r" % (who, a.shape))
     h, w = a.shape
     raw = np.empty((h, w + 1), dtype=np.uint8)
     raw[:, 0] = 0                       # filter type 0 (None) per scanline
@@ -52,8 +61,8 @@ def write_png(path, img):
         body = tag + data
         return struct.pack(">I", len(data)) + body + struct.pack(">I", zlib.crc32(body) & 0xFFFFFFFF)
 
-    png = b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0, 0, 0, 0)) \
-        + chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + chunk(b"IEND", b"")
+    png = b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, colour_type, 0, 0, 0)) \
+        + b"".join(chunk(t, d) for t, d in extra_chunks) + chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + chunk(b"IEND", b"")
     with open(path, "wb") as f:
         f.write(png)
 
@@ -204,3 +213,138 @@ class SequenceEvaluator(object):
         js, fs = self.per_frame()
         j, f = davis_statistics(js), davis_statistics(fs)
         return {"J": j, "F": f, "J&F": 0.5 * (j["mean"] + f["mean"]), "frames": self.frames}
+
+
+# ---- multi-object sequences (DAVIS 2017) ---------------------------------------------------------------------------------------------
+
+def merge_objects(logits, threshold=0.5):
+    """logits: float32 CUDA tensor [K,N,H,W] or [K,N,1,H,W], the fused outputs of K per-object networks for N frames -> uint8 CUDA tensor
+    [N,H,W]: per pixel the object (1..K) with the highest logit -- the lowest index on a tie, a NaN never wins -- or 0 (background) when
+    that logit does not exceed the one of ``threshold``.  Decided on the logits: no sigmoid is computed."""
+    if not logits.is_cuda:
+        raise RuntimeError("osvos_pytorch_amd.results needs CUDA (ROCm) tensors; there is no CPU fallback")
+    if not 0.0 < threshold < 1.0:
+        raise ValueError("threshold must be a probability in (0, 1)")
+    x = logits.detach().float().contiguous()
+    if x.dim() == 5 and x.shape[2] == 1:
+        x = x[:, :, 0]
+    if x.dim() != 4:
+        raise ValueError("expected K objects x N frames of H x W, got shape %r" % (tuple(logits.shape),))
+    k, n, h, w = [int(v) for v in x.shape]
+    if not 1 <= k <= MAX_OBJECTS:
+        raise ValueError("%d objects; the library is built for 1..%d" % (k, MAX_OBJECTS))
+    out = torch.empty((n, h, w), device=x.device, dtype=torch.uint8)
+    thr = float(np.log(threshold / (1.0 - threshold)))
+    check(lib().osvos_merge_objects(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), n, k, h, w, thr, _stream()), "merge_objects")
+    return out
+
+
+def davis_palette():
+    """The 256 x 3 uint8 PASCAL-VOC colour map the DAVIS 2017 annotations carry: bit b of the index goes, three bits at a time, to bit
+    7, 6, .. of red, green and blue (0 black, 1 (128,0,0), 2 (0,128,0), 3 (128,128,0), 4 (0,0,128), ...)."""
+    pal = np.zeros((256, 3), dtype=np.uint8)
+    for i in range(256):
+        c = i
+        for j in range(8):
+            for ch in range(3):
+                pal[i, ch] |= ((c >> ch) & 1) << (7 - j)
+            c >>= 3
+    return pal
+
+
+def write_indexed_png(path, labels, palette=None):
+    """8-bit indexed PNG (colour type 3 + PLTE) of a [H,W] uint8 label map; palette: [n <= 256, 3] uint8, default ``davis_palette()``."""
+    pal = np.ascontiguousarray(davis_palette() if palette is None else palette, dtype=np.uint8)
+    if pal.ndim != 2 or pal.shape[1] != 3 or not 1 <= pal.shape[0] <= 256:
+        raise ValueError("palette must be [1..256, 3] uint8, got shape %r" % (pal.shape,))
+    a = np.asarray(labels)
+    if a.size and int(a.max()) >= pal.shape[0]:
+        raise ValueError("label %d has no palette entry (%d entries)" % (int(a.max()), pal.shape[0]))
+    _write_png8(path, a, 3, [(b"PLTE", pal.tobytes())], "write_indexed_png")
+
+
+def save_label_maps(labels, paths):
+    """One indexed PNG per frame of a uint8 [N,H,W] label tensor (one byte per pixel crosses PCIe, in one copy)."""
+    b = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    if b.ndim != 3 or len(paths) != b.shape[0]:
+        raise ValueError("expected [N,H,W] labels and N paths, got shape %r and %d paths" % (b.shape, len(paths)))
+    pal = davis_palette()
+    for img, p in zip(b, paths):
+        write_indexed_png(p, img, pal)
+
+
+class MultiObjectEvaluator(object):
+    """J and F per object of a multi-object sequence, ``SequenceEvaluator``'s way: ``add`` takes uint8 label maps (prediction and ground
+    truth, ids 1..n_objects; 0 and larger ids belong to no object), enqueues the count kernels into a device table [frames, n_objects, 6]
+    and reads nothing back; ``per_object`` / ``summary`` copy the table to the host once.  One bitmap workspace serves every ``add``: call
+    them all on one stream (or order the streams yourself), as the kernels of two calls must not overlap."""
+
+    CHUNK = 256      # frames the count table grows by
+
+    def __init__(self, n_objects, bound_th=0.008):
+        if not 1 <= int(n_objects) <= MAX_OBJECTS:
+            raise ValueError("%r objects; the library is built for 1..%d" % (n_objects, MAX_OBJECTS))
+        self.n_objects, self.bound_th = int(n_objects), bound_th
+        self.frames = 0
+        self._table = None          # int64 [capacity, n_objects, 6] on the device
+        self._ws = None
+        self._host = None           # (frames, table) of the last read-back
+
+    def add(self, pred_labels, gt_labels):
+        if not (pred_labels.is_cuda and gt_labels.is_cuda):
+            raise RuntimeError("osvos_pytorch_amd.results needs CUDA (ROCm) tensors; there is no CPU fallback")
+        if pred_labels.dtype != torch.uint8 or gt_labels.dtype != torch.uint8:
+            raise ValueError("label maps are uint8 tensors, got %s and %s" % (pred_labels.dtype, gt_labels.dtype))
+        p = pred_labels.detach().contiguous()
+        g = gt_labels.detach().to(device=p.device).contiguous()
+        if p.dim() < 2 or g.numel() != p.numel():
+            raise ValueError("prediction and ground truth differ in size: %r vs %r" % (tuple(pred_labels.shape), tuple(gt_labels.shape)))
+        h, w = int(p.shape[-2]), int(p.shape[-1])
+        n = p.numel() // (h * w)
+        k = self.n_objects
+        if n * k > 65535:
+            raise ValueError("%d frames x %d objects in one call; add at most %d frames at a time" % (n, k, 65535 // k))
+        need = self.frames + n
+        if self._table is None or need > self._table.shape[0]:
+            grown = torch.zeros(((need + self.CHUNK - 1) // self.CHUNK * self.CHUNK, k, 6), device=p.device, dtype=torch.int64)
+            if self._table is not None:
+                grown[:self.frames].copy_(self._table[:self.frames])      # (device to device, in stream order)
+            self._table = grown
+        if self._table.device != p.device:
+            raise ValueError("all frames of a sequence must live on one device")
+        words = lib().osvos_labels_jf_ws_bytes(n, k, h, w) // 8
+        if self._ws is None or self._ws.numel() < words:
+            self._ws = torch.empty(words, device=p.device, dtype=torch.int64)
+        check(lib().osvos_labels_jf_counts(C.c_void_p(p.data_ptr()), C.c_void_p(g.data_ptr()), C.c_void_p(self._ws.data_ptr()),
+                                           C.c_void_p(self._table.data_ptr() + 48 * k * self.frames), n, k, h, w,
+                                           boundary_radius(h, w, self.bound_th), 0, _stream()), "labels_jf_counts")
+        self.frames = need
+
+    def _counts(self):
+        """host int64 [frames, n_objects, 6] (one device-to-host copy per new state of the table)"""
+        if self._host is None or self._host[0] != self.frames:
+            self._host = (self.frames, self._table[:self.frames].cpu().numpy())
+        return self._host[1]
+
+    def per_object(self):
+        """[(js, fs) for object 1..n_objects]: per-frame J and F of everything added so far (one device-to-host copy)."""
+        if self.frames == 0:
+            return [([], []) for _ in range(self.n_objects)]
+        c = self._counts()
+        return [_scores(c[:, k]) for k in range(self.n_objects)]
+
+    def summary(self, exclude_ends=False):
+        """Per object the DAVIS statistics of J and F and their J&F; 'J', 'F' and 'J&F' of the sequence are the means over the objects of
+        the per-object means.  exclude_ends: leave out the first and the last frame (the DAVIS 2017 semi-supervised protocol: the first
+        frame is given, the last one is not scored)."""
+        if self.frames < (3 if exclude_ends else 1):
+            raise ValueError("summary(exclude_ends=%s) needs at least %d frames, %d were added" % (bool(exclude_ends), 3 if exclude_ends else 1, self.frames))
+        objs = []
+        for js, fs in self.per_object():
+            if exclude_ends:
+                js, fs = js[1:-1], fs[1:-1]
+            j, f = davis_statistics(js), davis_statistics(fs)
+            objs.append({"J": j, "F": f, "J&F": 0.5 * (j["mean"] + f["mean"])})
+        jm = float(np.mean([o["J"]["mean"] for o in objs]))
+        fm = float(np.mean([o["F"]["mean"] for o in objs]))
+        return {"objects": objs, "J": jm, "F": fm, "J&F": 0.5 * (jm + fm), "frames": self.frames - 2 if exclude_ends else self.frames}

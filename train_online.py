@@ -10,6 +10,8 @@ running on the MI355X-native OSVOS path.  Differences by design:
     synthetic frame (benchmarking); with the reference's dataloaders package + cv2 installed next to
     this file the original transform chain is used
   * the loss is accumulated on the device and read back only when it is printed
+  * ``--multi-object`` (DAVIS 2017): one fine-tuning per object id of the first annotation, the K logit stacks merged into one label map
+    per frame on the device, indexed PNGs, J and F per object (osvos_pytorch_amd.results.merge_objects / MultiObjectEvaluator)
   * launched under torchrun with N processes, rank r fine-tunes sequences r, r+N, ... of the
     comma-separated SEQ_NAME list (independent replicas: online training has no exchange step)
 """
@@ -34,7 +36,7 @@ import torch
 
 import networks.vgg_osvos as vo
 from layers.osvos_layers import sigmoid_np  # noqa: F401  (kept importable like the reference)
-from osvos_pytorch_amd.results import SequenceEvaluator, save_masks
+from osvos_pytorch_amd.results import MultiObjectEvaluator, SequenceEvaluator, merge_objects, save_label_maps, save_masks
 from mypath import Path
 from osvos_pytorch_amd.parallel import shard_indices
 from osvos_pytorch_amd.train_common import TrainLoop, init_distributed, make_sgd
@@ -69,7 +71,7 @@ class DeviceTrainFrame(object):
 
     def __init__(self, img_u8, lab_u8, device):
         from osvos_pytorch_amd.augment import DeviceAugment
-        self.img, self.lab = torch.from_numpy(img_u8).to(device), torch.from_numpy(lab_u8).to(device)
+        self.img, self.lab = torch.as_tensor(img_u8).to(device), torch.as_tensor(lab_u8).to(device)
         self.aug = DeviceAugment(rots=(-30, 30), scales=(.75, 1.25))
 
     def __len__(self):
@@ -116,6 +118,122 @@ def device_loaders(args, seq_name, device, seed):
     return DeviceTrainFrame(img, lab, device), DeviceTestFrames(test, device, args.prefetch)
 
 
+def synthetic_objects(h, w):
+    """uint8 [H,W] indexed annotation of the --synthetic --multi-object frame: two disjoint ellipses, ids 1 and 2"""
+    yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing='ij')
+    lab = torch.zeros(h, w, dtype=torch.uint8)
+    for k, cx in ((1, 0.28), (2, 0.72)):
+        lab[(((yy - 0.5 * h) / (0.3 * h)) ** 2 + ((xx - cx * w) / (0.18 * w)) ** 2) <= 1] = k
+    return lab.numpy()
+
+
+def load_parent(args, save_dir, parentEpoch, device):
+    net = vo.OSVOS(pretrained=0)
+    parent = os.path.join(save_dir, 'parent_epoch-' + str(parentEpoch - 1) + '.pth')
+    if os.path.exists(parent):
+        net.load_state_dict(torch.load(parent, map_location=lambda storage, loc: storage))
+    elif not args.synthetic:
+        raise SystemExit('parent model %s not found' % parent)
+    net.to(device)
+    net.set_precision(args.precision)
+    return net, make_sgd(net, 'online')
+
+
+def fine_tune(args, net, optimizer, trainloader, device, nEpochs, nAveGrad, seed, snapshot_prefix):
+    """train_online.py:129-170 of the reference: nEpochs passes over the (augmented) first frame, an optimizer step every nAveGrad of them"""
+    snapshot = nEpochs
+    loop = TrainLoop(net, optimizer, mode='online', n_ave_grad=nAveGrad)
+    num_img_tr = len(trainloader)
+    start_time = timeit.default_timer()
+    window = []                      # --window-fused: the micro-batches of the open optimizer-step window
+    for epoch in range(0, nEpochs):
+        np.random.seed(seed + epoch)
+        for ii, sample in enumerate(trainloader):
+            inputs, gts = sample['image'], sample['gt']
+            inputs, gts = inputs.to(device), gts.to(device)
+            if args.window_fused:
+                window.append((inputs, gts))
+                if len(window) == nAveGrad:
+                    loop.window_batch(torch.cat([w[0] for w in window]).requires_grad_(), torch.cat([w[1] for w in window]))
+                    window = []
+                continue
+            inputs = inputs.detach().requires_grad_()      # (a fresh leaf: a frame the loader hands out again must not accumulate a .grad)
+            loop.micro_batch(inputs, gts)
+        if epoch % max(1, nEpochs // 20) == max(1, nEpochs // 20) - 1:
+            running = loop.pop_running()[0] / (num_img_tr * max(1, nEpochs // 20))
+            print('[Epoch: %d, numImages: %5d]' % (epoch + 1, num_img_tr))
+            print('Loss: %f' % running)
+        if (epoch % snapshot) == snapshot - 1 and epoch != 0:
+            torch.save(net.state_dict(), snapshot_prefix + '_epoch-' + str(epoch) + '.pth')
+    if device.type == 'cuda':
+        torch.cuda.synchronize()
+    print('Online training time: ' + str(timeit.default_timer() - start_time))
+
+
+def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, nEpochs, nAveGrad):
+    """DAVIS 2017 recipe for one sequence: one fine-tuning per object id of the first annotation on that object's binary mask, every frame
+    through each network, the K logit stacks merged into label maps, indexed PNGs, J and F per object -- one read-back for the PNGs, one for
+    the counts."""
+    import random
+    from osvos_pytorch_amd._lib import MAX_OBJECTS
+    from osvos_pytorch_amd.augment import augment_frame
+    from osvos_pytorch_amd.davis_io import ArrayFrames, DavisFrames, DevicePrefetcher, n_objects
+    if args.synthetic:
+        s = synthetic_loader(args.height, args.width, seed)[0]
+        img = (s['image'][0].permute(1, 2, 0) + 116.0).clamp(0, 255).to(torch.uint8).numpy()
+        test = ArrayFrames([(img, synthetic_objects(args.height, args.width))])
+    else:
+        test = DavisFrames(False, Path.db_root_dir(), seq_name=seq_name, indexed=True)
+    # the sequence lives on the device as decoded uint8 for the K passes: 3 H W bytes per frame, H W more per annotated frame
+    frames, gts, names = [], [], []
+    for idx, img, lab in DevicePrefetcher(test, range(len(test)), device, depth=args.prefetch):
+        frames.append(img)
+        gts.append(lab)
+        names.append(os.path.basename(test.fname(idx)))
+    if not gts or gts[0] is None:
+        raise SystemExit('--multi-object: sequence %s has no first annotation' % seq_name)
+    K = n_objects(gts[0].cpu().numpy())
+    if not 1 <= K <= MAX_OBJECTS:
+        raise SystemExit('--multi-object: the first annotation of %s holds %d object ids (1..%d are supported)' % (seq_name, K, MAX_OBJECTS))
+    h, w = int(frames[0].shape[0]), int(frames[0].shape[1])
+    logits = torch.empty((K, len(frames), h, w), device=device, dtype=torch.float32)
+    print('Start of Online Training, sequence: %s (%d objects)' % (seq_name, K))
+    test_time = 0.0
+    for k in range(1, K + 1):
+        net, optimizer = load_parent(args, save_dir, parentEpoch, device)
+        random.seed(seed)                      # every object sees the augmentation draws of a single-object run
+        trainloader = DeviceTrainFrame(frames[0], (gts[0] == k).to(torch.uint8) * 255, device)
+        print('Object %d of %d' % (k, K))
+        fine_tune(args, net, optimizer, trainloader, device, nEpochs, nAveGrad, seed, os.path.join(save_dir, '%s_object-%d' % (seq_name, k)))
+        start_time = timeit.default_timer()
+        if args.test_precision:
+            net.set_precision(args.test_precision)
+        with torch.no_grad():
+            for f, img in enumerate(frames):
+                logits[k - 1, f].copy_(net.forward(augment_frame(img, None, flip=False, rot=None)[0][None])[-1][0, 0])
+        torch.cuda.synchronize()
+        test_time += timeit.default_timer() - start_time
+        del net, optimizer, trainloader
+
+    save_dir_res = os.path.join(save_dir, 'Results', seq_name)
+    os.makedirs(save_dir_res, exist_ok=True)
+    print('Testing Network')
+    start_time = timeit.default_timer()
+    labels = merge_objects(logits)
+    evaluator = MultiObjectEvaluator(K)
+    scored = [f for f, g in enumerate(gts) if g is not None]
+    step = max(1, min(64, 65535 // K))
+    for s0 in range(0, len(scored), step):
+        at = scored[s0:s0 + step]
+        evaluator.add(labels[at], torch.stack([gts[f] for f in at]))      # (enqueued: nothing is read back here)
+    save_label_maps(labels, [os.path.join(save_dir_res, n + '.png') for n in names])
+    res = evaluator.summary()
+    for k, o in enumerate(res['objects']):
+        print('J&F on %s object %d: J %.4f F %.4f' % (seq_name, k + 1, o['J']['mean'], o['F']['mean']))
+    print('J&F on %s (%d objects): %.4f' % (seq_name, K, res['J&F']))
+    print('Testing time multi-object: ' + str(test_time + timeit.default_timer() - start_time))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--synthetic', action='store_true', help='seeded synthetic 854x480 frame instead of DAVIS')
@@ -134,7 +252,15 @@ def main():
     ap.add_argument('--window-fused', action='store_true',
                     help='run the nAveGrad micro-batches of every optimizer step as ONE batch with per-image class counts (TrainLoop.window_batch): '
                          'the same gradient up to fp32 summation order, one set of kernel launches per optimizer step instead of nAveGrad')
+    ap.add_argument('--multi-object', action='store_true',
+                    help='DAVIS 2017: fine-tune one network per object id of the first (indexed) annotation, run every frame through each, give '
+                         'each pixel the object with the highest logit (background when none passes 0.5), write indexed PNGs and report J and F '
+                         'per object.  Needs --device-augment or --synthetic.  The fused logits of the whole sequence stay on the device until '
+                         'the merge: 4 * K * frames * H * W bytes (under 1 GB for the largest DAVIS 2017 val sequence), next to the decoded '
+                         'uint8 frames')
     args = ap.parse_args()
+    if args.multi_object and not (args.device_augment or args.synthetic):
+        raise SystemExit('--multi-object needs --device-augment or --synthetic: the per-object labels are made on the device input pipeline')
 
     rank, world, device = init_distributed(collectives=False)      # sequences are sharded over the ranks: nothing is exchanged
     seqs = os.environ.get('SEQ_NAME', 'blackswan').split(',')
@@ -142,54 +268,23 @@ def main():
     os.makedirs(save_dir, exist_ok=True)
     nAveGrad = 5
     nEpochs = args.epochs or 2000 * nAveGrad
-    snapshot = nEpochs
     parentEpoch = 240
     seed = 0
 
     for si in shard_indices(len(seqs), rank, world):
         seq_name = seqs[si]
-        net = vo.OSVOS(pretrained=0)
-        parent = os.path.join(save_dir, 'parent_epoch-' + str(parentEpoch - 1) + '.pth')
-        if os.path.exists(parent):
-            net.load_state_dict(torch.load(parent, map_location=lambda storage, loc: storage))
-        elif not args.synthetic:
-            raise SystemExit('parent model %s not found' % parent)
-        net.to(device)
-        net.set_precision(args.precision)
-        optimizer = make_sgd(net, 'online')
+        if args.multi_object:
+            multi_object_sequence(args, seq_name, device, seed + si, save_dir, parentEpoch, nEpochs, nAveGrad)
+            continue
+        net, optimizer = load_parent(args, save_dir, parentEpoch, device)
         if args.device_augment:
             trainloader, testloader = device_loaders(args, seq_name, device, seed + si)
         elif args.synthetic:
             trainloader = testloader = synthetic_loader(args.height, args.width, seed + si)
         else:
             trainloader, testloader = davis_loaders(Path.db_root_dir(), seq_name)
-        loop = TrainLoop(net, optimizer, mode='online', n_ave_grad=nAveGrad)
-        num_img_tr = len(trainloader)
         print('Start of Online Training, sequence: ' + seq_name)
-        start_time = timeit.default_timer()
-        window = []                      # --window-fused: the micro-batches of the open optimizer-step window
-        for epoch in range(0, nEpochs):
-            np.random.seed(seed + epoch)
-            for ii, sample in enumerate(trainloader):
-                inputs, gts = sample['image'], sample['gt']
-                inputs, gts = inputs.to(device), gts.to(device)
-                if args.window_fused:
-                    window.append((inputs, gts))
-                    if len(window) == nAveGrad:
-                        loop.window_batch(torch.cat([w[0] for w in window]).requires_grad_(), torch.cat([w[1] for w in window]))
-                        window = []
-                    continue
-                inputs = inputs.detach().requires_grad_()      # (a fresh leaf: a frame the loader hands out again must not accumulate a .grad)
-                loop.micro_batch(inputs, gts)
-            if epoch % max(1, nEpochs // 20) == max(1, nEpochs // 20) - 1:
-                running = loop.pop_running()[0] / (num_img_tr * max(1, nEpochs // 20))
-                print('[Epoch: %d, numImages: %5d]' % (epoch + 1, num_img_tr))
-                print('Loss: %f' % running)
-            if (epoch % snapshot) == snapshot - 1 and epoch != 0:
-                torch.save(net.state_dict(), os.path.join(save_dir, seq_name + '_epoch-' + str(epoch) + '.pth'))
-        if device.type == 'cuda':
-            torch.cuda.synchronize()
-        print('Online training time: ' + str(timeit.default_timer() - start_time))
+        fine_tune(args, net, optimizer, trainloader, device, nEpochs, nAveGrad, seed, os.path.join(save_dir, seq_name))
 
         save_dir_res = os.path.join(save_dir, 'Results', seq_name)
         os.makedirs(save_dir_res, exist_ok=True)
