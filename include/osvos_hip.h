@@ -389,6 +389,32 @@ size_t osvos_labels_jf_ws_bytes(int N, int K, int H, int W);
 int osvos_labels_jf_counts(const unsigned char* pred, const unsigned char* gt, void* ws, void* counts, int N, int K, int H, int W, int radius,
                            int accumulate, void* stream);
 
+/* ---- connected components of the thresholded mask, and their selection (the clean-up step between the logits and the result writers) ----
+ * Definitions.  Foreground of a frame: P = logit > logit_threshold (osvos_mask_jf_counts' test: a NaN is background).  connectivity: 4
+ *   (edge neighbours) or 8 (edge and corner neighbours); a component is a maximal connected subset of P inside ONE frame.
+ *   labels [N][H][W] int: 0 off P, else 1 + min(y W + x) over the component's pixels -- independent of algorithm, tiling and scheduling.
+ *   area [N][H][W] int: the component's pixel count at its root pixel (flat index label - 1), 0 everywhere else.
+ *   stats [N][4] long long: {components, |P|, largest area, label of the largest component -- the lowest label on a tie, 0 when none}.
+ * osvos_mask_components: logits read once; area and stats may be NULL; labels, area, stats and ws may hold anything on entry.
+ *   N 1..65535, H W < 2^31 - 1, stats and ws 8-byte aligned.
+ * osvos_components_select: labels, area, stats as osvos_mask_components wrote them for these logits (stats may be NULL when keep_largest
+ *   is 0).  A component of frame n is kept when  area >= min_area  AND  (keep_largest == 0 OR its label is stats[n][3])  AND  the seed
+ *   test passes: seed == NULL, or the seed map of frame n has no non-zero pixel (the object was lost: everything passes, so tracking can
+ *   recover), or some pixel of the component lies within dy*dy + dx*dx <= seed_radius^2 of a non-zero seed pixel (seed_radius
+ *   0..OSVOS_BOUNDARY_MAX_RADIUS, 0 = plain overlap).  chain == 0: seed is [N][H][W] uint8, one map per frame.  chain != 0: seed is
+ *   [1][H][W] and seeds frame 0, frame n > 0 is seeded by kept[n - 1] (kept is required; hand kept[N - 1] back as the next call's seed).
+ *   kept [N][H][W] uint8: 1 at the foreground pixels of kept components, else 0.  out_logits (may be logits itself): logits, except
+ *   `fill` at the foreground pixels of dropped components; fill must not be NaN and must be <= logit_threshold (-inf is allowed).
+ *   Either output may be NULL, not both.
+ * ws: osvos_components_ws_bytes(N, H, W) bytes serve both calls -- sized for the larger need, the selection's: one flag word per pixel
+ *   and a one-bit-per-pixel seed map per frame, plus 16 N bytes -- contents irrelevant on entry.  0 for sizes the calls refuse. */
+size_t osvos_components_ws_bytes(int N, int H, int W);
+int osvos_mask_components(const float* logits, int* labels, int* area, void* stats, void* ws, int N, int H, int W, float logit_threshold,
+                          int connectivity, void* stream);
+int osvos_components_select(const float* logits, const int* labels, const int* area, const void* stats, const unsigned char* seed, int chain,
+                            int seed_radius, int min_area, int keep_largest, float fill, float* out_logits, unsigned char* kept, void* ws, int N,
+                            int H, int W, float logit_threshold, void* stream);
+
 /* ---- fused SGD (torch.optim.SGD semantics, train_online.py:79-88,147) ----------------------
  * for each i: d = g + wd*p; buf = first ? d : momentum*buf + d; p -= lr*buf      (flat tensors) */
 int osvos_sgd_step(float* p, const float* g, float* buf, long count, float lr, float momentum,

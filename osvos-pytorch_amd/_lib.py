@@ -25,6 +25,7 @@ X3_HALF_PIECES_BWD = 0x2000 # OSVOS_FLAG_X3_HALF_PIECES_BWD: net_pack only -- da
 BF16_W2 = 0x4000            # OSVOS_FLAG_BF16_W2: precision 'bf16w2' (dtype F32_BF16MFMA only) -- two-piece forward weight packs, two products per product
 INFERENCE = 0x400           # OSVOS_FLAG_INFERENCE: osvos_net_forward writes nothing only a backward would read (sign bits, pool codes)
 MAX_OBJECTS = 16            # OSVOS_MAX_OBJECTS: object ids per label map (osvos_merge_objects, osvos_labels_jf_counts)
+BOUNDARY_MAX_RADIUS = 64    # OSVOS_BOUNDARY_MAX_RADIUS: largest disk radius (osvos_mask_jf_counts, osvos_components_select)
 GENERIC_DECONV = 0x100      # OSVOS_FLAG_GENERIC_DECONV: OR-ed into the dtype of the osvos_net_* calls
 NPARAMS = 52
 
@@ -105,6 +106,9 @@ PROTOTYPES = {
     "osvos_merge_objects": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "osvos_labels_jf_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "osvos_labels_jf_counts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "osvos_components_ws_bytes": (_sz, [_i, _i, _i]),
+    "osvos_mask_components": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
+    "osvos_components_select": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "osvos_sgd_step": (_i, [_vp, _vp, _vp, _l, _f, _f, _f, _i, _vp]),
     "osvos_sgd_step_multi": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp]),
     "osvos_prof_start": (_i, [_i]),

@@ -12,6 +12,10 @@ the device and reads them back once.
 Multi-object sequences (DAVIS 2017: one fine-tuned network per object) end in the second half of this file: ``merge_objects`` turns the K
 logit stacks into one uint8 label map per frame on the device (``osvos_merge_objects``), ``save_label_maps`` writes them as indexed PNGs with
 the DAVIS palette, and ``MultiObjectEvaluator`` keeps J and F counts per frame AND object on the device (``osvos_labels_jf_counts``).
+
+Mask clean-up sits between the logits and all of these: ``components`` labels the connected components of the thresholded mask on the device
+(``osvos_mask_components``), ``filter_components`` drops components by area, rank or distance from a seed mask (``osvos_components_select``),
+and ``ComponentTracker`` chains the seed test from frame to frame without reading anything back.
 """
 import ctypes as C
 import math
@@ -21,7 +25,7 @@ import zlib
 import numpy as np
 import torch
 
-from ._lib import MAX_OBJECTS, check, lib
+from ._lib import BOUNDARY_MAX_RADIUS, MAX_OBJECTS, check, lib
 
 
 def _stream():
@@ -348,3 +352,147 @@ class MultiObjectEvaluator(object):
         jm = float(np.mean([o["J"]["mean"] for o in objs]))
         fm = float(np.mean([o["F"]["mean"] for o in objs]))
         return {"objects": objs, "J": jm, "F": fm, "J&F": 0.5 * (jm + fm), "frames": self.frames - 2 if exclude_ends else self.frames}
+
+
+# ---- connected components of the mask: clean-up and tracking ---------------------------------------------------------------------------
+
+def _component_inputs(logits, threshold, connectivity):
+    """_jf_inputs' argument handling without a ground truth -> (logits fp32 contiguous, N, H, W, logit threshold)"""
+    if not logits.is_cuda:
+        raise RuntimeError("osvos_pytorch_amd.results needs CUDA (ROCm) tensors; there is no CPU fallback")
+    if not 0.0 < threshold < 1.0:
+        raise ValueError("threshold must be a probability in (0, 1)")
+    if connectivity not in (4, 8):
+        raise ValueError("connectivity must be 4 or 8, got %r" % (connectivity,))
+    x = logits.detach().float().contiguous()
+    if x.dim() < 3:
+        raise ValueError("expected N frames of H x W, got shape %r" % (tuple(x.shape),))
+    n, h, w = int(x.shape[0]), int(x.shape[-2]), int(x.shape[-1])
+    if x.numel() != n * h * w:
+        raise ValueError("expected one channel per frame, got shape %r" % (tuple(x.shape),))
+    return x, n, h, w, float(np.log(threshold / (1.0 - threshold)))
+
+
+def _components_ws(n, h, w, device, ws=None):
+    words = (lib().osvos_components_ws_bytes(n, h, w) + 7) // 8
+    if words == 0:
+        raise ValueError("%d frames of %d x %d: the library takes 1..65535 frames of fewer than 2^31 - 1 pixels" % (n, h, w))
+    if ws is None or ws.numel() < words or ws.device != device:
+        ws = torch.empty(words, device=device, dtype=torch.int64)
+    return ws
+
+
+def _enqueue_components(x, n, h, w, thr, connectivity, ws):
+    labels = torch.empty((n, h, w), device=x.device, dtype=torch.int32)
+    area = torch.empty((n, h, w), device=x.device, dtype=torch.int32)
+    stats = torch.empty((n, 4), device=x.device, dtype=torch.int64)
+    check(lib().osvos_mask_components(C.c_void_p(x.data_ptr()), C.c_void_p(labels.data_ptr()), C.c_void_p(area.data_ptr()), C.c_void_p(stats.data_ptr()),
+                                      C.c_void_p(ws.data_ptr()), n, h, w, thr, connectivity, _stream()), "mask_components")
+    return labels, area, stats
+
+
+def components(logits, threshold=0.5, connectivity=8):
+    """Connected components of P = sigmoid(logit) > threshold per frame.  logits: CUDA tensor [N,1,H,W] or [N,H,W] -> CUDA tensors
+    (labels int32 [N,H,W]: 0 off P, else 1 + the lowest flat index y W + x of the pixel's component; area int32 [N,H,W]: the component's pixel
+    count at that root pixel, 0 elsewhere; stats int64 [N,4]: components, |P|, largest area, label of the largest -- lowest on a tie)."""
+    x, n, h, w, thr = _component_inputs(logits, threshold, connectivity)
+    return _enqueue_components(x, n, h, w, thr, connectivity, _components_ws(n, h, w, x.device))
+
+
+def _seed_bytes(seed, device, frames, h, w):
+    if not torch.is_tensor(seed) or not seed.is_cuda:
+        raise RuntimeError("osvos_pytorch_amd.results needs CUDA (ROCm) tensors; there is no CPU fallback")
+    s = seed.detach().to(device=device)
+    s = s.contiguous() if s.dtype == torch.uint8 else (s != 0).to(torch.uint8).contiguous()
+    if s.numel() != frames * h * w or tuple(s.shape[-2:]) != (h, w):
+        raise ValueError("seed of shape %r for %d frame(s) of %d x %d" % (tuple(seed.shape), frames, h, w))
+    return s
+
+
+def _enqueue_select(x, labels, area, stats, seed, chain, seed_radius, min_area, keep_largest, fill, thr, ws, n, h, w):
+    out = torch.empty_like(x)
+    kept = torch.empty((n, h, w), device=x.device, dtype=torch.uint8)
+    check(lib().osvos_components_select(C.c_void_p(x.data_ptr()), C.c_void_p(labels.data_ptr()), C.c_void_p(area.data_ptr()), C.c_void_p(stats.data_ptr()),
+                                        C.c_void_p(seed.data_ptr()) if seed is not None else None, 1 if chain else 0, int(seed_radius), int(min_area),
+                                        1 if keep_largest else 0, float(fill), C.c_void_p(out.data_ptr()), C.c_void_p(kept.data_ptr()),
+                                        C.c_void_p(ws.data_ptr()), n, h, w, thr, _stream()), "components_select")
+    return out, kept
+
+
+def _select_arguments(seed_radius, min_area, fill, thr):
+    if not 0 <= int(seed_radius) <= BOUNDARY_MAX_RADIUS:
+        raise ValueError("seed_radius must be 0..%d pixels, got %r" % (BOUNDARY_MAX_RADIUS, seed_radius))
+    if int(min_area) < 0:
+        raise ValueError("min_area must not be negative, got %r" % (min_area,))
+    if fill != fill or not float(np.float32(fill)) <= float(np.float32(thr)):
+        raise ValueError("fill must be a number at or below the threshold's logit %g, got %r" % (thr, fill))
+
+
+def filter_components(logits, threshold=0.5, connectivity=8, min_area=0, keep_largest=False, seed=None, seed_radius=0, chain=False,
+                      fill=float('-inf')):
+    """Drop connected components of the thresholded mask.  A component is kept when it has at least ``min_area`` pixels, is the largest of its
+    frame (``keep_largest``; the lowest label on a tie) and passes the seed test: no ``seed``, an all-zero seed map (the object was lost, so
+    everything passes), or a pixel within ``seed_radius`` pixels (a disk; 0 = overlap) of a non-zero seed pixel.  seed: uint8, bool or float
+    CUDA tensor, [N,H,W] -- one map per frame -- or with ``chain`` [H,W] / [1,H,W], the seed of frame 0; frame n > 0 is then seeded by what
+    was kept of frame n - 1.  -> (logits in the shape they came in, with ``fill`` at the foreground pixels of dropped components;
+    kept uint8 [N,H,W])."""
+    x, n, h, w, thr = _component_inputs(logits, threshold, connectivity)
+    _select_arguments(seed_radius, min_area, fill, thr)
+    if chain and seed is None:
+        raise ValueError("chain needs the seed of the first frame")
+    s = None if seed is None else _seed_bytes(seed, x.device, 1 if chain else n, h, w)
+    ws = _components_ws(n, h, w, x.device)
+    labels, area, stats = _enqueue_components(x, n, h, w, thr, connectivity, ws)
+    out, kept = _enqueue_select(x, labels, area, stats, s, chain, seed_radius, min_area, keep_largest, fill, thr, ws, n, h, w)
+    return out.view(logits.shape), kept
+
+
+class ComponentTracker(object):
+    """OSVOS segments every frame on its own; its typical failure is a false-positive blob far from the object.  The tracker keeps, frame after
+    frame, the components that touch what was kept of the previous frame dilated by ``radius`` pixels, starting from the annotation of
+    frame 0 (``first_mask`` [H,W] or [1,H,W], non-zero = object); when nothing was kept the next frame passes whole, so the object can be
+    found again.  ``__call__`` takes a batch of consecutive frames and returns the filtered logits (dropped pixels at -inf); it enqueues
+    only.  The last kept map, the workspace and the running counts live on the device; ``summary`` reads the counts back, once.  Call it on
+    one stream (or order the streams yourself): one workspace serves every call."""
+
+    def __init__(self, first_mask, radius, threshold=0.5, connectivity=8, min_area=0):
+        if not torch.is_tensor(first_mask) or not first_mask.is_cuda:
+            raise RuntimeError("osvos_pytorch_amd.results needs CUDA (ROCm) tensors; there is no CPU fallback")
+        if not 0.0 < threshold < 1.0:
+            raise ValueError("threshold must be a probability in (0, 1)")
+        if connectivity not in (4, 8):
+            raise ValueError("connectivity must be 4 or 8, got %r" % (connectivity,))
+        m = first_mask.detach()
+        if m.dim() == 3 and m.shape[0] == 1:
+            m = m[0]
+        if m.dim() != 2:
+            raise ValueError("first_mask must be [H,W] or [1,H,W], got shape %r" % (tuple(first_mask.shape),))
+        self.h, self.w = int(m.shape[0]), int(m.shape[1])
+        self.radius, self.threshold, self.connectivity, self.min_area = int(radius), threshold, connectivity, int(min_area)
+        _select_arguments(self.radius, self.min_area, float('-inf'), 0.0)
+        self._seed = _seed_bytes(m, m.device, 1, self.h, self.w).view(1, self.h, self.w)
+        self._counts = torch.zeros(3, device=m.device, dtype=torch.int64)      # components seen, components kept, frames
+        self._ws = None
+        self._host = None
+
+    def __call__(self, logits):
+        x, n, h, w, thr = _component_inputs(logits, self.threshold, self.connectivity)
+        if (h, w) != (self.h, self.w):
+            raise ValueError("frames of %d x %d follow a first mask of %d x %d" % (h, w, self.h, self.w))
+        if x.device != self._seed.device:
+            raise ValueError("all frames of a sequence must live on one device")
+        self._ws = _components_ws(n, h, w, x.device, self._ws)
+        labels, area, stats = _enqueue_components(x, n, h, w, thr, self.connectivity, self._ws)
+        out, kept = _enqueue_select(x, labels, area, stats, self._seed, True, self.radius, self.min_area, False, float('-inf'), thr, self._ws, n, h, w)
+        self._seed = kept[n - 1:n]
+        self._counts[0] += stats[:, 0].sum()
+        self._counts[1] += ((area > 0) & (kept != 0)).sum()                    # a component's root pixel carries its area
+        self._counts[2] += n
+        self._host = None
+        return out.view(logits.shape)
+
+    def summary(self):
+        """{'seen', 'kept', 'frames'}: components met, components kept, frames passed so far (one device-to-host copy)."""
+        if self._host is None:
+            self._host = [int(v) for v in self._counts.cpu().numpy()]
+        return {"seen": self._host[0], "kept": self._host[1], "frames": self._host[2]}

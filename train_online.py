@@ -12,6 +12,8 @@ running on the MI355X-native OSVOS path.  Differences by design:
   * the loss is accumulated on the device and read back only when it is printed
   * ``--multi-object`` (DAVIS 2017): one fine-tuning per object id of the first annotation, the K logit stacks merged into one label map
     per frame on the device, indexed PNGs, J and F per object (osvos_pytorch_amd.results.merge_objects / MultiObjectEvaluator)
+  * ``--track-components R``: connected-component clean-up of every test frame on the device -- a component of the thresholded mask is kept
+    when it lies within R pixels of what was kept of the previous frame, starting from the first annotation (results.ComponentTracker)
   * launched under torchrun with N processes, rank r fine-tunes sequences r, r+N, ... of the
     comma-separated SEQ_NAME list (independent replicas: online training has no exchange step)
 """
@@ -36,7 +38,7 @@ import torch
 
 import networks.vgg_osvos as vo
 from layers.osvos_layers import sigmoid_np  # noqa: F401  (kept importable like the reference)
-from osvos_pytorch_amd.results import MultiObjectEvaluator, SequenceEvaluator, merge_objects, save_label_maps, save_masks
+from osvos_pytorch_amd.results import ComponentTracker, MultiObjectEvaluator, SequenceEvaluator, merge_objects, save_label_maps, save_masks
 from mypath import Path
 from osvos_pytorch_amd.parallel import shard_indices
 from osvos_pytorch_amd.train_common import TrainLoop, init_distributed, make_sgd
@@ -219,6 +221,12 @@ def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, n
     os.makedirs(save_dir_res, exist_ok=True)
     print('Testing Network')
     start_time = timeit.default_timer()
+    trackers = []
+    if args.track_components is not None:
+        for k in range(1, K + 1):
+            trackers.append(ComponentTracker(gts[0] == k, args.track_components))
+            for s0 in range(0, len(frames), 64):                              # consecutive frames, in order (enqueued: nothing is read back)
+                logits[k - 1, s0:s0 + 64] = trackers[-1](logits[k - 1, s0:s0 + 64])
     labels = merge_objects(logits)
     evaluator = MultiObjectEvaluator(K)
     scored = [f for f, g in enumerate(gts) if g is not None]
@@ -231,6 +239,9 @@ def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, n
     for k, o in enumerate(res['objects']):
         print('J&F on %s object %d: J %.4f F %.4f' % (seq_name, k + 1, o['J']['mean'], o['F']['mean']))
     print('J&F on %s (%d objects): %.4f' % (seq_name, K, res['J&F']))
+    for k, t in enumerate(trackers):
+        c = t.summary()
+        print('Components kept on %s object %d: %d of %d over %d frames' % (seq_name, k + 1, c['kept'], c['seen'], c['frames']))
     print('Testing time multi-object: ' + str(test_time + timeit.default_timer() - start_time))
 
 
@@ -258,7 +269,13 @@ def main():
                          'per object.  Needs --device-augment or --synthetic.  The fused logits of the whole sequence stay on the device until '
                          'the merge: 4 * K * frames * H * W bytes (under 1 GB for the largest DAVIS 2017 val sequence), next to the decoded '
                          'uint8 frames')
+    ap.add_argument('--track-components', type=int, default=None, metavar='R',
+                    help='clean every test frame\'s mask on the device before it is written and scored: of the connected components of the '
+                         'thresholded mask keep those within R pixels (0..64) of what was kept of the previous frame, seeded with the first '
+                         'annotation; when nothing was kept the next frame passes whole.  With --multi-object: one tracker per object')
     args = ap.parse_args()
+    if args.track_components is not None and not 0 <= args.track_components <= 64:
+        raise SystemExit('--track-components takes a radius of 0..64 pixels, got %d' % args.track_components)
     if args.multi_object and not (args.device_augment or args.synthetic):
         raise SystemExit('--multi-object needs --device-augment or --synthetic: the per-object labels are made on the device input pipeline')
 
@@ -290,16 +307,24 @@ def main():
         os.makedirs(save_dir_res, exist_ok=True)
         print('Testing Network')
         evaluator = SequenceEvaluator()      # J and F counts stay on the device: one read-back after the last frame
+        tracker = None
         if args.test_precision:
             net.set_precision(args.test_precision)      # (re-packs the weights once: the FP16-pair packs are another format)
         with torch.no_grad():
             for sample in testloader:
                 img, fname = sample['image'], sample['fname']
                 outputs = net.forward(img.to(device))
+                fused = outputs[-1]
+                if args.track_components is not None:
+                    if tracker is None:
+                        if 'gt' not in sample:
+                            raise SystemExit('--track-components: sequence %s has no first annotation to seed the tracker' % seq_name)
+                        tracker = ComponentTracker(sample['gt'].to(device)[0, 0] > 0.5, args.track_components)
+                    fused = tracker(fused)
                 # sigmoid + scipy<=1.1 imsave byte scaling on the device, PNG written by osvos_pytorch_amd.results (reference :181-187)
-                save_masks(outputs[-1], [os.path.join(save_dir_res, os.path.basename(fname[jj]) + '.png') for jj in range(int(img.size()[0]))])
+                save_masks(fused, [os.path.join(save_dir_res, os.path.basename(fname[jj]) + '.png') for jj in range(int(img.size()[0]))])
                 if 'gt' in sample:
-                    evaluator.add(outputs[-1], sample['gt'].to(device))
+                    evaluator.add(fused, sample['gt'].to(device))
         if evaluator.frames:
             res = evaluator.summary()
             st = res['J']
@@ -307,6 +332,9 @@ def main():
             st = res['F']
             print('F (contour accuracy) on %s: mean %.4f recall %.4f decay %.4f over %d frames' % (seq_name, st['mean'], st['recall'], st['decay'], res['frames']))
             print('J&F on %s: %.4f' % (seq_name, res['J&F']))
+        if tracker is not None:
+            c = tracker.summary()
+            print('Components kept on %s: %d of %d over %d frames' % (seq_name, c['kept'], c['seen'], c['frames']))
 
 
 if __name__ == '__main__':
