@@ -7,6 +7,27 @@
 #define NEED_F32(dtype, what)                                                                     \
   OSVOS_ARG_CHECK(osvos_dtype_built(dtype), "%s: dtype %d not built (fp32 tensors only)", what, (int)(dtype))
 
+// Which weight-gradient family takes the launch (kernels.h): two rules, by what the tensors are
+int osvos_wgrad_dispatch(const WgradCall& c, int dtype) {
+  if (!c.x_bf16 && !c.dy_bf16) {      // fp32 tensors: by dtype
+    // the wide trunk layers go through the bf16 MFMA kernel; conv1_1 (Cin 3) and side_prep (Cout 16) keep
+    // their exact-fp32 skinny kernels (5 % of the weight-gradient FLOPs)
+    if (dtype == OSVOS_F32_BF16MFMA && c.Cin == c.Cin_s && c.Cout % 64 == 0 && osvos_wgrad_bf16_applicable(c.Cin_s, c.Cout))
+      return osvos_conv3x3_wgrad_bf16mfma(c);
+    // f32x3: the wide trunk layers and side_prep (the S16 form) on the bf16 matrix pipe with split operands; conv1_1 keeps its exact skinny kernel
+    if (dtype == OSVOS_F32_X3 && (osvos_wgrad_f32x3_applicable(c.Cin, c.Cin_s, c.Cout, c.Cout_s) || osvos_wgrad_f32x3_skinny_applicable(c.Cin, c.Cin_s, c.Cout, c.Cout_s)))
+      return osvos_conv3x3_wgrad_f32x3(c);
+    return osvos_conv3x3_wgrad_f32(c);
+  }
+  // a bf16 tensor (the network's bf16-store mode, osvos_conv3x3_wgrad_bf16act): the wide layers AND side_prep (Cout 16: one 64-cout tile with 16
+  // live rows, still 2x faster than the skinny kernel -- wgrad_bf16.hip) read both operands as bf16 on the bf16 MFMA kernel; conv1_1 (Cin 3) takes
+  // the skinny kernel with its fp32 input and the bf16 dy.  (The skinny Cout = 16 kernel's bf16-x path is reached by no layer of the network.)
+  if (osvos_wgrad_bf16_applicable(c.Cin_s, c.Cout) && c.Cin == c.Cin_s) return osvos_conv3x3_wgrad_bf16mfma(c);
+  const int r = osvos_conv3x3_wgrad_small_f32(c);
+  if (r == 1) osvos_set_error("net_backward: no bf16-store weight-gradient kernel for layer Cin %d/%d Cout %d", c.Cin, c.Cin_s, c.Cout);
+  return r;
+}
+
 extern "C" {
 
 int osvos_nchw_to_nhwc(const float* src, void* dst, int N, int C, int H, int W, int cpad, int dtype, void* stream) {
@@ -62,13 +83,23 @@ int osvos_pack_conv3x3_dgrad(const float* w, void* wpk, int Cout, int Cin, int d
   return osvos_pack_dgrad_f32(w, (float*)wpk, Cout, Cin, (hipStream_t)stream);
 }
 
-// what every op-level convolution entry passes: fp32 tensors, one pack in `wpk` (the entries below add what they have beyond that)
+// what every op-level convolution entry passes: fp32 tensors, one pack in `wpk`, this thread's pieces (the entries below add what they have beyond that)
 static ConvCall conv_call(const void* x, const void* wpk, const float* bias, const void* mask, void* y, int N, int H, int W, int Cin, int Cout, int y_cs,
                           int relu, int tile, void* stream) {
   ConvCall c;
   c.x = x; c.wpk = wpk; c.bias = bias; c.mask = mask; c.y = (float*)y;
   c.N = N; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.y_cs = y_cs; c.relu = relu; c.tile = tile;
+  c.pieces = osvos_x3_pieces();
   c.stream = (hipStream_t)stream;
+  return c;
+}
+// the same for the op-level weight-gradient entries
+static WgradCall wgrad_call(const void* x, const void* dy, int bf16, void* ws, float* dw, float* db, int N, int H, int W, int Cin, int Cin_s, int Cout,
+                            int Cout_s, int accumulate, void* stream) {
+  WgradCall c;
+  c.x = x; c.dy = dy; c.x_bf16 = c.dy_bf16 = bf16; c.ws = ws; c.dw = dw; c.db = db;
+  c.N = N; c.H = H; c.W = W; c.Cin = Cin; c.Cin_s = Cin_s; c.Cout = Cout; c.Cout_s = Cout_s; c.accumulate = accumulate;
+  c.pieces = osvos_x3_pieces(); c.stream = (hipStream_t)stream;
   return c;
 }
 
@@ -84,7 +115,7 @@ int osvos_conv3x3(const void* x, const void* wpk, const float* bias, const void*
 int osvos_conv3x3_f32x3_tiles(void) { return osvos_conv3x3_f32x3_num_tiles(); }
 size_t osvos_wpack_x3_bytes_abi(int Cout, int Cin, int dgrad) { return dgrad ? osvos_wpack_x3_bytes(Cin, Cout) : osvos_wpack_x3_bytes(Cout, Cin); }
 int osvos_pack_conv3x3_x3(const float* w, void* wpk3, int Cout, int Cin, int dgrad, void* stream) {
-  return osvos_pack_x3(w, wpk3, Cout, Cin, dgrad, (hipStream_t)stream);
+  return osvos_pack_x3(w, wpk3, Cout, Cin, dgrad, osvos_x3_pieces() == 22, (hipStream_t)stream);
 }
 int osvos_conv3x3_x3(const void* x, const void* wpk3, const float* bias, const void* mask, void* y,
                      int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, void* stream) {
@@ -117,7 +148,7 @@ int osvos_conv3x3_bf16io(const void* x, int x_is_bf16, const void* wpk, const fl
 // weight gradient of the wide layers (Cin_s, Cout multiples of 64) from bf16 x AND dy; dw/db fp32 as osvos_conv3x3_wgrad
 int osvos_conv3x3_wgrad_bf16act(const void* x_bf16, const void* dy_bf16, void* ws, float* dw, float* db, int N, int H, int W, int Cin, int Cin_s,
                                 int Cout, int Cout_s, int accumulate, void* stream) {
-  return osvos_conv3x3_wgrad_bf16mfma(x_bf16, dy_bf16, 1, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s, accumulate, (hipStream_t)stream);
+  return osvos_wgrad_dispatch(wgrad_call(x_bf16, dy_bf16, 1, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s, accumulate, stream), OSVOS_F32_BF16MFMA);
 }
 int osvos_maxpool2x2_bf16act(const void* x_bf16, void* y_bf16, int N, int H, int W, int C, void* stream) {
   return osvos_maxpool2x2_bf16(x_bf16, y_bf16, N, H, W, C, (hipStream_t)stream);
@@ -178,18 +209,7 @@ int osvos_conv3x3_wgrad(const void* x, const void* dy, void* ws, float* dw, floa
                         int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
                         int accumulate, int dtype, void* stream) {
   NEED_F32(dtype, "conv3x3_wgrad");
-  // the wide trunk layers go through the bf16 MFMA kernel; conv1_1 (Cin 3) and side_prep (Cout 16) keep
-  // their exact-fp32 skinny kernels (5 % of the weight-gradient FLOPs)
-  if (dtype == OSVOS_F32_BF16MFMA && Cin == Cin_s && Cout % 64 == 0 && osvos_wgrad_bf16_applicable(Cin_s, Cout))
-    return osvos_conv3x3_wgrad_bf16mfma(x, dy, 0, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s, accumulate, (hipStream_t)stream);
-  // f32x3 (dtype OSVOS_F32_X3): the wide trunk layers on the bf16 matrix pipe with three-way split operands; conv1_1 and side_prep keep
-  // their exact skinny kernels
-  if (dtype == OSVOS_F32_X3 &&
-      (osvos_wgrad_f32x3_applicable(Cin, Cin_s, Cout, Cout_s) || osvos_wgrad_f32x3_skinny_applicable(Cin, Cin_s, Cout, Cout_s)))
-    return osvos_conv3x3_wgrad_f32x3((const float*)x, (const float*)dy, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s, accumulate,
-                                     (hipStream_t)stream);
-  return osvos_conv3x3_wgrad_f32((const float*)x, (const float*)dy, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s,
-                                 accumulate, (hipStream_t)stream);
+  return osvos_wgrad_dispatch(wgrad_call(x, dy, 0, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s, accumulate, stream), dtype);
 }
 
 int osvos_maxpool2x2(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream) {

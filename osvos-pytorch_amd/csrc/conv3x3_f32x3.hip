@@ -805,15 +805,15 @@ int launch_x2(const ConvArgsX& a0, int sk_grid, hipStream_t stream) {
 // the pre-split form is built for the production tiles (eight waves, in-loop staging); the others take the fp32 pack.  Stream-K: the
 // pre-split production tiles of the wide layers (SKT).  PIPE: the tile has the pipelined K loop (10, 12, 14), taken unless OSVOS_X3_PIPE=0
 template <class C, bool SKT = false, bool PIPE = false>
-int launch_x(const ConvArgsX& a, int sk_grid, hipStream_t stream) {
-  if (osvos_x3_pieces() == 22) {     // two fp16 pieces with block exponents (precision 'fp32h2'): the pre-split production tiles only
+int launch_x(const ConvArgsX& a, int pieces, int sk_grid, hipStream_t stream) {
+  if (pieces == 22) {     // two fp16 pieces with block exponents (precision 'fp32h2'): the pre-split production tiles only
     if constexpr (C::ILV != 0 && (C::NT == 512 || C::NT == 256)) {
       if (a.wpk3 != nullptr) return launch_x2<C, 1, 0, 2, 1>(a, 0, stream);
     }
     osvos_set_error("conv3x3 f32x3: the fp16-pair form is built for the pre-split eight-wave tiles (10, 12, 14, 15, 16, 17) with a pre-split pack");
     return -1;
   }
-  if (osvos_x3_pieces() == 2) {      // two-piece mode (precision 'fp32x2'): the plain grid only, no stream-K form
+  if (pieces == 2) {      // two-piece mode (precision 'fp32x2'): the plain grid only, no stream-K form
     if constexpr (C::ILV != 0 && (C::NT == 512 || C::NT == 256)) {
       if (a.wpk3 != nullptr) return launch_x2<C, 1, 0, 2>(a, 0, stream);
     }
@@ -990,14 +990,14 @@ __global__ __launch_bounds__(256) void pack_x3_multi_kernel(PackX3Table t) {
 
 int osvos_pack_x3_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, const int* halfs, int n,
                         hipStream_t stream) {
-  OSVOS_ARG_CHECK(ws && dsts && Couts && Cins && dgrads && n >= 0 && n <= OSVOS_PACK_MAX, "pack_x3_multi: bad table (n = %d)", n);
+  OSVOS_ARG_CHECK(ws && dsts && Couts && Cins && dgrads && halfs && n >= 0 && n <= OSVOS_PACK_MAX, "pack_x3_multi: bad table (n = %d)", n);
   if (n == 0) return 0;
   PackX3Table t;
   t.n = n;
   t.start[0] = 0;
   bool any_half = false;
   for (int k = 0; k < n; ++k) {
-    t.half[k] = (halfs != nullptr ? halfs[k] != 0 : osvos_x3_pieces() == 22) ? 1 : 0;
+    t.half[k] = halfs[k] != 0 ? 1 : 0;
     any_half = any_half || t.half[k];
     const int K = dgrads[k] ? Couts[k] : Cins[k], M = dgrads[k] ? Cins[k] : Couts[k];
     OSVOS_ARG_CHECK(ws[k] && dsts[k] && K % 16 == 0 && M > 0, "pack_x3_multi: entry %d (K = %d, M = %d)", k, K, M);
@@ -1018,14 +1018,14 @@ int osvos_pack_x3_multi(const float* const* ws, void* const* dsts, const int* Co
 size_t osvos_wpack_x3_bytes(int M, int K) { return (size_t)3 * 9 * K * osvos_cout_pad(M) * 2; }
 
 // w: OIHW fp32 [Cout][Cin][3][3].  dgrad = 0: pack for the forward conv (K = Cin, M = Cout); 1: for the data gradient (K = Cout, M = Cin)
-int osvos_pack_x3(const float* w, void* wpk3, int Cout, int Cin, int dgrad, hipStream_t stream) {
+int osvos_pack_x3(const float* w, void* wpk3, int Cout, int Cin, int dgrad, int half, hipStream_t stream) {
   OSVOS_ARG_CHECK(w && wpk3 && Cout > 0 && Cin > 0, "pack_x3: bad arguments");
   const int K = dgrad ? Cout : Cin;
   OSVOS_ARG_CHECK(K % 16 == 0, "pack_x3: %d reduction channels (must be a multiple of 16)", K);
   const float* ws[1] = {w};
   void* dsts[1] = {wpk3};
-  const int co[1] = {Cout}, ci[1] = {Cin}, dg[1] = {dgrad};
-  return osvos_pack_x3_multi(ws, dsts, co, ci, dg, nullptr, 1, stream);
+  const int co[1] = {Cout}, ci[1] = {Cin}, dg[1] = {dgrad}, hf[1] = {half};
+  return osvos_pack_x3_multi(ws, dsts, co, ci, dg, hf, 1, stream);
 }
 
 int osvos_conv3x3_f32x3_num_tiles(void) { return kNumTilesX; }
@@ -1066,7 +1066,7 @@ int osvos_conv3x3_f32x3(const ConvCall& c) {
     // fused pool only: that epilogue exists for tiles 10, 12, 14)
     OSVOS_ENV_INT(wide2, "OSVOS_X2_TILE_FOR_10", 10);
     OSVOS_ENV_INT(mid2, "OSVOS_X2_TILE_FOR_12", 12);
-    if (env_tile < 0 && osvos_x3_pieces() != 3 && !pool_fwd) tile = tile == 10 ? wide2 : (tile == 12 ? mid2 : tile);
+    if (env_tile < 0 && c.pieces != 3 && !pool_fwd) tile = tile == 10 ? wide2 : (tile == 12 ? mid2 : tile);
     // XCD-local map (cout tiles of one spatial tile on one XCD) only where the activations are MUCH larger than the weights: the rule of rounds 2-4
     // (pixels > 9 CoutP, i.e. fp32 activation bytes > fp32 weight bytes) put conv4_x on it, where it measures 6-7 % slower per launch than the plain
     // order (X14 on conv4_2: 0.166 vs 0.155 ms; the pre-split pack is 1.5x the fp32 weights and every XCD then streams all of it) -- with the factor 3
@@ -1119,24 +1119,24 @@ int osvos_conv3x3_f32x3(const ConvCall& c) {
   }
   int rc;
   switch (tile) {
-    case 0: rc = launch_x<X0>(a, 0, stream); break;
-    case 1: rc = launch_x<X1>(a, 0, stream); break;
-    case 2: rc = launch_x<X2>(a, 0, stream); break;
-    case 3: rc = launch_x<X3>(a, 0, stream); break;
-    case 4: rc = launch_x<X4>(a, 0, stream); break;
-    case 5: rc = launch_x<X5>(a, 0, stream); break;
-    case 6: rc = launch_x<X6>(a, 0, stream); break;
-    case 7: rc = launch_x<X7>(a, 0, stream); break;
-    case 8: rc = launch_x<X8>(a, 0, stream); break;
-    case 9: rc = launch_x<X9>(a, 0, stream); break;
-    case 10: rc = launch_x<X10, true, true>(a, sk_grid, stream); break;
-    case 11: rc = launch_x<X11>(a, 0, stream); break;
-    case 12: rc = launch_x<X12, true, true>(a, sk_grid, stream); break;
-    case 13: rc = launch_x<X13>(a, 0, stream); break;
-    case 14: rc = launch_x<X14, true, true>(a, sk_grid, stream); break;
-    case 15: rc = launch_x<X15>(a, 0, stream); break;
-    case 16: rc = launch_x<X16>(a, 0, stream); break;
-    case 17: rc = launch_x<X17>(a, 0, stream); break;
+    case 0: rc = launch_x<X0>(a, c.pieces, 0, stream); break;
+    case 1: rc = launch_x<X1>(a, c.pieces, 0, stream); break;
+    case 2: rc = launch_x<X2>(a, c.pieces, 0, stream); break;
+    case 3: rc = launch_x<X3>(a, c.pieces, 0, stream); break;
+    case 4: rc = launch_x<X4>(a, c.pieces, 0, stream); break;
+    case 5: rc = launch_x<X5>(a, c.pieces, 0, stream); break;
+    case 6: rc = launch_x<X6>(a, c.pieces, 0, stream); break;
+    case 7: rc = launch_x<X7>(a, c.pieces, 0, stream); break;
+    case 8: rc = launch_x<X8>(a, c.pieces, 0, stream); break;
+    case 9: rc = launch_x<X9>(a, c.pieces, 0, stream); break;
+    case 10: rc = launch_x<X10, true, true>(a, c.pieces, sk_grid, stream); break;
+    case 11: rc = launch_x<X11>(a, c.pieces, 0, stream); break;
+    case 12: rc = launch_x<X12, true, true>(a, c.pieces, sk_grid, stream); break;
+    case 13: rc = launch_x<X13>(a, c.pieces, 0, stream); break;
+    case 14: rc = launch_x<X14, true, true>(a, c.pieces, sk_grid, stream); break;
+    case 15: rc = launch_x<X15>(a, c.pieces, 0, stream); break;
+    case 16: rc = launch_x<X16>(a, c.pieces, 0, stream); break;
+    case 17: rc = launch_x<X17>(a, c.pieces, 0, stream); break;
     default: osvos_set_error("conv3x3 f32x3: unknown tile config %d", tile); return -1;
   }
   if (rc) return rc;

@@ -34,6 +34,7 @@ struct ConvCall {
   void* pooled_bf16 = nullptr;
   void* pool_code = nullptr;
   int N = 0, H = 0, W = 0, Cin = 0, Cout = 0, relu = 0;
+  int pieces = 3;                      // f32x3 family, per operand: 3 bf16 pieces, 2 bf16 ('fp32x2') or 22 = two FP16 under block exponents ('fp32h2'; such a wpk3)
   int tile = -1;                       // -1: automatic; else the family's tile id (+100: XCD-local block map).  Exact fp32 launcher: 200 + t = f32x3
                                        // tile t, -2 = "automatic, in the f32x3 arithmetic where it applies"
   int ksplit = 0;                      // fp32 families: K parts (<= 8) of a launch cut along K; 0 = automatic.  Taken only with part_ws
@@ -44,6 +45,29 @@ struct ConvCall {
   int sk_grid = 0;
   hipStream_t stream = nullptr;
 };
+
+// One 3x3 weight-gradient launch (dw[co][ci][tap] = sum over pixels of dy[co] * x[ci] shifted by the tap; db = sum of dy), as every launcher below
+// takes it.  Host only, like ConvCall.  Each launcher states which operand formats it takes and rejects the others with an argument error.
+enum WgradPhase { WGRAD_BOTH = 0, WGRAD_PARTIALS = 1, WGRAD_REDUCE = 2 };
+struct WgradCall {
+  const void* x = nullptr;             // the layer's input, NHWC with channel stride Cin_s: fp32, or bf16 when x_bf16
+  const void* dy = nullptr;            // gradient of the layer's output, NHWC with channel stride Cout_s: fp32, or bf16 when dy_bf16
+  int x_bf16 = 0, dy_bf16 = 0;
+  void* ws = nullptr;                  // partial slabs [split][...] + bias partials: osvos_wgrad_ws_bytes() of the dtype (the family's *_ws_bytes)
+  float *dw = nullptr, *db = nullptr;  // results: OIHW fp32 [Cout][Cin][3][3]; [Cout] or NULL (no bias gradient)
+  int N = 0, H = 0, W = 0, Cin = 0, Cin_s = 0, Cout = 0, Cout_s = 0;
+  int accumulate = 0;                  // != 0: dw / db += instead of =
+  // both: partial slabs, then their reduce into dw / db.  osvos_net_backward enqueues the two halves on different streams (the bandwidth-bound
+  // reduces off the critical path of the MFMA weight-gradient chain): partials only, then -- same descriptor, stream-ordered behind it -- reduce only
+  WgradPhase phase = WGRAD_BOTH;
+  int pieces = 3;                      // f32x3 family: pieces per operand, as ConvCall::pieces
+  hipStream_t stream = nullptr;
+};
+// chooses the family by dtype and by what the tensors are, and launches (the rule: api.cpp)
+int osvos_wgrad_dispatch(const WgradCall& c, int dtype);
+// the slab reduce the families share (wgrad_f32.hip): slab [split][tap][co][ci] -> dw, bslab [split][co] -> db
+int osvos_wgrad_reduce_launch(const float* slab, const float* bslab, float* dw, float* db, int nsplit, int Cout, int Cin,
+                              int Cin_s, int accumulate, hipStream_t stream);
 
 // exact fp32 (conv3x3_f32.hip): fp32 tensors and fp32 pack, Cin % 8 == 0
 int osvos_conv3x3_f32(const ConvCall& c);
@@ -61,8 +85,7 @@ int osvos_conv3x3_f32x3(const ConvCall& c);
 bool osvos_wgrad_f32x3_applicable(int Cin, int Cin_s, int Cout, int Cout_s);
 bool osvos_wgrad_f32x3_skinny_applicable(int Cin, int Cin_s, int Cout, int Cout_s);
 size_t osvos_wgrad_f32x3_ws_bytes(int N, int H, int W, int Cin_s, int Cout);
-int osvos_conv3x3_wgrad_f32x3(const float* x, const float* dy, void* ws, float* dw, float* db,
-                              int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s, int accumulate, hipStream_t stream);
+int osvos_conv3x3_wgrad_f32x3(const WgradCall& c);
 size_t osvos_wpack_x3_bytes(int M, int K);
 #define OSVOS_PACK_MAX 40
 // n packs (n <= OSVOS_PACK_MAX) in one launch: ws[k] OIHW fp32 [Couts[k]][Cins[k]][3][3] -> dsts[k]; dgrads[k] != 0: data-gradient form.
@@ -70,18 +93,16 @@ size_t osvos_wpack_x3_bytes(int M, int K);
 // single-piece pack byte for byte)
 int osvos_pack_bf16_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, void* const* lo_dsts, int n,
                           hipStream_t stream);
-// pre-split f32x3 packs: halfs[k] != 0: entry k in the two-piece FP16 format (h2split.h; three launches instead of one); NULL: every entry in
-// the format of this thread's osvos_x3_pieces() (22 = FP16 pairs, else three bf16 planes)
+// pre-split f32x3 packs: halfs[k] / half != 0: the entry in the two-piece FP16 format (h2split.h; three launches instead of one), else three bf16 planes
 int osvos_pack_x3_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, const int* halfs, int n,
                         hipStream_t stream);
-int osvos_pack_x3(const float* w, void* wpk3, int Cout, int Cin, int dgrad, hipStream_t stream);
+int osvos_pack_x3(const float* w, void* wpk3, int Cout, int Cin, int dgrad, int half, hipStream_t stream);
 bool osvos_dgrad_c3_applicable(int Cin, int Cout);
 int osvos_conv3x3_dgrad_c3_f32(const float* dy, const float* wpk_dgrad, float* dx_nchw, int N, int H, int W, int Cout, hipStream_t stream);
 int osvos_conv3x3_dgrad_c3_bf16mfma(const void* dy_bf16, const void* wpk_bf16_dgrad, float* dx_nchw, int N, int H, int W, int Cout, hipStream_t stream);
 size_t osvos_wgrad_ws_bytes_f32(int N, int H, int W, int Cin_s, int Cout);
-int osvos_conv3x3_wgrad_f32(const float* x, const float* dy, void* ws, float* dw, float* db,
-                            int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
-                            int accumulate, hipStream_t stream);
+// exact fp32 weight gradient (wgrad_f32.hip): fp32 x and dy; hands conv1_1's and side_prep's shapes to the skinny launcher first
+int osvos_conv3x3_wgrad_f32(const WgradCall& c);
 int osvos_nchw_to_nhwc_f32(const float* src, float* dst, void* dstbf, int N, int C, int H, int W, int cpad, hipStream_t stream);
 int osvos_nhwc_to_nchw_f32(const float* src, float* dst, int N, int C, int H, int W, int cs, hipStream_t stream);
 int osvos_pack_fwd_f32(const float* w, float* wpk, int Cout, int Cin, hipStream_t stream);
@@ -133,11 +154,9 @@ int osvos_conv3x3_bf16_p64(const ConvCall& c, int map);
 // bf16-operand weight gradient (fp32 tensors): wgrad_bf16.hip
 bool osvos_wgrad_bf16_applicable(int Cin_s, int Cout);
 size_t osvos_wgrad_bf16_ws_bytes(int N, int H, int W, int Cin_s, int Cout);
-// bf16-store mode of the network: the trunk tensors are bf16.  xb: x AND dy are bf16 (wide layers); the skinny fp32 kernels take
-// their WIDE operand (dy of conv1_1, x of side_prep) as bf16 and the narrow one as fp32
-int osvos_conv3x3_wgrad_bf16mfma(const void* x, const void* dy, int xb, void* ws, float* dw, float* db,
-                                 int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
-                                 int accumulate, hipStream_t stream);
-int osvos_conv3x3_wgrad_small_f32(const void* x, const void* dy, int wide_bf16, void* ws, float* dw, float* db,
-                                  int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
-                                  int accumulate, hipStream_t stream);
+// x and dy both fp32 or both bf16 (the bf16-store mode of the network)
+int osvos_conv3x3_wgrad_bf16mfma(const WgradCall& c);
+// the skinny fp32 kernels (wgrad_small_f32.hip): Cin = 3 (conv1_1: x fp32, dy fp32 or bf16) and Cout = 16 (side_prep: dy fp32, x fp32 or bf16).
+// Returns 1 when the shape is neither (the caller falls through to another kernel)
+size_t osvos_wgrad_small_ws_bytes(int N, int H, int W, int Cin_s, int Cout);
+int osvos_conv3x3_wgrad_small_f32(const WgradCall& c);

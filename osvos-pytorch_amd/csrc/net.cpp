@@ -258,9 +258,11 @@ inline bool use_presplit() {
 }
 
 // The convolution of layer l (forward) or its data gradient (dgrad: Cin and Cout swap roles) on an h x w map, as far as the layer table and the
-// packed parameters decide it; the caller adds operands, results and workspaces by name.  Precision 'bf16w2': forward packs have two pieces
-ConvCall conv_of(const ConvDesc& dl, int l, bool dgrad, const void* wbuf, const WbufLayout& P, int N, int h, int w, hipStream_t stream) {
+// packed parameters and the call's f32x3 `pieces` decide it; the caller adds operands, results and workspaces by name.  Precision 'bf16w2':
+// forward packs have two pieces
+ConvCall conv_of(const ConvDesc& dl, int l, bool dgrad, const void* wbuf, const WbufLayout& P, int pieces, int N, int h, int w, hipStream_t stream) {
   ConvCall c;
+  c.pieces = pieces;
   const size_t w3 = dgrad ? P.dgrad3[l] : P.fwd3[l];
   c.wpk = at(wbuf, dgrad ? P.dgrad[l] : P.fwd[l]);
   if (w3 != (size_t)-1) c.wpk3 = at(wbuf, w3);
@@ -321,19 +323,13 @@ inline int dbg_skip() {
 constexpr int dbg_skip() { return 0; }
 #endif
 
-// precision 'fp32x2' (OSVOS_FLAG_X3_TWO_PIECES): the f32x3 kernels of this call take two bf16 pieces per operand (three products) instead of three
-// (six); the per-thread switch (errors.cpp) is set for the duration of the call and restored on every return path
-extern "C" int osvos_set_x3_pieces(int pieces);
-// precision 'fp32h2' (OSVOS_FLAG_X3_HALF_PIECES): two FP16 pieces under block exponents (h2split.h) -- the packs the call reads must have been
-// written in that format (osvos_net_pack with the matching flag)
-struct PiecesScope {
-  int prev;
-  explicit PiecesScope(int dtype_) : prev(osvos_x3_pieces()) {
-    const bool x3 = (dtype_ & 0xff) == OSVOS_F32_X3;
-    osvos_set_x3_pieces(x3 && (dtype_ & OSVOS_FLAG_X3_HALF_PIECES) ? 22 : (x3 && (dtype_ & OSVOS_FLAG_X3_TWO_PIECES) ? 2 : 3));
-  }
-  ~PiecesScope() { osvos_set_x3_pieces(prev); }
-};
+// Pieces per operand of the f32x3 kernels of one network call, from its dtype flags; every ConvCall / WgradCall the call builds carries it.  Precision
+// 'fp32x2' (OSVOS_FLAG_X3_TWO_PIECES): two bf16 pieces (three products) instead of three (six); 'fp32h2' (OSVOS_FLAG_X3_HALF_PIECES): two FP16 pieces
+// under block exponents (h2split.h) -- the packs the call reads must have been written in that format (osvos_net_pack with the matching flag)
+inline int x3_pieces_of(int dtype_) {
+  const bool x3 = (dtype_ & 0xff) == OSVOS_F32_X3;
+  return x3 && (dtype_ & OSVOS_FLAG_X3_HALF_PIECES) ? 22 : (x3 && (dtype_ & OSVOS_FLAG_X3_TWO_PIECES) ? 2 : 3);
+}
 
 // gradient-ready events armed for the next backward of this host thread (osvos_net_arm_grad_events)
 struct GradEvents { hipEvent_t ev[OSVOS_NGRAD_GROUPS]; int n = 0; };
@@ -458,7 +454,7 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
   const int dtype = dtype_ & 0xff;
   const bool generic = (dtype_ & OSVOS_FLAG_GENERIC_DECONV) != 0;
   const bool infer = (dtype_ & OSVOS_FLAG_INFERENCE) != 0;      // no backward will read the sign bits / pool codes: do not write them
-  PiecesScope pieces_scope(dtype_);
+  const int pieces = x3_pieces_of(dtype_);
   hipStream_t aux_all = aux_stream_ ? (hipStream_t)aux_stream_ : stream;
   const bool two = aux_all != stream;
   OSVOS_ARG_CHECK(x_nchw && wbuf && ws && outs, "net_forward: null pointer");
@@ -499,7 +495,7 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
     for (int j = 0; j < kStageN[si]; ++j, ++l) {
       {
         ProfScope ps(OSVOS_PROF_CONV_FWD, conv_flops(N, h, w, d[l].cin, d[l].cout), stream);
-        ConvCall c = conv_of(d[l], l, false, wbuf, P, N, h, w, stream);
+        ConvCall c = conv_of(d[l], l, false, wbuf, P, pieces, N, h, w, stream);
         c.relu = 1;
         const Tensor act = L.view(ws, L.act[l]);
         set_x(c, cur);
@@ -527,7 +523,7 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
       if (two && aux != stream && (rc = stream_wait(aux, stream))) return rc;
       {
         ProfScope ps(OSVOS_PROF_OTHER, conv_flops(N, h, w, d[sl].cin, 16), aux);
-        ConvCall c = conv_of(d[sl], sl, false, wbuf, P, N, h, w, aux);
+        ConvCall c = conv_of(d[sl], sl, false, wbuf, P, pieces, N, h, w, aux);
         set_x(c, cur);
         c.y = reinterpret_cast<float*>(at(ws, L.prep[i]));
         if (L.side_part[i] != (size_t)-1) c.part_ws = at(ws, L.side_part[i]);
@@ -578,7 +574,7 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
   hipStream_t stream = (hipStream_t)stream_;
   const int dtype = dtype_ & 0xff;
   const bool generic = (dtype_ & OSVOS_FLAG_GENERIC_DECONV) != 0;
-  PiecesScope pieces_scope(dtype_);
+  const int pieces = x3_pieces_of(dtype_);
   hipStream_t aux = aux_stream_ ? (hipStream_t)aux_stream_ : stream;
   hipStream_t aux2 = aux2_stream_ ? (hipStream_t)aux2_stream_ : aux;
   const GradEvents gev = grad_events();      // armed for this call only
@@ -609,35 +605,21 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
     if (r == 0 && three) r = stream_wait(stream, aux2);
     return r;
   };
-  // weight gradient of one layer: partial slabs on aux (MFMA kernel), slab reduce on aux2 (bandwidth kernel)
-  // (store mode: the wide layers read both operands as bf16; conv1_1 and side_prep keep their exact-fp32 skinny kernels, fed
-  //  with the bf16 tensor on the wide side -- xin stays fp32 for conv1_1, dprep for side_prep)
-  auto wgrad_launch = [&](const void* xin, const void* g, int l, int h, int w, hipStream_t st) -> int {
-    if (store) {
-      if (osvos_wgrad_bf16_applicable(d[l].cin_s, d[l].cout) && d[l].cin == d[l].cin_s)
-        return osvos_conv3x3_wgrad_bf16mfma(xin, g, 1, at(ws, L.wgrad[l]), grads[d[l].w_param], grads[d[l].b_param], N, h, w,
-                                            d[l].cin, d[l].cin_s, d[l].cout, d[l].cout, accumulate, st);
-      const int r = osvos_conv3x3_wgrad_small_f32(xin, g, 1, at(ws, L.wgrad[l]), grads[d[l].w_param], grads[d[l].b_param], N, h, w,
-                                                  d[l].cin, d[l].cin_s, d[l].cout, d[l].cout, accumulate, st);
-      if (r == 1) osvos_set_error("net_backward: no bf16-store weight-gradient kernel for layer %d", l);
-      return r;
-    }
-    return osvos_conv3x3_wgrad(xin, g, at(ws, L.wgrad[l]), grads[d[l].w_param], grads[d[l].b_param], N, h, w,
-                               d[l].cin, d[l].cin_s, d[l].cout, d[l].cout, accumulate, dtype, st);
-  };
-  auto wgrad = [&](const void* xin, const void* g, int l, int h, int w) -> int {
-    int r;
-    if (!three) return wgrad_launch(xin, g, l, h, w, aux);
-    osvos_wgrad_set_phase(1);
-    r = wgrad_launch(xin, g, l, h, w, aux);
-    osvos_wgrad_set_phase(0);
-    if (r) return r;
-    if (dbg_skip() & 1) return 0;
+  // Weight gradient of layer l from its input and the gradient of its output: partial slabs on aux (MFMA kernel), then -- the same descriptor --
+  // the slab reduce on aux2 (bandwidth kernel).  Without a third stream, and for conv1_1's tail on the main stream (on_main), both halves in one
+  // launch sequence.  Store mode: every trunk tensor and dprep's copy are bf16, conv1_1's input stays fp32 (which kernel: osvos_wgrad_dispatch)
+  auto wgrad = [&](const void* xin, const void* g, int l, int h, int w, bool on_main) -> int {
+    WgradCall c;
+    c.x = xin; c.dy = g; c.x_bf16 = store && l != 0; c.dy_bf16 = store;
+    c.ws = at(ws, L.wgrad[l]); c.dw = grads[d[l].w_param]; c.db = grads[d[l].b_param];
+    c.N = N; c.H = h; c.W = w; c.Cin = d[l].cin; c.Cin_s = d[l].cin_s; c.Cout = c.Cout_s = d[l].cout; c.accumulate = accumulate; c.pieces = pieces;
+    const bool split = three && !on_main;
+    c.phase = split ? WGRAD_PARTIALS : WGRAD_BOTH; c.stream = on_main ? stream : aux;
+    int r = osvos_wgrad_dispatch(c, dtype);
+    if (r || !split || (dbg_skip() & 1)) return r;
     if ((r = stream_wait(aux2, aux))) return r;
-    osvos_wgrad_set_phase(2);
-    r = wgrad_launch(xin, g, l, h, w, aux2);
-    osvos_wgrad_set_phase(0);
-    return r;
+    c.phase = WGRAD_REDUCE; c.stream = aux2;
+    return osvos_wgrad_dispatch(c, dtype);
   };
   int rc;
   double* acc = reinterpret_cast<double*>(at(ws, L.acc));
@@ -745,7 +727,7 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
     const int lx = last_of_stage(si);
     if (grads[d[sl].w_param] != nullptr && !(dbg_skip() & 16)) {
       const Tensor dprep = L.view(ws, L.dprep[i], L.dprep_b[i]);
-      rc = wgrad(at(ws, L.act[lx]), dprep.b ? dprep.b : dprep.f, sl, h, w);      // (store mode: bf16 x and bf16 dprep)
+      rc = wgrad(at(ws, L.act[lx]), dprep.b ? dprep.b : dprep.f, sl, h, w, false);      // (store mode: bf16 x and bf16 dprep)
       if (rc) return rc;
     }
   }
@@ -767,7 +749,7 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
     // upstream gradient of conv5_3; stages 1-3 are merged in maxpool2x2_bwd below
     if (dbg_skip() & 8) continue;
     hipStream_t st = (i == 3) ? stream : sds;
-    ConvCall c = conv_of(d[sl], sl, true, wbuf, P, N, h, w, st);
+    ConvCall c = conv_of(d[sl], sl, true, wbuf, P, pieces, N, h, w, st);
     set_x(c, L.view(ws, L.dprep[i], L.dprep_b[i]));
     set_y(c, L.view(ws, (i == 3) ? L.dy[lx] : L.dside[i]));
     if (i == 3) {
@@ -799,7 +781,7 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
     const bool tail_on_main = l == 0 && two && !defer_join;      // (deferred join: everything gradient-related stays on the side streams)
     if (grads[d[l].w_param] != nullptr && !tail_on_main) {
       if ((rc = signal())) return rc;   // dy[l] ready -> its weight gradient may start on aux
-      rc = wgrad(xin, g, l, h, w);
+      rc = wgrad(xin, g, l, h, w, false);
       if (rc) return rc;
     }
     if (first_of_stage && !tail_on_main && (rc = ready(2 + (4 - si), aux2))) return rc;      // stage si complete (its first conv is the last one processed)
@@ -815,7 +797,7 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
         rc = osvos_conv3x3_dgrad_c3_bf16mfma(dy.b, at(wbuf, P.dgrad[0]), dx_nchw, N, h, w, d[0].cout, stream);
         if (rc) return rc;
       } else if (dx_nchw != nullptr) {
-        ConvCall c = conv_of(d[0], 0, true, wbuf, P, N, h, w, stream);
+        ConvCall c = conv_of(d[0], 0, true, wbuf, P, pieces, N, h, w, stream);
         set_x(c, dy);
         c.y = reinterpret_cast<float*>(at(ws, L.dxin));
         c.y_cs = 4;
@@ -825,13 +807,13 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
         if (rc) return rc;
       }
       if (tail_on_main) {
-        if (grads[d[0].w_param] != nullptr && !(dbg_skip() & 64) && (rc = wgrad_launch(xin, g, 0, h, w, stream))) return rc;
+        if (grads[d[0].w_param] != nullptr && !(dbg_skip() & 64) && (rc = wgrad(xin, g, 0, h, w, true))) return rc;
         if ((rc = join())) return rc;
         return ready(2 + 4, stream);      // stage 0 complete: conv1_2's reduce (aux2, joined) and conv1_1's (main)
       }
       break;
     }
-    ConvCall c = conv_of(d[l], l, true, wbuf, P, N, h, w, stream);      // the data gradient of layer l; below: where it goes and what masks it
+    ConvCall c = conv_of(d[l], l, true, wbuf, P, pieces, N, h, w, stream);      // the data gradient of layer l; below: where it goes and what masks it
     set_x(c, dy);
     c.part_ws = at(ws, L.conv_part);
     c.sk_ws = sk_bwd;

@@ -17,6 +17,7 @@
 // All forms produce bit-identical weight gradients (same patches, splits and k-order).  Probe builds (-DOSVOS_WGRAD_PROF, -DOSVOS_WGRAD_ABL=n:
 // tools/native/) add s_memtime phase marks and timing ablations; the shipped library compiles none of that.
 #include "common.h"
+#include "kernels.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -609,9 +610,6 @@ WbPlan make_plan(int N, int H, int W, int Cin_s, int Cout, int bco = BCO) {
 
 }  // namespace
 
-int osvos_wgrad_reduce_launch(const float* slab, const float* bslab, float* dw, float* db, int nsplit, int Cout, int Cin,
-                              int Cin_s, int accumulate, hipStream_t stream);
-
 // shapes the bf16 kernel takes: the wide trunk layers (Cin_s, Cout multiples of 64); everything else stays on the fp32 kernels
 // (Cout = 16, the side_prep layers: one 64-cout tile with 16 live rows -- 75 % of the MFMA rows multiply zeros, still 2x faster than
 //  the exact-fp32 skinny kernel, whose cost is staging the wide X tile either way)
@@ -624,13 +622,15 @@ size_t osvos_wgrad_bf16_ws_bytes(int N, int H, int W, int Cin_s, int Cout) {
   return align_up((f > fw ? f : fw) * sizeof(float), 256);
 }
 
-// xb = 0: x and dy fp32; xb = 1: both bf16
-int osvos_conv3x3_wgrad_bf16mfma(const void* x, const void* dy, int xb, void* ws, float* dw, float* db,
-                                 int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
-                                 int accumulate, hipStream_t stream) {
-  OSVOS_ARG_CHECK(x && dy && ws && dw, "wgrad bf16: null pointer");
+// x and dy both fp32, or both bf16 (xb)
+int osvos_conv3x3_wgrad_bf16mfma(const WgradCall& c) {
+  float *const dw = c.dw, *const db = c.db;
+  void* const ws = c.ws; hipStream_t stream = c.stream;
+  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cin_s = c.Cin_s, Cout = c.Cout, Cout_s = c.Cout_s, accumulate = c.accumulate, phase = c.phase, xb = c.x_bf16 ? 1 : 0;
+  OSVOS_ARG_CHECK(c.x && c.dy && ws && dw, "wgrad bf16: null pointer");
   OSVOS_ARG_CHECK(osvos_wgrad_bf16_applicable(Cin_s, Cout) && Cin == Cin_s && Cout_s % 4 == 0, "wgrad bf16: unsupported shape");
   OSVOS_ARG_CHECK((long)H * W * Cin_s < (1L << 29) && (long)H * W * Cout_s < (1L << 29), "wgrad bf16: image too large for 31-bit byte offsets");
+  OSVOS_ARG_CHECK(!c.x_bf16 == !c.dy_bf16, "wgrad bf16: x and dy must both be fp32 or both be bf16");
   static const int form_env = getenv("OSVOS_WGRAD_FORM") ? atoi(getenv("OSVOS_WGRAD_FORM")) : -1;
 #ifdef OSVOS_WGRAD_ALL_FORMS
   const int form = xb ? (form_env >= 0 ? form_env : kDefaultForm) : 0;
@@ -640,7 +640,7 @@ int osvos_conv3x3_wgrad_bf16mfma(const void* x, const void* dy, int xb, void* ws
   const bool wide = form >= kWideForm && Cout % 128 == 0;        // eight-wave form: 128-cout tiles
   WbPlan p = make_plan(N, H, W, Cin_s, Cout, wide ? 128 : BCO);
   WbArgs a;
-  a.x = x; a.dy = dy;
+  a.x = c.x; a.dy = c.dy;
   a.slab = reinterpret_cast<float*>(ws);
   a.bslab = db ? a.slab + p.slab_floats : nullptr;
   a.N = N; a.H = H; a.W = W; a.Cin_s = Cin_s; a.Cout = Cout; a.Cout_s = Cout_s;
@@ -661,9 +661,8 @@ int osvos_conv3x3_wgrad_bf16mfma(const void* x, const void* dy, int xb, void* ws
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set = true;
   }
-  const int phase = osvos_wgrad_phase();
 #ifdef OSVOS_WGRAD_ALL_FORMS
-  if (phase != 2 && form >= 4 && wide) {                // LDS-DMA forms: 4 fragments one stage ahead, 5 ping-pong segments
+  if (phase != WGRAD_REDUCE && form >= 4 && wide) {                // LDS-DMA forms: 4 fragments one stage ahead, 5 ping-pong segments
     static bool attr4_set_dev[OSVOS_MAX_DEVICES] = {};
     bool& attr4_set = attr4_set_dev[osvos_current_device()];
     constexpr int lds_dma = (int)DM::LDS;
@@ -677,7 +676,7 @@ int osvos_conv3x3_wgrad_bf16mfma(const void* x, const void* dy, int xb, void* ws
     OSVOS_LAUNCH_CHECK();
   } else
 #endif
-  if (phase != 2 && form >= 3) {
+  if (phase != WGRAD_REDUCE && form >= 3) {
     static bool attr3_set_dev[OSVOS_MAX_DEVICES] = {};      // per device, like every other kernel attribute
     bool& attr3_set = attr3_set_dev[osvos_current_device()];
     constexpr size_t lds4 = PM<4>::LDS, lds8 = PM<8>::LDS;
@@ -690,7 +689,7 @@ int osvos_conv3x3_wgrad_bf16mfma(const void* x, const void* dy, int xb, void* ws
     else hipLaunchKernelGGL(wgrad_bf16pm_kernel<4>, dim3((unsigned)blocks), dim3(256), lds4, stream, a);
     OSVOS_LAUNCH_CHECK();
 #ifdef OSVOS_WGRAD_ALL_FORMS
-  } else if (phase != 2 && form != 0) {
+  } else if (phase != WGRAD_REDUCE && form != 0) {
     static bool attr2_set_dev[OSVOS_MAX_DEVICES] = {};
     bool& attr2_set = attr2_set_dev[osvos_current_device()];
     if (!attr2_set) {
@@ -702,12 +701,12 @@ int osvos_conv3x3_wgrad_bf16mfma(const void* x, const void* dy, int xb, void* ws
     else hipLaunchKernelGGL(wgrad_bf16v2_kernel<4>, dim3((unsigned)blocks), dim3(256), kLdsV2, stream, a);
     OSVOS_LAUNCH_CHECK();
 #endif
-  } else if (phase != 2) {
+  } else if (phase != WGRAD_REDUCE) {
     if (xb) hipLaunchKernelGGL(wgrad_bf16_kernel<1>, dim3((unsigned)blocks), dim3(256), lds, stream, a);
     else hipLaunchKernelGGL(wgrad_bf16_kernel<0>, dim3((unsigned)blocks), dim3(256), lds, stream, a);
     OSVOS_LAUNCH_CHECK();
   }
-  if (phase == 1) return 0;
+  if (phase == WGRAD_PARTIALS) return 0;
   return osvos_wgrad_reduce_launch(a.slab, a.bslab, dw, db, p.nsplit, Cout, Cin, Cin_s, accumulate, stream);
 }
 

@@ -17,6 +17,7 @@
 //     second deterministic, fully coalesced pass sums them and (optionally) accumulates
 //   * the bias gradient (column sums of dY) rides along in the workgroups of the first Cin tile
 #include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -446,11 +447,6 @@ int launch_wgrad_variant(const WgArgs& a, long blocks, hipStream_t stream) {
 
 }  // namespace
 
-size_t osvos_wgrad_small_ws_bytes(int N, int H, int W, int Cin_s, int Cout);
-int osvos_conv3x3_wgrad_small_f32(const void* x, const void* dy, int wide_bf16, void* ws, float* dw, float* db,
-                                  int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
-                                  int accumulate, hipStream_t stream);
-
 int osvos_wgrad_reduce_launch(const float* slab, const float* bslab, float* dw, float* db, int nsplit, int Cout, int Cin,
                               int Cin_s, int accumulate, hipStream_t stream) {
   OSVOS_ENV_INT(env_t, "OSVOS_WGRAD_REDUCE_T", 1);
@@ -476,24 +472,26 @@ size_t osvos_wgrad_ws_bytes_f32(int N, int H, int W, int Cin_s, int Cout) {
   return generic > small ? generic : small;
 }
 
-int osvos_conv3x3_wgrad_f32(const float* x, const float* dy, void* ws, float* dw, float* db,
-                            int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
-                            int accumulate, hipStream_t stream) {
-  OSVOS_ARG_CHECK(x && dy && ws && dw, "wgrad: null pointer");
+int osvos_conv3x3_wgrad_f32(const WgradCall& c) {
+  float *const dw = c.dw, *const db = c.db;
+  void* const ws = c.ws; hipStream_t stream = c.stream;
+  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cin_s = c.Cin_s, Cout = c.Cout, Cout_s = c.Cout_s, accumulate = c.accumulate;
+  OSVOS_ARG_CHECK(c.x && c.dy && ws && dw, "wgrad: null pointer");
   OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "wgrad: bad shape");
   OSVOS_ARG_CHECK((long)H * W * Cin_s < (1L << 29) && (long)H * W * Cout_s < (1L << 29), "wgrad: image too large for 31-bit byte offsets");
   OSVOS_ARG_CHECK(Cin_s % 4 == 0 && Cout_s % 4 == 0 && Cout % 4 == 0 && Cin <= Cin_s && Cout <= Cout_s,
                   "wgrad f32: channel strides must be multiples of 4 (Cin %d/%d Cout %d/%d)", Cin, Cin_s, Cout, Cout_s);
+  OSVOS_ARG_CHECK(!c.x_bf16 && !c.dy_bf16, "wgrad f32: fp32 tensors only");
   {
     OSVOS_ENV_INT(env_generic, "OSVOS_WGRAD_GENERIC", 0);     // tuning / tests: force the generic kernel
     if (!env_generic) {
-      const int rc = osvos_conv3x3_wgrad_small_f32(x, dy, 0, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s, accumulate, stream);
+      const int rc = osvos_conv3x3_wgrad_small_f32(c);
       if (rc <= 0) return rc;
     }
   }
   WgPlan p = make_plan(N, H, W, Cin_s, Cout);
   WgArgs a;
-  a.x = x; a.dy = dy;
+  a.x = (const float*)c.x; a.dy = (const float*)c.dy;
   a.slab = reinterpret_cast<float*>(ws);
   a.bslab = db ? a.slab + p.slab_floats : nullptr;
   a.N = N; a.H = H; a.W = W; a.Cin_s = Cin_s; a.Cout = Cout; a.Cout_s = Cout_s;
@@ -501,14 +499,13 @@ int osvos_conv3x3_wgrad_f32(const float* x, const float* dy, void* ws, float* dw
   a.nco_t = p.nco_t; a.nci_t = p.nci_t;
   const long blocks = (long)p.nsplit * p.nco_t * p.nci_t;
   a.oihw = (wgrad_variant() >> 3) & 1;
-  const int phase = osvos_wgrad_phase();
-  if (phase != 2) {
+  if (c.phase != WGRAD_REDUCE) {
     int rc = (p.cb == 1) ? launch_wgrad_variant<1, 4>(a, blocks, stream)
                          : (p.pw == 16 ? launch_wgrad<2, 2, 1, 0, 2, 16>(a, blocks, stream)      // (the measured-best variant only)
                                        : launch_wgrad_variant<2, 2>(a, blocks, stream));
     if (rc) return rc;
   }
-  if (phase == 1) return 0;
+  if (c.phase == WGRAD_PARTIALS) return 0;
   if (!a.oihw) return osvos_wgrad_reduce_launch(a.slab, a.bslab, dw, db, p.nsplit, Cout, Cin, Cin_s, accumulate, stream);
   const int total = Cout * Cin_s * 9;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ceil_div(total, 128) + (db ? ceil_div(Cout, 32) : 0)), dim3(256), 0, stream,

@@ -429,9 +429,6 @@ int launch3(const W3Args& a, long blocks, hipStream_t stream) {
 
 }  // namespace
 
-int osvos_wgrad_reduce_launch(const float* slab, const float* bslab, float* dw, float* db, int nsplit, int Cout, int Cin,
-                              int Cin_s, int accumulate, hipStream_t stream);
-
 // the wide trunk layers (channel counts multiples of 64, no channel padding); conv1_1 and side_prep keep their exact skinny kernels
 bool osvos_wgrad_f32x3_applicable(int Cin, int Cin_s, int Cout, int Cout_s) {
   return Cin == Cin_s && Cin_s % 64 == 0 && Cout % 64 == 0 && Cout_s % 4 == 0;
@@ -451,18 +448,20 @@ size_t osvos_wgrad_f32x3_ws_bytes(int N, int H, int W, int Cin_s, int Cout) {
   return align_up((p.slab_floats + p.bslab_floats) * sizeof(float), 256);
 }
 
-namespace {
-int wgrad3_run(const void* x, const void* dy, void* ws, float* dw, float* db,
-               int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s, int accumulate, hipStream_t stream) {
-  OSVOS_ARG_CHECK(x && dy && ws && dw, "wgrad f32x3: null pointer");
+int osvos_conv3x3_wgrad_f32x3(const WgradCall& c) {
+  float *const dw = c.dw, *const db = c.db;
+  void* const ws = c.ws; hipStream_t stream = c.stream;
+  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cin_s = c.Cin_s, Cout = c.Cout, Cout_s = c.Cout_s, accumulate = c.accumulate;
+  OSVOS_ARG_CHECK(c.x && c.dy && ws && dw, "wgrad f32x3: null pointer");
   OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0, "wgrad f32x3: bad shape");
   const bool skinny = Cout == 16 && Cout_s == 16 && Cin == Cin_s && Cin_s % 128 == 0;      // side_prep
   OSVOS_ARG_CHECK(skinny || osvos_wgrad_f32x3_applicable(Cin, Cin_s, Cout, Cout_s),
                   "wgrad f32x3: unsupported shape (Cin %d/%d Cout %d/%d)", Cin, Cin_s, Cout, Cout_s);
   OSVOS_ARG_CHECK((long)H * W * Cin_s < (1L << 28) && (long)H * W * Cout_s < (1L << 28), "wgrad f32x3: image too large for 31-bit byte offsets");
+  OSVOS_ARG_CHECK(!c.x_bf16 && !c.dy_bf16, "wgrad f32x3: fp32 tensors only");
   const W3Plan p = make_plan3(N, H, W, Cin_s, Cout);
   W3Args a;
-  a.x = x; a.dy = dy;
+  a.x = c.x; a.dy = c.dy;
   a.slab = reinterpret_cast<float*>(ws);
   a.bslab = db ? a.slab + p.slab_floats : nullptr;
   a.N = N; a.H = H; a.W = W; a.Cin_s = Cin_s; a.Cout = Cout; a.Cout_s = Cout_s;
@@ -470,11 +469,10 @@ int wgrad3_run(const void* x, const void* dy, void* ws, float* dw, float* db,
   const long blocks = (long)p.nsplit * p.nco_t * p.nci_t;
   OSVOS_ENV_INT(map_env, "OSVOS_WGRAD_MAP", 1);
   a.map = (map_env == 1 && blocks % 8 == 0) ? 1 : 0;
-  const int phase = osvos_wgrad_phase();
-  if (phase != 2) {
+  if (c.phase != WGRAD_REDUCE) {
     // gathers / staging loads interleaved with the MFMAs of the previous stage (round 3; the block-issue form measured level and is gone)
-    const bool two = osvos_x3_pieces() == 2;      // precision 'fp32x2'
-    const bool h2 = osvos_x3_pieces() == 22;      // precision 'fp32h2'
+    const bool two = c.pieces == 2;      // precision 'fp32x2'
+    const bool h2 = c.pieces == 22;      // precision 'fp32h2'
     const int rc = h2  ? (skinny ? launch3<4, 4, 1, 1, 2, 1>(a, blocks, stream)
                                  : (p.ph == 6 ? launch3<6, 4, 0, 1, 2, 1>(a, blocks, stream) : launch3<4, 4, 0, 1, 2, 1>(a, blocks, stream)))
                  : two ? (skinny ? launch3<4, 4, 1, 1, 2>(a, blocks, stream)
@@ -483,12 +481,6 @@ int wgrad3_run(const void* x, const void* dy, void* ws, float* dw, float* db,
                                  : (p.ph == 6 ? launch3<6, 4, 0, 1>(a, blocks, stream) : launch3<4, 4, 0, 1>(a, blocks, stream)));
     if (rc) return rc;
   }
-  if (phase == 1) return 0;
+  if (c.phase == WGRAD_PARTIALS) return 0;
   return osvos_wgrad_reduce_launch(a.slab, a.bslab, dw, db, p.nsplit, Cout, Cin, Cin_s, accumulate, stream);
-}
-}  // namespace
-
-int osvos_conv3x3_wgrad_f32x3(const float* x, const float* dy, void* ws, float* dw, float* db,
-                              int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s, int accumulate, hipStream_t stream) {
-  return wgrad3_run(x, dy, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s, accumulate, stream);
 }

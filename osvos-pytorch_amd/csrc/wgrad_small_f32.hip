@@ -12,6 +12,7 @@
 // Both write coalesced per-split slabs [split][tap][co][ci] (co16) / [split][co][32] (c3) and share
 // the deterministic two-pass reduction idea of the generic kernel.
 #include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -484,6 +485,17 @@ SmallPlan plan_co16(int N, int H, int W, int Cin_s) {
   return p;
 }
 
+// conv1_1's argument struct, the same for both of its kernels but for the plan
+C3Args c3_args(const WgradCall& c, const SmallPlan& p) {
+  C3Args a;
+  a.x = reinterpret_cast<const float*>(c.x); a.dy = c.dy; a.dy_bf16 = c.dy_bf16 ? 1 : 0;
+  a.slab = reinterpret_cast<float*>(c.ws);
+  a.bslab = c.db ? a.slab + p.slab_floats : nullptr;
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cout = c.Cout; a.Cout_s = c.Cout_s;
+  a.npx = p.npx; a.npy = p.npy; a.npatches = p.npatches; a.per_split = p.per_split;
+  return a;
+}
+
 int g_c3_bf16 = 1;      // the bf16-operand conv1_1 weight gradient (osvos_debug_set_c3_bf16: tests compare it with the fp32 kernel)
 
 }  // namespace
@@ -493,10 +505,6 @@ extern "C" int osvos_debug_set_c3_bf16(int on) {
   g_c3_bf16 = on ? 1 : 0;
   return prev;
 }
-
-// generic slab reduce of wgrad_f32.hip (layout [split][tap][co][ci])
-int osvos_wgrad_reduce_launch(const float* slab, const float* bslab, float* dw, float* db, int nsplit, int Cout, int Cin,
-                              int Cin_s, int accumulate, hipStream_t stream);
 
 size_t osvos_wgrad_small_ws_bytes(int N, int H, int W, int Cin_s, int Cout) {
   if (Cin_s == 8 && Cout <= 64) {
@@ -511,26 +519,22 @@ size_t osvos_wgrad_small_ws_bytes(int N, int H, int W, int Cin_s, int Cout) {
   return 0;
 }
 
-// returns 1 if the shape is not one of the two special cases (caller falls through to the generic kernel)
-// wide_bf16: the WIDE operand is a bf16 tensor (dy of the Cin = 3 layer, x of the Cout = 16 layers); the narrow one stays fp32
-int osvos_conv3x3_wgrad_small_f32(const void* x, const void* dy, int wide_bf16, void* ws, float* dw, float* db,
-                                  int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
-                                  int accumulate, hipStream_t stream) {
-  if (Cin == 3 && Cin_s == 8 && Cout == 64 && Cout_s % 8 == 0 && wide_bf16 && g_c3_bf16) {      // bf16-store mode: dY is bf16 -> bf16 matrix pipe
+// returns 1 if the shape is not one of the two special cases (caller falls through to the generic kernel).  The WIDE operand may be a bf16
+// tensor (dy of the Cin = 3 layer, x of the Cout = 16 layers); the narrow one is fp32
+int osvos_conv3x3_wgrad_small_f32(const WgradCall& c) {
+  float *const dw = c.dw, *const db = c.db;
+  void* const ws = c.ws; hipStream_t stream = c.stream;
+  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cin_s = c.Cin_s, Cout = c.Cout, Cout_s = c.Cout_s, accumulate = c.accumulate, phase = c.phase;
+  if (Cin == 3 && Cin_s == 8 && Cout == 64 && Cout_s % 8 == 0 && c.dy_bf16 && g_c3_bf16) {      // bf16-store mode: dY is bf16 -> bf16 matrix pipe
     SmallPlan p = plan_c3_bf16(N, H, W);
-    C3Args a;
-    a.x = reinterpret_cast<const float*>(x); a.dy = dy; a.dy_bf16 = 1;
-    a.slab = reinterpret_cast<float*>(ws);
-    a.bslab = db ? a.slab + p.slab_floats : nullptr;
-    a.N = N; a.H = H; a.W = W; a.Cout = Cout; a.Cout_s = Cout_s;
-    a.npx = p.npx; a.npy = p.npy; a.npatches = p.npatches; a.per_split = p.per_split;
+    const C3Args a = c3_args(c, p);
     OSVOS_ARG_CHECK((long)H * W * Cout_s < (1L << 30), "wgrad c3 bf16: image too large for 31-bit byte offsets");
-    const int phase = osvos_wgrad_phase();
-    if (phase != 2) {
+    OSVOS_ARG_CHECK(!c.x_bf16, "wgrad c3: x (3 channels) must be fp32");
+    if (phase != WGRAD_REDUCE) {
       hipLaunchKernelGGL(wgrad_c3_bf16_kernel, dim3(p.nsplit), dim3(256), Q_LDS, stream, a);
       OSVOS_LAUNCH_CHECK();
     }
-    if (phase == 1) return 0;
+    if (phase == WGRAD_PARTIALS) return 0;
     hipLaunchKernelGGL(wgrad_c3_reduce_kernel, dim3(ceil_div(Cout * 28, 4)), dim3(256), 0, stream,
                        a.slab, a.bslab, dw, db, p.nsplit, Cout, accumulate);
     OSVOS_LAUNCH_CHECK();
@@ -538,46 +542,41 @@ int osvos_conv3x3_wgrad_small_f32(const void* x, const void* dy, int wide_bf16, 
   }
   if (Cin == 3 && Cin_s == 8 && Cout <= 64 && Cout % 4 == 0) {
     SmallPlan p = plan_c3(N, H, W);
-    C3Args a;
-    a.x = reinterpret_cast<const float*>(x); a.dy = dy; a.dy_bf16 = wide_bf16;
-    a.slab = reinterpret_cast<float*>(ws);
-    a.bslab = db ? a.slab + p.slab_floats : nullptr;
-    a.N = N; a.H = H; a.W = W; a.Cout = Cout; a.Cout_s = Cout_s;
-    a.npx = p.npx; a.npy = p.npy; a.npatches = p.npatches; a.per_split = p.per_split;
+    const C3Args a = c3_args(c, p);
+    OSVOS_ARG_CHECK(!c.x_bf16, "wgrad c3: x (3 channels) must be fp32");
     constexpr size_t lds = (size_t)(C3_PPIX * 64 + C3_XPIX * 4) * 4;
     static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};      // hipFuncSetAttribute is per device
-  bool& attr_set = attr_set_dev[osvos_current_device()];
+    bool& attr_set = attr_set_dev[osvos_current_device()];
     if (!attr_set) {
       OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_c3_f32_kernel),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       attr_set = true;
     }
-    const int phase = osvos_wgrad_phase();
-    if (phase != 2) {
+    if (phase != WGRAD_REDUCE) {
       hipLaunchKernelGGL(wgrad_c3_f32_kernel, dim3(p.nsplit), dim3(256), lds, stream, a);
       OSVOS_LAUNCH_CHECK();
     }
-    if (phase == 1) return 0;
+    if (phase == WGRAD_PARTIALS) return 0;
     hipLaunchKernelGGL(wgrad_c3_reduce_kernel, dim3(ceil_div(Cout * 28, 4)), dim3(256), 0, stream,
                        a.slab, a.bslab, dw, db, p.nsplit, Cout, accumulate);
     OSVOS_LAUNCH_CHECK();
     return 0;
   }
   if (Cout == 16 && Cout_s % 4 == 0 && Cin_s % 32 == 0 && Cin == Cin_s) {
+    OSVOS_ARG_CHECK(!c.dy_bf16, "wgrad co16: dy (16 channels) must be fp32");
     SmallPlan p = plan_co16(N, H, W, Cin_s);
     S16Args a;
-    a.x = x; a.x_bf16 = wide_bf16; a.dy = reinterpret_cast<const float*>(dy);
+    a.x = c.x; a.x_bf16 = c.x_bf16 ? 1 : 0; a.dy = reinterpret_cast<const float*>(c.dy);
     a.slab = reinterpret_cast<float*>(ws);
     a.bslab = db ? a.slab + p.slab_floats : nullptr;
     a.N = N; a.H = H; a.W = W; a.Cin_s = Cin_s; a.Cout_s = Cout_s;
     a.npx = p.npx; a.npy = p.npy; a.npatches = p.npatches; a.per_split = p.per_split; a.nci_t = p.nci_t;
     constexpr size_t lds = (size_t)(S_PPIX * S_BCI + S_YPIX * 16) * 4;
-    const int phase = osvos_wgrad_phase();
-    if (phase != 2) {
+    if (phase != WGRAD_REDUCE) {
       hipLaunchKernelGGL(wgrad_co16_f32_kernel, dim3(p.nsplit * p.nci_t), dim3(256), lds, stream, a);
       OSVOS_LAUNCH_CHECK();
     }
-    if (phase == 1) return 0;
+    if (phase == WGRAD_PARTIALS) return 0;
     return osvos_wgrad_reduce_launch(a.slab, a.bslab, dw, db, p.nsplit, 16, Cin, Cin_s, accumulate, stream);
   }
   return 1;

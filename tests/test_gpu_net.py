@@ -781,3 +781,93 @@ def test_pool_code_bytes_change_nothing_but_the_bytes_read_bf16(tmp_path):
         assert got[tag].keys() == base.keys()
         for k in base:
             assert np.array_equal(got[tag][k], base[k]), (tag, k, float(np.abs(got[tag][k] - base[k]).max()))
+
+
+@pytest.mark.gpu
+def test_weight_gradient_halves_on_two_streams_equal_the_whole_launch(tmp_path):
+    """osvos_net_backward enqueues every weight gradient either whole (one side stream, OSVOS_THREE_STREAMS=0; everything on the caller's stream,
+    OSVOS_TWO_STREAMS=0) or as two halves of one WgradCall: partial slabs on the weight-gradient stream, their reduce on the third stream (the
+    default).  Same kernels, same slabs, same order of summation: every parameter gradient and the input gradient must be BYTE-EQUAL across the
+    three settings, for every weight-gradient family and piece count (exact fp32; f32x3 with 3, 2 and FP16-pair pieces, side_prep on its S16 form;
+    the bf16-store mode, side_prep on the Cout = 16 route of the bf16 kernel).  All five heads; the streams are read when the runtime is
+    built: one subprocess per setting."""
+    import os, subprocess, sys, textwrap
+    code = textwrap.dedent('''
+        import sys, numpy as np, torch
+        sys.path.insert(0, %r); sys.path.insert(0, %r)
+        import test_gpu_net as T
+        from oracle import synth
+        from layers.osvos_layers import class_balanced_cross_entropy_loss as cbce
+        res = {}
+        wts, x, m = synth.calibrated_problem(1, 64, 96, seed=21)
+        for prec in ("fp32", "fp32x3", "fp32x3b2", "fp32h2", "bf16"):
+            net = T.build_net(wts, prec)
+            xg = torch.from_numpy(x).cuda().requires_grad_()
+            gt = torch.from_numpy(m).cuda()
+            sum(cbce(o, gt, size_average=False) for o in net.forward(xg)).backward()
+            torch.cuda.synchronize()
+            for k, v in net.named_parameters():
+                if v.grad is not None:
+                    res["%%s:%%s" %% (prec, k)] = v.grad.cpu().numpy()
+            res[prec + ":input"] = xg.grad.cpu().numpy()
+        np.savez(sys.argv[1], **res)
+    ''') % (os.path.dirname(os.path.abspath(__file__)), os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    got = {}
+    for tag, env in (("three", {}), ("two", {"OSVOS_THREE_STREAMS": "0"}), ("one", {"OSVOS_TWO_STREAMS": "0"})):
+        out = str(tmp_path / (tag + ".npz"))
+        subprocess.run([sys.executable, "-c", code, out], check=True, env=dict(os.environ, **env), timeout=900)
+        got[tag] = dict(np.load(out))
+    base = got["three"]
+    for prec in ("fp32", "fp32x3", "fp32x3b2", "fp32h2", "bf16"):
+        assert sum(k.startswith(prec + ":") for k in base) > 40, prec
+    for tag in ("two", "one"):
+        assert got[tag].keys() == base.keys()
+        for k in base:
+            assert np.isfinite(base[k]).all(), k
+            assert got[tag][k].tobytes() == base[k].tobytes(), (tag, k, float(np.abs(got[tag][k] - base[k]).max()))
+
+
+@pytest.mark.gpu
+def test_op_level_x3_pieces_and_network_calls_do_not_see_each_other():
+    """ops.set_x3_pieces is the arithmetic of the OP-LEVEL f32x3 entries on this thread; a network call takes its pieces from its precision.
+    Neither leaks into the other: an 'fp32x3' forward + backward after set_x3_pieces(2) equals the one without it byte for byte, and an
+    op-level conv3x3_x3 (default three pieces) gives the same bytes before and after an 'fp32x2' network step."""
+    from oracle import synth
+    from osvos_pytorch_amd import ops
+    from osvos_pytorch_amd.layers.osvos_layers import class_balanced_cross_entropy_loss as cbce
+    wts, x, m = synth.calibrated_problem(1, 64, 96, seed=21)
+    gt = torch.from_numpy(m).cuda()
+
+    def step(precision):
+        net = build_net(wts, precision)
+        xin = torch.from_numpy(x).cuda().requires_grad_()
+        outs = net.forward(xin)
+        sum(cbce(o, gt, size_average=False) for o in outs).backward()
+        res = {"out%d" % i: o.detach().clone() for i, o in enumerate(outs)}
+        res.update({k: p.grad.detach().clone() for k, p in net.named_parameters() if p.grad is not None})
+        res["input"] = xin.grad.detach().clone()
+        return res
+
+    g = torch.Generator().manual_seed(7)
+    xo = torch.randn(1, 16, 24, 64, generator=g).cuda()
+    wo = (torch.randn(64, 64, 3, 3, generator=g) / 24).cuda()
+    bo = torch.randn(64, generator=g).cuda()
+    op = lambda: ops.conv3x3_x3(xo, ops.pack_x3(wo), bo, 64, relu=True)
+    try:
+        plain = step("fp32x3")
+        ops.set_x3_pieces(2)
+        y2 = op()
+        under2 = step("fp32x3")
+        assert torch.equal(op(), y2)                         # ... and the op-level setting survives the network call
+        ops.set_x3_pieces(3)
+        before = op()
+        assert not torch.equal(before, y2)                   # (the setting does reach the op-level entry)
+        step("fp32x2")
+        after = op()
+    finally:
+        ops.set_x3_pieces(3)
+    assert set(plain) == set(under2) and len(plain) > 45
+    for k in plain:
+        assert torch.isfinite(plain[k]).all(), k
+        assert plain[k].cpu().numpy().tobytes() == under2[k].cpu().numpy().tobytes(), k
+    assert before.cpu().numpy().tobytes() == after.cpu().numpy().tobytes()

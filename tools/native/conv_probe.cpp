@@ -46,7 +46,7 @@ int main(int argc, char** argv) {
   void* dwp3 = nullptr;
   if (x3ps) {
     CK(hipMalloc(&dwp3, osvos_wpack_x3_bytes(Cout, Cin)));
-    if (osvos_pack_x3(dw, dwp3, Cout, Cin, 0, 0)) { fprintf(stderr, "pack x3: %s\n", osvos_last_error()); return 1; }
+    if (osvos_pack_x3(dw, dwp3, Cout, Cin, 0, 0, 0)) { fprintf(stderr, "pack x3: %s\n", osvos_last_error()); return 1; }
   }
   const int ks_env = getenv("PROBE_KSPLIT") ? atoi(getenv("PROBE_KSPLIT")) : 0;
   auto launch = [&](int tile) {

@@ -38,14 +38,17 @@ static void run(int N, int H, int W, int Cin, int Cout) {
   CK(hipMalloc(&prof, nprof * 8)); CK(hipMemset(prof, 0, nprof * 8));
   osvos_debug_set_wgrad_prof_bf16(prof);
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+  WgradCall c;
+  c.x = dx; c.dy = ddy; c.x_bf16 = c.dy_bf16 = 1; c.ws = ws; c.dw = dw; c.db = db;
+  c.N = N; c.H = H; c.W = W; c.Cin = c.Cin_s = Cin; c.Cout = c.Cout_s = Cout;
   for (int phase = 1; phase >= 0; --phase) {        // 1: the MFMA kernel alone, 0: kernel + slab reduce
-    osvos_wgrad_set_phase(phase);
+    c.phase = phase ? WGRAD_PARTIALS : WGRAD_BOTH;
     for (int i = 0; i < 3; ++i)
-      if (osvos_conv3x3_wgrad_bf16mfma(dx, ddy, 1, ws, dw, db, N, H, W, Cin, Cin, Cout, Cout, 0, 0)) { fprintf(stderr, "launch failed: %s\n", osvos_last_error()); exit(1); }
+      if (osvos_conv3x3_wgrad_bf16mfma(c)) { fprintf(stderr, "launch failed: %s\n", osvos_last_error()); exit(1); }
     CK(hipDeviceSynchronize());
     const int reps = getenv("PROBE_REPS") ? atoi(getenv("PROBE_REPS")) : 10;
     CK(hipEventRecord(e0, 0));
-    for (int i = 0; i < reps; ++i) osvos_conv3x3_wgrad_bf16mfma(dx, ddy, 1, ws, dw, db, N, H, W, Cin, Cin, Cout, Cout, 0, 0);
+    for (int i = 0; i < reps; ++i) osvos_conv3x3_wgrad_bf16mfma(c);
     CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
     float ms; CK(hipEventElapsedTime(&ms, e0, e1));
     const double fl = 2.0 * N * H * W * (double)Cout * Cin * 9;
