@@ -415,6 +415,25 @@ int osvos_components_select(const float* logits, const int* labels, const int* a
                             int seed_radius, int min_area, int keep_largest, float fill, float* out_logits, unsigned char* kept, void* ws, int N,
                             int H, int W, float logit_threshold, void* stream);
 
+/* ---- test-time augmentation: resized / mirrored network inputs from the decoded frame, and the views' logit maps fused on one grid ----
+ * Sampling rule of both calls: separable bilinear with half-pixel centres (the geometry of F.interpolate(mode='bilinear',
+ *   align_corners=False)), taps in integers: for destination index i of n_dst over a source of n_src
+ *     num = max((2 i + 1) n_src - n_dst, 0), den = 2 n_dst, i0 = min(num / den, n_src - 1), i1 = min(i0 + 1, n_src - 1),
+ *     f = float(num % den) / float(den) is the weight of i1, 1 - f that of i0;  value = f == 0 ? s[i0] : (1 - f) s[i0] + f s[i1]
+ *   along x first, then along y, without fused multiply-adds.  A tap of weight zero is not read into the sum, so a source of the
+ *   destination's own size passes through bit for bit (inf and NaN included).  Every side 1..16384 (num stays inside int32), N 1..65535.
+ * osvos_tta_view: bgr [N][H][W][3] uint8 (device) -> out [N][3][Hv][Wv] fp32 = sample of channel c minus mean3[c] (mean3: HOST pointer,
+ *   as in osvos_augment_frame).  flip != 0: destination column x holds exactly what the unflipped view holds at column Wv - 1 - x.
+ *   Hv == H, Wv == W, flip == 0 is bit-identical to osvos_augment_frame's image output for the identity transform.
+ * osvos_tta_fuse: views[v] [N][Hv[v]][Wv[v]] fp32 (device pointers, 4-byte aligned) -> out [N][H][W] = sum_v weight[v] * sample_v(y, x),
+ *   summed in the order of v starting from the first product; sample_v reads view v through column Wv[v] - 1 - c where flip[v] != 0.
+ *   views, Hv, Wv, flip and weight are HOST arrays of length V, 1 <= V <= OSVOS_TTA_MAX_VIEWS; weight == NULL means 1 / V each.  The maps
+ *   are logits: a mean of logits, never of sigmoids.  One launch each on `stream`, no workspace, nothing uploaded. */
+#define OSVOS_TTA_MAX_VIEWS 16
+int osvos_tta_view(const unsigned char* bgr, const float* mean3, float* out, int N, int H, int W, int Hv, int Wv, int flip, void* stream);
+int osvos_tta_fuse(const float* const* views, const int* Hv, const int* Wv, const int* flip, const float* weight, int V, float* out, int N,
+                   int H, int W, void* stream);
+
 /* ---- fused SGD (torch.optim.SGD semantics, train_online.py:79-88,147) ----------------------
  * for each i: d = g + wd*p; buf = first ? d : momentum*buf + d; p -= lr*buf      (flat tensors) */
 int osvos_sgd_step(float* p, const float* g, float* buf, long count, float lr, float momentum,

@@ -14,6 +14,8 @@ running on the MI355X-native OSVOS path.  Differences by design:
     per frame on the device, indexed PNGs, J and F per object (osvos_pytorch_amd.results.merge_objects / MultiObjectEvaluator)
   * ``--track-components R``: connected-component clean-up of every test frame on the device -- a component of the thresholded mask is kept
     when it lies within R pixels of what was kept of the previous frame, starting from the first annotation (results.ComponentTracker)
+  * ``--tta-scales S1,S2,..`` / ``--tta-flip``: test-time augmentation of the test forwards -- every frame at each scale and (flip) mirrored,
+    the views' logit maps resampled onto the frame's grid and averaged on the device (osvos_pytorch_amd.tta.TestTimeAugment)
   * launched under torchrun with N processes, rank r fine-tunes sequences r, r+N, ... of the
     comma-separated SEQ_NAME list (independent replicas: online training has no exchange step)
 """
@@ -88,8 +90,9 @@ class DeviceTestFrames(object):
     """train_online.py:98-100 on the device: every frame of the sequence, decoded on the host a few frames ahead, mean-subtracted and
     laid out CHW by the augmentation kernel with the identity transform (the reference's test transform is ToTensor only)."""
 
-    def __init__(self, frames, device, depth):
-        self.frames, self.device, self.depth = frames, device, depth
+    def __init__(self, frames, device, depth, raw_only=False):
+        # raw_only (test-time augmentation makes its own views from 'frame_u8'): no identity pass, and no 'image', for a frame without annotation
+        self.frames, self.device, self.depth, self.raw_only = frames, device, depth, raw_only
 
     def __len__(self):
         return len(self.frames)
@@ -98,8 +101,12 @@ class DeviceTestFrames(object):
         from osvos_pytorch_amd.augment import augment_frame
         from osvos_pytorch_amd.davis_io import DevicePrefetcher
         for idx, img, lab in DevicePrefetcher(self.frames, range(len(self.frames)), self.device, depth=self.depth):
+            out = {'fname': [self.frames.fname(idx)], 'frame_u8': img}      # (the decoded frame: test-time augmentation)
+            if lab is None and self.raw_only:
+                yield out
+                continue
             image, gt = augment_frame(img, lab, flip=False, rot=None)
-            out = {'image': image[None], 'fname': [self.frames.fname(idx)]}
+            out['image'] = image[None]
             if lab is not None:
                 out['gt'] = gt[None]
             yield out
@@ -117,7 +124,7 @@ def device_loaders(args, seq_name, device, seed):
     else:
         train, test = DavisFrames(True, Path.db_root_dir(), seq_name=seq_name), DavisFrames(False, Path.db_root_dir(), seq_name=seq_name)
     img, lab = train[0]
-    return DeviceTrainFrame(img, lab, device), DeviceTestFrames(test, device, args.prefetch)
+    return DeviceTrainFrame(img, lab, device), DeviceTestFrames(test, device, args.prefetch, raw_only=bool(args.tta))
 
 
 def synthetic_objects(h, w):
@@ -172,6 +179,25 @@ def fine_tune(args, net, optimizer, trainloader, device, nEpochs, nAveGrad, seed
     print('Online training time: ' + str(timeit.default_timer() - start_time))
 
 
+def tta_scales(args):
+    """the scales of --tta-scales / --tta-flip (() = test-time augmentation off); SystemExit on a bad list -- checked before any GPU work"""
+    from osvos_pytorch_amd import tta
+    try:
+        scales = tta.parse_scales(args.tta_scales)
+        if not scales and not args.tta_flip:
+            return ()
+        scales = scales or (1.0,)
+        tta.plan(args.height, args.width, scales, args.tta_flip)      # (duplicates and the view count; the real frame size is checked per frame)
+    except ValueError as e:
+        raise SystemExit('--tta-scales: %s' % e)
+    return scales
+
+
+def make_tta(args, net):
+    from osvos_pytorch_amd.tta import TestTimeAugment
+    return TestTimeAugment(net.forward, args.tta, args.tta_flip) if args.tta else None
+
+
 def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, nEpochs, nAveGrad):
     """DAVIS 2017 recipe for one sequence: one fine-tuning per object id of the first annotation on that object's binary mask, every frame
     through each network, the K logit stacks merged into label maps, indexed PNGs, J and F per object -- one read-back for the PNGs, one for
@@ -210,12 +236,16 @@ def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, n
         start_time = timeit.default_timer()
         if args.test_precision:
             net.set_precision(args.test_precision)
+        tta = make_tta(args, net)
         with torch.no_grad():
             for f, img in enumerate(frames):
-                logits[k - 1, f].copy_(net.forward(augment_frame(img, None, flip=False, rot=None)[0][None])[-1][0, 0])
+                if tta is not None:
+                    logits[k - 1, f].copy_(tta(img)[0, 0])
+                else:
+                    logits[k - 1, f].copy_(net.forward(augment_frame(img, None, flip=False, rot=None)[0][None])[-1][0, 0])
         torch.cuda.synchronize()
         test_time += timeit.default_timer() - start_time
-        del net, optimizer, trainloader
+        del net, optimizer, trainloader, tta
 
     save_dir_res = os.path.join(save_dir, 'Results', seq_name)
     os.makedirs(save_dir_res, exist_ok=True)
@@ -273,7 +303,19 @@ def main():
                     help='clean every test frame\'s mask on the device before it is written and scored: of the connected components of the '
                          'thresholded mask keep those within R pixels (0..64) of what was kept of the previous frame, seeded with the first '
                          'annotation; when nothing was kept the next frame passes whole.  With --multi-object: one tracker per object')
+    ap.add_argument('--tta-scales', default='', metavar='S1,S2,..',
+                    help='test-time augmentation: run every test frame at these scales (view size floor(side * s + 0.5)), bring the logit maps '
+                         'back to the frame\'s grid and average them on the device, before --track-components, the PNG writer and the evaluator.  '
+                         'Costs about the sum of s^2 forwards per frame.  Needs the decoded uint8 frame: --device-augment, or --multi-object '
+                         '--synthetic')
+    ap.add_argument('--tta-flip', action='store_true',
+                    help='test-time augmentation: every scale (scale 1 alone without --tta-scales) also runs mirrored, in the same batch; twice '
+                         'the forwards')
     args = ap.parse_args()
+    args.tta = tta_scales(args)
+    if args.tta and not (args.device_augment or (args.multi_object and args.synthetic)):
+        raise SystemExit('--tta-scales / --tta-flip need --device-augment (or --multi-object --synthetic): test-time augmentation makes its views '
+                         'from the decoded uint8 frame on the device')
     if args.track_components is not None and not 0 <= args.track_components <= 64:
         raise SystemExit('--track-components takes a radius of 0..64 pixels, got %d' % args.track_components)
     if args.multi_object and not (args.device_augment or args.synthetic):
@@ -310,11 +352,15 @@ def main():
         tracker = None
         if args.test_precision:
             net.set_precision(args.test_precision)      # (re-packs the weights once: the FP16-pair packs are another format)
+        tta = make_tta(args, net)
         with torch.no_grad():
             for sample in testloader:
-                img, fname = sample['image'], sample['fname']
-                outputs = net.forward(img.to(device))
-                fused = outputs[-1]
+                fname = sample['fname']
+                if tta is not None:
+                    fused = tta(sample['frame_u8'])
+                else:
+                    outputs = net.forward(sample['image'].to(device))
+                    fused = outputs[-1]
                 if args.track_components is not None:
                     if tracker is None:
                         if 'gt' not in sample:
@@ -322,7 +368,7 @@ def main():
                         tracker = ComponentTracker(sample['gt'].to(device)[0, 0] > 0.5, args.track_components)
                     fused = tracker(fused)
                 # sigmoid + scipy<=1.1 imsave byte scaling on the device, PNG written by osvos_pytorch_amd.results (reference :181-187)
-                save_masks(fused, [os.path.join(save_dir_res, os.path.basename(fname[jj]) + '.png') for jj in range(int(img.size()[0]))])
+                save_masks(fused, [os.path.join(save_dir_res, os.path.basename(fname[jj]) + '.png') for jj in range(int(fused.size()[0]))])
                 if 'gt' in sample:
                     evaluator.add(fused, sample['gt'].to(device))
         if evaluator.frames:
