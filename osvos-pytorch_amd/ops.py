@@ -26,6 +26,14 @@ def _need_cuda(*ts):
             raise RuntimeError("osvos_pytorch_amd ops need CUDA (ROCm) tensors; there is no CPU fallback")
 
 
+def _out(out, shape, dtype, like):
+    """a caller's result buffer (`out=`: the kernel writes into memory the caller chose, reused workspace for one) checked against what the
+    wrapper would have allocated"""
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != like.device or not out.is_contiguous():
+        raise RuntimeError("out= must be a contiguous %s tensor of shape %s on %s" % (dtype, tuple(shape), like.device))
+    return out
+
+
 def nchw_to_nhwc(x, cpad):
     _need_cuda(x)
     x = x.contiguous().float()
@@ -61,35 +69,44 @@ def pack_dgrad(w_oihw, dtype=F32):
     return buf
 
 
-def conv3x3_splitk(x, wpk, bias, cout, ksplit, relu=False, mask=None, tile=-1, dtype=F32):
-    """fp32 conv cut into `ksplit` K parts (0 = automatic) + finalize kernel; dtype F32_X3: in the f32x3 arithmetic where it applies."""
-    _need_cuda(x, wpk, bias, mask)
+def conv3x3_splitk(x, wpk, bias, cout, ksplit, relu=False, mask=None, tile=-1, dtype=F32, out=None):
+    """fp32 conv cut into `ksplit` K parts (0 = automatic) + finalize kernel; dtype F32_X3: in the f32x3 arithmetic where it applies.
+    out: write the result into this [N,H,W,cout] fp32 tensor."""
+    _need_cuda(x, wpk, bias, mask, out)
     n, h, w, cin = x.shape
-    y = torch.empty((n, h, w, cout), device=x.device, dtype=torch.float32)
+    y = torch.empty((n, h, w, cout), device=x.device, dtype=torch.float32) if out is None else _out(out, (n, h, w, cout), torch.float32, x)
     part = torch.empty(lib().osvos_conv3x3_splitk_ws_bytes(n, h, w, cout, F32), device=x.device, dtype=torch.uint8)
     check(lib().osvos_conv3x3_splitk(_p(x), _p(wpk), _p(bias), _p(mask), _p(y), n, h, w, cin, cout, cout, int(relu), dtype, tile,
                                      ksplit, _p(part), _stream()), "conv3x3_splitk")
     return y
 
 
-def conv3x3(x, wpk, bias, cout, relu=False, mask=None, y_cs=None, tile=-1, dtype=F32):
-    """x [N,H,W,Cin] (Cin % 8 == 0), wpk from pack_fwd / pack_dgrad -> [N,H,W,y_cs]."""
-    _need_cuda(x, wpk, bias, mask)
+def conv3x3(x, wpk, bias, cout, relu=False, mask=None, y_cs=None, tile=-1, dtype=F32, out=None):
+    """x [N,H,W,Cin] (Cin % 8 == 0), wpk from pack_fwd / pack_dgrad -> [N,H,W,y_cs]; out: write the result into this fp32 tensor."""
+    _need_cuda(x, wpk, bias, mask, out)
     n, h, w, cin = x.shape
     y_cs = y_cs or cout
-    y = torch.zeros((n, h, w, y_cs), device=x.device, dtype=torch.float32) if y_cs != cout else \
-        torch.empty((n, h, w, y_cs), device=x.device, dtype=torch.float32)
+    if out is not None:
+        y = _out(out, (n, h, w, y_cs), torch.float32, x)
+    else:
+        y = torch.zeros((n, h, w, y_cs), device=x.device, dtype=torch.float32) if y_cs != cout else \
+            torch.empty((n, h, w, y_cs), device=x.device, dtype=torch.float32)
     check(lib().osvos_conv3x3(_p(x), _p(wpk), _p(bias), _p(mask), _p(y), n, h, w, cin, cout, y_cs, int(relu), dtype, tile, _stream()), "conv3x3")
     return y
 
 
-def conv3x3_bf16io(x, wpk, bias, cout, relu=False, mask=None, y_cs=None, tile=-1, want_bf16=True, want_f32=True):
-    """bf16-MFMA convolution with explicit formats: x and mask fp32 or torch.bfloat16 [N,H,W,C]; returns (y fp32 | None, y bf16 | None)."""
-    _need_cuda(x, wpk, bias, mask)
+def conv3x3_bf16io(x, wpk, bias, cout, relu=False, mask=None, y_cs=None, tile=-1, want_bf16=True, want_f32=True, out=None):
+    """bf16-MFMA convolution with explicit formats: x and mask fp32 or torch.bfloat16 [N,H,W,C]; returns (y fp32 | None, y bf16 | None).
+    out: (fp32 tensor | None, bf16 tensor | None) to write the wanted results into."""
+    out_f32, out_bf16 = out if out is not None else (None, None)
+    _need_cuda(x, wpk, bias, mask, out_f32, out_bf16)
     n, h, w, cin = x.shape
     y_cs = y_cs or cout
-    y = torch.zeros((n, h, w, y_cs), device=x.device, dtype=torch.float32) if want_f32 else None
-    yb = torch.zeros((n, h, w, y_cs), device=x.device, dtype=torch.bfloat16) if want_bf16 else None
+    y = yb = None
+    if want_f32:
+        y = torch.zeros((n, h, w, y_cs), device=x.device, dtype=torch.float32) if out_f32 is None else _out(out_f32, (n, h, w, y_cs), torch.float32, x)
+    if want_bf16:
+        yb = torch.zeros((n, h, w, y_cs), device=x.device, dtype=torch.bfloat16) if out_bf16 is None else _out(out_bf16, (n, h, w, y_cs), torch.bfloat16, x)
     check(lib().osvos_conv3x3_bf16io(_p(x), int(x.dtype == torch.bfloat16), _p(wpk), _p(bias), _p(mask),
                                      int(mask is not None and mask.dtype == torch.bfloat16), _p(y), _p(yb), n, h, w, cin, cout,
                                      y_cs, int(relu), tile, _stream()), "conv3x3_bf16io")
@@ -102,13 +119,13 @@ def set_x3_pieces(pieces):
     check(lib().osvos_set_x3_pieces(int(pieces)), "set_x3_pieces")
 
 
-def conv3x3_bf16act_fused(x, wpk, bias, cout, relu=False, mask_bits=None, want_bits=False, want_pool=False, tile=-1):
+def conv3x3_bf16act_fused(x, wpk, bias, cout, relu=False, mask_bits=None, want_bits=False, want_pool=False, tile=-1, out=None):
     """The bf16-store trunk convolution with its fused epilogues (osvos_conv3x3_bf16act_fused): x torch.bfloat16 [N,H,W,Cin];
-    returns (y bf16, y_bits int32 [N,H,W,cout/32] | None, pooled bf16 | None, pool_code uint8 | None)."""
-    _need_cuda(x, wpk, bias, mask_bits)
+    returns (y bf16, y_bits int32 [N,H,W,cout/32] | None, pooled bf16 | None, pool_code uint8 | None).  out: write y into this bf16 tensor."""
+    _need_cuda(x, wpk, bias, mask_bits, out)
     assert x.dtype == torch.bfloat16
     n, h, w, cin = x.shape
-    y = torch.zeros((n, h, w, cout), device=x.device, dtype=torch.bfloat16)
+    y = torch.zeros((n, h, w, cout), device=x.device, dtype=torch.bfloat16) if out is None else _out(out, (n, h, w, cout), torch.bfloat16, x)
     bits = torch.zeros((n, h, w, cout // 32), device=x.device, dtype=torch.int32) if want_bits else None
     pooled = torch.zeros((n, (h + 1) // 2, (w + 1) // 2, cout), device=x.device, dtype=torch.bfloat16) if want_pool else None
     code = torch.zeros((n, (h + 1) // 2, (w + 1) // 2, cout), device=x.device, dtype=torch.uint8) if want_pool else None
@@ -340,12 +357,15 @@ def pack_x3(w_oihw, dgrad=False):
     return buf
 
 
-def conv3x3_x3(x, wpk3, bias, cout, relu=False, mask=None, y_cs=None, tile=-1):
-    """f32x3 convolution with pre-split weights: x [N,H,W,Cin] fp32 -> [N,H,W,y_cs] fp32"""
-    _need_cuda(x, wpk3, bias, mask)
+def conv3x3_x3(x, wpk3, bias, cout, relu=False, mask=None, y_cs=None, tile=-1, out=None):
+    """f32x3 convolution with pre-split weights: x [N,H,W,Cin] fp32 -> [N,H,W,y_cs] fp32; out: write the result into this fp32 tensor"""
+    _need_cuda(x, wpk3, bias, mask, out)
     n, h, w, cin = x.shape
     y_cs = y_cs or cout
-    y = torch.zeros((n, h, w, y_cs), device=x.device, dtype=torch.float32) if y_cs != cout else torch.empty((n, h, w, y_cs), device=x.device, dtype=torch.float32)
+    if out is not None:
+        y = _out(out, (n, h, w, y_cs), torch.float32, x)
+    else:
+        y = torch.zeros((n, h, w, y_cs), device=x.device, dtype=torch.float32) if y_cs != cout else torch.empty((n, h, w, y_cs), device=x.device, dtype=torch.float32)
     check(lib().osvos_conv3x3_x3(_p(x), _p(wpk3), _p(bias), _p(mask), _p(y), n, h, w, cin, cout, y_cs, int(relu), tile, _stream()), "conv3x3_x3")
     return y
 
@@ -366,11 +386,12 @@ def streamk_workspace(device):
     return _SK_WS[key]
 
 
-def conv3x3_x3_streamk(x, wpk3, bias, cout, relu=False, mask=None, tile=-1, grid=0, want_pooled=False):
-    """stream-K form of conv3x3_x3 (grid 0 = automatic, > 0 = that many persistent workgroups); returns y or (y, pooled)"""
-    _need_cuda(x, wpk3, bias, mask)
+def conv3x3_x3_streamk(x, wpk3, bias, cout, relu=False, mask=None, tile=-1, grid=0, want_pooled=False, out=None):
+    """stream-K form of conv3x3_x3 (grid 0 = automatic, > 0 = that many persistent workgroups); returns y or (y, pooled); out: write y into
+    this fp32 tensor"""
+    _need_cuda(x, wpk3, bias, mask, out)
     n, h, w, cin = x.shape
-    y = torch.empty((n, h, w, cout), device=x.device, dtype=torch.float32)
+    y = torch.empty((n, h, w, cout), device=x.device, dtype=torch.float32) if out is None else _out(out, (n, h, w, cout), torch.float32, x)
     pooled = torch.empty((n, (h + 1) // 2, (w + 1) // 2, cout), device=x.device, dtype=torch.float32) if want_pooled else None
     check(lib().osvos_conv3x3_x3_streamk(_p(x), _p(wpk3), _p(bias), _p(mask), _p(y), _p(pooled), n, h, w, cin, cout, cout, int(relu), tile, grid,
                                          _p(streamk_workspace(x.device)), _stream()), "conv3x3_x3_streamk")

@@ -1151,7 +1151,8 @@ def test_conv3x3_f32x3_streamk(case):
     assert torch.equal(y, y3), case
     # data-gradient form: rotated pack, ReLU mask of the producer, no bias
     dy = torch.randn(n, cout, h, w, generator=g)
-    m = torch.randn(n, cin, h, w, generator=g)
+    from relu_mask_cases import post_relu_mask
+    m = post_relu_mask((n, cin, h, w), cin + cout + h, torch.float32)      # a real post-ReLU operand: exact zeros, -0.0, dead blocks
     dpk3 = ops.pack_x3(wt.cuda(), dgrad=True)
     dx = ops.conv3x3_x3_streamk(nhwc(dy), dpk3, None, cin, mask=nhwc(m), tile=tile, grid=grid)
     ref_dx = torch.nn.grad.conv2d_input(x.shape, wt.double(), dy.double(), padding=1) * (m > 0)

@@ -28,9 +28,11 @@ WIDE = [
 ]
 
 CHILD = r"""
-import sys, torch
+import os, sys, torch
 sys.path.insert(0, sys.argv[1])
+sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
 from osvos_pytorch_amd import ops
+from relu_mask_cases import post_relu_mask
 shapes = eval(sys.argv[2])
 out = {}
 def nhwc(t):
@@ -41,7 +43,7 @@ for k, (n, h, w, cin, cout) in enumerate(shapes):
     wt = torch.randn(cout, cin, 3, 3, generator=g) / (3 * cin ** 0.5)
     b = torch.randn(cout, generator=g)
     dy = torch.randn(n, cout, h, w, generator=g)
-    m = torch.randn(n, cin, h, w, generator=g)
+    m = post_relu_mask((n, cin, h, w), 100 + k, torch.float32)      # a real post-ReLU operand: exact zeros, -0.0, dead blocks
     xg, pk3, dpk3 = nhwc(x), ops.pack_x3(wt.cuda()), ops.pack_x3(wt.cuda(), dgrad=True)
     for t in (-1, 10, 12, 14):
         out["fwd", k, t] = ops.conv3x3_x3(xg, pk3, b.cuda(), cout, relu=True, tile=t).cpu()
