@@ -209,6 +209,16 @@ size_t osvos_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int dtype);
 int osvos_conv3x3_wgrad(const void* x, const void* dy, void* ws, float* dw, float* db,
                         int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s,
                         int accumulate, int dtype, void* stream);
+/* conv1_1's weight gradient as the bf16-store mode runs it: x the 3-channel input as fp32 NHWC8 (channels 3..7 zero), dy bf16 NHWC with
+ * channel stride Cout_s; Cout <= 64, Cout % 4 == 0, Cout_s % 4 == 0.  Cout == 64 with Cout_s % 8 == 0 runs on the bf16 matrix pipe (x rounded
+ * to bf16 while staged) unless osvos_debug_set_c3_bf16(0), everything else on the exact fp32 kernel reading the bf16 dy.  ws: workspace of
+ * osvos_wgrad_ws_bytes(N, H, W, 8, Cout, OSVOS_F32_BF16MFMA); dw fp32 [Cout,3,3,3]; db fp32 [Cout] or NULL; accumulate as above */
+int osvos_conv3x3_wgrad_c3_bf16dy(const float* x_nhwc8, const void* dy_bf16, void* ws, float* dw, float* db, int N, int H, int W, int Cout,
+                                  int Cout_s, int accumulate, void* stream);
+/* host only, launches nothing: how conv1_1's weight gradient cuts N x H x W into patches and splits (one workgroup walks the per_split
+ * consecutive patches of a split; patches are numbered x fastest, then y, then image).  bf16_dy = 0: the fp32 kernel (32 x 8 pixel patches),
+ * 1: the bf16-pipe kernel (16 x 8).  out[5] = {npx, npy, npatches, per_split, nsplit} */
+int osvos_wgrad_c3_plan(int N, int H, int W, int bf16_dy, int* out);
 
 /* ---- 2x2/2 max-pool, ceil_mode (aten::max_pool2d_with_indices, vgg_osvos.py:140) ---------- */
 int osvos_maxpool2x2(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream);

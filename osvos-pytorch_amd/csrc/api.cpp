@@ -150,6 +150,18 @@ int osvos_conv3x3_wgrad_bf16act(const void* x_bf16, const void* dy_bf16, void* w
                                 int Cout, int Cout_s, int accumulate, void* stream) {
   return osvos_wgrad_dispatch(wgrad_call(x_bf16, dy_bf16, 1, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s, accumulate, stream), OSVOS_F32_BF16MFMA);
 }
+// conv1_1's weight gradient of the bf16-store mode at op level: fp32 NHWC8 input, bf16 dy (the skinny launcher picks the kernel)
+int osvos_conv3x3_wgrad_c3_bf16dy(const float* x_nhwc8, const void* dy_bf16, void* ws, float* dw, float* db, int N, int H, int W, int Cout,
+                                  int Cout_s, int accumulate, void* stream) {
+  OSVOS_ARG_CHECK(x_nhwc8 && dy_bf16 && ws && dw, "wgrad_c3_bf16dy: null pointer");
+  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0, "wgrad_c3_bf16dy: bad shape");
+  OSVOS_ARG_CHECK(Cout > 0 && Cout <= 64 && Cout % 4 == 0 && Cout_s % 4 == 0 && Cout <= Cout_s,
+                  "wgrad_c3_bf16dy: Cout <= 64, Cout and its stride multiples of 4 (Cout %d/%d)", Cout, Cout_s);
+  OSVOS_ARG_CHECK((long)H * W * Cout_s < (1L << 29), "wgrad_c3_bf16dy: image too large for 31-bit byte offsets");
+  WgradCall c = wgrad_call(x_nhwc8, dy_bf16, 0, ws, dw, db, N, H, W, 3, 8, Cout, Cout_s, accumulate, stream);
+  c.dy_bf16 = 1;
+  return osvos_wgrad_dispatch(c, OSVOS_F32_BF16MFMA);
+}
 int osvos_maxpool2x2_bf16act(const void* x_bf16, void* y_bf16, int N, int H, int W, int C, void* stream) {
   return osvos_maxpool2x2_bf16(x_bf16, y_bf16, N, H, W, C, (hipStream_t)stream);
 }

@@ -506,6 +506,13 @@ extern "C" int osvos_debug_set_c3_bf16(int on) {
   return prev;
 }
 
+extern "C" int osvos_wgrad_c3_plan(int N, int H, int W, int bf16_dy, int* out) {
+  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && out != nullptr, "wgrad_c3_plan: bad arguments");
+  const SmallPlan p = bf16_dy ? plan_c3_bf16(N, H, W) : plan_c3(N, H, W);
+  out[0] = p.npx; out[1] = p.npy; out[2] = p.npatches; out[3] = p.per_split; out[4] = p.nsplit;
+  return 0;
+}
+
 size_t osvos_wgrad_small_ws_bytes(int N, int H, int W, int Cin_s, int Cout) {
   if (Cin_s == 8 && Cout <= 64) {
     SmallPlan p = plan_c3(N, H, W), q = plan_c3_bf16(N, H, W);

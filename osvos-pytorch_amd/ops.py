@@ -244,12 +244,49 @@ def maxpool2x2_bwd_bf16copy(x, dy, dside=None):
     return dx, dxb
 
 
-def conv3x3_wgrad(x, dy, cin, cout, want_bias=True, accumulate_into=None, dtype=F32):
-    """x [N,H,W,Cin_s], dy [N,H,W,Cout_s] -> (dW [cout,cin,3,3], db [cout])."""
-    _need_cuda(x, dy)
+def _wgrad_ws(ws, nbytes, like):
+    """the weight-gradient workspace: a fresh one, or the caller's uint8 tensor of at least the queried size"""
+    if ws is None:
+        return torch.empty(nbytes, device=like.device, dtype=torch.uint8)
+    if ws.dtype != torch.uint8 or ws.device != like.device or not ws.is_contiguous() or ws.numel() < nbytes:
+        raise RuntimeError("ws= must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, like.device))
+    return ws
+
+
+def wgrad_c3_plan(n, h, w, bf16_dy):
+    """How conv1_1's weight gradient cuts the pixels (osvos_wgrad_c3_plan; host only, needs no GPU): dict of npx, npy, npatches,
+    per_split, nsplit for the fp32 kernel (bf16_dy False) or the bf16-pipe kernel (True)."""
+    out = (C.c_int * 5)()
+    check(lib().osvos_wgrad_c3_plan(n, h, w, int(bool(bf16_dy)), out), "wgrad_c3_plan")
+    return dict(zip(("npx", "npy", "npatches", "per_split", "nsplit"), [int(v) for v in out]))
+
+
+def conv3x3_wgrad_c3_bf16dy(x, dy, cout, want_bias=True, accumulate_into=None, ws=None):
+    """conv1_1's weight gradient of the bf16-store mode: x fp32 [N,H,W,8] (channels 3..7 zero), dy torch.bfloat16 [N,H,W,Cout_s]
+    -> (dW fp32 [cout,3,3,3], db fp32 [cout] | None).  ws: the caller's workspace instead of a fresh one."""
+    _need_cuda(x, dy, ws)
+    assert x.dtype == torch.float32 and dy.dtype == torch.bfloat16 and x.shape[3] == 8 and x.shape[:3] == dy.shape[:3]
+    assert x.is_contiguous() and dy.is_contiguous()
+    n, h, w, _ = x.shape
+    ws = _wgrad_ws(ws, lib().osvos_wgrad_ws_bytes(n, h, w, 8, cout, F32_BF16MFMA), x)
+    if accumulate_into is not None:
+        dw, db = accumulate_into
+        acc = 1
+    else:
+        dw = torch.empty((cout, 3, 3, 3), device=x.device, dtype=torch.float32)
+        db = torch.empty((cout,), device=x.device, dtype=torch.float32) if want_bias else None
+        acc = 0
+    check(lib().osvos_conv3x3_wgrad_c3_bf16dy(_p(x), _p(dy), _p(ws), _p(dw), _p(db), n, h, w, cout, dy.shape[3], acc, _stream()), "wgrad_c3_bf16dy")
+    return dw, db
+
+
+def conv3x3_wgrad(x, dy, cin, cout, want_bias=True, accumulate_into=None, dtype=F32, ws=None):
+    """x [N,H,W,Cin_s], dy [N,H,W,Cout_s] -> (dW [cout,cin,3,3], db [cout]).  ws: the caller's workspace (uint8, at least
+    osvos_wgrad_ws_bytes) instead of a fresh one."""
+    _need_cuda(x, dy, ws)
     n, h, w, cin_s = x.shape
     cout_s = dy.shape[3]
-    ws = torch.empty(lib().osvos_wgrad_ws_bytes(n, h, w, cin_s, cout, dtype), device=x.device, dtype=torch.uint8)
+    ws = _wgrad_ws(ws, lib().osvos_wgrad_ws_bytes(n, h, w, cin_s, cout, dtype), x)
     if accumulate_into is not None:
         dw, db = accumulate_into
         acc = 1
