@@ -219,6 +219,13 @@ int osvos_conv3x3_wgrad_c3_bf16dy(const float* x_nhwc8, const void* dy_bf16, voi
  * consecutive patches of a split; patches are numbered x fastest, then y, then image).  bf16_dy = 0: the fp32 kernel (32 x 8 pixel patches),
  * 1: the bf16-pipe kernel (16 x 8).  out[5] = {npx, npy, npatches, per_split, nsplit} */
 int osvos_wgrad_c3_plan(int N, int H, int W, int bf16_dy, int* out);
+/* host only, launches nothing: what the launcher of the WIDE weight-gradient kernels does with a shape (dense dY) -- dtype OSVOS_F32_X3: the
+ * f32x3 kernels (Cin_s, Cout multiples of 64, or Cout 16 with Cin_s % 128 == 0: the skinny form); OSVOS_F32_BF16MFMA: the bf16 kernels on fp32
+ * tensors (bf16_tensors = 0; Cout % 64 == 0) or on bf16 tensors (1; also Cout 16).  out[12] = {patch width, patch height, npx, npy, npatches,
+ * per_split, nsplit, nco_t, nci_t, workgroups, 1 if the XCD-local block map is taken, 1 if the 128-cout eight-wave bf16 form runs}; the
+ * workgroup of split s walks patches [s per_split, min((s + 1) per_split, npatches)), numbered x fastest, then y, then image.  Any other
+ * shape / dtype is an argument error. */
+int osvos_wgrad_wide_plan(int N, int H, int W, int Cin_s, int Cout, int dtype, int bf16_tensors, int* out);
 
 /* ---- 2x2/2 max-pool, ceil_mode (aten::max_pool2d_with_indices, vgg_osvos.py:140) ---------- */
 int osvos_maxpool2x2(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream);

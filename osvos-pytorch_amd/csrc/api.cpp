@@ -224,6 +224,18 @@ int osvos_conv3x3_wgrad(const void* x, const void* dy, void* ws, float* dw, floa
   return osvos_wgrad_dispatch(wgrad_call(x, dy, 0, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s, accumulate, stream), dtype);
 }
 
+// host only: which wide kernel osvos_wgrad_dispatch hands this shape to, and what that launcher's own plan / form / map selection says
+int osvos_wgrad_wide_plan(int N, int H, int W, int Cin_s, int Cout, int dtype, int bf16_tensors, int* out) {
+  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && Cin_s > 0 && Cout > 0 && out != nullptr, "wgrad_wide_plan: bad arguments");
+  if (bf16_tensors) {
+    OSVOS_ARG_CHECK(dtype == OSVOS_F32_BF16MFMA, "wgrad_wide_plan: bf16 tensors go with dtype OSVOS_F32_BF16MFMA (got %d)", dtype);
+    return osvos_wgrad_bf16_plan(N, H, W, Cin_s, Cout, 1, out);
+  }
+  if (dtype == OSVOS_F32_X3) return osvos_wgrad_f32x3_plan(N, H, W, Cin_s, Cout, out);
+  OSVOS_ARG_CHECK(dtype == OSVOS_F32_BF16MFMA && Cout % 64 == 0, "wgrad_wide_plan: no wide weight-gradient kernel for dtype %d Cout %d on fp32 tensors", dtype, Cout);
+  return osvos_wgrad_bf16_plan(N, H, W, Cin_s, Cout, 0, out);
+}
+
 int osvos_maxpool2x2(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream) {
   NEED_F32(dtype, "maxpool2x2");
   return osvos_maxpool2x2_f32((const float*)x, (float*)y, nullptr, N, H, W, C, (hipStream_t)stream);

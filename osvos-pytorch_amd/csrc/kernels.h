@@ -86,6 +86,9 @@ bool osvos_wgrad_f32x3_applicable(int Cin, int Cin_s, int Cout, int Cout_s);
 bool osvos_wgrad_f32x3_skinny_applicable(int Cin, int Cin_s, int Cout, int Cout_s);
 size_t osvos_wgrad_f32x3_ws_bytes(int N, int H, int W, int Cin_s, int Cout);
 int osvos_conv3x3_wgrad_f32x3(const WgradCall& c);
+// host only: the launcher's plan, form and block map for a dense dY, as osvos_wgrad_wide_plan lays them out (out[12]); same in wgrad_bf16.hip
+int osvos_wgrad_f32x3_plan(int N, int H, int W, int Cin_s, int Cout, int* out);
+int osvos_wgrad_bf16_plan(int N, int H, int W, int Cin_s, int Cout, int xb, int* out);
 size_t osvos_wpack_x3_bytes(int M, int K);
 #define OSVOS_PACK_MAX 40
 // n packs (n <= OSVOS_PACK_MAX) in one launch: ws[k] OIHW fp32 [Couts[k]][Cins[k]][3][3] -> dsts[k]; dgrads[k] != 0: data-gradient form.

@@ -608,6 +608,30 @@ WbPlan make_plan(int N, int H, int W, int Cin_s, int Cout, int bco = BCO) {
   return p;
 }
 
+// which form takes a launch (xb: bf16 tensors), its plan, its grid and its block map
+struct WbChoice {
+  int form;
+  bool wide;
+  WbPlan p;
+  long blocks;
+  int map;
+};
+WbChoice choose(int N, int H, int W, int Cin_s, int Cout, int xb) {
+  WbChoice ch;
+  static const int form_env = getenv("OSVOS_WGRAD_FORM") ? atoi(getenv("OSVOS_WGRAD_FORM")) : -1;
+#ifdef OSVOS_WGRAD_ALL_FORMS
+  ch.form = xb ? (form_env >= 0 ? form_env : kDefaultForm) : 0;
+#else      // the shipped library holds two forms: 0 (first staging form; the only one for fp32 tensors) and 3 (pixel-major, the default for bf16 tensors)
+  ch.form = xb ? ((form_env == 0) ? 0 : kDefaultForm) : 0;
+#endif
+  ch.wide = ch.form >= kWideForm && Cout % 128 == 0;        // eight-wave form: 128-cout tiles
+  ch.p = make_plan(N, H, W, Cin_s, Cout, ch.wide ? 128 : BCO);
+  ch.blocks = (long)ch.p.nsplit * ch.p.nco_t * ch.p.nci_t;
+  static const int map_env = getenv("OSVOS_WGRAD_MAP") ? atoi(getenv("OSVOS_WGRAD_MAP")) : -1;
+  ch.map = (map_env >= 0 ? map_env : kDefaultMap) == 1 && ch.blocks % 8 == 0 ? 1 : 0;
+  return ch;
+}
+
 }  // namespace
 
 // shapes the bf16 kernel takes: the wide trunk layers (Cin_s, Cout multiples of 64); everything else stays on the fp32 kernels
@@ -622,6 +646,16 @@ size_t osvos_wgrad_bf16_ws_bytes(int N, int H, int W, int Cin_s, int Cout) {
   return align_up((f > fw ? f : fw) * sizeof(float), 256);
 }
 
+// what the launcher below does with this shape (osvos_wgrad_wide_plan): launches nothing
+int osvos_wgrad_bf16_plan(int N, int H, int W, int Cin_s, int Cout, int xb, int* out) {
+  OSVOS_ARG_CHECK(osvos_wgrad_bf16_applicable(Cin_s, Cout), "wgrad_wide_plan: no bf16 weight-gradient kernel for Cin %d Cout %d", Cin_s, Cout);
+  const WbChoice ch = choose(N, H, W, Cin_s, Cout, xb);
+  const WbPlan& p = ch.p;
+  out[0] = PW; out[1] = PH; out[2] = p.npx; out[3] = p.npy; out[4] = p.npatches; out[5] = p.per_split; out[6] = p.nsplit;
+  out[7] = p.nco_t; out[8] = p.nci_t; out[9] = (int)ch.blocks; out[10] = ch.map; out[11] = ch.wide ? 1 : 0;
+  return 0;
+}
+
 // x and dy both fp32, or both bf16 (xb)
 int osvos_conv3x3_wgrad_bf16mfma(const WgradCall& c) {
   float *const dw = c.dw, *const db = c.db;
@@ -631,23 +665,18 @@ int osvos_conv3x3_wgrad_bf16mfma(const WgradCall& c) {
   OSVOS_ARG_CHECK(osvos_wgrad_bf16_applicable(Cin_s, Cout) && Cin == Cin_s && Cout_s % 4 == 0, "wgrad bf16: unsupported shape");
   OSVOS_ARG_CHECK((long)H * W * Cin_s < (1L << 29) && (long)H * W * Cout_s < (1L << 29), "wgrad bf16: image too large for 31-bit byte offsets");
   OSVOS_ARG_CHECK(!c.x_bf16 == !c.dy_bf16, "wgrad bf16: x and dy must both be fp32 or both be bf16");
-  static const int form_env = getenv("OSVOS_WGRAD_FORM") ? atoi(getenv("OSVOS_WGRAD_FORM")) : -1;
-#ifdef OSVOS_WGRAD_ALL_FORMS
-  const int form = xb ? (form_env >= 0 ? form_env : kDefaultForm) : 0;
-#else      // the shipped library holds two forms: 0 (first staging form; the only one for fp32 tensors) and 3 (pixel-major, the default for bf16 tensors)
-  const int form = xb ? ((form_env == 0) ? 0 : kDefaultForm) : 0;
-#endif
-  const bool wide = form >= kWideForm && Cout % 128 == 0;        // eight-wave form: 128-cout tiles
-  WbPlan p = make_plan(N, H, W, Cin_s, Cout, wide ? 128 : BCO);
+  const WbChoice ch = choose(N, H, W, Cin_s, Cout, xb);
+  const int form = ch.form;
+  const bool wide = ch.wide;
+  const WbPlan& p = ch.p;
   WbArgs a;
   a.x = c.x; a.dy = c.dy;
   a.slab = reinterpret_cast<float*>(ws);
   a.bslab = db ? a.slab + p.slab_floats : nullptr;
   a.N = N; a.H = H; a.W = W; a.Cin_s = Cin_s; a.Cout = Cout; a.Cout_s = Cout_s;
   a.npx = p.npx; a.npy = p.npy; a.npatches = p.npatches; a.per_split = p.per_split; a.nco_t = p.nco_t; a.nci_t = p.nci_t;
-  const long blocks = (long)p.nsplit * p.nco_t * p.nci_t;
-  static const int map_env = getenv("OSVOS_WGRAD_MAP") ? atoi(getenv("OSVOS_WGRAD_MAP")) : -1;
-  a.map = (map_env >= 0 ? map_env : kDefaultMap) == 1 && blocks % 8 == 0 ? 1 : 0;
+  const long blocks = ch.blocks;
+  a.map = ch.map;
   a.prof = g_wgrad_prof;
   static const int dbg_env = getenv("OSVOS_WGRAD_DBG") ? atoi(getenv("OSVOS_WGRAD_DBG")) : 0;
   a.dbg = dbg_env;

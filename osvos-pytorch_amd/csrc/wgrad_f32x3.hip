@@ -412,6 +412,12 @@ W3Plan make_plan3(int N, int H, int W, int Cin_s, int Cout) {
   return p;
 }
 
+// the XCD-local block map: where the switch is on and the grid divides among the eight XCDs
+int block_map3(long blocks) {
+  OSVOS_ENV_INT(map_env, "OSVOS_WGRAD_MAP", 1);
+  return (map_env == 1 && blocks % 8 == 0) ? 1 : 0;
+}
+
 template <int PH, int WAVES, int S16 = 0, int ILV = 0, int NP = 3, int HP = 0>
 int launch3(const W3Args& a, long blocks, hipStream_t stream) {
   static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};
@@ -448,6 +454,17 @@ size_t osvos_wgrad_f32x3_ws_bytes(int N, int H, int W, int Cin_s, int Cout) {
   return align_up((p.slab_floats + p.bslab_floats) * sizeof(float), 256);
 }
 
+// what the launcher below does with a dense dY of this shape (osvos_wgrad_wide_plan): launches nothing
+int osvos_wgrad_f32x3_plan(int N, int H, int W, int Cin_s, int Cout, int* out) {
+  OSVOS_ARG_CHECK(osvos_wgrad_f32x3_applicable(Cin_s, Cin_s, Cout, Cout) || osvos_wgrad_f32x3_skinny_applicable(Cin_s, Cin_s, Cout, Cout),
+                  "wgrad_wide_plan: no f32x3 weight-gradient kernel for Cin %d Cout %d", Cin_s, Cout);
+  const W3Plan p = make_plan3(N, H, W, Cin_s, Cout);
+  const long blocks = (long)p.nsplit * p.nco_t * p.nci_t;
+  out[0] = PW; out[1] = p.ph; out[2] = p.npx; out[3] = p.npy; out[4] = p.npatches; out[5] = p.per_split; out[6] = p.nsplit;
+  out[7] = p.nco_t; out[8] = p.nci_t; out[9] = (int)blocks; out[10] = block_map3(blocks); out[11] = 0;
+  return 0;
+}
+
 int osvos_conv3x3_wgrad_f32x3(const WgradCall& c) {
   float *const dw = c.dw, *const db = c.db;
   void* const ws = c.ws; hipStream_t stream = c.stream;
@@ -467,8 +484,7 @@ int osvos_conv3x3_wgrad_f32x3(const WgradCall& c) {
   a.N = N; a.H = H; a.W = W; a.Cin_s = Cin_s; a.Cout = Cout; a.Cout_s = Cout_s;
   a.npx = p.npx; a.npy = p.npy; a.npatches = p.npatches; a.per_split = p.per_split; a.nco_t = p.nco_t; a.nci_t = p.nci_t;
   const long blocks = (long)p.nsplit * p.nco_t * p.nci_t;
-  OSVOS_ENV_INT(map_env, "OSVOS_WGRAD_MAP", 1);
-  a.map = (map_env == 1 && blocks % 8 == 0) ? 1 : 0;
+  a.map = block_map3(blocks);
   if (c.phase != WGRAD_REDUCE) {
     // gathers / staging loads interleaved with the MFMAs of the previous stage (round 3; the block-issue form measured level and is gone)
     const bool two = c.pieces == 2;      // precision 'fp32x2'

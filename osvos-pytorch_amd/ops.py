@@ -158,15 +158,20 @@ def conv3x3_bf16w2_tiles():
     return [buf[i] for i in range(n)]
 
 
-def conv3x3_wgrad_bf16act(x, dy, cin, cout, want_bias=True):
-    """x, dy torch.bfloat16 NHWC (wide layers) -> (dW fp32 [cout,cin,3,3], db fp32)"""
-    _need_cuda(x, dy)
+def conv3x3_wgrad_bf16act(x, dy, cin, cout, want_bias=True, accumulate_into=None, ws=None):
+    """x, dy torch.bfloat16 NHWC (wide layers) -> (dW fp32 [cout,cin,3,3], db fp32).  accumulate_into / ws: as conv3x3_wgrad"""
+    _need_cuda(x, dy, ws)
     assert x.dtype == torch.bfloat16 and dy.dtype == torch.bfloat16
     n, h, w, cin_s = x.shape
-    ws = torch.empty(lib().osvos_wgrad_ws_bytes(n, h, w, cin_s, cout, F32_BF16MFMA), device=x.device, dtype=torch.uint8)
-    dw = torch.empty((cout, cin, 3, 3), device=x.device, dtype=torch.float32)
-    db = torch.empty((cout,), device=x.device, dtype=torch.float32) if want_bias else None
-    check(lib().osvos_conv3x3_wgrad_bf16act(_p(x), _p(dy), _p(ws), _p(dw), _p(db), n, h, w, cin, cin_s, cout, dy.shape[3], 0, _stream()), "wgrad_bf16act")
+    ws = _wgrad_ws(ws, lib().osvos_wgrad_ws_bytes(n, h, w, cin_s, cout, F32_BF16MFMA), x)
+    if accumulate_into is not None:
+        dw, db = accumulate_into
+        acc = 1
+    else:
+        dw = torch.empty((cout, cin, 3, 3), device=x.device, dtype=torch.float32)
+        db = torch.empty((cout,), device=x.device, dtype=torch.float32) if want_bias else None
+        acc = 0
+    check(lib().osvos_conv3x3_wgrad_bf16act(_p(x), _p(dy), _p(ws), _p(dw), _p(db), n, h, w, cin, cin_s, cout, dy.shape[3], acc, _stream()), "wgrad_bf16act")
     return dw, db
 
 
@@ -259,6 +264,15 @@ def wgrad_c3_plan(n, h, w, bf16_dy):
     out = (C.c_int * 5)()
     check(lib().osvos_wgrad_c3_plan(n, h, w, int(bool(bf16_dy)), out), "wgrad_c3_plan")
     return dict(zip(("npx", "npy", "npatches", "per_split", "nsplit"), [int(v) for v in out]))
+
+
+def wgrad_wide_plan(n, h, w, cin_s, cout, dtype, bf16_tensors=False):
+    """What the launcher of the wide weight-gradient kernels does with a shape (osvos_wgrad_wide_plan; host only, needs no GPU): dict of
+    pw, ph (patch size), npx, npy, npatches, per_split, nsplit, nco_t, nci_t, blocks, map (XCD-local block map taken), wide (the bf16
+    family's 128-cout eight-wave form).  dtype F32_X3, or F32_BF16MFMA on fp32 tensors / on bf16 tensors (bf16_tensors)."""
+    out = (C.c_int * 12)()
+    check(lib().osvos_wgrad_wide_plan(n, h, w, cin_s, cout, dtype, int(bool(bf16_tensors)), out), "wgrad_wide_plan")
+    return dict(zip(("pw", "ph", "npx", "npy", "npatches", "per_split", "nsplit", "nco_t", "nci_t", "blocks", "map", "wide"), [int(v) for v in out]))
 
 
 def conv3x3_wgrad_c3_bf16dy(x, dy, cout, want_bias=True, accumulate_into=None, ws=None):

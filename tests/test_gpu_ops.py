@@ -885,17 +885,25 @@ def test_wgrad_bf16_forms_are_bit_identical(tmp_path):
     pixel-major tiles read with ds_read_b64_tr_b16, eight waves / 128-cout tiles where Cout allows): same patches, same k-order -> the weight
     gradient must be bit-identical, the bias gradient equal up to fp32 summation order.  (The retired forms 1, 2, 4, 5 live in
     tools/native/wgrad_bf16_forms.inc and are built into the probe harness only.)  Shapes cover ragged right / bottom edges, one and two
-    128-cout tiles, 64-cout tiles and several images.  The switch is read once per process: every form runs in a subprocess."""
+    128-cout tiles, 64-cout tiles and several images -- and one long walk, (3,17,65,512,512) of tests/wide_wgrad_cases.py: form 0 walks 4 patches
+    per workgroup in 7 splits, form 3 (eight waves) 5 in 6, both with a short last split and splits spanning two images; the fp32 sums of the
+    two cuts differ in rounding on random operands, so this shape carries small integers, whose sums are exact in any order.  The switch is read
+    once per process: every form runs in a subprocess."""
     import os, subprocess, sys, textwrap
     code = textwrap.dedent('''
         import sys, numpy as np, torch
         sys.path.insert(0, %r)
         import osvos_pytorch_amd.ops as ops
         res = {}
-        for n, h, w, cin, cout in [(1, 9, 11, 64, 64), (2, 17, 35, 64, 128), (1, 33, 70, 128, 64), (3, 8, 40, 64, 64), (2, 30, 54, 256, 256), (1, 60, 107, 128, 256)]:
+        for n, h, w, cin, cout in [(1, 9, 11, 64, 64), (2, 17, 35, 64, 128), (1, 33, 70, 128, 64), (3, 8, 40, 64, 64), (2, 30, 54, 256, 256), (1, 60, 107, 128, 256),
+                                   (3, 17, 65, 512, 512)]:
             g = torch.Generator().manual_seed(1000 + h)
-            x = torch.randn(n, h, w, cin, generator=g).bfloat16().cuda()
-            dy = torch.randn(n, h, w, cout, generator=g).bfloat16().cuda()
+            if cin == 512:      # the long walk: small integers, exact in any summation order (the two forms cut these patches into different splits)
+                x = torch.randint(-3, 4, (n, h, w, cin), generator=g).bfloat16().cuda()
+                dy = torch.randint(-1, 2, (n, h, w, cout), generator=g).bfloat16().cuda()
+            else:
+                x = torch.randn(n, h, w, cin, generator=g).bfloat16().cuda()
+                dy = torch.randn(n, h, w, cout, generator=g).bfloat16().cuda()
             dw, db = ops.conv3x3_wgrad_bf16act(x, dy, cin, cout)
             res["dw_%%dx%%dx%%d_%%d_%%d" %% (n, h, w, cin, cout)] = dw.cpu().numpy()
             res["db_%%dx%%dx%%d_%%d_%%d" %% (n, h, w, cin, cout)] = db.cpu().numpy()
