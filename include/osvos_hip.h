@@ -289,9 +289,16 @@ int osvos_cbce_step_multi(const float* const* outs, const float* label, float* c
  *     from them, no count sweep runs.  Summed over the shards the losses / gradients are those of the whole batch.  Not with PER_IMAGE.
  *   scratch: osvos_cbce_scratch_bytes(n_heads, N, flags) bytes, zeroed by the call -- or, with flags & OSVOS_CBCE_SCRATCH_ZEROED, already zero by
  *     the caller's promise (no memset is enqueued).  Every call LEAVES the scratch zero (its last workgroup forms the losses and clears what it
- *     read), so a buffer that was zeroed once can be handed to call after call on one stream. */
+ *     read), so a buffer that was zeroed once can be handed to call after call on one stream.
+ *   flags & OSVOS_CBCE_VOID: a pixel whose label is < 0 is VOID (online adaptation: "don't know").  It is in neither class count and in
+ *     neither loss sum, and its gradient is WRITTEN as +0.0f.  Per count group n_total is the number of non-void pixels; size_average divides
+ *     by it, batch_average is unchanged: for one group the loss is the reference's function on the non-void pixels as a flat one-image tensor,
+ *     the gradient on those pixels that call's gradient.  A group without a non-void pixel contributes loss 0 and gradient 0 (no NaN is
+ *     formed).  The scratch holds a void count per group more (the size query takes the flag).  Not with counts != NULL.  Without the flag a
+ *     negative label is a negative-class pixel, as ever. */
 #define OSVOS_CBCE_PER_IMAGE 1
 #define OSVOS_CBCE_SCRATCH_ZEROED 2
+#define OSVOS_CBCE_VOID 4
 size_t osvos_cbce_scratch_bytes(int n_heads, int N, int flags);
 int osvos_cbce_step_ex(const float* const* outs, const float* label, float* const* losses, float* const* grads, void* scratch, long count,
                        int N, int mode, int flags, const float* counts, int n_heads, const float* grad_scales, float* const* running,
@@ -450,6 +457,33 @@ int osvos_components_select(const float* logits, const int* labels, const int* a
 int osvos_tta_view(const unsigned char* bgr, const float* mean3, float* out, int N, int H, int W, int Hv, int Wv, int flip, void* stream);
 int osvos_tta_fuse(const float* const* views, const int* Hv, const int* Wv, const int* flip, const float* weight, int V, float* out, int N,
                    int H, int W, void* stream);
+
+/* ---- online adaptation: exact squared Euclidean distance maps and the adaptation targets made from them ----
+ * osvos_mask_sqdist: mask [N][H][W] uint8 -> sqdist [N][H][W] int32.  A pixel q is a SOURCE when (mask[q] != 0) != (invert != 0);
+ *   sqdist[n][y][x] = min over the sources q of image n of |p - q|^2, an exact integer, OSVOS_SQDIST_NONE everywhere in an image without a
+ *   source.  Sides 1..OSVOS_SQDIST_MAX_SIDE (the largest distance, 2 * 4095^2, stays inside int32), N 1..65535.  Two launches: a column
+ *   pass (one lane per column: the vertical distance to the column's nearest source, or "none") and a row pass (one workgroup per row and
+ *   image with the row of column distances in LDS; each output pixel walks outwards from its own column and stops once dx^2 >= best, which
+ *   is exact because every later candidate is at least dx^2; columns without a source are skipped, never squared).
+ *   ws: osvos_mask_sqdist_ws_bytes(N, H, W) bytes (the column distances), contents irrelevant on entry; 0 for sizes the call refuses.
+ * osvos_adapt_targets: the label map of one online-adaptation step (OnAVOS) from the network's own fused logits [N][H][W] fp32 and the
+ *   previous frame's final mask prev_mask [N][H][W] uint8 (non-zero = object).  Per image:
+ *     E        = { p in prev_mask : sqdist(p, background of prev_mask) > erosion^2 }; the image border is not background (a mask that
+ *                fills the image erodes to itself); erosion = 0 gives E = prev_mask
+ *     negative   label 0.0f:  sqdist(p, E) > distance^2 (OSVOS_SQDIST_NONE counts as far: an empty E makes every pixel negative)
+ *     positive   label 1.0f:  not negative and logits[p] > pos_logit (strict; a NaN logit is not positive); pos_logit = log(a / (1 - a))
+ *     void       label -1.0f: everything else (the loss ignores it under OSVOS_CBCE_VOID)
+ *   counts [N][3] unsigned long long = {n_pos, n_neg, n_void}, overwritten.  erosion, distance >= 0.  Integer and raw-float comparisons
+ *   only: the label map is exact.  Sizes as osvos_mask_sqdist; ws: osvos_adapt_ws_bytes(N, H, W) bytes, contents irrelevant on entry.
+ *   Four launches (two distance maps; E is decided inside the second one's column pass, the labels inside its row pass) and one small memset
+ *   on `stream`. */
+#define OSVOS_SQDIST_NONE 2147483647
+#define OSVOS_SQDIST_MAX_SIDE 4096
+size_t osvos_mask_sqdist_ws_bytes(int N, int H, int W);
+int osvos_mask_sqdist(const unsigned char* mask, int invert, int* sqdist, int N, int H, int W, void* ws, void* stream);
+size_t osvos_adapt_ws_bytes(int N, int H, int W);
+int osvos_adapt_targets(const float* logits, const unsigned char* prev_mask, float pos_logit, int erosion, int distance, float* label,
+                        void* counts, int N, int H, int W, void* ws, void* stream);
 
 /* ---- fused SGD (torch.optim.SGD semantics, train_online.py:79-88,147) ----------------------
  * for each i: d = g + wd*p; buf = first ? d : momentum*buf + d; p -= lr*buf      (flat tensors) */

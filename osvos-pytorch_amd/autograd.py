@@ -287,7 +287,10 @@ class CBCELossFunction(torch.autograd.Function):
     of the same kernel pass, the backward only scales by the (device-resident) upstream gradient."""
 
     @staticmethod
-    def forward(ctx, output, label, mode):
+    def forward(ctx, output, label, mode, *void_labels):
+        # (an optional fourth argument: True = labels below 0 are void; the backward answers as many inputs as the forward was given)
+        ctx.n_extra = len(void_labels)
+        void_labels = bool(void_labels and void_labels[0])
         if not output.is_cuda:
             raise RuntimeError("class_balanced_cross_entropy_loss (osvos_pytorch_amd) needs CUDA tensors; no CPU fallback")
         l = lib()
@@ -295,8 +298,12 @@ class CBCELossFunction(torch.autograd.Function):
         lab = label.detach().to(device=out.device, dtype=torch.float32).contiguous()
         if lab.numel() != out.numel():
             raise RuntimeError("output and label must have the same number of elements")
-        loss = torch.empty((), device=out.device, dtype=torch.float32)
         need = ctx.needs_input_grad[0]
+        if void_labels:      # labels < 0 are void (OSVOS_CBCE_VOID): the general entry point, same kernels
+            loss, grad = cbce_step(out, lab, mode, 1.0, None, void_labels=True)
+            ctx.grad = grad if need else None
+            return loss
+        loss = torch.empty((), device=out.device, dtype=torch.float32)
         grad = torch.empty_like(out) if need else None
         scratch = torch.empty(4, device=out.device, dtype=torch.float64)
         check(l.osvos_cbce(C.c_void_p(out.data_ptr()), C.c_void_p(lab.data_ptr()), C.c_void_p(loss.data_ptr()),
@@ -309,12 +316,12 @@ class CBCELossFunction(torch.autograd.Function):
     def backward(ctx, g):
         grad = ctx.grad
         if grad is None:
-            return None, None, None
+            return (None, None, None) + (None,) * ctx.n_extra
         g = g.detach().to(torch.float32).contiguous()
         gx = torch.empty_like(grad)
         check(lib().osvos_scale(C.c_void_p(grad.data_ptr()), C.c_void_p(g.data_ptr()), C.c_void_p(gx.data_ptr()),
                                 grad.numel(), _stream()), "scale")
-        return gx, None, None
+        return (gx, None, None) + (None,) * ctx.n_extra
 
 
 class CBCECountsFunction(torch.autograd.Function):
@@ -340,6 +347,7 @@ class CBCECountsFunction(torch.autograd.Function):
 
 CBCE_PER_IMAGE = 1      # include/osvos_hip.h OSVOS_CBCE_PER_IMAGE
 CBCE_SCRATCH_ZEROED = 2  # include/osvos_hip.h OSVOS_CBCE_SCRATCH_ZEROED
+CBCE_VOID = 4           # include/osvos_hip.h OSVOS_CBCE_VOID
 
 # The loss call's scratch (class counts, loss sums, arrival ticket): every call leaves it zero, so ONE zero-initialised buffer per (device, stream,
 # size) serves every call of a training loop and the call enqueues no memset (a 32-byte hipMemsetAsync is two fill kernels: 14 us between the
@@ -375,7 +383,7 @@ def _counts_tensor(counts, dev):
     return t
 
 
-def cbce_step(output, label, mode, grad_scale=1.0, running=None, per_image=False, counts=None):
+def cbce_step(output, label, mode, grad_scale=1.0, running=None, per_image=False, counts=None, void_labels=False):
     """One training-loop use of the class-balanced BCE without the autograd scalar chain behind it: returns ``(loss, grad)`` where ``loss``
     is the plain 0-dim loss (detached; what the reference adds to ``running_loss``, train_online.py:128) and ``grad`` =
     ``grad_scale * dLoss/dOutput`` -- ready for ``torch.autograd.backward([output], [grad])``.  ``grad_scale`` is the upstream gradient the
@@ -384,12 +392,14 @@ def cbce_step(output, label, mode, grad_scale=1.0, running=None, per_image=False
     ATen launches (ones, div, its backward, add, scale) per micro-batch fewer between the loss and the head's backward.
     ``per_image``: every image of the batch is its own reference batch of one (own class weights; the losses are summed) -- the micro-batches
     of an accumulation window in one call.  ``counts``: ``(n_pos, n_total, n_images)`` of the GLOBAL batch this tensor is a shard of
-    (``parallel.global_class_counts``): weights and divisors come from them."""
-    losses, grads = cbce_step_multi([output], label, mode, [grad_scale], [running], per_image=per_image, counts=counts)
+    (``parallel.global_class_counts``): weights and divisors come from them.  ``void_labels``: a label below 0 is void -- in neither class
+    count and neither loss sum, gradient exactly +0.0, ``size_average`` divides by the non-void count (online adaptation targets); not with
+    ``counts``."""
+    losses, grads = cbce_step_multi([output], label, mode, [grad_scale], [running], per_image=per_image, counts=counts, void_labels=void_labels)
     return losses[0], grads[0]
 
 
-def cbce_step_multi(outputs, label, mode, grad_scales, runnings=None, per_image=False, counts=None):
+def cbce_step_multi(outputs, label, mode, grad_scales, runnings=None, per_image=False, counts=None, void_labels=False):
     """``cbce_step`` for several heads against one label (the parent loop's five losses, train_parent.py:143-147) in ONE library call: the
     label's class counts are formed once and the loss / gradient sweep of all heads is one launch.  Returns ``(losses, grads)``: ``losses`` a
     float32 CUDA tensor of ``len(outputs)`` plain losses (detached), ``grads[k] = grad_scales[k] * dLoss_k/dOutput_k``; ``runnings`` (list of
@@ -401,6 +411,8 @@ def cbce_step_multi(outputs, label, mode, grad_scales, runnings=None, per_image=
         raise RuntimeError("class_balanced_cross_entropy_loss (osvos_pytorch_amd) needs CUDA tensors; no CPU fallback")
     if per_image and counts is not None:
         raise RuntimeError("per_image and counts exclude each other")
+    if void_labels and counts is not None:
+        raise RuntimeError("void_labels and counts exclude each other")
     outs = [o.detach().contiguous().float() for o in outputs]
     dev = outs[0].device
     lab = label.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -410,7 +422,7 @@ def cbce_step_multi(outputs, label, mode, grad_scales, runnings=None, per_image=
         if r is not None and not (r.is_cuda and r.dtype == torch.float32 and r.numel() == 1):
             raise RuntimeError("running entries must be one-element float32 CUDA tensors")
     n_img = int(outs[0].shape[0])
-    flags = CBCE_PER_IMAGE if per_image else 0
+    flags = (CBCE_PER_IMAGE if per_image else 0) | (CBCE_VOID if void_labels else 0)
     cnt = _counts_tensor(counts, dev)
     losses = torch.empty(n, device=dev, dtype=torch.float32)
     grads = [torch.empty_like(o) for o in outs]

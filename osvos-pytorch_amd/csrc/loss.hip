@@ -16,48 +16,67 @@ namespace {
 // head the first form of the interface asked for.  Zero on entry (zeroed by the call, or by the caller's promise: OSVOS_CBCE_SCRATCH_ZEROED) and
 // ALWAYS left zero on exit: the workgroup that arrives last forms the losses and clears what it read (round 6: the loss call is two launches --
 // count, sweep -- instead of memset (two fill kernels for a 32-byte region) + count + sweep + final: 114 -> ~90 us between forward and backward).
+// With OSVOS_CBCE_VOID the void counts nvoid[G] (unsigned long long) follow the ticket: 8 G bytes more, the layout without the flag is unchanged.
 struct ScratchView {
   unsigned long long* npos;
   double* lpos;
   double* lneg;
   unsigned* ticket;
+  unsigned long long* nvoid;      // NULL without OSVOS_CBCE_VOID
 };
-__device__ __host__ inline ScratchView scratch_view(void* p, int G, int H) {
+__device__ __host__ inline ScratchView scratch_view(void* p, int G, int H, bool with_void) {
   ScratchView v;
   v.npos = reinterpret_cast<unsigned long long*>(p);
   v.lpos = reinterpret_cast<double*>(v.npos + G);
   v.lneg = v.lpos + (size_t)H * G;
   v.ticket = reinterpret_cast<unsigned*>(v.lneg + (size_t)H * G);
+  v.nvoid = with_void ? reinterpret_cast<unsigned long long*>(v.ticket + 2) : nullptr;
   return v;
 }
 
 // (both sweeps read 16 bytes per lane and load over the first 4 * n4 elements of a group, element-wise over the rest: n4 = elements / 4 for
 //  16-byte aligned tensors -- the rest is then at most 3 elements -- and 0 for tensors that are not: a contiguous but offset view such as
 //  outputs[-1][1:2] with H * W % 4 != 0 takes the scalar sweep instead of being refused)
-__global__ void cbce_count_kernel(const float* __restrict__ label, long per_group, long n4, unsigned long long* npos) {
+// kVoid (OSVOS_CBCE_VOID): a label < 0 is void -- counted into nvoid, in neither class
+template <bool kVoid>
+__global__ void cbce_count_kernel(const float* __restrict__ label, long per_group, long n4, unsigned long long* npos, unsigned long long* nvoid) {
   const int grp = blockIdx.y;
   const float* lab = label + (size_t)grp * per_group;
-  unsigned int c = 0;
+  unsigned int c = 0, cv = 0;
   const f32x4* l4 = reinterpret_cast<const f32x4*>(lab);
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
   for (long i = tid; i < n4; i += nth) {
     const f32x4 v = l4[i];
     c += (v[0] >= 0.5f ? 1u : 0u) + (v[1] >= 0.5f ? 1u : 0u) + (v[2] >= 0.5f ? 1u : 0u) + (v[3] >= 0.5f ? 1u : 0u);
+    if (kVoid) cv += (v[0] < 0.f ? 1u : 0u) + (v[1] < 0.f ? 1u : 0u) + (v[2] < 0.f ? 1u : 0u) + (v[3] < 0.f ? 1u : 0u);
   }
-  for (long i = 4 * n4 + tid; i < per_group; i += nth) c += lab[i] >= 0.5f ? 1u : 0u;
+  for (long i = 4 * n4 + tid; i < per_group; i += nth) {
+    c += lab[i] >= 0.5f ? 1u : 0u;
+    if (kVoid) cv += lab[i] < 0.f ? 1u : 0u;
+  }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  __shared__ unsigned int red[4];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+  if (kVoid) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cv += __shfl_xor(cv, o, 64);
+  }
+  __shared__ unsigned int red[4], redv[4];
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = c; if (kVoid) redv[threadIdx.x >> 6] = cv; }
   __syncthreads();
   if (threadIdx.x == 0) {
     c = red[0] + red[1] + red[2] + red[3];
     if (c) atomicAdd(&npos[grp], (unsigned long long)c);     // one atomic per workgroup
+    if (kVoid) {
+      cv = redv[0] + redv[1] + redv[2] + redv[3];
+      if (cv) atomicAdd(&nvoid[grp], (unsigned long long)cv);
+    }
   }
 }
 
-// one element: accumulates the two loss sums, returns the gradient
+// one element: accumulates the two loss sums, returns the gradient (kVoid: a void element accumulates nothing and returns +0.0f)
+template <bool kVoid>
 __device__ __forceinline__ float cbce_elem(float x, float lab, float wpos, float wneg, float inv_div, float gscale, bool want_grad, double& lpos, double& lneg) {
+  if (kVoid && lab < 0.f) return 0.f;
   const float y = lab >= 0.5f ? 1.f : 0.f;
   const float g = x >= 0.f ? 1.f : 0.f;
   const float val = x * (y - g) - logf(1.f + expf(x - 2.f * x * g));
@@ -96,20 +115,28 @@ struct CbceNorm {
   int N;                    // images of this call
   int per_image;
 };
-__device__ __forceinline__ void cbce_weights(const CbceNorm& nm, const unsigned long long* npos_grp, int grp, long per_group, float& wpos, float& wneg, float& inv_div) {
+//   void labels      (kVoid) n_total = the group's non-void pixels; a group without one gets weights 0 and divisor factor 0: loss 0, no NaN
+template <bool kVoid>
+__device__ __forceinline__ void cbce_weights(const CbceNorm& nm, const ScratchView& sc, int grp, long per_group, float& wpos, float& wneg, float& inv_div) {
   float ntot, npos, nimg;
   if (nm.counts != nullptr) { npos = nm.counts[0]; ntot = nm.counts[1]; nimg = nm.counts[2]; }
-  else { npos = (float)npos_grp[grp]; ntot = (float)per_group; nimg = nm.per_image ? 1.f : (float)nm.N; }
+  else { npos = (float)sc.npos[grp]; ntot = (float)per_group; nimg = nm.per_image ? 1.f : (float)nm.N; }
+  if (kVoid) {
+    const unsigned long long live = (unsigned long long)per_group - sc.nvoid[grp];
+    if (live == 0ull) { wpos = wneg = 0.f; inv_div = nm.mode == 0 ? 0.f : (nm.mode == 1 ? 1.f / nimg : 1.f); return; }
+    ntot = (float)live;
+  }
   wpos = (ntot - npos) / ntot;
   wneg = npos / ntot;
   inv_div = nm.mode == 0 ? 1.f / ntot : (nm.mode == 1 ? 1.f / nimg : 1.f);
 }
 
 // grid (workgroups, count groups, heads)
+template <bool kVoid>
 __global__ void cbce_main_kernel(CbceHeads hd, const float* __restrict__ label, long per_group, long n4, CbceNorm nm, ScratchView sc, int G) {
   const int grp = blockIdx.y, head = blockIdx.z;
   float wpos, wneg, inv_div;
-  cbce_weights(nm, sc.npos, grp, per_group, wpos, wneg, inv_div);
+  cbce_weights<kVoid>(nm, sc, grp, per_group, wpos, wneg, inv_div);
   const float* __restrict__ out = hd.out[head] + (size_t)grp * per_group;
   const float* __restrict__ lab = label + (size_t)grp * per_group;
   float* __restrict__ grad = hd.grad[head] != nullptr ? hd.grad[head] + (size_t)grp * per_group : nullptr;
@@ -124,11 +151,11 @@ __global__ void cbce_main_kernel(CbceHeads hd, const float* __restrict__ label, 
     const f32x4 x = o4[i], lb = l4[i];
     f32x4 g;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) g[e] = cbce_elem(x[e], lb[e], wpos, wneg, inv_div, gscale, want, lpos, lneg);
+    for (int e = 0; e < 4; ++e) g[e] = cbce_elem<kVoid>(x[e], lb[e], wpos, wneg, inv_div, gscale, want, lpos, lneg);
     if (want) g4[i] = g;
   }
   for (long i = 4 * n4 + tid; i < per_group; i += nth) {
-    const float g = cbce_elem(out[i], lab[i], wpos, wneg, inv_div, gscale, want, lpos, lneg);
+    const float g = cbce_elem<kVoid>(out[i], lab[i], wpos, wneg, inv_div, gscale, want, lpos, lneg);
     if (want) grad[i] = g;
   }
   lpos = wave_sum(lpos);
@@ -157,7 +184,7 @@ __global__ void cbce_main_kernel(CbceHeads hd, const float* __restrict__ label, 
     float total = 0.f;
     for (int g2 = 0; g2 < G; ++g2) {
       float wp, wn, idv;
-      cbce_weights(nm, sc.npos, g2, per_group, wp, wn, idv);
+      cbce_weights<kVoid>(nm, sc, g2, per_group, wp, wn, idv);
       const double lp = __hip_atomic_load(&sc.lpos[(size_t)h2 * G + g2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       const double ln = __hip_atomic_load(&sc.lneg[(size_t)h2 * G + g2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       const float l = (float)(((double)wp * lp + (double)wn * ln) * (double)idv);
@@ -169,6 +196,7 @@ __global__ void cbce_main_kernel(CbceHeads hd, const float* __restrict__ label, 
   __syncthreads();
   // leave the scratch zero for the next call (everything this call accumulated has been consumed)
   for (int i = threadIdx.x; i < G; i += blockDim.x) sc.npos[i] = 0ull;
+  if (kVoid) for (int i = threadIdx.x; i < G; i += blockDim.x) sc.nvoid[i] = 0ull;
   for (int i = threadIdx.x; i < 2 * hd.n * G; i += blockDim.x) sc.lpos[i] = 0.0;      // (lpos and lneg are contiguous)
   if (threadIdx.x == 0) sc.ticket[0] = 0u;
 }
@@ -202,7 +230,7 @@ inline int grid_for(long total, int cap) {
 
 extern "C" size_t osvos_cbce_scratch_bytes(int n_heads, int N, int flags) {
   const size_t G = (flags & OSVOS_CBCE_PER_IMAGE) ? (size_t)(N > 0 ? N : 1) : 1, H = (size_t)(n_heads > 0 ? n_heads : 1);
-  return 8 * G + 16 * H * G + 8;
+  return 8 * G + 16 * H * G + 8 + ((flags & OSVOS_CBCE_VOID) ? 8 * G : 0);
 }
 
 extern "C" int osvos_cbce_step_ex(const float* const* outs, const float* label, float* const* losses, float* const* grads, void* scratch, long count,
@@ -213,8 +241,10 @@ extern "C" int osvos_cbce_step_ex(const float* const* outs, const float* label, 
   OSVOS_ARG_CHECK(n_heads >= 1 && n_heads <= kMaxHeads, "cbce: %d heads (1..%d)", n_heads, kMaxHeads);
   OSVOS_ARG_CHECK(mode >= 0 && mode <= 2, "cbce: mode %d", mode);
   const bool per_image = (flags & OSVOS_CBCE_PER_IMAGE) != 0;
-  OSVOS_ARG_CHECK((flags & ~(OSVOS_CBCE_PER_IMAGE | OSVOS_CBCE_SCRATCH_ZEROED)) == 0 && !(per_image && counts != nullptr),
+  const bool with_void = (flags & OSVOS_CBCE_VOID) != 0;
+  OSVOS_ARG_CHECK((flags & ~(OSVOS_CBCE_PER_IMAGE | OSVOS_CBCE_SCRATCH_ZEROED | OSVOS_CBCE_VOID)) == 0 && !(per_image && counts != nullptr),
                   "cbce: flags 0x%x (per-image counts and external counts exclude each other)", flags);
+  OSVOS_ARG_CHECK(!(with_void && counts != nullptr), "cbce: void labels (flags 0x%x) and external counts exclude each other", flags);
   OSVOS_ARG_CHECK(!per_image || (count % N == 0 && N <= 65535), "cbce: per-image mode needs count %% N == 0 (%ld, %d)", count, N);
   const int G = per_image ? N : 1;
   const long per_group = count / G;
@@ -237,14 +267,19 @@ extern "C" int osvos_cbce_step_ex(const float* const* outs, const float* label, 
   const long n4 = vec ? per_group >> 2 : 0;
   CbceNorm nm;
   nm.counts = counts; nm.mode = mode; nm.N = N; nm.per_image = per_image ? 1 : 0;
-  const ScratchView sc = scratch_view(scratch, G, n_heads);
+  const ScratchView sc = scratch_view(scratch, G, n_heads, with_void);
   if (!(flags & OSVOS_CBCE_SCRATCH_ZEROED)) OSVOS_HIP_CHECK(hipMemsetAsync(scratch, 0, osvos_cbce_scratch_bytes(n_heads, N, flags), stream));
   // one double atomic pair per workgroup: few workgroups for a single frame (11 us), more for batches (94 -> ~25 us at batch 12)
   const long work = vec ? n4 : per_group;
   int g = grid_for(work, count > (1L << 21) ? 512 : 128);
   if (G > 1) { g = (g + G - 1) / G; if (g < 16) g = 16; }
-  if (counts == nullptr) hipLaunchKernelGGL(cbce_count_kernel, dim3(g, G), dim3(256), 0, stream, label, per_group, n4, sc.npos);
-  hipLaunchKernelGGL(cbce_main_kernel, dim3(g, G, n_heads), dim3(256), 0, stream, hd, label, per_group, n4, nm, sc, G);
+  if (with_void) {
+    hipLaunchKernelGGL(cbce_count_kernel<true>, dim3(g, G), dim3(256), 0, stream, label, per_group, n4, sc.npos, sc.nvoid);
+    hipLaunchKernelGGL(cbce_main_kernel<true>, dim3(g, G, n_heads), dim3(256), 0, stream, hd, label, per_group, n4, nm, sc, G);
+  } else {
+    if (counts == nullptr) hipLaunchKernelGGL(cbce_count_kernel<false>, dim3(g, G), dim3(256), 0, stream, label, per_group, n4, sc.npos, sc.nvoid);
+    hipLaunchKernelGGL(cbce_main_kernel<false>, dim3(g, G, n_heads), dim3(256), 0, stream, hd, label, per_group, n4, nm, sc, G);
+  }
   OSVOS_LAUNCH_CHECK();
   return 0;
 }

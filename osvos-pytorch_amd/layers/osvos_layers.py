@@ -20,33 +20,41 @@ def sigmoid_np(x):
     return 1 / (1 + np.exp(-x))
 
 
-def class_balanced_cross_entropy_loss(output, label, size_average=True, batch_average=True):
+def class_balanced_cross_entropy_loss(output, label, size_average=True, batch_average=True, void_pixels=None):
     """Class-balanced BCE with logits.  Positives are ``label >= 0.5``; the two class weights are
     counted over the whole tensor; ``size_average`` divides by numel, else ``batch_average`` by N.
-    Returns a 0-dim CUDA tensor that supports ``.item()``, ``/=`` and ``.backward()``."""
+    Returns a 0-dim CUDA tensor that supports ``.item()``, ``/=`` and ``.backward()``.
+    ``void_pixels`` (an extension: a tensor of the label's size, ``>= 0.5`` = void): such pixels are in neither class count and neither
+    loss sum, get gradient 0, and ``size_average`` divides by the number of the others."""
     mode = 0 if size_average else (1 if batch_average else 2)
-    return CBCELossFunction.apply(output, label, mode)
+    if void_pixels is None:
+        return CBCELossFunction.apply(output, label, mode)
+    if not torch.is_tensor(void_pixels) or void_pixels.numel() != label.numel():
+        raise RuntimeError("void_pixels must be a tensor with the label's number of elements")
+    lab = label.detach().to(device=output.device, dtype=torch.float32)
+    lab = torch.where(void_pixels.detach().to(device=output.device).reshape(lab.shape) >= 0.5, lab.new_tensor(-1.0), (lab >= 0.5).to(torch.float32))
+    return CBCELossFunction.apply(output, lab, mode, True)
 
 
 def class_balanced_cross_entropy_loss_step(output, label, size_average=True, batch_average=True, grad_scale=1.0, running=None, per_image=False,
-                                           counts=None):
+                                           counts=None, void_labels=False):
     """The loss as ONE micro-batch of the training loops uses it (train_online.py:127-141): ``(loss, grad)`` with ``grad`` already
     multiplied by the upstream gradient ``grad_scale`` (1 / nAveGrad ...) and ``running += loss`` done on the device; hand ``grad`` to
     ``torch.autograd.backward([output], [grad])``.  An extension next to the reference's function above, not a replacement.
     ``per_image=True``: the N images of ``output`` are N reference micro-batches of one image each (own class weights per image, the N losses
     summed) -- a whole accumulation window in one call.  ``counts=(n_pos, n_total, n_images)``: the tensors are a shard of a global batch with
-    these counts (``parallel.global_class_counts``)."""
+    these counts (``parallel.global_class_counts``).  ``void_labels=True``: labels below 0 are void pixels (no count, no loss, gradient 0)."""
     mode = 0 if size_average else (1 if batch_average else 2)
-    return cbce_step(output, label, mode, grad_scale, running, per_image=per_image, counts=counts)
+    return cbce_step(output, label, mode, grad_scale, running, per_image=per_image, counts=counts, void_labels=void_labels)
 
 
 def class_balanced_cross_entropy_loss_step_multi(outputs, label, size_average=True, batch_average=True, grad_scales=None, running=None, per_image=False,
-                                                 counts=None):
+                                                 counts=None, void_labels=False):
     """``class_balanced_cross_entropy_loss_step`` for all heads of a micro-batch in one call (the parent loop: train_parent.py:143-147):
     ``(losses, grads)`` with ``losses`` a float32 tensor of the plain per-head losses."""
     mode = 0 if size_average else (1 if batch_average else 2)
     return cbce_step_multi(list(outputs), label, mode, list(grad_scales) if grad_scales is not None else [1.0] * len(outputs), running,
-                           per_image=per_image, counts=counts)
+                           per_image=per_image, counts=counts, void_labels=void_labels)
 
 
 def center_crop(x, height, width):

@@ -25,7 +25,7 @@ import zlib
 import numpy as np
 import torch
 
-from ._lib import BOUNDARY_MAX_RADIUS, MAX_OBJECTS, check, lib
+from ._lib import BOUNDARY_MAX_RADIUS, MAX_OBJECTS, SQDIST_MAX_SIDE, check, lib
 
 
 def _stream():
@@ -496,3 +496,34 @@ class ComponentTracker(object):
         if self._host is None:
             self._host = [int(v) for v in self._counts.cpu().numpy()]
         return {"seen": self._host[0], "kept": self._host[1], "frames": self._host[2]}
+
+
+# ---- distance maps ----------------------------------------------------------------------------------------------------------------------
+
+def _mask_bytes_nhw(mask, who):
+    """a mask tensor [N,1,H,W], [N,H,W] or [H,W] (uint8, bool or float; non-zero = set) -> (uint8 contiguous [N,H,W], N, H, W)"""
+    if not torch.is_tensor(mask) or not mask.is_cuda:
+        raise RuntimeError("osvos_pytorch_amd.results needs CUDA (ROCm) tensors; there is no CPU fallback")
+    m = mask.detach()
+    if m.dim() == 2:
+        m = m[None]
+    if m.dim() == 4 and m.shape[1] == 1:
+        m = m[:, 0]
+    if m.dim() != 3:
+        raise ValueError("%s: expected a mask of shape [N,1,H,W], [N,H,W] or [H,W], got %r" % (who, tuple(mask.shape)))
+    m = m.contiguous() if m.dtype == torch.uint8 else (m != 0).to(torch.uint8).contiguous()
+    n, h, w = (int(v) for v in m.shape)
+    if not (1 <= n <= 65535 and 1 <= h <= SQDIST_MAX_SIDE and 1 <= w <= SQDIST_MAX_SIDE):
+        raise ValueError("%s: %d frames of %d x %d: the library takes 1..65535 frames with sides of 1..%d" % (who, n, h, w, SQDIST_MAX_SIDE))
+    return m, n, h, w
+
+
+def distance_map(mask, invert=False):
+    """Exact squared Euclidean distance of every pixel to the nearest set pixel of its frame (``invert``: to the nearest pixel that is NOT
+    set): int32 CUDA tensor [N,H,W], ``_lib.SQDIST_NONE`` everywhere in a frame without such a pixel (``osvos_mask_sqdist``).  Enqueued only."""
+    m, n, h, w = _mask_bytes_nhw(mask, "distance_map")
+    out = torch.empty((n, h, w), device=m.device, dtype=torch.int32)
+    ws = torch.empty((lib().osvos_mask_sqdist_ws_bytes(n, h, w) + 3) // 4, device=m.device, dtype=torch.int32)
+    check(lib().osvos_mask_sqdist(C.c_void_p(m.data_ptr()), 1 if invert else 0, C.c_void_p(out.data_ptr()), n, h, w, C.c_void_p(ws.data_ptr()),
+                                  _stream()), "mask_sqdist")
+    return out

@@ -90,15 +90,21 @@ class TrainLoop(object):
             self.counts[epoch] = 0
         return r
 
-    def micro_batch(self, inputs, gts, epoch=0):
+    def micro_batch(self, inputs, gts, epoch=0, void_labels=False, grad_scale=1.0):
         """One micro-batch.  Returns ``(loss, stepped)``: ``loss`` is the PLAIN loss of the fused head (detached 0-dim tensor; not divided by
         nAveGrad, side heads not mixed in) on every code path -- what the reference prints per iteration; sums over an epoch come from
-        ``pop_running``.  ``stepped``: this micro-batch closed an optimizer-step window."""
+        ``pop_running``.  ``stepped``: this micro-batch closed an optimizer-step window.
+        ``void_labels``: labels below 0 are void pixels (the loss kernel's OSVOS_CBCE_VOID; online adaptation); ``grad_scale``: one more factor
+        on this micro-batch's gradient (the weight of an adaptation step), not on the loss it reports.  Both live on the fused-loss path."""
+        if (void_labels or grad_scale != 1.0) and not self.fused_loss:
+            raise RuntimeError("micro_batch: void_labels / grad_scale need the fused HIP loss step (no loss_fn, OSVOS_FUSED_LOSS_STEP not 0)")
         outputs = self.net.forward(inputs)
         running = self._acc(epoch)
         self.counts[epoch] += 1
         if self.fused_loss and outputs[-1].is_cuda:
-            return self._micro_batch_fused(outputs, gts, running, epoch)
+            return self._micro_batch_fused(outputs, gts, running, epoch, void_labels, grad_scale)
+        if void_labels or grad_scale != 1.0:
+            raise RuntimeError("micro_batch: void_labels / grad_scale need CUDA tensors (the void rule lives in the HIP loss kernel)")
         if self.mode == 'online':
             loss = self.loss_fn(outputs[-1], gts, size_average=False)
             running[0] += loss.detach()
@@ -153,11 +159,13 @@ class TrainLoop(object):
             self.ave = 0      # past max_steps the window's gradients are computed and dropped, like micro_batch's trailing windows: the next call starts a window
         return losses[-1], stepped
 
-    def _micro_batch_fused(self, outputs, gts, running, epoch):
+    def _micro_batch_fused(self, outputs, gts, running, epoch, void_labels=False, grad_scale=1.0):
         """The same micro-batch with the upstream gradients of ``loss /= nAveGrad; loss.backward()`` (train_online.py:140-141;
         train_parent.py:147,163-164: side heads weighted by 1 - epoch / nEpochs) folded into the loss kernel -- float32 products formed
         the way autograd forms them (1 / nAveGrad, then times the float32 side weight)."""
         inv = np.float32(1.0) / np.float32(self.n_ave_grad)
+        if grad_scale != 1.0:
+            inv = np.float32(inv * np.float32(grad_scale))
         if self.mode == 'online':
             heads, scales = [outputs[-1]], [inv]
         else:
@@ -165,12 +173,12 @@ class TrainLoop(object):
             heads, scales = list(outputs), [side] * (len(outputs) - 1) + [inv]
         if len(heads) > 1 and os.environ.get('OSVOS_CBCE_MULTI', '1') != '0':      # the parent loop's five losses: one library call (class counts formed once, one sweep)
             losses, grads = class_balanced_cross_entropy_loss_step_multi(heads, gts, size_average=False, grad_scales=[float(s) for s in scales],
-                                                                         running=list(running))
+                                                                         running=list(running), void_labels=void_labels)
             loss = losses[-1]
         else:
             grads, loss = [], None
             for o, s, r in zip(heads, scales, running):
-                loss, g = class_balanced_cross_entropy_loss_step(o, gts, size_average=False, grad_scale=float(s), running=r)
+                loss, g = class_balanced_cross_entropy_loss_step(o, gts, size_average=False, grad_scale=float(s), running=r, void_labels=void_labels)
                 grads.append(g)
         will_step = (self.ave + 1) % self.local_ave == 0 and (self.max_steps is None or self.steps < self.max_steps)
         if self.reducer is not None and will_step:

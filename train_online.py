@@ -16,6 +16,9 @@ running on the MI355X-native OSVOS path.  Differences by design:
     when it lies within R pixels of what was kept of the previous frame, starting from the first annotation (results.ComponentTracker)
   * ``--tta-scales S1,S2,..`` / ``--tta-flip``: test-time augmentation of the test forwards -- every frame at each scale and (flip) mirrored,
     the views' logit maps resampled onto the frame's grid and averaged on the device (osvos_pytorch_amd.tta.TestTimeAugment)
+  * ``--adapt-steps N``: online adaptation over the sequence (OnAVOS-style) -- before a frame after the first is segmented, N optimizer steps
+    interleave the annotated first frame with the frame itself, trained against targets made on the device from the network's own confident
+    output and the previous frame's mask, the rest void (osvos_pytorch_amd.adapt.OnlineAdapter)
   * launched under torchrun with N processes, rank r fine-tunes sequences r, r+N, ... of the
     comma-separated SEQ_NAME list (independent replicas: online training has no exchange step)
 """
@@ -120,7 +123,9 @@ def device_loaders(args, seq_name, device, seed):
         s = synthetic_loader(args.height, args.width, seed)[0]
         img = (s['image'][0].permute(1, 2, 0) + 116.0).clamp(0, 255).to(torch.uint8).numpy()
         lab = (s['gt'][0, 0] * 255).to(torch.uint8).numpy()
-        train, test = ArrayFrames([(img, lab)]), ArrayFrames([(img, lab)])
+        # --synthetic-frames K: frame f is the seeded frame with image and ellipse moved right by 4 f pixels (columns wrap), annotated on every frame
+        moved = [(np.roll(img, 4 * f, axis=1), np.roll(lab, 4 * f, axis=1)) for f in range(args.synthetic_frames)]
+        train, test = ArrayFrames(moved[:1]), ArrayFrames(moved)
     else:
         train, test = DavisFrames(True, Path.db_root_dir(), seq_name=seq_name), DavisFrames(False, Path.db_root_dir(), seq_name=seq_name)
     img, lab = train[0]
@@ -177,6 +182,43 @@ def fine_tune(args, net, optimizer, trainloader, device, nEpochs, nAveGrad, seed
     if device.type == 'cuda':
         torch.cuda.synchronize()
     print('Online training time: ' + str(timeit.default_timer() - start_time))
+
+
+def check_adapt_args(args):
+    """the --adapt-* / --synthetic-frames rules; SystemExit on a combination the script does not run -- checked before any GPU work"""
+    if args.synthetic_frames < 1:
+        raise SystemExit('--synthetic-frames takes a frame count >= 1, got %d' % args.synthetic_frames)
+    if args.synthetic_frames > 1 and not (args.synthetic and args.device_augment and not args.multi_object):
+        raise SystemExit('--synthetic-frames needs --synthetic --device-augment (single-object loop): the moved frames are made for the device input pipeline')
+    if args.adapt_steps < 0:
+        raise SystemExit('--adapt-steps takes a step count >= 0, got %d' % args.adapt_steps)
+    if not args.adapt_steps:
+        return
+    if args.multi_object:
+        raise SystemExit('--adapt-steps runs in the single-object loop only: --multi-object fine-tunes one network per object and runs them pass '
+                         'by pass, online adaptation needs each frame\'s final mask before the next frame')
+    if not args.device_augment:
+        raise SystemExit('--adapt-steps needs --device-augment: the first-frame steps re-augment the annotated frame on the device')
+    if args.tta:
+        raise SystemExit('--adapt-steps does not combine with --tta-scales / --tta-flip: the adapter returns its own final forward')
+    if args.adapt_mix < 1:
+        raise SystemExit('--adapt-mix takes a period >= 1, got %d' % args.adapt_mix)
+    if not 0.0 < args.adapt_prob < 1.0:
+        raise SystemExit('--adapt-prob takes a probability in (0, 1), got %r' % args.adapt_prob)
+    if args.adapt_erosion < 0 or args.adapt_distance < 0:
+        raise SystemExit('--adapt-erosion and --adapt-distance take pixel counts >= 0, got %d and %d' % (args.adapt_erosion, args.adapt_distance))
+    if args.adapt_lr is not None and not args.adapt_lr > 0:
+        raise SystemExit('--adapt-lr takes a learning rate > 0, got %r' % args.adapt_lr)
+
+
+def make_adapter(args, net, trainloader):
+    """the online adapter of --adapt-steps on a FRESH optimizer (no momentum carried over from the first-frame fine-tuning), or None"""
+    if not args.adapt_steps:
+        return None
+    from osvos_pytorch_amd.adapt import OnlineAdapter, first_frame_source
+    optimizer = make_sgd(net, 'online', lr=args.adapt_lr) if args.adapt_lr is not None else make_sgd(net, 'online')
+    return OnlineAdapter(net, optimizer, first_frame_source(trainloader), steps=args.adapt_steps, mix=args.adapt_mix, weight=args.adapt_weight,
+                         prob=args.adapt_prob, erosion=args.adapt_erosion, distance=args.adapt_distance)
 
 
 def tta_scales(args):
@@ -275,7 +317,8 @@ def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, n
     print('Testing time multi-object: ' + str(test_time + timeit.default_timer() - start_time))
 
 
-def main():
+def parse_args(argv=None):
+    """the command line, with every refusal that needs no GPU (bad lists, combinations the script does not run) raised as SystemExit"""
     ap = argparse.ArgumentParser()
     ap.add_argument('--synthetic', action='store_true', help='seeded synthetic 854x480 frame instead of DAVIS')
     ap.add_argument('--epochs', type=int, default=0, help='0 = reference value 2000 * nAveGrad')
@@ -311,8 +354,22 @@ def main():
     ap.add_argument('--tta-flip', action='store_true',
                     help='test-time augmentation: every scale (scale 1 alone without --tta-scales) also runs mirrored, in the same batch; twice '
                          'the forwards')
-    args = ap.parse_args()
+    ap.add_argument('--adapt-steps', type=int, default=0, metavar='N',
+                    help='online adaptation over the sequence (0 = off): before every frame after the first is segmented, N optimizer steps -- '
+                         'every --adapt-mix-th on the frame itself against targets from the network\'s own confident output and the previous '
+                         'frame\'s mask (the rest void), the others on the re-augmented annotated first frame.  Needs --device-augment; '
+                         'single-object loop only; not with --tta-*')
+    ap.add_argument('--adapt-mix', type=int, default=5, metavar='M', help='--adapt-steps: step k trains on the current frame when k %% M == M - 1')
+    ap.add_argument('--adapt-prob', type=float, default=0.97, help='--adapt-steps: a pixel is a positive target above this probability')
+    ap.add_argument('--adapt-erosion', type=int, default=15, help='--adapt-steps: the previous mask is eroded by this many pixels ...')
+    ap.add_argument('--adapt-distance', type=int, default=220, help='... and pixels farther than this from what is left are negative targets')
+    ap.add_argument('--adapt-weight', type=float, default=1.0, help='--adapt-steps: factor on the gradient of the current-frame steps')
+    ap.add_argument('--adapt-lr', type=float, default=None, help='--adapt-steps: learning rate of the adaptation steps (default: the online rate)')
+    ap.add_argument('--synthetic-frames', type=int, default=1, metavar='K',
+                    help='--synthetic --device-augment: a sequence of K frames, frame f the seeded frame moved right by 4 f pixels, all annotated')
+    args = ap.parse_args(argv)
     args.tta = tta_scales(args)
+    check_adapt_args(args)
     if args.tta and not (args.device_augment or (args.multi_object and args.synthetic)):
         raise SystemExit('--tta-scales / --tta-flip need --device-augment (or --multi-object --synthetic): test-time augmentation makes its views '
                          'from the decoded uint8 frame on the device')
@@ -320,7 +377,11 @@ def main():
         raise SystemExit('--track-components takes a radius of 0..64 pixels, got %d' % args.track_components)
     if args.multi_object and not (args.device_augment or args.synthetic):
         raise SystemExit('--multi-object needs --device-augment or --synthetic: the per-object labels are made on the device input pipeline')
+    return args
 
+
+def main():
+    args = parse_args()
     rank, world, device = init_distributed(collectives=False)      # sequences are sharded over the ranks: nothing is exchanged
     seqs = os.environ.get('SEQ_NAME', 'blackswan').split(',')
     save_dir = Path.save_root_dir()
@@ -353,11 +414,15 @@ def main():
         if args.test_precision:
             net.set_precision(args.test_precision)      # (re-packs the weights once: the FP16-pair packs are another format)
         tta = make_tta(args, net)
+        adapter = make_adapter(args, net, trainloader)
+        prev_mask = None                     # --adapt-steps: the previous frame's final mask (frame 0: its annotation)
         with torch.no_grad():
             for sample in testloader:
                 fname = sample['fname']
                 if tta is not None:
                     fused = tta(sample['frame_u8'])
+                elif adapter is not None and prev_mask is not None:
+                    fused = adapter(sample['image'].to(device), prev_mask)      # (turns gradients on for its own training steps)
                 else:
                     outputs = net.forward(sample['image'].to(device))
                     fused = outputs[-1]
@@ -367,6 +432,10 @@ def main():
                             raise SystemExit('--track-components: sequence %s has no first annotation to seed the tracker' % seq_name)
                         tracker = ComponentTracker(sample['gt'].to(device)[0, 0] > 0.5, args.track_components)
                     fused = tracker(fused)
+                if adapter is not None:
+                    if prev_mask is None and 'gt' not in sample:
+                        raise SystemExit('--adapt-steps: sequence %s has no first annotation to start from' % seq_name)
+                    prev_mask = sample['gt'].to(device) > 0.5 if prev_mask is None else fused > 0
                 # sigmoid + scipy<=1.1 imsave byte scaling on the device, PNG written by osvos_pytorch_amd.results (reference :181-187)
                 save_masks(fused, [os.path.join(save_dir_res, os.path.basename(fname[jj]) + '.png') for jj in range(int(fused.size()[0]))])
                 if 'gt' in sample:
@@ -381,6 +450,10 @@ def main():
         if tracker is not None:
             c = tracker.summary()
             print('Components kept on %s: %d of %d over %d frames' % (seq_name, c['kept'], c['seen'], c['frames']))
+        if adapter is not None:
+            c = adapter.summary()
+            print('Online adaptation on %s: %d frames seen, %d adapted, %d skipped, %d steps' % (seq_name, c['adapted'] + c['skipped'], c['adapted'],
+                                                                                                c['skipped'], c['steps']))
 
 
 if __name__ == '__main__':
