@@ -160,9 +160,34 @@ __device__ inline void split8_hm(const u32x4& lo, const u32x4& hi, uint4& p0, ui
 // the pre-split pack (every (piece, tap, group) run of BN couts is contiguous in the pack and in LDS) into a ring of two TAP-ROW slots (3 taps
 // x 16 channels x BN x 3 pieces: 36.9 KB at BN = 128); the DMA of tap row j + 1 is issued at the start of row j.  The activations have two
 // buffers: chunk k + 1's raw values (loaded during chunk k - 1) are split and written into the idle buffer between the MFMAs of chunk k's
-// first tap row, then chunk k + 2's loads are issued.  One raw s_barrier per tap row (three per chunk) with counted vmcnt / lgkmcnt, never
+// first tap row, then chunk k + 2's loads are issued.  One raw s_barrier per tap row (three per chunk; placed one step early, below) with counted vmcnt / lgkmcnt, never
 // __syncthreads() (its fence would drain the DMA in flight).  The MFMA sequence of every accumulator is the one above (chunk, tap, piece
 // products small-first), so the results are bit-identical.
+//
+// EARLY BARRIER.  The barrier that opens tap row j + 1 sits at the start of row j's LAST step (s = 2, mi = WM - 1), in front of that step's
+// MFMAs, followed by the first fragment reads of row j + 1 (B of tap 0, A of (tap 0, M block 0)): all eight waves leave a barrier together,
+// and with the barrier at the top of a row every one of them then waited for its first 3 (WN + 1) ds_read_b128 with the matrix pipe empty.
+// Now those reads land under the 6 WN MFMAs of the last step and a row starts with its operands in registers.  Only the first barrier of a
+// segment (and the segment-opening lgkmcnt(0) + s_barrier) stands outside a row; every wave executes exactly nrows row barriers per segment,
+// all under uniform control flow (j + 1 < nrows depends on the segment only).  The prologue issues row 0's DMA BEFORE chunk kc_begin's
+// activation loads (its latency runs under theirs).  Why this is safe:
+//   * RAW, weights.  Row j + 1's DMA is issued in row j at step 2 (r = 0) or step 0 (r = 1, 2), three to five steps before the early barrier,
+//     and it is the newest DMA of the wave there.  Loads return in order, so the counted wait means what it meant at the top of row j + 1:
+//     vmcnt(4) when chunk kc + 2's four activation loads were issued behind the DMA in this row (r = 0, step 3), vmcnt(0) otherwise.  In the
+//     prologue the DMA is the OLDEST load: put_a's waits for its registers drain it, and the first barrier only lets chunk kc_begin + 1's four
+//     loads stay in flight (vmcnt(4)), or nothing (vmcnt(0)).
+//   * WAR, ring slot.  Row j + 2's DMA overwrites the slot row j was read from.  It is issued in row j + 1, i.e. by a wave that has passed
+//     the early barrier in row j; a wave arrives there with every B fragment of row j requested (the last, tap 2, at s = 1) and landed
+//     (lgkmcnt(0) in front of the s_barrier).  Likewise row j + 1's DMA (issued in row j) overwrites row j - 1's slot, whose reads every wave
+//     finished before the early barrier in row j - 1.
+//   * WAR / RAW, activation buffers.  put_a writes chunk kc + 1 into Anext (= chunk kc - 1's buffer) in row 0, steps 0-1, of chunk kc: after
+//     the early barrier in the last step of chunk kc - 1's row 2, where every wave's last A fragments of chunk kc - 1 had landed.  Those
+//     writes are read first behind the early barrier of chunk kc's row 2, whose lgkmcnt(0) covers this wave's ds_writes.
+//   * Fragment registers.  A: the sets alternate per step and a row has 3 WM = 6 steps, so row j + 1's first fragment goes to set 0 while the
+//     last step computes from set 1.  B: one set per tap of a row (three sets: + 3 WN 4 = 24 VGPRs on tile 10, 12 on tiles 12 / 14); the last
+//     step computes from set 2, set 0 was last used at step WM - 1.  The indices are compile-time constants.
+//   * The MFMAs of the last step use fragments requested BEFORE the barrier; the compiler's own lgkmcnt for them counts the 3 (WN + 1) <= 9
+//     younger reads (LDS returns in order), so they do not wait for row j + 1's fragments.
 template <class C, int PS, int SK, int NP = 3, int HP = 0, int PIPE = 0>
 __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_f32x3_kernel(ConvArgsX a) {
   static_assert(NP == 2 || NP == 3, "two or three bf16 pieces per operand");
@@ -498,14 +523,42 @@ __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_f32x3_kernel(ConvArgsX 
         Ab[a_dst[i] + 4 * C::PLANE] = p2;
       }
     };
-    const int nrows = 3 * (kc_end - kc_begin);
+    // this segment has nrows = 3 (kc_end - kc_begin) tap rows and as many row barriers: the one below + one in every row but the last
+    static_assert((3 * C::WM) % 2 == 0, "pipelined loop: a tap row's steps must leave the A fragment set parity where it started");
+    // fragment registers live across tap rows: the B set of tap s is set s (the third set is what lets the next row's first tap be read during
+    // this row's last one), the A sets alternate per step (a row has an even number of steps, so the next row's first fragment takes the set
+    // the last step does not use).  Compile-time indices only.
+    uint4 fb[3][3][C::WN], fa[2][3];
+    auto ldB = [&](const uint4* Bc, int rr, int s) {
+#if defined(OSVOS_X3_ABL) && OSVOS_X3_ABL == 2
+      if (rr + s > 0) return;
+#endif
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int ni = 0; ni < C::WN; ++ni) fb[s][p][ni] = Bc[b_idx + (p * 3 + s) * 2 * C::BN + ni * 32];
+    };
+    auto ldA = [&](const uint4* Ac, int rr, int s, int mi, int set) {
+#if defined(OSVOS_X3_ABL) && OSVOS_X3_ABL == 2
+      if (rr + s > 0 || mi > 1) return;
+#endif
+#pragma unroll
+      for (int p = 0; p < 3; ++p) fa[set][p] = Ac[a_idx[mi] + p * 2 * C::PLANE + rr * C::PITCH + s];
+    };
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // (stream-K) every wave is done with the previous segment's LDS
+    // prologue: the weight DMA first, so that its latency runs under the activation loads'.  The loads return in order and the DMA is the
+    // oldest, so the waits put_a needs for its registers have drained it as well; the first barrier only has to let chunk kc_begin + 1's
+    // four loads (issued last) stay in flight: vmcnt(4) with them, vmcnt(0) without.
+    dma_row(0);
     ld_a(kc_begin);
     put_a(0, As);
     put_a(1, As);
-    dma_row(0);
     bool ra_behind = kc_begin + 1 < kc_end;
     if (ra_behind) ld_a(kc_begin + 1);
+    X3P_BARRIER(ra_behind);              // row 0's weights and chunk kc_begin's activations are in LDS
+    ra_behind = false;
+    ldB(Bring, 0, 0);
+    ldA(As, 0, 0, 0, 0);
     for (int kc = kc_begin; kc < kc_end; ++kc) {
       const int buf = (kc - kc_begin) & 1;
       const uint4* const Acur = As + buf * C::A_U4;
@@ -514,39 +567,19 @@ __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_f32x3_kernel(ConvArgsX 
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
         const int j = 3 * (kc - kc_begin) + r;
-        X3P_BARRIER(ra_behind);          // row j's weights (and, r = 0, chunk kc's activations) are in LDS; every wave has left row j - 1
-        ra_behind = false;
         const uint4* const Bcur = Bring + (j & 1) * C::ROW_U4;
-        const bool dma_next = j + 1 < nrows;
-        uint4 fb[2][3][C::WN], fa[2][3];
-        auto ldB = [&](int s, int set) {
-#if defined(OSVOS_X3_ABL) && OSVOS_X3_ABL == 2
-          if (r + s > 0) return;
-#endif
-#pragma unroll
-          for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int ni = 0; ni < C::WN; ++ni) fb[set][p][ni] = Bcur[b_idx + (p * 3 + s) * 2 * C::BN + ni * 32];
-        };
-        auto ldA = [&](int s, int mi, int set) {
-#if defined(OSVOS_X3_ABL) && OSVOS_X3_ABL == 2
-          if (r + s > 0 || mi > 1) return;
-#endif
-#pragma unroll
-          for (int p = 0; p < 3; ++p) fa[set][p] = Acur[a_idx[mi] + p * 2 * C::PLANE + r * C::PITCH + s];
-        };
-        ldB(0, 0);
-        ldA(0, 0, 0);
+        const uint4* const Bnxt = Bring + ((j + 1) & 1) * C::ROW_U4;
+        const bool dma_next = r < 2 || more;             // j + 1 < nrows
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
 #pragma unroll
           for (int mi = 0; mi < C::WM; ++mi) {
             const int step = s * C::WM + mi;
-            if (mi + 1 < C::WM) ldA(s, mi + 1, (step + 1) & 1);
-            else if (s + 1 < 3) ldA(s + 1, 0, (step + 1) & 1);
-            if (mi == 0 && s + 1 < 3) ldB(s + 1, (s + 1) & 1);
+            if (mi + 1 < C::WM) ldA(Acur, r, s, mi + 1, (step + 1) & 1);
+            else if (s + 1 < 3) ldA(Acur, r, s + 1, 0, (step + 1) & 1);
+            if (mi == 0 && s + 1 < 3) ldB(Bcur, r, s + 1);
             // staging, one item per step behind the fragment reads: row 0 -- split + write chunk kc + 1's activations (2 steps), the DMA
-            // of row j + 1, chunk kc + 2's loads (after the DMA: the barrier of row j + 1 lets them stay in flight); rows 1, 2 -- the DMA
+            // of row j + 1, chunk kc + 2's loads (after the DMA: the barrier that opens row j + 1 lets them stay in flight); rows 1, 2 -- the DMA
             if (r == 0) {
 #if !(defined(OSVOS_X3_ABL) && OSVOS_X3_ABL == 4)
               if (step < 2 && more) put_a(step, Anext);
@@ -560,8 +593,16 @@ __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_f32x3_kernel(ConvArgsX 
               if (step == 0 && dma_next) dma_row(j + 1);
 #endif
             }
+            // the row's last step opens row j + 1 (header, "early barrier"): this step's own fragments have landed with the barrier's
+            // lgkmcnt(0), the next row's first ones are requested in front of this step's MFMAs
+            if (step == 3 * C::WM - 1 && dma_next) {
+              X3P_BARRIER(ra_behind);    // row j + 1's weights (and, r = 2, chunk kc + 1's activations) are in LDS; no wave reads row j's any more
+              ra_behind = false;
+              ldB(Bnxt, (r + 1) % 3, 0);
+              ldA(r == 2 ? Anext : Acur, (r + 1) % 3, 0, 0, 0);
+            }
             __builtin_amdgcn_sched_barrier(0);
-            const int sa = step & 1, sb = s & 1;
+            const int sa = step & 1, sb = s;
             constexpr int PB[6] = {2, 0, 1, 1, 0, 0};      // (piece of B, piece of A) per product, small first, hi x hi last (as above)
             constexpr int PA[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
