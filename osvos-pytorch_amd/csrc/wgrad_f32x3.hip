@@ -110,12 +110,18 @@ __device__ __forceinline__ void stage_groups() {
 // ILV = 1 (four-wave forms): the next stage's 18-24 fragment gathers and the staging loads are INTERLEAVED with the stage's 18 MFMAs (one
 // gather per MFMA, sched_group_barrier) instead of being issued as a block in front of them: with one wave per SIMD nothing else covers
 // the ~150-250 cycles that block takes while the matrix pipe drains (576 cycles of MFMA per stage; the pipe was busy 51 % of the time).
+// INVARIANT: a stage must stay ONE BASIC BLOCK.  sched_group_barrier orders instructions inside one scheduling region only; anything in a
+// stage that the compiler can turn into a branch or an EXEC-masked region (a divergent `ok ? <expensive address> : OOB` was: the multiplies were
+// sunk under s_and_saveexec) leaves the gathers in the block before it and the MFMAs in the block after it, and the lists below have nothing to
+// place.  So what can become control flow belongs OUTSIDE the stage loop (the staging addresses: OA below); tools/asm_schedule.py prints the
+// compiled order per kernel (profiles/r10_wgrad_x3_schedule_*.txt): the whole unrolled patch loop must come out as one block of MFMAs.
+// OA = 1: the staging-address form before that (bf16 pieces only; OSVOS_WGRAD_X3_OLDADDR=1), kept for one A/B.
 // NP = 2 (round 6, precision 'fp32x2'): two bf16 pieces per operand, three products (conv3x3_f32x3.hip) -- same tiles, the low planes unused
 // HP = 1 ("h2", precision 'fp32h2'; h2split.h): the two pieces are FP16 with a block exponent per operand.  Both operands are activations
 // here, so both exponents are the workgroup's own running ones: the waves exchange the largest magnitudes of the patch about to be staged
 // (dY and X separately) through two words of LDS before the barrier that opens the staging phase; when an exponent drops the nine accumulators
 // are multiplied by the power of two that separates the scales; the slab epilogue un-scales.  (The bias gradient stays the exact fp32 column sum.)
-template <int PH, int WAVES, int S16 = 0, int ILV = 0, int NP = 3, int HP = 0>
+template <int PH, int WAVES, int S16 = 0, int ILV = 0, int NP = 3, int HP = 0, int OA = 0>
 __global__ __launch_bounds__(64 * WAVES) void wgrad_f32x3_kernel(W3Args a) {
   static_assert(HP == 0 || NP == 2, "h2: two pieces");
   using G = G3<PH, WAVES, S16>;
@@ -145,7 +151,32 @@ __global__ __launch_bounds__(64 * WAVES) void wgrad_f32x3_kernel(W3Args a) {
   const bool want_bias = a.bslab != nullptr && cit == 0;
   const int img_dy_bytes = a.H * a.W * a.Cout_s * 4, img_x_bytes = a.H * a.W * a.Cin_s * 4;
 
-  struct Patch { __amdgpu_buffer_rsrc_t drs, xrs; int x0, y0; };
+  // The staging addresses are BRANCH-FREE (OA = 0).  What does not change from patch to patch is computed here, once per thread: each item's
+  // byte offset inside a patch whose origin is pixel (0, 0) (X: one pixel up and left of it; may be negative, the sums wrap like the old int
+  // expression did) and its column inside the patch.  The static validity (channel tail, pixel past the tile) is folded into the column as
+  // a value no patch origin can bring into the image, so a stage does one add, one unsigned compare and one select per item: no multiply
+  // and nothing the compiler can turn into control flow (see the invariant at the stage loop).
+  constexpr int DEADCOL = 0x40000000;
+  unsigned dy_inv[G::NDY], x_inv[G::NX];
+  unsigned dy_col[G::NDY], x_col[G::NX];
+  if constexpr (OA == 0) {
+#pragma unroll
+    for (int it = 0; it < G::NDY; ++it) {
+      const int p = dpg + G::DPG * it, py = p / PW, pxx = p - py * PW;
+      const bool ok = dy_ch_ok && (G::DY_ITEMS % NT == 0 || p < G::PPIX);
+      dy_inv[it] = (unsigned)(((py * a.W + pxx) * a.Cout_s + co0 + 8 * doct) * 4);
+      dy_col[it] = (unsigned)(ok ? pxx : DEADCOL);
+    }
+#pragma unroll
+    for (int j = 0; j < G::NX; ++j) {
+      const int hp = xpg + G::XPG * j, hy = hp / G::HW_, hx = hp - hy * G::HW_;
+      const bool ok = x_ch_ok && hp < G::XPIX;
+      x_inv[j] = (unsigned)((((hy - 1) * a.W + hx - 1) * a.Cin_s + ci0 + 8 * xoct) * 4);
+      x_col[j] = (unsigned)(ok ? hx - 1 : DEADCOL);
+    }
+  }
+
+  struct Patch { __amdgpu_buffer_rsrc_t drs, xrs; int x0, y0; unsigned dorg, xorg; };
   auto locate = [&](int p, bool live) -> Patch {
     const int px = p % a.npx;
     int t = p / a.npx;
@@ -154,6 +185,9 @@ __global__ __launch_bounds__(64 * WAVES) void wgrad_f32x3_kernel(W3Args a) {
     Patch q;
     q.x0 = live ? px * PW : 0x40000000;            // dead patch: every column test fails -> all loads out of range
     q.y0 = py * PH;
+    const unsigned org = (unsigned)(q.y0 * a.W + (live ? px * PW : 0));      // pixel index of the patch origin inside its image
+    q.dorg = org * (unsigned)a.Cout_s * 4u;
+    q.xorg = org * (unsigned)a.Cin_s * 4u;
     q.drs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(a.dy)) + (size_t)n * img_dy_bytes, 0, img_dy_bytes, 0x00020000);
     q.xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(a.x)) + (size_t)n * img_x_bytes, 0, img_x_bytes, 0x00020000);
     return q;
@@ -162,16 +196,26 @@ __global__ __launch_bounds__(64 * WAVES) void wgrad_f32x3_kernel(W3Args a) {
   // columns outside the image must be pushed out explicitly (they would alias the neighbouring row)
   auto issue = [&](const Patch& q, int it) {      // it: compile-time item index (dY items first)
     if (it < G::NDY) {
-      const int p = dpg + G::DPG * it, py = p / PW, pxx = p - py * PW;
-      const bool ok = dy_ch_ok && (G::DY_ITEMS % NT == 0 || p < G::PPIX) && q.x0 + pxx < a.W;
-      const unsigned off = ok ? (unsigned)((((q.y0 + py) * a.W + q.x0 + pxx) * a.Cout_s + co0 + 8 * doct) * 4) : OOB;
+      unsigned off;
+      if constexpr (OA == 0) {
+        off = (unsigned)q.x0 + dy_col[it] < (unsigned)a.W ? q.dorg + dy_inv[it] : OOB;
+      } else {      // the address form before: the select became a branch with the multiplies under it (kept for one A/B)
+        const int p = dpg + G::DPG * it, py = p / PW, pxx = p - py * PW;
+        const bool ok = dy_ch_ok && (G::DY_ITEMS % NT == 0 || p < G::PPIX) && q.x0 + pxx < a.W;
+        off = ok ? (unsigned)((((q.y0 + py) * a.W + q.x0 + pxx) * a.Cout_s + co0 + 8 * doct) * 4) : OOB;
+      }
       rdy[it][0] = __builtin_amdgcn_raw_buffer_load_b128(q.drs, off, 0, 0);
       rdy[it][1] = __builtin_amdgcn_raw_buffer_load_b128(q.drs, off + 16u, 0, 0);
     } else if (it < G::NIT) {
       const int j = it - G::NDY;
-      const int hp = xpg + G::XPG * j, hy = hp / G::HW_, hx = hp - hy * G::HW_;
-      const bool ok = x_ch_ok && hp < G::XPIX && (unsigned)(q.x0 - 1 + hx) < (unsigned)a.W;
-      const unsigned off = ok ? (unsigned)((((q.y0 - 1 + hy) * a.W + q.x0 - 1 + hx) * a.Cin_s + ci0 + 8 * xoct) * 4) : OOB;
+      unsigned off;
+      if constexpr (OA == 0) {
+        off = (unsigned)q.x0 + x_col[j] < (unsigned)a.W ? q.xorg + x_inv[j] : OOB;
+      } else {
+        const int hp = xpg + G::XPG * j, hy = hp / G::HW_, hx = hp - hy * G::HW_;
+        const bool ok = x_ch_ok && hp < G::XPIX && (unsigned)(q.x0 - 1 + hx) < (unsigned)a.W;
+        off = ok ? (unsigned)((((q.y0 - 1 + hy) * a.W + q.x0 - 1 + hx) * a.Cin_s + ci0 + 8 * xoct) * 4) : OOB;
+      }
       rx[j][0] = __builtin_amdgcn_raw_buffer_load_b128(q.xrs, off, 0, 0);
       rx[j][1] = __builtin_amdgcn_raw_buffer_load_b128(q.xrs, off + 16u, 0, 0);
     }
@@ -418,17 +462,17 @@ int block_map3(long blocks) {
   return (map_env == 1 && blocks % 8 == 0) ? 1 : 0;
 }
 
-template <int PH, int WAVES, int S16 = 0, int ILV = 0, int NP = 3, int HP = 0>
+template <int PH, int WAVES, int S16 = 0, int ILV = 0, int NP = 3, int HP = 0, int OA = 0>
 int launch3(const W3Args& a, long blocks, hipStream_t stream) {
   static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};
   bool& attr_set = attr_set_dev[osvos_current_device()];
   if (!attr_set) {
-    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_f32x3_kernel<PH, WAVES, S16, ILV, NP, HP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_f32x3_kernel<PH, WAVES, S16, ILV, NP, HP, OA>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)G3<PH, WAVES, S16>::LDS));
     attr_set = true;
   }
   constexpr size_t lds = G3<PH, WAVES, S16>::LDS;
-  hipLaunchKernelGGL((wgrad_f32x3_kernel<PH, WAVES, S16, ILV, NP, HP>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, stream, a);
+  hipLaunchKernelGGL((wgrad_f32x3_kernel<PH, WAVES, S16, ILV, NP, HP, OA>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, stream, a);
   OSVOS_LAUNCH_CHECK();
   return 0;
 }
@@ -486,10 +530,17 @@ int osvos_conv3x3_wgrad_f32x3(const WgradCall& c) {
   const long blocks = (long)p.nsplit * p.nco_t * p.nci_t;
   a.map = block_map3(blocks);
   if (c.phase != WGRAD_REDUCE) {
-    // gathers / staging loads interleaved with the MFMAs of the previous stage (round 3; the block-issue form measured level and is gone)
+    // gathers / staging loads interleaved with the MFMAs of the previous stage (round 3: 'the block-issue form measured level and is gone' -- in the
+    // stages that issue staging loads the two forms were the same code until the staging addresses became branch-free: the kernel's INVARIANT)
     const bool two = c.pieces == 2;      // precision 'fp32x2'
     const bool h2 = c.pieces == 22;      // precision 'fp32h2'
-    const int rc = h2  ? (skinny ? launch3<4, 4, 1, 1, 2, 1>(a, blocks, stream)
+    OSVOS_ENV_INT(oldaddr_env, "OSVOS_WGRAD_X3_OLDADDR", 0);      // 1: the staging-address form before (bf16 pieces only), for one A/B
+    const bool oa = oldaddr_env == 1 && !h2;
+    const int rc = oa  ? (two ? (skinny ? launch3<4, 4, 1, 1, 2, 0, 1>(a, blocks, stream)
+                                        : (p.ph == 6 ? launch3<6, 4, 0, 1, 2, 0, 1>(a, blocks, stream) : launch3<4, 4, 0, 1, 2, 0, 1>(a, blocks, stream)))
+                              : (skinny ? launch3<4, 4, 1, 1, 3, 0, 1>(a, blocks, stream)
+                                        : (p.ph == 6 ? launch3<6, 4, 0, 1, 3, 0, 1>(a, blocks, stream) : launch3<4, 4, 0, 1, 3, 0, 1>(a, blocks, stream))))
+                 : h2  ? (skinny ? launch3<4, 4, 1, 1, 2, 1>(a, blocks, stream)
                                  : (p.ph == 6 ? launch3<6, 4, 0, 1, 2, 1>(a, blocks, stream) : launch3<4, 4, 0, 1, 2, 1>(a, blocks, stream)))
                  : two ? (skinny ? launch3<4, 4, 1, 1, 2>(a, blocks, stream)
                                  : (p.ph == 6 ? launch3<6, 4, 0, 1, 2>(a, blocks, stream) : launch3<4, 4, 0, 1, 2>(a, blocks, stream)))
