@@ -458,6 +458,31 @@ int osvos_tta_view(const unsigned char* bgr, const float* mean3, float* out, int
 int osvos_tta_fuse(const float* const* views, const int* Hv, const int* Wv, const int* flip, const float* weight, int V, float* out, int N,
                    int H, int W, void* stream);
 
+/* ---- mask refinement: mean field of a local two-label dense CRF (Potts compatibility, ConvCRF-style window), logits in, logits out ----
+ * Per image: unary [H][W] fp32 logits u, bgr [H][W][3] uint8 (the decoded frame I), a start state z^0 = init (NULL: unary).  For t = 0..iters-1
+ *     s_j       = 2 sigmoid(z_j^t) - 1
+ *     k(i, j)   = w_a exp(-(a_s ds + a_c dc)) + w_s exp(-g_s ds)
+ *     z_i^(t+1) = u_i + sum over j in W(i), j != i, j inside the image, of k(i, j) s_j
+ *   W(i): the offsets (dy * dilation, dx * dilation), |dy|, |dx| <= radius;  ds = (dy dilation)^2 + (dx dilation)^2;
+ *   dc = sum_c (I_i,c - I_j,c)^2 (an integer, at most 195075).  No other normalisation; a neighbour outside the image contributes nothing.
+ *   out [N][H][W] = z^iters.  iters == 0: out is the start state, copied bit for bit.  A pixel whose messages sum to zero (no neighbour
+ *   inside the image, radius 0, zero weights) leaves as u bit for bit.  Images of a batch are independent.
+ * Arithmetic: fp32.  The spatial factors w_a exp(-a_s ds) and w_s exp(-g_s ds) are made once per call on the host (float64, rounded once),
+ *   dc is exact, the colour factor is one hardware exp2 per neighbour, the sum runs over the window row by row (dy, then dx, ascending) with
+ *   one fused multiply-add per neighbour: no atomics, a fixed order per pixel -- identical calls give identical bits.
+ * One launch per iteration on `stream`; the states alternate between ws and out so that the last iteration writes out.
+ *   ws: osvos_crf_ws_bytes(N, H, W, iters) bytes (one state; 0 below two iterations and for sizes the call refuses), contents irrelevant on
+ *   entry; may be NULL when iters < 2.  out must not be unary or init (each iteration reads a neighbourhood of its source).
+ * Limits: radius 0..OSVOS_CRF_MAX_RADIUS (0: no neighbours), dilation >= 1, radius * dilation <= OSVOS_CRF_MAX_REACH, iters
+ *   0..OSVOS_CRF_MAX_ITERS, sides 1..16384, N 1..65535; the five coefficients finite and >= 0; float pointers 4-byte aligned.  Every
+ *   argument error returns < 0 before any device call. */
+#define OSVOS_CRF_MAX_RADIUS 7
+#define OSVOS_CRF_MAX_REACH 16
+#define OSVOS_CRF_MAX_ITERS 64
+size_t osvos_crf_ws_bytes(int N, int H, int W, int iters);
+int osvos_crf_refine(const float* unary, const float* init, const unsigned char* bgr, float* out, void* ws, int N, int H, int W, int iters,
+                     int radius, int dilation, float w_a, float w_s, float a_s, float a_c, float g_s, void* stream);
+
 /* ---- online adaptation: exact squared Euclidean distance maps and the adaptation targets made from them ----
  * osvos_mask_sqdist: mask [N][H][W] uint8 -> sqdist [N][H][W] int32.  A pixel q is a SOURCE when (mask[q] != 0) != (invert != 0);
  *   sqdist[n][y][x] = min over the sources q of image n of |p - q|^2, an exact integer, OSVOS_SQDIST_NONE everywhere in an image without a

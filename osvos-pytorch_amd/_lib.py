@@ -27,6 +27,9 @@ INFERENCE = 0x400           # OSVOS_FLAG_INFERENCE: osvos_net_forward writes not
 MAX_OBJECTS = 16            # OSVOS_MAX_OBJECTS: object ids per label map (osvos_merge_objects, osvos_labels_jf_counts)
 BOUNDARY_MAX_RADIUS = 64    # OSVOS_BOUNDARY_MAX_RADIUS: largest disk radius (osvos_mask_jf_counts, osvos_components_select)
 TTA_MAX_VIEWS = 16          # OSVOS_TTA_MAX_VIEWS: logit maps per osvos_tta_fuse call
+CRF_MAX_RADIUS = 7          # OSVOS_CRF_MAX_RADIUS: largest window radius of osvos_crf_refine
+CRF_MAX_REACH = 16          # OSVOS_CRF_MAX_REACH: largest radius * dilation
+CRF_MAX_ITERS = 64          # OSVOS_CRF_MAX_ITERS: mean-field iterations per osvos_crf_refine call
 SQDIST_NONE = 2147483647    # OSVOS_SQDIST_NONE: osvos_mask_sqdist's value in an image without a source pixel
 SQDIST_MAX_SIDE = 4096      # OSVOS_SQDIST_MAX_SIDE: largest H / W of osvos_mask_sqdist and osvos_adapt_targets
 GENERIC_DECONV = 0x100      # OSVOS_FLAG_GENERIC_DECONV: OR-ed into the dtype of the osvos_net_* calls
@@ -117,6 +120,8 @@ PROTOTYPES = {
     "osvos_components_select": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "osvos_tta_view": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "osvos_tta_fuse": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "osvos_crf_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "osvos_crf_refine": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _vp]),
     "osvos_mask_sqdist_ws_bytes": (_sz, [_i, _i, _i]),
     "osvos_mask_sqdist": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "osvos_adapt_ws_bytes": (_sz, [_i, _i, _i]),

@@ -19,6 +19,9 @@ running on the MI355X-native OSVOS path.  Differences by design:
   * ``--adapt-steps N``: online adaptation over the sequence (OnAVOS-style) -- before a frame after the first is segmented, N optimizer steps
     interleave the annotated first frame with the frame itself, trained against targets made on the device from the network's own confident
     output and the previous frame's mask, the rest void (osvos_pytorch_amd.adapt.OnlineAdapter)
+  * ``--crf-iters N``: edge-aware refinement of every test frame's logit map against the decoded frame -- N mean-field steps of a local
+    dense CRF on the device (osvos_pytorch_amd.refine.CrfRefiner), after the forward / test-time augmentation / adapter and before
+    --track-components; parameters --crf-radius, --crf-dilation, --crf-weights, --crf-thetas (starting values, not tuned on DAVIS)
   * launched under torchrun with N processes, rank r fine-tunes sequences r, r+N, ... of the
     comma-separated SEQ_NAME list (independent replicas: online training has no exchange step)
 """
@@ -240,6 +243,34 @@ def make_tta(args, net):
     return TestTimeAugment(net.forward, args.tta, args.tta_flip) if args.tta else None
 
 
+def check_crf_args(args):
+    """the --crf-* rules; SystemExit on values the refinement does not take -- checked before any GPU work.  Sets args.crf to the
+    keyword arguments of refine.CrfRefiner, or None with --crf-iters 0"""
+    from osvos_pytorch_amd import refine
+    args.crf = None
+    try:
+        refine.check_window(args.crf_radius, args.crf_dilation, max(args.crf_iters, 0))
+        if args.crf_iters < 0:
+            raise ValueError('--crf-iters takes an iteration count >= 0 (0 = off), got %d' % args.crf_iters)
+        w_a, w_s = refine.parse_pair(args.crf_weights, 2, '--crf-weights WA,WS')
+        t_a, t_b, t_g = refine.parse_pair(args.crf_thetas, 3, '--crf-thetas A,B,G')
+        refine.crf_coefficients(args.crf_radius, args.crf_dilation, w_a, w_s, t_a, t_b, t_g)
+    except ValueError as e:
+        raise SystemExit('--crf-*: %s' % e)
+    if not args.crf_iters:
+        return
+    if not (args.device_augment or (args.multi_object and args.synthetic)):
+        raise SystemExit('--crf-iters needs --device-augment (or --multi-object --synthetic): the refinement reads the decoded uint8 frame '
+                         'on the device')
+    args.crf = dict(iters=args.crf_iters, radius=args.crf_radius, dilation=args.crf_dilation, w_appearance=w_a, w_smooth=w_s, theta_alpha=t_a,
+                    theta_beta=t_b, theta_gamma=t_g)
+
+
+def make_crf(args):
+    from osvos_pytorch_amd.refine import CrfRefiner
+    return CrfRefiner(**args.crf) if args.crf else None
+
+
 def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, nEpochs, nAveGrad):
     """DAVIS 2017 recipe for one sequence: one fine-tuning per object id of the first annotation on that object's binary mask, every frame
     through each network, the K logit stacks merged into label maps, indexed PNGs, J and F per object -- one read-back for the PNGs, one for
@@ -293,6 +324,12 @@ def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, n
     os.makedirs(save_dir_res, exist_ok=True)
     print('Testing Network')
     start_time = timeit.default_timer()
+    crf = make_crf(args)
+    if crf is not None:
+        for s0 in range(0, len(frames), 64):                                  # (enqueued: nothing is read back)
+            stacked = torch.stack(frames[s0:s0 + 64])
+            for k in range(K):
+                logits[k, s0:s0 + 64] = crf(logits[k, s0:s0 + 64], stacked)
     trackers = []
     if args.track_components is not None:
         for k in range(1, K + 1):
@@ -367,9 +404,22 @@ def parse_args(argv=None):
     ap.add_argument('--adapt-lr', type=float, default=None, help='--adapt-steps: learning rate of the adaptation steps (default: the online rate)')
     ap.add_argument('--synthetic-frames', type=int, default=1, metavar='K',
                     help='--synthetic --device-augment: a sequence of K frames, frame f the seeded frame moved right by 4 f pixels, all annotated')
+    ap.add_argument('--crf-iters', type=int, default=0, metavar='N',
+                    help='edge-aware mask refinement (0 = off): N mean-field steps of a local dense CRF on every test frame\'s logit map '
+                         'against the decoded frame, on the device, after the forward / --tta-* / --adapt-steps and before --track-components '
+                         '(so --adapt-steps sees the refined mask as the previous mask).  Needs --device-augment, or --multi-object '
+                         '--synthetic.  With --multi-object every object is refined as its own binary problem before the merge.  The '
+                         'default parameters are starting values, not tuned on DAVIS')
+    ap.add_argument('--crf-radius', type=int, default=5, help='--crf-iters: window radius 0..7 in steps of the dilation: (2 R + 1)^2 - 1 neighbours')
+    ap.add_argument('--crf-dilation', type=int, default=3, help='--crf-iters: pixels between window taps; radius x dilation <= 16')
+    ap.add_argument('--crf-weights', default='4,1', metavar='WA,WS',
+                    help='--crf-iters: weights of the appearance and the smoothness kernel, in logits (each normalised by its kernel\'s mass)')
+    ap.add_argument('--crf-thetas', default='8,13,3', metavar='A,B,G',
+                    help='--crf-iters: standard deviations -- appearance kernel in pixels, in grey levels, smoothness kernel in pixels')
     args = ap.parse_args(argv)
     args.tta = tta_scales(args)
     check_adapt_args(args)
+    check_crf_args(args)
     if args.tta and not (args.device_augment or (args.multi_object and args.synthetic)):
         raise SystemExit('--tta-scales / --tta-flip need --device-augment (or --multi-object --synthetic): test-time augmentation makes its views '
                          'from the decoded uint8 frame on the device')
@@ -415,6 +465,7 @@ def main():
             net.set_precision(args.test_precision)      # (re-packs the weights once: the FP16-pair packs are another format)
         tta = make_tta(args, net)
         adapter = make_adapter(args, net, trainloader)
+        crf = make_crf(args)
         prev_mask = None                     # --adapt-steps: the previous frame's final mask (frame 0: its annotation)
         with torch.no_grad():
             for sample in testloader:
@@ -426,6 +477,8 @@ def main():
                 else:
                     outputs = net.forward(sample['image'].to(device))
                     fused = outputs[-1]
+                if crf is not None:
+                    fused = crf(fused, sample['frame_u8'])
                 if args.track_components is not None:
                     if tracker is None:
                         if 'gt' not in sample:
