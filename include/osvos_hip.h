@@ -127,6 +127,35 @@ int osvos_conv3x3_x3_streamk(const void* x, const void* wpk3, const float* bias,
                              int Cout, int y_cs, int relu, int tile, int grid, void* sk_ws, void* stream);
 int osvos_conv3x3_x3(const void* x, const void* wpk3, const float* bias, const void* mask, void* y,
                      int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int tile, void* stream);
+/* host only, launches nothing: what the convolution launchers decide for a call -- the kernel family, its tile, the block order, the K split,
+ * stream-K and the loop form -- through the same code the launches go through (osvos_net_forward / osvos_net_backward build their calls the
+ * same way).  dtype: as osvos_conv3x3, with OSVOS_FLAG_BF16_W2 (two-piece weights) and, for OSVOS_F32_X3, the piece flags OSVOS_FLAG_X3_TWO_PIECES /
+ * OSVOS_FLAG_X3_HALF_PIECES.  flags: what the call carries (OSVOS_PLAN_*; a tensor mask is in the format of x).  tile: -1 = automatic, else a
+ * public tile id; ksplit: 0 = automatic; sk_grid: 0 = automatic.  out[OSVOS_CONV_PLAN_INTS] = {family (OSVOS_CONV_FAMILY_*), tile (row of the
+ * family's table: its tile id; two-piece: id - 40; LDS-DMA: id - 30; p64: epilogue mode 0 plain / 1 fused pool / 2 one-bit mask), block order
+ * (1: XCD-local; p64: 2 = banded), ksplit, 1 if a finalize launch follows, stream-K workgroups (0: plain grid), stream-K tile order, f32x3: 1 if
+ * the pre-split pack is read, f32x3: 1 if the pipelined K loop runs, 1 if the pooling kernel is a separate launch behind the convolution}.
+ * A call no launcher takes is the launcher's argument error. */
+#define OSVOS_PLAN_X_BF16 0x1
+#define OSVOS_PLAN_Y_BF16 0x2
+#define OSVOS_PLAN_Y_F32 0x4
+#define OSVOS_PLAN_RELU 0x8
+#define OSVOS_PLAN_MASK 0x10        /* a ReLU mask as a tensor */
+#define OSVOS_PLAN_MASK_BITS 0x20   /* ... as one bit per element */
+#define OSVOS_PLAN_Y_BITS 0x40      /* the result's sign bits are written */
+#define OSVOS_PLAN_POOL 0x80        /* the max-pool of the result is asked of the same call */
+#define OSVOS_PLAN_POOL_CODE 0x100
+#define OSVOS_PLAN_PART_WS 0x200    /* a partial-sum workspace: the launch may be cut along K */
+#define OSVOS_PLAN_SK_WS 0x400      /* a stream-K workspace */
+#define OSVOS_PLAN_WPK3 0x800       /* f32x3: the pre-split pack (beside the fp32 pack) */
+#define OSVOS_CONV_FAMILY_F32 0
+#define OSVOS_CONV_FAMILY_F32X3 1
+#define OSVOS_CONV_FAMILY_BF16 2
+#define OSVOS_CONV_FAMILY_BF16_DMA 3
+#define OSVOS_CONV_FAMILY_BF16_P64 4
+#define OSVOS_CONV_FAMILY_BF16_W2 5
+#define OSVOS_CONV_PLAN_INTS 10
+int osvos_conv3x3_plan(int N, int H, int W, int Cin, int Cout, int y_cs, int dtype, int flags, int tile, int ksplit, int sk_grid, int* out);
 /* same convolution cut into `ksplit` parts along K = 9*Cin (0 = automatic, 1..8): layers too small to balance over
  * 256 CUs (conv4_x, conv5_x at batch 1) get more, shorter workgroups; partial sums go to part_ws
  * (osvos_conv3x3_splitk_ws_bytes) and a second kernel applies bias / ReLU / mask.  fp32 only. */

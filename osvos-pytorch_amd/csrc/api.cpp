@@ -28,6 +28,39 @@ int osvos_wgrad_dispatch(const WgradCall& c, int dtype) {
   return r;
 }
 
+// Which convolution family takes the launch (kernels.h): by dtype, by the public tile id and by what the call carries.  Edits the call it is
+// handed into the one the family's launcher takes
+struct ConvEntry {
+  int (*launch)(const ConvCall&);
+  int (*plan)(const ConvCall&, ConvPlan*);
+};
+static const ConvEntry& conv_family(ConvCall& c, int dtype) {
+  static const ConvEntry f32 = {osvos_conv3x3_f32, osvos_conv3x3_f32_plan}, f32x3 = {osvos_conv3x3_f32x3, osvos_conv3x3_f32x3_plan},
+                         bf16 = {osvos_conv3x3_bf16mfma, osvos_conv3x3_bf16mfma_plan};
+  if (dtype == OSVOS_F32_BF16MFMA) return bf16;
+  // f32x3: the same fp32 problem on the bf16 matrix pipe with three-way split operands (conv3x3_f32x3.hip).  Public tile ids 200 + t force its
+  // tile t whatever the dtype (tests, tuning); dtype OSVOS_F32_X3 without a tile = automatic, in the f32x3 arithmetic where it applies (round 4:
+  // the arithmetic is a per-call argument of the ABI, not a process-wide mode) -- also for launches cut along K (part_ws)
+  if (c.tile >= 200) {
+    c.tile -= 200;
+    return f32x3;
+  }
+  if (dtype == OSVOS_F32_X3 && c.tile < 0 && osvos_conv3x3_f32x3_applicable(c.Cin, c.Cout, c.y_cs)) {
+    // (with a pre-split pack the fp32 pack of the layer is not even built -- osvos_net_pack -- so it is not handed over either)
+    if (!osvos_x3_presplit()) c.wpk3 = nullptr;
+    if (c.wpk3 != nullptr) c.wpk = nullptr;
+    return f32x3;
+  }
+  // exact fp32.  Launches may be cut along K (split-K, partial sums in c.part_ws) when the layer is too small to balance across 256 CUs; fused
+  // epilogues, bits and stream-K exist in the f32x3 / bf16 families only (net.cpp's fuse_pool() etc. say when a caller may ask for them) and the
+  // exact kernels ignore them
+  return f32;
+}
+int osvos_conv3x3_dispatch(const ConvCall& c0, int dtype) {
+  ConvCall c = c0;
+  return conv_family(c, dtype).launch(c);
+}
+
 extern "C" {
 
 int osvos_nchw_to_nhwc(const float* src, void* dst, int N, int C, int H, int W, int cpad, int dtype, void* stream) {
@@ -106,10 +139,40 @@ static WgradCall wgrad_call(const void* x, const void* dy, int bf16, void* ws, f
 int osvos_conv3x3(const void* x, const void* wpk, const float* bias, const void* mask, void* y,
                   int N, int H, int W, int Cin, int Cout, int y_cs, int relu, int dtype, int tile, void* stream) {
   NEED_F32(dtype, "conv3x3");
-  const ConvCall c = conv_call(x, wpk, bias, mask, y, N, H, W, Cin, Cout, y_cs, relu, tile, stream);
-  if (dtype == OSVOS_F32_BF16MFMA) return osvos_conv3x3_bf16mfma(c);
-  if (dtype == OSVOS_F32_X3 && tile < 0 && osvos_conv3x3_f32x3_applicable(Cin, Cout, y_cs)) return osvos_conv3x3_f32x3(c);
-  return osvos_conv3x3_f32(c);
+  return osvos_conv3x3_dispatch(conv_call(x, wpk, bias, mask, y, N, H, W, Cin, Cout, y_cs, relu, tile, stream), dtype);
+}
+
+// host only: what osvos_conv3x3_dispatch decides for a call of this shape that carries what `flags` says (launches nothing, reads no tensor)
+int osvos_conv3x3_plan(int N, int H, int W, int Cin, int Cout, int y_cs, int dtype_, int flags, int tile, int ksplit, int sk_grid, int* out) {
+  OSVOS_ARG_CHECK(out != nullptr, "conv3x3_plan: null result array");
+  const int dtype = dtype_ & 0xff;
+  NEED_F32(dtype, "conv3x3_plan");
+  OSVOS_ARG_CHECK(!(dtype_ & OSVOS_FLAG_BF16_W2) || dtype == OSVOS_F32_BF16MFMA, "conv3x3_plan: OSVOS_FLAG_BF16_W2 needs dtype OSVOS_F32_BF16MFMA (got dtype %d)", dtype);
+  static char here[8];      // any non-null address stands for a tensor the call carries: no launcher's choose() reads through one
+  void* const some = here;
+  ConvCall c;
+  c.N = N; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.y_cs = y_cs; c.tile = tile; c.ksplit = ksplit; c.sk_grid = sk_grid;
+  c.x = some; c.x_bf16 = (flags & OSVOS_PLAN_X_BF16) != 0;
+  c.wpk = some;
+  if (flags & OSVOS_PLAN_WPK3) c.wpk3 = some;
+  if (dtype_ & OSVOS_FLAG_BF16_W2) { c.w_pieces = 2; c.w_lo = osvos_wpack_bytes(Cout, Cin, OSVOS_F32_BF16MFMA); }
+  c.pieces = dtype != OSVOS_F32_X3 ? 3 : (dtype_ & OSVOS_FLAG_X3_HALF_PIECES) ? 22 : (dtype_ & OSVOS_FLAG_X3_TWO_PIECES) ? 2 : 3;
+  c.relu = (flags & OSVOS_PLAN_RELU) != 0;
+  if (flags & OSVOS_PLAN_Y_F32) c.y = reinterpret_cast<float*>(some);
+  if (flags & OSVOS_PLAN_Y_BF16) c.y_bf16 = some;
+  if (flags & OSVOS_PLAN_MASK) c.mask = some;
+  c.mask_bf16 = (flags & OSVOS_PLAN_MASK) && c.x_bf16;
+  if (flags & OSVOS_PLAN_MASK_BITS) c.mask_bits = reinterpret_cast<const unsigned*>(some);
+  if (flags & OSVOS_PLAN_Y_BITS) c.y_bits = reinterpret_cast<unsigned*>(some);
+  if (flags & OSVOS_PLAN_POOL) { c.pooled = reinterpret_cast<float*>(some); c.pooled_bf16 = some; }
+  if (flags & OSVOS_PLAN_POOL_CODE) c.pool_code = some;
+  if (flags & OSVOS_PLAN_PART_WS) c.part_ws = some;
+  if (flags & OSVOS_PLAN_SK_WS) c.sk_ws = some;
+  ConvPlan p;
+  if (conv_family(c, dtype).plan(c, &p)) return -1;
+  const int v[OSVOS_CONV_PLAN_INTS] = {p.family, p.tile, p.map, p.ksplit, p.ksplit > 1, p.sk_grid, p.sk_order, p.presplit, p.pipe, p.pool_after};
+  for (int k = 0; k < OSVOS_CONV_PLAN_INTS; ++k) out[k] = v[k];
+  return 0;
 }
 
 int osvos_conv3x3_f32x3_tiles(void) { return osvos_conv3x3_f32x3_num_tiles(); }
@@ -207,9 +270,9 @@ int osvos_conv3x3_splitk(const void* x, const void* wpk, const float* bias, cons
                          void* part_ws, void* stream) {
   OSVOS_ARG_CHECK(dtype == OSVOS_F32 || dtype == OSVOS_F32_X3, "conv3x3_splitk: fp32 only (dtype %d)", dtype);
   OSVOS_ARG_CHECK(part_ws != nullptr && ksplit >= 0 && ksplit <= 8, "conv3x3_splitk: bad ksplit / workspace");
-  ConvCall c = conv_call(x, wpk, bias, mask, y, N, H, W, Cin, Cout, y_cs, relu, (dtype == OSVOS_F32_X3 && tile < 0) ? -2 : tile, stream);
+  ConvCall c = conv_call(x, wpk, bias, mask, y, N, H, W, Cin, Cout, y_cs, relu, tile, stream);
   c.ksplit = ksplit; c.part_ws = part_ws;
-  return osvos_conv3x3_f32(c);
+  return osvos_conv3x3_dispatch(c, dtype);
 }
 
 size_t osvos_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int dtype) {

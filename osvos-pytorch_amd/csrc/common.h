@@ -1,6 +1,7 @@
 // Internal helpers shared by the HIP translation units of libosvos_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -52,6 +53,18 @@ static inline int osvos_cu_count() {
     c = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, osvos_current_device()) == hipSuccess && v > 0) ? v : 256;
   }
   return c;
+}
+// a kernel's dynamic-LDS limit, raised once per device (hipFuncSetAttribute is per device).  Two host threads that launch for the first time
+// may both set it (the same value); neither launches before it is set
+template <auto Kernel>
+static inline int osvos_set_dyn_lds_once(size_t bytes) {
+  static std::atomic<bool> done[OSVOS_MAX_DEVICES];
+  std::atomic<bool>& d = done[osvos_current_device()];
+  if (!d.load(std::memory_order_acquire)) {
+    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    d.store(true, std::memory_order_release);
+  }
+  return 0;
 }
 // integer environment knob, read once per process (tuning / test switches must not cost a getenv per launch)
 #define OSVOS_ENV_INT(var, name, dflt) static const int var = [] { const char* e_ = getenv(name); return e_ ? atoi(e_) : (dflt); }()

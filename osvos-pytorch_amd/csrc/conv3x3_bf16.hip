@@ -464,13 +464,7 @@ template <class C, int XB = 0, int WP = 1>
 int launch_cfg(const ConvArgsB& a0, hipStream_t stream) {
   static_assert(lds_bytes<C, WP>() <= 160 * 1024, "LDS budget of a CU");
   constexpr size_t LDS = lds_bytes<C, WP>();
-  static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};      // hipFuncSetAttribute is per device
-  bool& attr_set = attr_set_dev[osvos_current_device()];
-  if (!attr_set) {
-    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_bf16_kernel<C, XB, WP>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-    attr_set = true;
-  }
+  if (int rc = osvos_set_dyn_lds_once<&conv3x3_bf16_kernel<C, XB, WP>>(LDS)) return rc;
   ConvArgsB a = a0;
   a.tiles_x = ceil_div(a.W, C::TW);
   a.tiles_y = ceil_div(a.H, C::TH);
@@ -484,6 +478,16 @@ int launch_cfg(const ConvArgsB& a0, hipStream_t stream) {
 }
 
 struct TileInfoB { int tw, th, bn, wm, wn; size_t lds; };
+// A tile table: ONE list of tile types, from which the info rows and -- per activation format XB -- the launchers are expanded.  (The launchers
+// are a column per XB and not two pointers in a row: the kernels land in the code object in the order their launchers are first named, and the
+// launcher below names them per weight-piece count and activation format, which keeps that order from edit to edit.)
+template <int WP, class... C>
+struct TileSet {
+  static constexpr int N = sizeof...(C);
+  static constexpr TileInfoB info[N] = {TileInfoB{C::TW, C::TH, C::BN, C::WM, C::WN, C::LDS_BYTES}...};
+  template <int XB>
+  static constexpr int (*launch[N])(const ConvArgsB&, hipStream_t) = {&launch_cfg<C, XB, WP>...};
+};
 
 //                 RBW TBX TBY NB WGM WGN
 using B0 = CfgB<32, 1, 8, 4, 2, 2>;   // 256 px x 128 co, 4x2 accumulators per wave
@@ -502,11 +506,10 @@ using B11 = CfgB<16, 1, 8, 2, 2, 2, 1, 1, 4>;  // B1 as a 16 x 16 pixel tile
 // (B6 on 16-channel chunks with three workgroups per CU, tried for the K = 64 input gradient: 279 against 276 us at batch 12 -- not kept)
 // (tile ids in the round-1 profile files predate a clean-up: 20 -> 8, 23 -> 9, 28 -> 10, 29 -> 11; the 8-wave, row-re-use and
 //  interleaved-load variants 8-19 / 21-22 / 24-27 of those files were measured, lost, and are gone)
-constexpr int kNumTilesB = 12;
-template <class C>
-constexpr TileInfoB infoB() { return TileInfoB{C::TW, C::TH, C::BN, C::WM, C::WN, C::LDS_BYTES}; }
-const TileInfoB kTilesB[kNumTilesB] = {infoB<B0>(), infoB<B1>(), infoB<B2>(), infoB<B3>(), infoB<B4>(), infoB<B5>(), infoB<B6>(), infoB<B7>(),
-                                       infoB<B8>(), infoB<B9>(), infoB<B10>(), infoB<B11>()};
+using TilesB = TileSet<1, B0, B1, B2, B3, B4, B5, B6, B7, B8, B9, B10, B11>;
+constexpr const TileInfoB* kTilesB = TilesB::info;
+constexpr int kNumTilesB = TilesB::N;
+constexpr int kDmaFirst = 30, kP64Tile = 38;      // public ids of the LDS-DMA variants (conv3x3_bf16_dma.hip) and of the p64 kernel (conv3x3_bf16_p64.hip)
 
 // Measured (profiles/r01_tune_bf16_*.txt): with >= 128 couts the 256 px x 128 co tile on 16-channel chunks (B8: 4x2
 // accumulators per wave, two workgroups per CU) moves the fewest bytes per MFMA and wins whenever it yields enough
@@ -558,8 +561,9 @@ using W2 = CfgB<32, 1, 8, 2, 2, 2, 1, 2, 2>;
 using W3 = CfgB<32, 1, 8, 1, 4, 1, 1, 2, 2>;
 using W4 = CfgB<16, 1, 4, 2, 2, 2, 1, 2, 2>;
 using W5 = CfgB<8, 1, 2, 2, 2, 2, 1, 2, 2>;
-constexpr int kW2First = 40, kNumTilesW2 = 6;
-const TileInfoB kTilesW2[kNumTilesW2] = {infoB<W0>(), infoB<W1>(), infoB<W2>(), infoB<W3>(), infoB<W4>(), infoB<W5>()};
+using TilesW2 = TileSet<2, W0, W1, W2, W3, W4, W5>;
+constexpr const TileInfoB* kTilesW2 = TilesW2::info;
+constexpr int kW2First = 40, kNumTilesW2 = TilesW2::N;
 inline bool is_w2_tile(int t) { return t >= kW2First && t < kW2First + kNumTilesW2; }
 
 // the single-piece rule's shape classes with the two-piece tiles: B9 / B1 / B8 -> 42, B6 -> 43, B5 -> 44, B7 -> 45.  Measured at batch 12, 854x480
@@ -577,6 +581,94 @@ int pick_tile_w2(int N, int H, int W, int CoutP, int Cin) {
     if (tiles(order[k]) >= 400 || k == 2) return order[k];
   }
   return 45;
+}
+
+// the bf16 family's decisions for one call: checks, the tile and map rule of the pack's piece count, the hand-off to the LDS-DMA and p64 kernels
+int choose(const ConvCall& c, ConvPlan* p) {
+  const void *const mask = c.mask, *const ybf = c.y_bf16, *const pooled_bf16 = c.pooled_bf16;
+  const unsigned *const mask_bits = c.mask_bits, *const y_bits = c.y_bits;
+  const int xb = c.x_bf16, wp = c.w_pieces, N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cout = c.Cout, y_cs = c.y_cs, relu = c.relu;
+  const int CinP = (Cin + 31) / 32 * 32, CoutP = osvos_cout_pad(Cout);
+  int tile = c.tile;
+  OSVOS_ARG_CHECK(c.pool_code == nullptr || pooled_bf16 != nullptr, "conv3x3 bf16: pool code bytes without a pooled result");
+  OSVOS_ARG_CHECK(wp == 1 || wp == 2, "conv3x3 bf16: %d weight pieces (1 or 2)", wp);
+  OSVOS_ARG_CHECK(pooled_bf16 == nullptr || (ybf != nullptr && relu && mask == nullptr && mask_bits == nullptr && Cout % 8 == 0 && y_cs == Cout),
+                  "conv3x3 bf16: the fused forward pool needs a bf16 result, ReLU, no mask and a dense Cout %% 8 == 0 (Cout %d, stride %d)", Cout, y_cs);
+  OSVOS_ARG_CHECK(c.x && c.wpk && (c.y || ybf), "conv3x3 bf16: null pointer");
+  OSVOS_ARG_CHECK((mask_bits == nullptr && y_bits == nullptr) || (Cout % 32 == 0 && y_cs == Cout), "conv3x3 bf16: one-bit masks need Cout %% 32 == 0 and a dense result (Cout %d, stride %d)", Cout, y_cs);
+  OSVOS_ARG_CHECK((Cout % 4 == 0 && y_cs % 4 == 0) || (c.y != nullptr && !(mask && c.mask_bf16)),
+                  "conv3x3 bf16: ragged channel counts (Cout %d, stride %d) support fp32 outputs and masks only", Cout, y_cs);
+  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3 bf16: bad shape");
+  OSVOS_ARG_CHECK(Cin % 8 == 0, "conv3x3 bf16: Cin (%d) must be a multiple of 8", Cin);
+  OSVOS_ARG_CHECK(y_cs >= Cout, "conv3x3 bf16: y channel stride %d < Cout %d", y_cs, Cout);
+  OSVOS_ARG_CHECK((long)H * W * Cin < (1L << 29), "conv3x3 bf16: image too large for 31-bit byte offsets");
+  OSVOS_ARG_CHECK((long)H * W * y_cs < (1L << 29), "conv3x3 bf16: output image too large for 31-bit byte offsets");
+  OSVOS_ARG_CHECK(ybf == nullptr || (Cout % 8 == 0 && y_cs % 8 == 0), "conv3x3 bf16: the bf16 output copy needs Cout and y_cs multiples of 8");
+  *p = ConvPlan();
+  // A pack and the kernel that reads it must agree on the number of weight pieces: the two-piece tiles (40-45) exist for two-piece packs only, and no
+  // other tile (register-staged 0-11, LDS-DMA 30-37, persistent 38) may be handed one -- they would read the hi plane and silently drop the lo one.
+  if (wp == 2) {
+    const size_t plane = (size_t)9 * CinP * CoutP * 2;
+    OSVOS_ARG_CHECK(c.w_lo >= plane && c.w_lo + plane < (1UL << 31), "conv3x3 bf16w2: lo plane offset %zu (plane %zu bytes, 31-bit offsets)", c.w_lo, plane);
+    if (tile < 0) {
+      OSVOS_ENV_INT(env_tile_w2, "OSVOS_CONV_TILE_W2", -1);
+      tile = env_tile_w2 >= 0 ? env_tile_w2 : pick_tile_w2(N, H, W, CoutP, Cin);
+      if (env_tile_w2 < 0 && (double)H * W * Cin * 4 > 9.0 * Cin * CoutP * 2 * 2) tile += 100;      // (the single-piece map rule, both planes)
+    }
+    p->map = tile >= 100 ? 1 : 0;
+    tile %= 100;
+    OSVOS_ARG_CHECK(is_w2_tile(tile), "conv3x3 bf16w2: tile %d is a single-piece kernel; two-piece packs need tiles %d-%d", tile, kW2First, kW2First + kNumTilesW2 - 1);
+    p->family = CONV_BF16_W2;
+    p->tile = tile - kW2First;
+    p->pool_after = pooled_bf16 != nullptr && !(xb && tile != 45);      // waves without whole windows / fp32 staging: separate pooling launch, as single-piece
+    return 0;
+  }
+  OSVOS_ARG_CHECK(!is_w2_tile(tile % 100), "conv3x3 bf16: tile %d needs a two-piece (bf16w2) pack", tile % 100);
+  if (tile < 0) {
+    OSVOS_ENV_INT(env_tile, "OSVOS_CONV_TILE_BF16", -1);
+    const bool env = env_tile >= 0;
+    tile = env ? env_tile : pick_tile_b(N, H, W, CoutP, Cin);
+    if (!env && !xb && tile == 10) tile = 8;     // (the 16 x 16 form spills with fp32 staging registers)
+    // bf16 activations, deep layers (K = 9 x 512): the LDS-DMA staged 512 px x 128 co kernel wins when it still fills the chip
+    // (conv4_x 0.355 -> 0.331 ms, conv5_x 0.117 -> 0.098 ms at batch 12)
+    OSVOS_ENV_INT(dma_min_cin, "OSVOS_DMA_MIN_CIN", kDmaMinCin);
+    OSVOS_ENV_INT(dma_tile, "OSVOS_DMA_TILE", kDmaTile);
+    // (grid threshold 256 -> 128 in round 5: at batch 12 conv5_x's 192 DMA workgroups still beat the register-staged tile, 0.100-0.104 vs 0.108 ms per
+    //  launch and +0.4-0.8 % on configs[2], profiles/r05_ab_small.txt; the persistent DMA tile 35 and "DMA only for Cout >= 512" measured -0.6 % / +0.2 %)
+    if (!env && xb && Cin >= dma_min_cin && CoutP >= 128 && osvos_conv3x3_bf16_dma_applicable(Cin, Cout, y_cs) &&
+        (long)N * ceil_div(H, 16) * ceil_div(W, 32) * ceil_div(CoutP, 128) >= 128)
+      tile = dma_tile;
+    // Cin = 64, bf16 in / out, FORWARD launches with enough 512-pixel tiles to give every CU several: the persistent resident-filter kernel with the
+    // deferred + skewed packed epilogue (conv3x3_bf16_p64.hip; round 6): 6-10 % faster at op level at batch 12 (conv1_2 + pool 0.524 vs 0.582 ms,
+    // conv2_1 0.207 vs 0.226), step level within noise (profiles/r06_p64_diagnosis.txt).  NOT the data gradient (17 % faster alone, but one 160 KB / 256-VGPR
+    // workgroup per CU cannot share a CU with the weight-gradient stream the way tile 9's three small workgroups do).  OSVOS_P64_MIN_TILES: tiles per
+    // launch from which it is taken (0 = never); OSVOS_P64_DGRAD=1 takes it for masked launches too.
+    OSVOS_ENV_INT(p64_min, "OSVOS_P64_MIN_TILES", 1024);
+    OSVOS_ENV_INT(p64_dgrad, "OSVOS_P64_DGRAD", 0);
+    if (!env && xb && p64_min > 0 && (p64_dgrad || mask_bits == nullptr) && (long)N * ceil_div(H, 16) * ceil_div(W, 32) * ceil_div(Cout, 64) >= p64_min &&
+        osvos_conv3x3_bf16_p64_applicable(c))
+      tile = kP64Tile;
+    // (round 5 re-check at step level, configs[2]: always / never / 3x / 10x this threshold all within +-0.3 % -- unlike the f32x3 rule)
+    if (!env && (double)H * W * Cin * 4 > 9.0 * Cin * CoutP * 2) tile += 100;
+  }
+  p->map = tile >= 100 ? 1 : 0;
+  tile %= 100;
+  if (xb && tile == kP64Tile) {      // Cin = 64: persistent, resident filter, deferred + skewed packed epilogue (conv3x3_bf16_p64.hip)
+    OSVOS_ARG_CHECK(osvos_conv3x3_bf16_p64_applicable(c),
+                    "conv3x3 bf16: tile 38 needs Cin = 64, bf16 in / out only, no full-tensor mask, sign bits only with ReLU (Cin %d, Cout %d)", Cin, Cout);
+    return osvos_conv3x3_bf16_p64_plan(c, p);
+  }
+  if (xb && tile >= kDmaFirst && tile < kDmaFirst + osvos_conv3x3_bf16_dma_num_variants()) {      // LDS-DMA staged kernel (its fused pool writes the code bytes too: round 6)
+    OSVOS_ARG_CHECK(osvos_conv3x3_bf16_dma_applicable(Cin, Cout, y_cs), "conv3x3 bf16: tile %d (DMA staging) needs Cin %% 16 == 0, Cout, y_cs %% 8 == 0", tile);
+    OSVOS_ARG_CHECK(tile < 36 || Cin == 64, "conv3x3 bf16: tile %d (resident filter) is built for Cin = 64 (got %d)", tile, Cin);
+    p->tile = tile - kDmaFirst;
+    return osvos_conv3x3_bf16_dma_plan(c, p);
+  }
+  OSVOS_ARG_CHECK(tile >= 0 && tile < kNumTilesB, "conv3x3 bf16: unknown tile config %d", tile);
+  p->family = CONV_BF16;
+  p->tile = tile;
+  p->pool_after = pooled_bf16 != nullptr && !(xb && tile != 7);      // a tile whose waves do not hold whole windows: separate pooling launch
+  return 0;
 }
 
 // wpk[((tap*CG + cg)*CoutP + co)*8 + e] = bf16(W[co][8cg+e][tap])   (zero padded)
@@ -702,159 +794,31 @@ extern "C" void osvos_debug_set_conv_prof(void* p) { g_conv_prof = (unsigned lon
 #define OSVOS_CONV_PROF_PTR nullptr
 #endif
 
-// the convolution on the chosen tile without its fused pool, then the pooling kernel
-static int conv_then_pool(const ConvCall& c, int tile) {
-  ConvCall cc = c;
-  cc.pooled_bf16 = nullptr; cc.pool_code = nullptr; cc.tile = tile;
-  const int rc = osvos_conv3x3_bf16mfma(cc);
-  return rc ? rc : osvos_maxpool2x2_bf16_code(c.y_bf16, c.pooled_bf16, c.pool_code, c.N, c.H, c.W, c.Cout, c.stream);
-}
+int osvos_conv3x3_bf16mfma_plan(const ConvCall& c, ConvPlan* p) { return choose(c, p); }
 
 int osvos_conv3x3_bf16mfma(const ConvCall& c) {
-  const void *x = c.x, *wpk = c.wpk, *mask = c.mask;
-  const float* const bias = c.bias;
-  const unsigned* const mask_bits = c.mask_bits;
-  float* const y = c.y;
-  void *ybf = c.y_bf16, *pooled_bf16 = c.pooled_bf16, *pool_code = c.pool_code;
-  unsigned* const y_bits = c.y_bits;
-  const int xb = c.x_bf16, mask_bf16 = c.mask_bf16, wp = c.w_pieces, N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cout = c.Cout, y_cs = c.y_cs, relu = c.relu;
-  const size_t w_lo = c.w_lo;
-  int tile = c.tile;
-  hipStream_t stream = c.stream;
-  OSVOS_ARG_CHECK(pool_code == nullptr || pooled_bf16 != nullptr, "conv3x3 bf16: pool code bytes without a pooled result");
-  OSVOS_ARG_CHECK(wp == 1 || wp == 2, "conv3x3 bf16: %d weight pieces (1 or 2)", wp);
-  OSVOS_ARG_CHECK(pooled_bf16 == nullptr || (ybf != nullptr && relu && mask == nullptr && mask_bits == nullptr && Cout % 8 == 0 && y_cs == Cout),
-                  "conv3x3 bf16: the fused forward pool needs a bf16 result, ReLU, no mask and a dense Cout %% 8 == 0 (Cout %d, stride %d)", Cout, y_cs);
-  OSVOS_ARG_CHECK(x && wpk && (y || ybf), "conv3x3 bf16: null pointer");
-  OSVOS_ARG_CHECK((mask_bits == nullptr && y_bits == nullptr) || (Cout % 32 == 0 && y_cs == Cout), "conv3x3 bf16: one-bit masks need Cout %% 32 == 0 and a dense result (Cout %d, stride %d)", Cout, y_cs);
-  OSVOS_ARG_CHECK((Cout % 4 == 0 && y_cs % 4 == 0) || (y != nullptr && !(mask && mask_bf16)),
-                  "conv3x3 bf16: ragged channel counts (Cout %d, stride %d) support fp32 outputs and masks only", Cout, y_cs);
-  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3 bf16: bad shape");
-  OSVOS_ARG_CHECK(Cin % 8 == 0, "conv3x3 bf16: Cin (%d) must be a multiple of 8", Cin);
-  OSVOS_ARG_CHECK(y_cs >= Cout, "conv3x3 bf16: y channel stride %d < Cout %d", y_cs, Cout);
-  OSVOS_ARG_CHECK((long)H * W * Cin < (1L << 29), "conv3x3 bf16: image too large for 31-bit byte offsets");
-  OSVOS_ARG_CHECK((long)H * W * y_cs < (1L << 29), "conv3x3 bf16: output image too large for 31-bit byte offsets");
-  OSVOS_ARG_CHECK(ybf == nullptr || (Cout % 8 == 0 && y_cs % 8 == 0), "conv3x3 bf16: the bf16 output copy needs Cout and y_cs multiples of 8");
+  ConvPlan p;
+  if (choose(c, &p)) return -1;
+  if (p.family == CONV_BF16_P64) return osvos_conv3x3_bf16_p64(c, p);
+  if (p.family == CONV_BF16_DMA) return osvos_conv3x3_bf16_dma(c, p);
+  const bool w2 = p.family == CONV_BF16_W2;
   ConvArgsB a;
-  a.x = x; a.wpk = reinterpret_cast<const uint4*>(wpk); a.bias = bias; a.mask = mask; a.mask_bf16 = mask_bf16 ? 1 : 0; a.y = y;
-  a.ybf = reinterpret_cast<bf16_t*>(ybf);
-  a.mask_bits = mask_bits; a.y_bits = y_bits; a.pooled = reinterpret_cast<bf16_t*>(pooled_bf16);
-  a.pool_code = reinterpret_cast<unsigned char*>(pool_code);
-  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.CinP = (Cin + 31) / 32 * 32; a.Cout = Cout; a.CoutP = osvos_cout_pad(Cout); a.y_cs = y_cs;
-  a.relu = relu;
+  a.x = c.x; a.wpk = reinterpret_cast<const uint4*>(c.wpk); a.bias = c.bias; a.mask = c.mask; a.mask_bf16 = c.mask_bf16 ? 1 : 0; a.y = c.y;
+  a.ybf = reinterpret_cast<bf16_t*>(c.y_bf16);
+  a.mask_bits = c.mask_bits; a.y_bits = c.y_bits;
+  // pool_after: the convolution on the chosen tile without its fused pool, then the pooling kernel
+  a.pooled = p.pool_after ? nullptr : reinterpret_cast<bf16_t*>(c.pooled_bf16);
+  a.pool_code = p.pool_after ? nullptr : reinterpret_cast<unsigned char*>(c.pool_code);
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cin = c.Cin; a.CinP = (c.Cin + 31) / 32 * 32; a.Cout = c.Cout; a.CoutP = osvos_cout_pad(c.Cout); a.y_cs = c.y_cs;
+  a.relu = c.relu;
   a.prof = OSVOS_CONV_PROF_PTR;
-  a.w_lo = 0;
-  // A pack and the kernel that reads it must agree on the number of weight pieces: the two-piece tiles (40-45) exist for two-piece packs only, and no
-  // other tile (register-staged 0-11, LDS-DMA 30-37, persistent 38) may be handed one -- they would read the hi plane and silently drop the lo one.
-  if (wp == 2) {
-    const size_t plane = (size_t)9 * a.CinP * a.CoutP * 2;
-    OSVOS_ARG_CHECK(w_lo >= plane && w_lo + plane < (1UL << 31), "conv3x3 bf16w2: lo plane offset %zu (plane %zu bytes, 31-bit offsets)", w_lo, plane);
-    a.w_lo = (unsigned)w_lo;
-    if (tile < 0) {
-      OSVOS_ENV_INT(env_tile_w2, "OSVOS_CONV_TILE_W2", -1);
-      tile = env_tile_w2 >= 0 ? env_tile_w2 : pick_tile_w2(N, H, W, a.CoutP, Cin);
-      if (env_tile_w2 < 0 && (double)H * W * Cin * 4 > 9.0 * Cin * a.CoutP * 2 * 2) tile += 100;      // (the single-piece map rule, both planes)
-    }
-    a.map = tile >= 100 ? 1 : 0;
-    tile %= 100;
-    OSVOS_ARG_CHECK(is_w2_tile(tile), "conv3x3 bf16w2: tile %d is a single-piece kernel; two-piece packs need tiles %d-%d", tile, kW2First, kW2First + kNumTilesW2 - 1);
-    if (a.pooled != nullptr && !(xb && tile != 45)) {      // waves without whole windows / fp32 staging: separate pooling launch, as single-piece
-      return conv_then_pool(c, tile + 100 * a.map);
-    }
-    if (xb) {
-      switch (tile) {
-        case 40: return launch_cfg<W0, 1, 2>(a, stream);
-        case 41: return launch_cfg<W1, 1, 2>(a, stream);
-        case 42: return launch_cfg<W2, 1, 2>(a, stream);
-        case 43: return launch_cfg<W3, 1, 2>(a, stream);
-        case 44: return launch_cfg<W4, 1, 2>(a, stream);
-        default: return launch_cfg<W5, 1, 2>(a, stream);
-      }
-    }
-    switch (tile) {
-      case 40: return launch_cfg<W0, 0, 2>(a, stream);
-      case 41: return launch_cfg<W1, 0, 2>(a, stream);
-      case 42: return launch_cfg<W2, 0, 2>(a, stream);
-      case 43: return launch_cfg<W3, 0, 2>(a, stream);
-      case 44: return launch_cfg<W4, 0, 2>(a, stream);
-      default: return launch_cfg<W5, 0, 2>(a, stream);
-    }
-  }
-  OSVOS_ARG_CHECK(!is_w2_tile(tile % 100), "conv3x3 bf16: tile %d needs a two-piece (bf16w2) pack", tile % 100);
-  if (tile < 0) {
-    OSVOS_ENV_INT(env_tile, "OSVOS_CONV_TILE_BF16", -1);
-    const bool env = env_tile >= 0;
-    tile = env ? env_tile : pick_tile_b(N, H, W, a.CoutP, Cin);
-    if (!env && !xb && tile == 10) tile = 8;     // (the 16 x 16 form spills with fp32 staging registers)
-    // bf16 activations, deep layers (K = 9 x 512): the LDS-DMA staged 512 px x 128 co kernel wins when it still fills the chip
-    // (conv4_x 0.355 -> 0.331 ms, conv5_x 0.117 -> 0.098 ms at batch 12)
-    static const int dma_min_cin = getenv("OSVOS_DMA_MIN_CIN") ? atoi(getenv("OSVOS_DMA_MIN_CIN")) : kDmaMinCin;
-    static const int dma_tile = getenv("OSVOS_DMA_TILE") ? atoi(getenv("OSVOS_DMA_TILE")) : kDmaTile;
-    // (grid threshold 256 -> 128 in round 5: at batch 12 conv5_x's 192 DMA workgroups still beat the register-staged tile, 0.100-0.104 vs 0.108 ms per
-    //  launch and +0.4-0.8 % on configs[2], profiles/r05_ab_small.txt; the persistent DMA tile 35 and "DMA only for Cout >= 512" measured -0.6 % / +0.2 %)
-    if (!env && xb && Cin >= dma_min_cin && a.CoutP >= 128 && osvos_conv3x3_bf16_dma_applicable(Cin, Cout, y_cs) &&
-        (long)N * ceil_div(H, 16) * ceil_div(W, 32) * ceil_div(a.CoutP, 128) >= 128)
-      tile = dma_tile;
-    // Cin = 64, bf16 in / out, FORWARD launches with enough 512-pixel tiles to give every CU several: the persistent resident-filter kernel with the
-    // deferred + skewed packed epilogue (conv3x3_bf16_p64.hip; round 6): 6-10 % faster at op level at batch 12 (conv1_2 + pool 0.524 vs 0.582 ms,
-    // conv2_1 0.207 vs 0.226), step level within noise (profiles/r06_p64_diagnosis.txt).  NOT the data gradient (17 % faster alone, but one 160 KB / 256-VGPR
-    // workgroup per CU cannot share a CU with the weight-gradient stream the way tile 9's three small workgroups do).  OSVOS_P64_MIN_TILES: tiles per
-    // launch from which it is taken (0 = never); OSVOS_P64_DGRAD=1 takes it for masked launches too.
-    OSVOS_ENV_INT(p64_min, "OSVOS_P64_MIN_TILES", 1024);
-    OSVOS_ENV_INT(p64_dgrad, "OSVOS_P64_DGRAD", 0);
-    if (!env && xb && p64_min > 0 && (p64_dgrad || mask_bits == nullptr) && (long)N * ceil_div(H, 16) * ceil_div(W, 32) * ceil_div(Cout, 64) >= p64_min &&
-        osvos_conv3x3_bf16_p64_applicable(Cin, Cout, y_cs, y != nullptr, mask != nullptr, mask_bits != nullptr, y_bits != nullptr, pooled_bf16 != nullptr, relu))
-      tile = 38;
-    // (round 5 re-check at step level, configs[2]: always / never / 3x / 10x this threshold all within +-0.3 % -- unlike the f32x3 rule)
-    if (!env && (double)H * W * Cin * 4 > 9.0 * Cin * a.CoutP * 2) tile += 100;
-  }
-  a.map = tile >= 100 ? 1 : 0;
-  tile %= 100;
-  if (xb && tile == 38) {      // Cin = 64: persistent, resident filter, deferred + skewed packed epilogue (conv3x3_bf16_p64.hip)
-    OSVOS_ARG_CHECK(osvos_conv3x3_bf16_p64_applicable(Cin, Cout, y_cs, y != nullptr, mask != nullptr, mask_bits != nullptr, y_bits != nullptr, pooled_bf16 != nullptr, relu),
-                    "conv3x3 bf16: tile 38 needs Cin = 64, bf16 in / out only, no full-tensor mask, sign bits only with ReLU (Cin %d, Cout %d)", Cin, Cout);
-    return osvos_conv3x3_bf16_p64(c, a.map);
-  }
-  if (xb && tile >= 30 && tile <= 37) {      // LDS-DMA staged kernel (its fused pool writes the code bytes too: round 6)
-    OSVOS_ARG_CHECK(osvos_conv3x3_bf16_dma_applicable(Cin, Cout, y_cs), "conv3x3 bf16: tile %d (DMA staging) needs Cin %% 16 == 0, Cout, y_cs %% 8 == 0", tile);
-    OSVOS_ARG_CHECK(tile < 36 || Cin == 64, "conv3x3 bf16: tile %d (resident filter) is built for Cin = 64 (got %d)", tile, Cin);
-    return osvos_conv3x3_bf16_dma(c, tile - 30, a.map);
-  }
-  if (a.pooled != nullptr && !(xb && tile != 7 && tile >= 0 && tile < kNumTilesB)) {      // a tile whose waves do not hold whole windows: separate pooling launch
-    return conv_then_pool(c, tile + 100 * a.map);
-  }
-  if (xb) {
-    switch (tile) {
-      case 0: return launch_cfg<B0, 1>(a, stream);
-      case 1: return launch_cfg<B1, 1>(a, stream);
-      case 2: return launch_cfg<B2, 1>(a, stream);
-      case 3: return launch_cfg<B3, 1>(a, stream);
-      case 4: return launch_cfg<B4, 1>(a, stream);
-      case 5: return launch_cfg<B5, 1>(a, stream);
-      case 6: return launch_cfg<B6, 1>(a, stream);
-      case 7: return launch_cfg<B7, 1>(a, stream);
-      case 8: return launch_cfg<B8, 1>(a, stream);
-      case 9: return launch_cfg<B9, 1>(a, stream);
-      case 10: return launch_cfg<B10, 1>(a, stream);
-      case 11: return launch_cfg<B11, 1>(a, stream);
-      default: osvos_set_error("conv3x3 bf16: unknown tile config %d", tile); return -1;
-    }
-  }
-  switch (tile) {
-    case 0: return launch_cfg<B0>(a, stream);
-    case 1: return launch_cfg<B1>(a, stream);
-    case 2: return launch_cfg<B2>(a, stream);
-    case 3: return launch_cfg<B3>(a, stream);
-    case 4: return launch_cfg<B4>(a, stream);
-    case 5: return launch_cfg<B5>(a, stream);
-    case 6: return launch_cfg<B6>(a, stream);
-    case 7: return launch_cfg<B7>(a, stream);
-    case 8: return launch_cfg<B8>(a, stream);
-    case 9: return launch_cfg<B9>(a, stream);
-    case 10: return launch_cfg<B10>(a, stream);
-    case 11: return launch_cfg<B11>(a, stream);
-    default: osvos_set_error("conv3x3 bf16: unknown tile config %d", tile); return -1;
-  }
+  a.w_lo = w2 ? (unsigned)c.w_lo : 0;
+  a.map = p.map;
+  const bool xb = c.x_bf16 != 0;
+  const auto* const launch = w2 ? (xb ? TilesW2::launch<1> : TilesW2::launch<0>) : (xb ? TilesB::launch<1> : TilesB::launch<0>);
+  const int rc = launch[p.tile](a, c.stream);
+  if (rc || !p.pool_after) return rc;
+  return osvos_maxpool2x2_bf16_code(c.y_bf16, c.pooled_bf16, c.pool_code, c.N, c.H, c.W, c.Cout, c.stream);
 }
 
 int osvos_conv3x3_bf16w2_tiles_impl(int* tiles, int max) {      // tile ids built for two-piece weights (bf16 or fp32 activations)
@@ -863,10 +827,10 @@ int osvos_conv3x3_bf16w2_tiles_impl(int* tiles, int max) {      // tile ids buil
   return n;
 }
 
-int osvos_conv3x3_bf16mfma_xb_tiles(int* tiles, int max) {      // tile ids built for bf16 activations
-  static const int t[] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 30, 31, 32, 33, 34, 35, 36, 37};      // (36, 37: Cin = 64 only)
+int osvos_conv3x3_bf16mfma_xb_tiles(int* tiles, int max) {      // tile ids built for bf16 activations: the register-staged tiles, then the LDS-DMA variants
+  const int nd = osvos_conv3x3_bf16_dma_num_variants();         // (the last two, 36 and 37: Cin = 64 only)
   int n = 0;
-  for (; n < (int)(sizeof(t) / sizeof(t[0])) && n < max; ++n) tiles[n] = t[n];
+  for (; n < kNumTilesB + nd && n < max; ++n) tiles[n] = n < kNumTilesB ? n : kDmaFirst + n - kNumTilesB;
   return n;
 }
 

@@ -430,13 +430,7 @@ int launch(const DmaArgs& a0, int persist, hipStream_t stream) {
   using C = DmaCfg<NB, WGM, CINR>;
   OSVOS_ARG_CHECK(CINR == 0 || a0.Cin == CINR, "conv3x3 bf16 dma: the resident-filter form is built for Cin = %d (got %d)", CINR, a0.Cin);
   constexpr int TH = C::TH;
-  static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};      // hipFuncSetAttribute is per device
-  bool& attr_set = attr_set_dev[osvos_current_device()];
-  if (!attr_set) {
-    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_bf16_dma_kernel<NB, WGM, CINR>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)C::LDS_BYTES));
-    attr_set = true;
-  }
+  if (int rc = osvos_set_dyn_lds_once<&conv3x3_bf16_dma_kernel<NB, WGM, CINR>>(C::LDS_BYTES)) return rc;
   DmaArgs a = a0;
   a.tiles_x = ceil_div(a.W, TW);
   a.tiles_y = ceil_div(a.H, TH);
@@ -447,14 +441,7 @@ int launch(const DmaArgs& a0, int persist, hipStream_t stream) {
   a.ntiles = (int)blocks;
   // persistent: one workgroup per CU (the LDS footprint allows no more) walks tiles b, b + G, ...; the DMA of a tile's first chunks
   // overlaps the previous tile's epilogue.  G is a multiple of 8 so that a workgroup's tiles stay on its XCD's L2.
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    OSVOS_HIP_CHECK(hipGetDevice(&dev));
-    OSVOS_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    n_cu = n_cu / 8 * 8;
-    if (n_cu < 8) n_cu = 8;
-  }
+  const int n_cu = std::max(osvos_cu_count() / 8 * 8, 8);
   // (resident filter: a workgroup keeps ONE cout tile -- map 0 needs G % nct == 0, map 1 (G / 8) % nct == 0: G a multiple of 8 nct serves both)
   const int gmul = 8 * (CINR > 0 ? a.nct : 1);
   const long gmax = (long)n_cu / gmul * gmul;
@@ -469,40 +456,50 @@ int launch(const DmaArgs& a0, int persist, hipStream_t stream) {
   return 0;
 }
 
+// the variant table (public tile id = 30 + row)
+struct DmaVariant {
+  int (*launch)(const DmaArgs&, int, hipStream_t);
+  int persist;
+};
+constexpr DmaVariant kVariants[] = {
+    {&launch<4, 2>, 0},          // 0: 256 px x 128 couts (4 waves)
+    {&launch<2, 2>, 0},          // 1: 256 px x 64 couts (4 waves)
+    {&launch<4, 4>, 0},          // 2: 512 px x 128 couts (8 waves)
+    {&launch<2, 4>, 0},          // 3: 512 px x 64 couts (8 waves)
+    {&launch<4, 2>, 1},          // 4 / 5: variants 0 / 2 as persistent workgroups (one per CU, tiles pipelined back to back)
+    {&launch<4, 4>, 1},
+    {&launch<2, 4, 64>, 1},      // 6 / 7: RESIDENT-FILTER persistent forms for Cin = 64 (512 px / 256 px x 64 couts): see the head of this file
+    {&launch<2, 2, 64>, 1}};
+constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
+
+// checks the call against the variant and the map the bf16 family's choose() put into the plan
+int choose(const ConvCall& c, ConvPlan* p) {
+  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cout = c.Cout, y_cs = c.y_cs;
+  OSVOS_ARG_CHECK(c.x && c.wpk && (c.y || c.y_bf16), "conv3x3 bf16 dma: null pointer");
+  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && osvos_conv3x3_bf16_dma_applicable(Cin, Cout, y_cs) && y_cs >= Cout,
+                  "conv3x3 bf16 dma: needs Cin %% 16 == 0, Cout %% 8 == 0, y_cs %% 8 == 0 (got %d, %d, %d)", Cin, Cout, y_cs);
+  OSVOS_ARG_CHECK((long)H * W * Cin < (1L << 29) && (long)H * W * y_cs < (1L << 29), "conv3x3 bf16 dma: image too large for 31-bit byte offsets");
+  OSVOS_ARG_CHECK(p->tile >= 0 && p->tile < kNumVariants, "conv3x3 bf16 dma: unknown variant %d", p->tile);
+  p->family = CONV_BF16_DMA;
+  p->map = p->map ? 1 : 0;
+  return 0;
+}
+
 }  // namespace
 
 bool osvos_conv3x3_bf16_dma_applicable(int Cin, int Cout, int y_cs) { return Cin % 16 == 0 && Cout % 8 == 0 && y_cs % 8 == 0; }
 
-// variant 0: 256 px x 128 couts (4 waves), 1: 256 px x 64 couts (4 waves), 2: 512 px x 128 couts (8 waves), 3: 512 px x 64 couts (8 waves),
-// 4 / 5: variants 0 / 2 as persistent workgroups (one per CU, tiles pipelined back to back);
-// map = 1: XCD-local spatial block order
-// 6 / 7: RESIDENT-FILTER persistent forms for Cin = 64 (512 px / 256 px x 64 couts): see the head of this file
-int osvos_conv3x3_bf16_dma(const ConvCall& c, int variant, int map) {
-  const void *x = c.x, *wpk = c.wpk;
-  float* const y = c.y;
-  void* const ybf = c.y_bf16;
-  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cout = c.Cout, y_cs = c.y_cs;
-  hipStream_t stream = c.stream;
-  OSVOS_ARG_CHECK(x && wpk && (y || ybf), "conv3x3 bf16 dma: null pointer");
-  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && osvos_conv3x3_bf16_dma_applicable(Cin, Cout, y_cs) && y_cs >= Cout,
-                  "conv3x3 bf16 dma: needs Cin %% 16 == 0, Cout %% 8 == 0, y_cs %% 8 == 0 (got %d, %d, %d)", Cin, Cout, y_cs);
-  OSVOS_ARG_CHECK((long)H * W * Cin < (1L << 29) && (long)H * W * y_cs < (1L << 29), "conv3x3 bf16 dma: image too large for 31-bit byte offsets");
+int osvos_conv3x3_bf16_dma_num_variants(void) { return kNumVariants; }
+int osvos_conv3x3_bf16_dma_plan(const ConvCall& c, ConvPlan* p) { return choose(c, p); }
+
+int osvos_conv3x3_bf16_dma(const ConvCall& c, const ConvPlan& p) {
   DmaArgs a;
-  a.x = reinterpret_cast<const bf16_t*>(x); a.wpk = reinterpret_cast<const uint4*>(wpk); a.bias = c.bias; a.mask = c.mask; a.mask_bf16 = c.mask_bf16 ? 1 : 0;
-  a.y = y; a.ybf = reinterpret_cast<bf16_t*>(ybf);
+  a.x = reinterpret_cast<const bf16_t*>(c.x); a.wpk = reinterpret_cast<const uint4*>(c.wpk); a.bias = c.bias; a.mask = c.mask; a.mask_bf16 = c.mask_bf16 ? 1 : 0;
+  a.y = c.y; a.ybf = reinterpret_cast<bf16_t*>(c.y_bf16);
   a.mask_bits = c.mask_bits; a.y_bits = c.y_bits; a.pooled = reinterpret_cast<bf16_t*>(c.pooled_bf16);
   a.pool_code = reinterpret_cast<unsigned char*>(c.pool_code);
-  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.CinP = (Cin + 31) / 32 * 32; a.Cout = Cout; a.CoutP = osvos_cout_pad(Cout); a.y_cs = y_cs;
-  a.relu = c.relu; a.map = map ? 1 : 0;
-  switch (variant) {
-    case 0: return launch<4, 2>(a, 0, stream);
-    case 1: return launch<2, 2>(a, 0, stream);
-    case 2: return launch<4, 4>(a, 0, stream);
-    case 3: return launch<2, 4>(a, 0, stream);
-    case 4: return launch<4, 2>(a, 1, stream);      // persistent forms of 0 and 2
-    case 5: return launch<4, 4>(a, 1, stream);
-    case 6: return launch<2, 4, 64>(a, 1, stream);  // resident 64-channel filter, persistent
-    case 7: return launch<2, 2, 64>(a, 1, stream);
-    default: osvos_set_error("conv3x3 bf16 dma: unknown variant %d", variant); return -1;
-  }
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cin = c.Cin; a.CinP = (c.Cin + 31) / 32 * 32; a.Cout = c.Cout; a.CoutP = osvos_cout_pad(c.Cout); a.y_cs = c.y_cs;
+  a.relu = c.relu; a.map = p.map;
+  const DmaVariant& v = kVariants[p.tile];
+  return v.launch(a, v.persist, c.stream);
 }

@@ -550,12 +550,7 @@ int p64_env_grid() {      // (outside the template: read once per process, not o
 
 template <int MODE>
 int launch(const P64Args& a0, hipStream_t stream) {
-  static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};
-  bool& attr_set = attr_set_dev[osvos_current_device()];
-  if (!attr_set) {
-    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_bf16_p64_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
-    attr_set = true;
-  }
+  if (int rc = osvos_set_dyn_lds_once<&conv3x3_bf16_p64_kernel<MODE>>(LDS_BYTES)) return rc;
   P64Args a = a0;
   a.tiles_x = ceil_div(a.W, TW);
   a.tiles_y = ceil_div(a.H, TH);
@@ -592,37 +587,40 @@ extern "C" void osvos_debug_set_p64_prof(void* p) { g_p64_prof = (unsigned long 
 #endif
 
 // what the kernel takes: Cin = 64, bf16 in / out only (no fp32 result, no full-tensor mask), dense 8-channel-aligned result, sign bits only with ReLU
-bool osvos_conv3x3_bf16_p64_applicable(int Cin, int Cout, int y_cs, bool has_y_f32, bool has_tensor_mask, bool has_mask_bits, bool has_y_bits, bool has_pool,
-                                       int relu) {
-  if (Cin != 64 || Cout % 8 != 0 || y_cs % 8 != 0 || has_y_f32 || has_tensor_mask) return false;
-  if ((has_mask_bits || has_y_bits) && (Cout % 32 != 0 || y_cs != Cout)) return false;
-  if (has_y_bits && !relu) return false;
-  if (has_pool && (!relu || has_mask_bits || has_y_bits || y_cs != Cout)) return false;
+bool osvos_conv3x3_bf16_p64_applicable(const ConvCall& c) {
+  const bool has_mask_bits = c.mask_bits != nullptr, has_y_bits = c.y_bits != nullptr, has_pool = c.pooled_bf16 != nullptr;
+  if (c.Cin != 64 || c.Cout % 8 != 0 || c.y_cs % 8 != 0 || c.y != nullptr || c.mask != nullptr) return false;
+  if ((has_mask_bits || has_y_bits) && (c.Cout % 32 != 0 || c.y_cs != c.Cout)) return false;
+  if (has_y_bits && !c.relu) return false;
+  if (has_pool && (!c.relu || has_mask_bits || has_y_bits || c.y_cs != c.Cout)) return false;
   if (has_mask_bits && has_y_bits) return false;
   return true;
 }
 
-int osvos_conv3x3_bf16_p64(const ConvCall& c, int map) {
-  const void *x = c.x, *wpk = c.wpk;
-  const unsigned* const mask_bits = c.mask_bits;
-  void *ybf = c.y_bf16, *pooled_bf16 = c.pooled_bf16, *pool_code = c.pool_code;
-  unsigned* const y_bits = c.y_bits;
-  const int N = c.N, H = c.H, W = c.W, Cout = c.Cout, y_cs = c.y_cs, relu = c.relu;
-  hipStream_t stream = c.stream;
-  OSVOS_ARG_CHECK(x && wpk && ybf, "conv3x3 bf16 p64: null pointer");
-  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && y_cs >= Cout, "conv3x3 bf16 p64: bad shape");
-  OSVOS_ARG_CHECK(osvos_conv3x3_bf16_p64_applicable(64, Cout, y_cs, false, false, mask_bits != nullptr, y_bits != nullptr, pooled_bf16 != nullptr, relu),
-                  "conv3x3 bf16 p64: unsupported epilogue combination (Cout %d, stride %d, relu %d)", Cout, y_cs, relu);
-  OSVOS_ARG_CHECK(pool_code == nullptr || pooled_bf16 != nullptr, "conv3x3 bf16 p64: pool code bytes without a pooled result");
-  OSVOS_ARG_CHECK((long)H * W * 64 < (1L << 29) && (long)H * W * y_cs < (1L << 29), "conv3x3 bf16 p64: image too large for 31-bit byte offsets");
-  P64Args a;
-  a.x = reinterpret_cast<const bf16_t*>(x); a.wpk = reinterpret_cast<const uint4*>(wpk); a.bias = c.bias; a.ybf = reinterpret_cast<bf16_t*>(ybf);
-  a.N = N; a.H = H; a.W = W; a.Cout = Cout; a.CoutP = osvos_cout_pad(Cout); a.y_cs = y_cs;
+// checks the call and completes the plan the bf16 family's choose() started (its map) with the epilogue mode
+static int choose(const ConvCall& c, ConvPlan* p) {
+  OSVOS_ARG_CHECK(c.x && c.wpk && c.y_bf16, "conv3x3 bf16 p64: null pointer");
+  OSVOS_ARG_CHECK(c.N > 0 && c.H > 0 && c.W > 0 && c.y_cs >= c.Cout, "conv3x3 bf16 p64: bad shape");
+  OSVOS_ARG_CHECK(osvos_conv3x3_bf16_p64_applicable(c), "conv3x3 bf16 p64: unsupported epilogue combination (Cout %d, stride %d, relu %d)", c.Cout, c.y_cs, c.relu);
+  OSVOS_ARG_CHECK(c.pool_code == nullptr || c.pooled_bf16 != nullptr, "conv3x3 bf16 p64: pool code bytes without a pooled result");
+  OSVOS_ARG_CHECK((long)c.H * c.W * 64 < (1L << 29) && (long)c.H * c.W * c.y_cs < (1L << 29), "conv3x3 bf16 p64: image too large for 31-bit byte offsets");
   OSVOS_ENV_INT(band, "OSVOS_P64_BAND", 1);      // 0: XCD-local requests keep the interleaved map 1
-  a.relu = relu; a.map = map ? (band ? 2 : 1) : 0;
-  a.mask_bits = mask_bits; a.y_bits = y_bits; a.pooled = reinterpret_cast<bf16_t*>(pooled_bf16); a.pool_code = reinterpret_cast<unsigned char*>(pool_code);
+  p->family = CONV_BF16_P64;
+  p->tile = c.pooled_bf16 != nullptr ? 1 : (c.mask_bits != nullptr ? 2 : 0);
+  p->map = p->map ? (band ? 2 : 1) : 0;
+  return 0;
+}
+
+int osvos_conv3x3_bf16_p64_plan(const ConvCall& c, ConvPlan* p) { return choose(c, p); }
+
+int osvos_conv3x3_bf16_p64(const ConvCall& c, const ConvPlan& p) {
+  P64Args a;
+  a.x = reinterpret_cast<const bf16_t*>(c.x); a.wpk = reinterpret_cast<const uint4*>(c.wpk); a.bias = c.bias; a.ybf = reinterpret_cast<bf16_t*>(c.y_bf16);
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cout = c.Cout; a.CoutP = osvos_cout_pad(c.Cout); a.y_cs = c.y_cs;
+  a.relu = c.relu; a.map = p.map;
+  a.mask_bits = c.mask_bits; a.y_bits = c.y_bits; a.pooled = reinterpret_cast<bf16_t*>(c.pooled_bf16); a.pool_code = reinterpret_cast<unsigned char*>(c.pool_code);
   a.prof = P64_PROF_PTR;
-  if (pooled_bf16 != nullptr) return launch<1>(a, stream);
-  if (mask_bits != nullptr) return launch<2>(a, stream);
-  return launch<0>(a, stream);
+  if (p.tile == 1) return launch<1>(a, c.stream);      // the epilogue mode: fused pool, one-bit mask, plain
+  if (p.tile == 2) return launch<2>(a, c.stream);
+  return launch<0>(a, c.stream);
 }

@@ -302,13 +302,7 @@ __global__ __launch_bounds__(256) void conv3x3_f32_kernel(ConvArgs a) {
 
 template <class C>
 int launch_cfg(const ConvArgs& a0, hipStream_t stream) {
-  static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};      // hipFuncSetAttribute is per device
-  bool& attr_set = attr_set_dev[osvos_current_device()];
-  if (!attr_set) {
-    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_f32_kernel<C>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES));
-    attr_set = true;
-  }
+  if (int rc = osvos_set_dyn_lds_once<&conv3x3_f32_kernel<C>>(C::LDS_BYTES)) return rc;
   ConvArgs a = a0;
   a.tiles_x = ceil_div(a.W, C::TW);
   a.tiles_y = ceil_div(a.H, C::TH);
@@ -321,9 +315,11 @@ int launch_cfg(const ConvArgs& a0, hipStream_t stream) {
   return 0;
 }
 
+// a row of the tile table: the tile's shape and its launcher
 struct TileInfo {
   int tw, th, bn, wm, wn;
   size_t lds;
+  int (*launch)(const ConvArgs&, hipStream_t);
 };
 
 //                RBW TBX TBY NB WGM WGN
@@ -343,13 +339,12 @@ using T11 = Cfg<8, 1, 4, 1, 4, 1>;   //  8x16 px x 32 co
 using T12 = Cfg<16, 1, 8, 1, 4, 1>;  // 16x16 px x 32 co (16x2 row blocks)
 using T13 = Cfg<8, 2, 3, 2, 2, 2>;   // 16x12 px x 64 co
 using T14 = Cfg<32, 1, 4, 1, 4, 1>;  // 32x4 px x 32 co: T9's shape with 32-wide row blocks (conflict-free LDS reads)
-constexpr int kNumTiles = 15;
-
 template <class C>
-constexpr TileInfo info() { return TileInfo{C::TW, C::TH, C::BN, C::WM, C::WN, C::LDS_BYTES}; }
-const TileInfo kTiles[kNumTiles] = {info<T0>(), info<T1>(), info<T2>(), info<T3>(), info<T4>(),
-                                    info<T5>(), info<T6>(), info<T7>(), info<T8>(), info<T9>(),
-                                    info<T10>(), info<T11>(), info<T12>(), info<T13>(), info<T14>()};
+constexpr TileInfo info() { return TileInfo{C::TW, C::TH, C::BN, C::WM, C::WN, C::LDS_BYTES, &launch_cfg<C>}; }
+constexpr TileInfo kTiles[] = {info<T0>(), info<T1>(), info<T2>(), info<T3>(), info<T4>(),
+                               info<T5>(), info<T6>(), info<T7>(), info<T8>(), info<T9>(),
+                               info<T10>(), info<T11>(), info<T12>(), info<T13>(), info<T14>()};
+constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
 
 // Measured on MI355X (tools/tune_conv.py, profiles/r01_tune_conv_tiles.txt): the 128-pixel x 32-cout tile T9 -- one
 // accumulator per wave, 5-7 workgroups per CU -- is the fastest or within 2 % of the fastest on every layer of the
@@ -400,6 +395,36 @@ int pick_ksplit(const TileInfo& t, int N, int H, int W, int Cin, int Cout, int C
   return ks;
 }
 
+// the exact-fp32 family's decisions for one call: checks, tile and map rule, K split
+int choose(const ConvCall& c, ConvPlan* p) {
+  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cout = c.Cout, y_cs = c.y_cs, CoutP = osvos_cout_pad(Cout);
+  int tile = c.tile;
+  OSVOS_ARG_CHECK(c.x && c.wpk && c.y, "conv3x3: null pointer");
+  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3: bad shape");
+  OSVOS_ARG_CHECK(Cin % 8 == 0, "conv3x3 f32: Cin (%d) must be a multiple of 8 (pad the input)", Cin);
+  OSVOS_ARG_CHECK(y_cs >= Cout, "conv3x3: y channel stride %d < Cout %d", y_cs, Cout);
+  OSVOS_ARG_CHECK((long)H * W * Cin < (1L << 29) && (long)H * W * y_cs < (1L << 29), "conv3x3: image too large for 31-bit byte offsets");
+  if (tile < 0) {
+    OSVOS_ENV_INT(env_tile, "OSVOS_CONV_TILE", -1);
+    tile = env_tile >= 0 ? env_tile : pick_tile(N, H, W, Cin, CoutP);
+    // activations larger than the weights -> keep the halo tile XCD-local
+    if (env_tile < 0 && (double)H * W * Cin > 9.0 * Cin * CoutP) tile += 100;
+  }
+  *p = ConvPlan();
+  p->family = CONV_F32;
+  p->map = tile >= 100 ? 1 : 0;
+  p->tile = tile % 100;
+  OSVOS_ARG_CHECK(p->tile >= 0 && p->tile < kNumTiles, "conv3x3: unknown tile config %d", p->tile);
+  if (c.part_ws != nullptr) {
+    // OSVOS_CONV_KSPLIT overrides the automatic choice, but only where the automatic choice could split as well (Cin >= 256):
+    // the caller sizes `part_ws` for those layers only (net.cpp ws_layout), a forced split of a shallow layer would overrun it
+    OSVOS_ENV_INT(env_ks, "OSVOS_CONV_KSPLIT", 0);
+    p->ksplit = c.ksplit > 0 ? c.ksplit : ((env_ks > 0 && Cin >= 256) ? env_ks : pick_ksplit(kTiles[p->tile], N, H, W, Cin, Cout, CoutP, y_cs));
+    if (p->ksplit < 1 || p->ksplit > 8 || Cout % 4 != 0 || y_cs % 4 != 0 || p->ksplit > (Cin >> 3)) p->ksplit = 1;
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int osvos_conv3x3_num_tiles(void) { return kNumTiles; }
@@ -417,70 +442,22 @@ extern "C" void osvos_debug_set_conv_prof_f32(void* p) { g_conv_prof_f32 = (unsi
 #else
 #define OSVOS_CONV_PROF_PTR nullptr
 #endif
+int osvos_conv3x3_f32_plan(const ConvCall& c, ConvPlan* p) { return choose(c, p); }
+
 int osvos_conv3x3_f32(const ConvCall& c) {
-  const float *x = (const float*)c.x, *wpk = (const float*)c.wpk, *bias = c.bias, *mask = (const float*)c.mask;
-  float* const y = c.y;
-  void* const part_ws = c.part_ws;
-  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cout = c.Cout, y_cs = c.y_cs, relu = c.relu;
-  int tile = c.tile;
-  hipStream_t stream = c.stream;
-  OSVOS_ARG_CHECK(x && wpk && y, "conv3x3: null pointer");
-  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3: bad shape");
-  OSVOS_ARG_CHECK(Cin % 8 == 0, "conv3x3 f32: Cin (%d) must be a multiple of 8 (pad the input)", Cin);
-  OSVOS_ARG_CHECK(y_cs >= Cout, "conv3x3: y channel stride %d < Cout %d", y_cs, Cout);
-  OSVOS_ARG_CHECK((long)H * W * Cin < (1L << 29) && (long)H * W * y_cs < (1L << 29), "conv3x3: image too large for 31-bit byte offsets");
-  // f32x3: the same fp32 problem on the bf16 matrix pipe with three-way split operands (conv3x3_f32x3.hip).  Tile ids
-  // 200.. force it (tests, tuning); tile -2 = "automatic, in the f32x3 arithmetic where it applies" (what the callers that were handed
-  // dtype OSVOS_F32_X3 pass; round 4: this replaces a process-wide mutable mode -- the arithmetic is a per-call argument of the ABI).
-  if ((tile >= 200 || (tile == -2 && osvos_conv3x3_f32x3_applicable(Cin, Cout, y_cs)))) {
-    ConvCall cx = c;
-    cx.tile = tile >= 200 ? tile - 200 : -1;
-    return osvos_conv3x3_f32x3(cx);
-  }
+  ConvPlan p;
+  if (choose(c, &p)) return -1;
   ConvArgs a;
-  a.x = x; a.wpk = wpk; a.bias = bias; a.mask = mask; a.y = y;
-  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.CoutP = osvos_cout_pad(Cout); a.y_cs = y_cs;
-  a.relu = relu;
-  if (tile < 0) {
-    OSVOS_ENV_INT(env_tile, "OSVOS_CONV_TILE", -1);
-    tile = env_tile >= 0 ? env_tile : pick_tile(N, H, W, Cin, a.CoutP);
-    // activations larger than the weights -> keep the halo tile XCD-local
-    if (env_tile < 0 && (double)H * W * Cin > 9.0 * Cin * a.CoutP) tile += 100;
-  }
-  a.map = tile >= 100 ? 1 : 0;
-  tile %= 100;
-  OSVOS_ARG_CHECK(tile >= 0 && tile < kNumTiles, "conv3x3: unknown tile config %d", tile);
-  a.ksplit = 1;
+  a.x = (const float*)c.x; a.wpk = (const float*)c.wpk; a.bias = c.bias; a.mask = (const float*)c.mask; a.y = c.y;
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cin = c.Cin; a.Cout = c.Cout; a.CoutP = osvos_cout_pad(c.Cout); a.y_cs = c.y_cs;
+  a.relu = c.relu;
+  a.map = p.map;
+  a.ksplit = p.ksplit;
   a.prof = OSVOS_CONV_PROF_PTR;
-  a.part = reinterpret_cast<float*>(part_ws);
-  if (part_ws != nullptr) {
-    // OSVOS_CONV_KSPLIT overrides the automatic choice, but only where the automatic choice could split as well (Cin >= 256):
-    // the caller sizes `part_ws` for those layers only (net.cpp ws_layout), a forced split of a shallow layer would overrun it
-    OSVOS_ENV_INT(env_ks, "OSVOS_CONV_KSPLIT", 0);
-    a.ksplit = c.ksplit > 0 ? c.ksplit : ((env_ks > 0 && Cin >= 256) ? env_ks : pick_ksplit(kTiles[tile], N, H, W, Cin, Cout, a.CoutP, y_cs));
-    if (a.ksplit < 1 || a.ksplit > 8 || Cout % 4 != 0 || y_cs % 4 != 0 || a.ksplit > (Cin >> 3)) a.ksplit = 1;
-  }
-  int rc;
-  switch (tile) {
-    case 0: rc = launch_cfg<T0>(a, stream); break;
-    case 1: rc = launch_cfg<T1>(a, stream); break;
-    case 2: rc = launch_cfg<T2>(a, stream); break;
-    case 3: rc = launch_cfg<T3>(a, stream); break;
-    case 4: rc = launch_cfg<T4>(a, stream); break;
-    case 5: rc = launch_cfg<T5>(a, stream); break;
-    case 6: rc = launch_cfg<T6>(a, stream); break;
-    case 7: rc = launch_cfg<T7>(a, stream); break;
-    case 8: rc = launch_cfg<T8>(a, stream); break;
-    case 9: rc = launch_cfg<T9>(a, stream); break;
-    case 10: rc = launch_cfg<T10>(a, stream); break;
-    case 11: rc = launch_cfg<T11>(a, stream); break;
-    case 12: rc = launch_cfg<T12>(a, stream); break;
-    case 13: rc = launch_cfg<T13>(a, stream); break;
-    case 14: rc = launch_cfg<T14>(a, stream); break;
-    default: osvos_set_error("conv3x3: unknown tile config %d", tile); return -1;
-  }
-  if (rc || a.ksplit == 1) return rc;
-  return osvos_conv3x3_splitk_finalize_f32(a.part, bias, mask, y, (long)N * H * W, Cout, y_cs, a.ksplit, relu, stream);
+  a.part = reinterpret_cast<float*>(c.part_ws);
+  const int rc = kTiles[p.tile].launch(a, c.stream);
+  if (rc || p.ksplit == 1) return rc;
+  return osvos_conv3x3_splitk_finalize_f32(a.part, a.bias, a.mask, a.y, (long)c.N * c.H * c.W, c.Cout, c.y_cs, p.ksplit, c.relu, c.stream);
 }
 
 int osvos_conv3x3_splitk_finalize_f32(const float* part, const float* bias, const float* mask, float* y, long npix, int Cout, int y_cs,

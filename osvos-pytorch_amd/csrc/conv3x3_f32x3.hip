@@ -815,15 +815,9 @@ constexpr size_t kSkTicketBytes = (size_t)kSkMaxTiles * 4;
 // sk_grid > 0: the stream-K kernel with that many persistent workgroups (the caller has checked that the tile order has >= sk_grid units)
 template <class C, int PS, int SK, int NP = 3, int HP = 0, int PIPE = 0>
 int launch_x2(const ConvArgsX& a0, int sk_grid, hipStream_t stream) {
-  static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};      // hipFuncSetAttribute is per device
-  bool& attr_set = attr_set_dev[osvos_current_device()];
   constexpr size_t lds_bytes = PIPE ? C::LDS_BYTES_PIPE : (NP == 3 ? C::LDS_BYTES : C::LDS_BYTES_2);
   static_assert(lds_bytes <= 160 * 1024, "tile does not fit the 160 KB LDS of a gfx950 CU");
-  if (!attr_set) {
-    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_f32x3_kernel<C, PS, SK, NP, HP, PIPE>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    attr_set = true;
-  }
+  if (int rc = osvos_set_dyn_lds_once<&conv3x3_f32x3_kernel<C, PS, SK, NP, HP, PIPE>>(lds_bytes)) return rc;
   ConvArgsX a = a0;
   a.tiles_x = ceil_div(a.W, C::TW);
   a.tiles_y = ceil_div(a.H, C::TH);
@@ -843,44 +837,47 @@ int launch_x2(const ConvArgsX& a0, int sk_grid, hipStream_t stream) {
   OSVOS_LAUNCH_CHECK();
   return 0;
 }
-// the pre-split form is built for the production tiles (eight waves, in-loop staging); the others take the fp32 pack.  Stream-K: the
-// pre-split production tiles of the wide layers (SKT).  PIPE: the tile has the pipelined K loop (10, 12, 14), taken unless OSVOS_X3_PIPE=0
+// Which loop forms a tile is built in (columns of its table row; choose() picks among them, launch_x maps the pick to the instantiation): the
+// pre-split forms for the production tiles (in-loop staging; two pieces / fp16 pairs: four or eight waves, three pieces: eight waves), the others
+// take the fp32 pack.  SKT: the stream-K form of the pre-split production tiles of the wide layers.  PIPE: the tile has the pipelined K loop
+// (10, 12, 14), taken unless OSVOS_X3_PIPE=0
+template <class C>
+constexpr bool kPs2 = C::ILV != 0 && (C::NT == 512 || C::NT == 256);
+template <class C>
+constexpr bool kPs3 = C::ILV != 0 && C::NT == 512;
 template <class C, bool SKT = false, bool PIPE = false>
-int launch_x(const ConvArgsX& a, int pieces, int sk_grid, hipStream_t stream) {
-  if (pieces == 22) {     // two fp16 pieces with block exponents (precision 'fp32h2'): the pre-split production tiles only
-    if constexpr (C::ILV != 0 && (C::NT == 512 || C::NT == 256)) {
-      if (a.wpk3 != nullptr) return launch_x2<C, 1, 0, 2, 1>(a, 0, stream);
-    }
-    osvos_set_error("conv3x3 f32x3: the fp16-pair form is built for the pre-split eight-wave tiles (10, 12, 14, 15, 16, 17) with a pre-split pack");
-    return -1;
+int launch_x(const ConvArgsX& a, const ConvPlan& p, int pieces, hipStream_t stream) {
+  if constexpr (kPs2<C>) {
+    if (p.presplit && pieces == 22) return launch_x2<C, 1, 0, 2, 1>(a, 0, stream);     // two fp16 pieces with block exponents (precision 'fp32h2')
+    if (p.presplit && pieces == 2) return launch_x2<C, 1, 0, 2>(a, 0, stream);         // two-piece mode (precision 'fp32x2'): the plain grid only
   }
-  if (pieces == 2) {      // two-piece mode (precision 'fp32x2'): the plain grid only, no stream-K form
-    if constexpr (C::ILV != 0 && (C::NT == 512 || C::NT == 256)) {
-      if (a.wpk3 != nullptr) return launch_x2<C, 1, 0, 2>(a, 0, stream);
-    }
-    OSVOS_ARG_CHECK(a.wpk != nullptr, "conv3x3 f32x3: this tile config has no pre-split form and no fp32 pack was given");
-    return launch_x2<C, 0, 0, 2>(a, 0, stream);
-  }
-  if constexpr (C::ILV != 0 && C::NT == 512) {
-    if constexpr (PIPE) {
-      OSVOS_ENV_INT(env_pipe, "OSVOS_X3_PIPE", 1);       // 0: the single-buffered loop (A/B comparisons)
-      if (env_pipe != 0) {
-        if constexpr (SKT) {
-          if (a.wpk3 != nullptr && sk_grid > 0) return launch_x2<C, 1, 1, 3, 0, 1>(a, sk_grid, stream);
+  if (pieces == 2) return launch_x2<C, 0, 0, 2>(a, 0, stream);
+  if constexpr (kPs3<C>) {
+    if (p.presplit) {
+      if constexpr (PIPE) {
+        if (p.pipe) {
+          if constexpr (SKT) {
+            if (p.sk_grid > 0) return launch_x2<C, 1, 1, 3, 0, 1>(a, p.sk_grid, stream);
+          }
+          return launch_x2<C, 1, 0, 3, 0, 1>(a, 0, stream);
         }
-        if (a.wpk3 != nullptr) return launch_x2<C, 1, 0, 3, 0, 1>(a, 0, stream);
       }
+      if constexpr (SKT) {
+        if (p.sk_grid > 0) return launch_x2<C, 1, 1>(a, p.sk_grid, stream);
+      }
+      return launch_x2<C, 1, 0>(a, 0, stream);
     }
-    if constexpr (SKT) {
-      if (a.wpk3 != nullptr && sk_grid > 0) return launch_x2<C, 1, 1>(a, sk_grid, stream);
-    }
-    if (a.wpk3 != nullptr) return launch_x2<C, 1, 0>(a, 0, stream);
   }
-  OSVOS_ARG_CHECK(a.wpk != nullptr, "conv3x3 f32x3: this tile config has no pre-split form and no fp32 pack was given");
   return launch_x2<C, 0, 0>(a, 0, stream);
 }
 
-struct TileInfoX { int tw, th, bn, nt; size_t lds; };
+// a row of the tile table: the tile's shape, the forms it is built in and its launcher
+struct TileInfoX {
+  int tw, th, bn, nt;
+  size_t lds;
+  bool ps2, ps3, skt, pipe;
+  int (*launch)(const ConvArgsX&, const ConvPlan&, int, hipStream_t);
+};
 
 //                 RBW TBX TBY NB WGM WGN OCC
 using X0 = CfgX<32, 1, 8, 4, 2, 2, 1>;   // 32x8 px x 128 co, 4 waves (4x2 accumulators per wave), 143 KB LDS
@@ -901,12 +898,13 @@ using X14 = CfgX<16, 1, 8, 2, 4, 2, 1, 1>;  // X8 ...
 using X15 = CfgX<32, 1, 8, 1, 8, 1, 1, 1>;  // 32x8 px x 32 co, 8 waves (1x1): the skinny outputs (side_prep: 16 couts, input gradient: 3)
 using X16 = CfgX<32, 1, 16, 2, 8, 1, 1, 1>; // 32x16 px x 64 co, 8 waves (2x2): twice the pixels per weight byte of X12, a third fewer staging instructions per MFMA than X10
 using X17 = CfgX<16, 1, 16, 2, 8, 1, 1, 1>; // 16x32 px x 64 co, 8 waves (2x2): the same for narrow maps
-constexpr int kNumTilesX = 18;
-template <class C>
-constexpr TileInfoX infoX() { return TileInfoX{C::TW, C::TH, C::BN, C::NT, C::LDS_BYTES}; }
-const TileInfoX kTilesX[kNumTilesX] = {infoX<X0>(), infoX<X1>(), infoX<X2>(), infoX<X3>(), infoX<X4>(),
-                                       infoX<X5>(), infoX<X6>(), infoX<X7>(), infoX<X8>(), infoX<X9>(),
-                                       infoX<X10>(), infoX<X11>(), infoX<X12>(), infoX<X13>(), infoX<X14>(), infoX<X15>(), infoX<X16>(), infoX<X17>()};
+template <class C, bool SKT = false, bool PIPE = false>
+constexpr TileInfoX infoX() { return TileInfoX{C::TW, C::TH, C::BN, C::NT, C::LDS_BYTES, kPs2<C>, kPs3<C>, SKT, PIPE, &launch_x<C, SKT, PIPE>}; }
+constexpr TileInfoX kTilesX[] = {infoX<X0>(), infoX<X1>(), infoX<X2>(), infoX<X3>(), infoX<X4>(),
+                                 infoX<X5>(), infoX<X6>(), infoX<X7>(), infoX<X8>(), infoX<X9>(),
+                                 infoX<X10, true, true>(), infoX<X11>(), infoX<X12, true, true>(), infoX<X13>(), infoX<X14, true, true>(),
+                                 infoX<X15>(), infoX<X16>(), infoX<X17>()};
+constexpr int kNumTilesX = sizeof(kTilesX) / sizeof(kTilesX[0]);
 
 long tiles_of(const TileInfoX& t, int N, int H, int W, int CoutP) {
   return (long)N * ceil_div(H, t.th) * ceil_div(W, t.tw) * ceil_div(CoutP, t.bn);
@@ -929,6 +927,93 @@ int pick_ksplit_x(const TileInfoX& t, int N, int H, int W, int Cin, int Cout, in
   int ks = 1;
   while (ks < 8 && blocks * ks < 200 && (Cin / 16) / (ks * 2) >= 4) ks *= 2;
   return ks;
+}
+
+// the f32x3 family's decisions for one call: checks, tile and map rule, K split, stream-K, loop form
+int choose(const ConvCall& c, ConvPlan* p) {
+  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cout = c.Cout, y_cs = c.y_cs, CoutP = osvos_cout_pad(Cout);
+  int tile = c.tile;
+  const bool pool_fwd = c.pooled != nullptr;
+  OSVOS_ARG_CHECK(c.x && (c.wpk || c.wpk3) && c.y, "conv3x3 f32x3: null pointer");
+  OSVOS_ARG_CHECK(!pool_fwd || (c.relu && Cout % 4 == 0 && y_cs == Cout), "conv3x3 f32x3: fused pool forward needs ReLU and a dense Cout %% 4 == 0 result");
+  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3 f32x3: bad shape");
+  OSVOS_ARG_CHECK(osvos_conv3x3_f32x3_applicable(Cin, Cout, y_cs), "conv3x3 f32x3: needs Cin %% 16 == 0 (%d), y_cs %% 4 == 0 and >= Cout rounded up to 4 (%d, %d)",
+                  Cin, Cout, y_cs);
+  OSVOS_ARG_CHECK(Cout % 4 == 0 || (c.bias == nullptr && c.mask == nullptr), "conv3x3 f32x3: ragged Cout (%d) takes no bias / mask", Cout);
+  OSVOS_ARG_CHECK(y_cs >= Cout, "conv3x3 f32x3: y channel stride %d < Cout %d", y_cs, Cout);
+  OSVOS_ARG_CHECK((long)H * W * Cin < (1L << 29) && (long)H * W * y_cs < (1L << 29), "conv3x3 f32x3: image too large for 31-bit byte offsets");
+  if (tile < 0) {
+    OSVOS_ENV_INT(env_tile, "OSVOS_X3_TILE", -1);
+    tile = env_tile >= 0 ? env_tile : pick_tile_x(N, H, W, CoutP);
+    // tuning knobs for the two-piece forms (half the matrix work per staged byte): another tile where the rule says 10 / 12 (launches without the
+    // fused pool only: that epilogue exists for tiles 10, 12, 14)
+    OSVOS_ENV_INT(wide2, "OSVOS_X2_TILE_FOR_10", 10);
+    OSVOS_ENV_INT(mid2, "OSVOS_X2_TILE_FOR_12", 12);
+    if (env_tile < 0 && c.pieces != 3 && !pool_fwd) tile = tile == 10 ? wide2 : (tile == 12 ? mid2 : tile);
+    // XCD-local map (cout tiles of one spatial tile on one XCD) only where the activations are MUCH larger than the weights: the rule of rounds 2-4
+    // (pixels > 9 CoutP, i.e. fp32 activation bytes > fp32 weight bytes) put conv4_x on it, where it measures 6-7 % slower per launch than the plain
+    // order (X14 on conv4_2: 0.166 vs 0.155 ms; the pre-split pack is 1.5x the fp32 weights and every XCD then streams all of it) -- with the factor 3
+    // the headline step gains 1.0-2.8 % on three boxes, configs[4] and the window-fused form are level (profiles/r05_ab_x3_map_rule.txt)
+    if (env_tile < 0 && (double)H * W * Cin > 27.0 * Cin * CoutP) tile += 100;
+  }
+  *p = ConvPlan();
+  p->family = CONV_F32X3;
+  p->map = tile >= 100 ? 1 : 0;
+  tile %= 100;
+  p->tile = tile;
+  OSVOS_ARG_CHECK(tile >= 0 && tile < kNumTilesX, "conv3x3 f32x3: unknown tile config %d", tile);
+  const TileInfoX& t = kTilesX[tile];
+  if (c.part_ws != nullptr) {
+    OSVOS_ENV_INT(env_ks, "OSVOS_X3_KSPLIT", 0);
+    p->ksplit = c.ksplit > 0 ? c.ksplit : (env_ks > 0 && Cin >= 256 ? env_ks : pick_ksplit_x(t, N, H, W, Cin, Cout, CoutP));
+    if (p->ksplit < 1 || p->ksplit > 8 || p->ksplit > (Cin >> 4) || Cout % 4 != 0) p->ksplit = 1;
+  }
+  if (c.mask_bits != nullptr || c.y_bits != nullptr)
+    OSVOS_ARG_CHECK(Cout % 32 == 0 && y_cs == Cout, "conv3x3 f32x3: one-bit masks need a dense result with Cout %% 32 == 0 (Cout %d, stride %d)", Cout, y_cs);
+  if (c.y_bits != nullptr) p->ksplit = 1;
+  if (pool_fwd) {
+    p->ksplit = 1;
+    OSVOS_ARG_CHECK(tile == 10 || tile == 12 || tile == 14, "conv3x3 f32x3: fused pool forward is built for tiles 10, 12 and 14 (got %d)", tile);
+  }
+  // stream-K (kernel header): taken when the caller hands a workspace and the plain grid would leave a sizeable part of the chip without a
+  // tile -- one workgroup per CU, so a grid of `ntiles` runs in ceil(ntiles / CUs) rounds and loses 1 - ntiles / (rounds x CUs) of them
+  // (conv3_x at 854x480 batch 1: 210 tiles, 18 %) -- or would need partial-sum launches + a finalize kernel to fill it (conv5_x)
+  if (c.sk_ws != nullptr && c.wpk3 != nullptr && t.skt && Cout % 4 == 0) {
+    const long ntiles = tiles_of(t, N, H, W, CoutP), units = ntiles * (Cin >> 4);
+    OSVOS_ENV_INT(env_grid, "OSVOS_X3_STREAMK_GRID", 0);            // tuning: persistent workgroups (default: the CU count)
+    OSVOS_ENV_INT(env_loss, "OSVOS_X3_STREAMK_MIN_LOSS", 6);        // tuning: percent of the chip a plain grid must leave idle
+    int g = c.sk_grid > 0 ? c.sk_grid : (env_grid > 0 ? env_grid : osvos_cu_count());
+    if (g > kSkMaxGrid) g = kSkMaxGrid;
+    const long rounds = (ntiles * p->ksplit + g - 1) / g;
+    // Measured per layer at 854x480 batch 1 (profiles/r04_tune_streamk.txt, three boxes): the 64-cout tiles (12, 14: 64 KB partial slots) WIN --
+    // conv1_2 -6 %, conv4_1 -4 %, conv4_2 / 4_3 -5...-7 %, conv5_x level with partial-sum launches + finalize and one launch fewer -- while the
+    // 128-cout tile (10: conv2_x / conv3_x, 128 KB slots, short K ranges on conv2_x / conv3_1) LOSES 1-12 % although every workgroup issues a
+    // fifth fewer MFMAs.  The automatic choice therefore covers tiles 12 and 14 only; tile 10 runs stream-K when forced (tests, tuning).
+    const bool lossy = (tile == 12 || tile == 14) && (p->ksplit > 1 || (rounds * g - ntiles) * 100 >= (long)env_loss * rounds * g);
+    if (ntiles <= kSkMaxTiles && units >= g && (c.sk_grid > 0 || lossy)) {
+      p->sk_grid = g;
+      p->ksplit = 1;
+      p->sk_order = p->map ? 0 : 1;      // activations > weights: Cout tiles of one halo back to back; else one weight slice per XCD
+      OSVOS_ENV_INT(env_order, "OSVOS_X3_STREAMK_ORDER", -1);
+      if (env_order == 0 || env_order == 1) p->sk_order = env_order;
+    }
+  }
+  // the loop form: pre-split where the tile is built for it and the pack is there, else the fp32 pack
+  if (c.pieces == 22) {     // two fp16 pieces with block exponents (precision 'fp32h2'): the pre-split production tiles only
+    OSVOS_ARG_CHECK(t.ps2 && c.wpk3 != nullptr,
+                    "conv3x3 f32x3: the fp16-pair form is built for the pre-split eight-wave tiles (10, 12, 14, 15, 16, 17) with a pre-split pack");
+    p->presplit = 1;
+  } else {
+    p->presplit = (c.pieces == 2 ? t.ps2 : t.ps3) && c.wpk3 != nullptr;
+    OSVOS_ARG_CHECK(p->presplit || c.wpk != nullptr, "conv3x3 f32x3: this tile config has no pre-split form and no fp32 pack was given");
+  }
+  const bool three = c.pieces != 2 && c.pieces != 22;
+  if (three && p->presplit && t.pipe) {
+    OSVOS_ENV_INT(env_pipe, "OSVOS_X3_PIPE", 1);       // 0: the single-buffered loop (A/B comparisons)
+    p->pipe = env_pipe != 0;
+  }
+  if (!three) p->sk_grid = p->sk_order = 0;     // (the two-piece forms have no stream-K kernel: a plain grid -- uncut, as decided above)
+  return 0;
 }
 
 // pre-split pack: wpk3[((piece * 9 + tap) * CG + cg) * CoutP + co][e] = piece(W[co][8 cg + e][tap])  (dgrad = 0), or the rotated /
@@ -1078,108 +1163,24 @@ size_t osvos_conv3x3_f32x3_streamk_ticket_bytes(void) { return kSkTicketBytes; }
 
 bool osvos_conv3x3_f32x3_applicable(int Cin, int Cout, int y_cs) { return Cin % 16 == 0 && y_cs % 4 == 0 && ((Cout + 3) & ~3) <= y_cs; }
 
+int osvos_conv3x3_f32x3_plan(const ConvCall& c, ConvPlan* p) { return choose(c, p); }
+
 int osvos_conv3x3_f32x3(const ConvCall& c) {
-  const float *x = (const float*)c.x, *wpk = (const float*)c.wpk, *bias = c.bias, *mask = (const float*)c.mask;
-  const void* const wpk3 = c.wpk3;
-  float* const y = c.y;
-  void* const part_ws = c.part_ws;
-  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cout = c.Cout, y_cs = c.y_cs, relu = c.relu, ksplit = c.ksplit;
-  int tile = c.tile;
-  hipStream_t stream = c.stream;
-  const bool pool_fwd = c.pooled != nullptr;
-  OSVOS_ARG_CHECK(x && (wpk || wpk3) && y, "conv3x3 f32x3: null pointer");
-  OSVOS_ARG_CHECK(!pool_fwd || (relu && Cout % 4 == 0 && y_cs == Cout), "conv3x3 f32x3: fused pool forward needs ReLU and a dense Cout %% 4 == 0 result");
-  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3 f32x3: bad shape");
-  OSVOS_ARG_CHECK(osvos_conv3x3_f32x3_applicable(Cin, Cout, y_cs), "conv3x3 f32x3: needs Cin %% 16 == 0 (%d), y_cs %% 4 == 0 and >= Cout rounded up to 4 (%d, %d)",
-                  Cin, Cout, y_cs);
-  OSVOS_ARG_CHECK(Cout % 4 == 0 || (bias == nullptr && mask == nullptr), "conv3x3 f32x3: ragged Cout (%d) takes no bias / mask", Cout);
-  OSVOS_ARG_CHECK(y_cs >= Cout, "conv3x3 f32x3: y channel stride %d < Cout %d", y_cs, Cout);
-  OSVOS_ARG_CHECK((long)H * W * Cin < (1L << 29) && (long)H * W * y_cs < (1L << 29), "conv3x3 f32x3: image too large for 31-bit byte offsets");
+  ConvPlan p;
+  if (choose(c, &p)) return -1;
   ConvArgsX a;
-  a.x = x; a.wpk = wpk; a.wpk3 = reinterpret_cast<const uint4*>(wpk3); a.bias = bias; a.mask = mask; a.y = y;
-  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = (Cout + 3) & ~3; a.CoutP = osvos_cout_pad(Cout); a.y_cs = y_cs;
-  a.relu = relu;
+  a.x = (const float*)c.x; a.wpk = (const float*)c.wpk; a.wpk3 = reinterpret_cast<const uint4*>(c.wpk3); a.bias = c.bias; a.mask = (const float*)c.mask;
+  a.y = c.y;
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cin = c.Cin; a.Cout = (c.Cout + 3) & ~3; a.CoutP = osvos_cout_pad(c.Cout); a.y_cs = c.y_cs;
+  a.relu = c.relu;
   a.epi.pooled = c.pooled; a.epi.mask_bits = c.mask_bits; a.epi.y_bits = c.y_bits; a.epi.sk_ws = c.sk_ws; a.epi.sk_grid = c.sk_grid;
-  if (tile < 0) {
-    OSVOS_ENV_INT(env_tile, "OSVOS_X3_TILE", -1);
-    tile = env_tile >= 0 ? env_tile : pick_tile_x(N, H, W, a.CoutP);
-    // tuning knobs for the two-piece forms (half the matrix work per staged byte): another tile where the rule says 10 / 12 (launches without the
-    // fused pool only: that epilogue exists for tiles 10, 12, 14)
-    OSVOS_ENV_INT(wide2, "OSVOS_X2_TILE_FOR_10", 10);
-    OSVOS_ENV_INT(mid2, "OSVOS_X2_TILE_FOR_12", 12);
-    if (env_tile < 0 && c.pieces != 3 && !pool_fwd) tile = tile == 10 ? wide2 : (tile == 12 ? mid2 : tile);
-    // XCD-local map (cout tiles of one spatial tile on one XCD) only where the activations are MUCH larger than the weights: the rule of rounds 2-4
-    // (pixels > 9 CoutP, i.e. fp32 activation bytes > fp32 weight bytes) put conv4_x on it, where it measures 6-7 % slower per launch than the plain
-    // order (X14 on conv4_2: 0.166 vs 0.155 ms; the pre-split pack is 1.5x the fp32 weights and every XCD then streams all of it) -- with the factor 3
-    // the headline step gains 1.0-2.8 % on three boxes, configs[4] and the window-fused form are level (profiles/r05_ab_x3_map_rule.txt)
-    if (env_tile < 0 && (double)H * W * Cin > 27.0 * Cin * a.CoutP) tile += 100;
-  }
-  a.map = tile >= 100 ? 1 : 0;
-  tile %= 100;
-  OSVOS_ARG_CHECK(tile >= 0 && tile < kNumTilesX, "conv3x3 f32x3: unknown tile config %d", tile);
-  a.part = reinterpret_cast<float*>(part_ws);
-  a.ksplit = 1;
-  if (part_ws != nullptr) {
-    OSVOS_ENV_INT(env_ks, "OSVOS_X3_KSPLIT", 0);
-    a.ksplit = ksplit > 0 ? ksplit : (env_ks > 0 && Cin >= 256 ? env_ks : pick_ksplit_x(kTilesX[tile], N, H, W, Cin, Cout, a.CoutP));
-    if (a.ksplit < 1 || a.ksplit > 8 || a.ksplit > (Cin >> 4) || Cout % 4 != 0) a.ksplit = 1;
-  }
-  if (c.mask_bits != nullptr || c.y_bits != nullptr)
-    OSVOS_ARG_CHECK(Cout % 32 == 0 && y_cs == Cout, "conv3x3 f32x3: one-bit masks need a dense result with Cout %% 32 == 0 (Cout %d, stride %d)", Cout, y_cs);
-  if (c.y_bits != nullptr) a.ksplit = 1;
-  if (pool_fwd) {
-    a.ksplit = 1;
-    OSVOS_ARG_CHECK(tile == 10 || tile == 12 || tile == 14, "conv3x3 f32x3: fused pool forward is built for tiles 10, 12 and 14 (got %d)", tile);
-  }
-  // stream-K (kernel header): taken when the caller hands a workspace and the plain grid would leave a sizeable part of the chip without a
-  // tile -- one workgroup per CU, so a grid of `ntiles` runs in ceil(ntiles / CUs) rounds and loses 1 - ntiles / (rounds x CUs) of them
-  // (conv3_x at 854x480 batch 1: 210 tiles, 18 %) -- or would need partial-sum launches + a finalize kernel to fill it (conv5_x)
-  int sk_grid = 0;
-  a.sk_order = 0; a.sk_tickets = nullptr; a.sk_part = nullptr;
-  if (c.sk_ws != nullptr && wpk3 != nullptr && (tile == 10 || tile == 12 || tile == 14) && Cout % 4 == 0) {
-    const long ntiles = tiles_of(kTilesX[tile], N, H, W, a.CoutP), units = ntiles * (Cin >> 4);
-    OSVOS_ENV_INT(env_grid, "OSVOS_X3_STREAMK_GRID", 0);            // tuning: persistent workgroups (default: the CU count)
-    OSVOS_ENV_INT(env_loss, "OSVOS_X3_STREAMK_MIN_LOSS", 6);        // tuning: percent of the chip a plain grid must leave idle
-    int g = c.sk_grid > 0 ? c.sk_grid : (env_grid > 0 ? env_grid : osvos_cu_count());
-    if (g > kSkMaxGrid) g = kSkMaxGrid;
-    const long rounds = (ntiles * a.ksplit + g - 1) / g;
-    // Measured per layer at 854x480 batch 1 (profiles/r04_tune_streamk.txt, three boxes): the 64-cout tiles (12, 14: 64 KB partial slots) WIN --
-    // conv1_2 -6 %, conv4_1 -4 %, conv4_2 / 4_3 -5...-7 %, conv5_x level with partial-sum launches + finalize and one launch fewer -- while the
-    // 128-cout tile (10: conv2_x / conv3_x, 128 KB slots, short K ranges on conv2_x / conv3_1) LOSES 1-12 % although every workgroup issues a
-    // fifth fewer MFMAs.  The automatic choice therefore covers tiles 12 and 14 only; tile 10 runs stream-K when forced (tests, tuning).
-    const bool lossy = (tile == 12 || tile == 14) && (a.ksplit > 1 || (rounds * g - ntiles) * 100 >= (long)env_loss * rounds * g);
-    if (ntiles <= kSkMaxTiles && units >= g && (c.sk_grid > 0 || lossy)) {
-      sk_grid = g;
-      a.ksplit = 1;
-      a.sk_order = a.map ? 0 : 1;      // activations > weights: Cout tiles of one halo back to back; else one weight slice per XCD
-      OSVOS_ENV_INT(env_order, "OSVOS_X3_STREAMK_ORDER", -1);
-      if (env_order == 0 || env_order == 1) a.sk_order = env_order;
-      a.sk_tickets = reinterpret_cast<unsigned*>(c.sk_ws);
-      a.sk_part = reinterpret_cast<float*>(reinterpret_cast<char*>(c.sk_ws) + kSkTicketBytes);
-    }
-  }
-  int rc;
-  switch (tile) {
-    case 0: rc = launch_x<X0>(a, c.pieces, 0, stream); break;
-    case 1: rc = launch_x<X1>(a, c.pieces, 0, stream); break;
-    case 2: rc = launch_x<X2>(a, c.pieces, 0, stream); break;
-    case 3: rc = launch_x<X3>(a, c.pieces, 0, stream); break;
-    case 4: rc = launch_x<X4>(a, c.pieces, 0, stream); break;
-    case 5: rc = launch_x<X5>(a, c.pieces, 0, stream); break;
-    case 6: rc = launch_x<X6>(a, c.pieces, 0, stream); break;
-    case 7: rc = launch_x<X7>(a, c.pieces, 0, stream); break;
-    case 8: rc = launch_x<X8>(a, c.pieces, 0, stream); break;
-    case 9: rc = launch_x<X9>(a, c.pieces, 0, stream); break;
-    case 10: rc = launch_x<X10, true, true>(a, c.pieces, sk_grid, stream); break;
-    case 11: rc = launch_x<X11>(a, c.pieces, 0, stream); break;
-    case 12: rc = launch_x<X12, true, true>(a, c.pieces, sk_grid, stream); break;
-    case 13: rc = launch_x<X13>(a, c.pieces, 0, stream); break;
-    case 14: rc = launch_x<X14, true, true>(a, c.pieces, sk_grid, stream); break;
-    case 15: rc = launch_x<X15>(a, c.pieces, 0, stream); break;
-    case 16: rc = launch_x<X16>(a, c.pieces, 0, stream); break;
-    case 17: rc = launch_x<X17>(a, c.pieces, 0, stream); break;
-    default: osvos_set_error("conv3x3 f32x3: unknown tile config %d", tile); return -1;
-  }
+  a.map = p.map;
+  a.part = reinterpret_cast<float*>(c.part_ws);
+  a.ksplit = p.ksplit;
+  a.sk_order = p.sk_order;
+  a.sk_tickets = p.sk_grid > 0 ? reinterpret_cast<unsigned*>(c.sk_ws) : nullptr;
+  a.sk_part = p.sk_grid > 0 ? reinterpret_cast<float*>(reinterpret_cast<char*>(c.sk_ws) + kSkTicketBytes) : nullptr;
+  const int rc = kTilesX[p.tile].launch(a, p, c.pieces, c.stream);
   if (rc) return rc;
-  return a.ksplit > 1 ? osvos_conv3x3_splitk_finalize_f32(a.part, bias, mask, y, (long)N * H * W, Cout, y_cs, a.ksplit, relu, stream) : 0;
+  return p.ksplit > 1 ? osvos_conv3x3_splitk_finalize_f32(a.part, a.bias, a.mask, a.y, (long)c.N * c.H * c.W, c.Cout, c.y_cs, p.ksplit, c.relu, c.stream) : 0;
 }

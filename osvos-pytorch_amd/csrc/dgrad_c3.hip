@@ -215,12 +215,7 @@ int osvos_conv3x3_dgrad_c3_f32(const float* dy, const float* wpk_dgrad, float* d
 int osvos_conv3x3_dgrad_c3_bf16mfma(const void* dy_bf16, const void* wpk_bf16_dgrad, float* dx_nchw, int N, int H, int W, int Cout, hipStream_t stream) {
   OSVOS_ARG_CHECK(dy_bf16 && wpk_bf16_dgrad && dx_nchw && N > 0 && H > 0 && W > 0, "dgrad c3 (bf16 mfma): bad arguments");
   OSVOS_ARG_CHECK(Cout == 64 && (long)H * W * 128 < (1L << 31), "dgrad c3 (bf16 mfma): Cout %d (64 only) / image too large", Cout);
-  static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};
-  bool& attr_set = attr_set_dev[osvos_current_device()];
-  if (!attr_set) {
-    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dgrad_c3_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, M_LDS_BYTES));
-    attr_set = true;
-  }
+  if (int rc = osvos_set_dyn_lds_once<&dgrad_c3_mfma_kernel>(M_LDS_BYTES)) return rc;
   D3mArgs a;
   a.dy = dy_bf16; a.wpk = reinterpret_cast<const uint4*>(wpk_bf16_dgrad); a.dx = dx_nchw;
   a.N = N; a.H = H; a.W = W;

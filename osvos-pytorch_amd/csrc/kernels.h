@@ -35,8 +35,7 @@ struct ConvCall {
   void* pool_code = nullptr;
   int N = 0, H = 0, W = 0, Cin = 0, Cout = 0, relu = 0;
   int pieces = 3;                      // f32x3 family, per operand: 3 bf16 pieces, 2 bf16 ('fp32x2') or 22 = two FP16 under block exponents ('fp32h2'; such a wpk3)
-  int tile = -1;                       // -1: automatic; else the family's tile id (+100: XCD-local block map).  Exact fp32 launcher: 200 + t = f32x3
-                                       // tile t, -2 = "automatic, in the f32x3 arithmetic where it applies"
+  int tile = -1;                       // -1: automatic; else the family's tile id (+100: XCD-local block map)
   int ksplit = 0;                      // fp32 families: K parts (<= 8) of a launch cut along K; 0 = automatic.  Taken only with part_ws
   void* part_ws = nullptr;             // NULL (never cut) or osvos_conv3x3_splitk_ws_bytes_f32() bytes for the partial sums
   // f32x3 stream-K: workspace of osvos_conv3x3_f32x3_streamk_ws_bytes(), tickets zeroed once by the caller (NULL = plain grids only); sk_grid 0 =
@@ -45,6 +44,31 @@ struct ConvCall {
   int sk_grid = 0;
   hipStream_t stream = nullptr;
 };
+
+// What a launcher decides about one ConvCall before it launches: written by the family's choose() (argument checks, measured rules, environment
+// overrides; host only, no launch, no device memory), read by the launcher, which fills its kernel arguments and calls the tile's table row.
+// osvos_conv3x3_plan reports it without launching (tests/test_conv_plan_cpu.py pins it for every layer of the network)
+enum ConvFamily {
+  CONV_F32 = OSVOS_CONV_FAMILY_F32, CONV_F32X3 = OSVOS_CONV_FAMILY_F32X3, CONV_BF16 = OSVOS_CONV_FAMILY_BF16, CONV_BF16_DMA = OSVOS_CONV_FAMILY_BF16_DMA,
+  CONV_BF16_P64 = OSVOS_CONV_FAMILY_BF16_P64, CONV_BF16_W2 = OSVOS_CONV_FAMILY_BF16_W2
+};
+struct ConvPlan {
+  int family = CONV_F32;
+  int tile = 0;                        // row of the family's tile table (two-piece: public id - 40; LDS-DMA: the variant, public id - 30; p64: the epilogue mode)
+  int map = 0;                         // 1: XCD-local block order (p64: 2 = its banded form)
+  int ksplit = 1;                      // fp32 families: K parts; > 1: partial sums into part_ws and a finalize launch behind the convolution
+  int sk_grid = 0, sk_order = 0;       // f32x3 stream-K: persistent workgroups (0 = plain grid) and their tile order
+  int presplit = 0, pipe = 0;          // f32x3 loop form: reads the pre-split pack (else splits the fp32 pack itself); the pipelined K loop (OSVOS_X3_PIPE)
+  int pool_after = 0;                  // bf16 family: the tile cannot pool in its epilogue -- the pooling kernel is a separate launch behind the convolution
+};
+// chooses the family by dtype and by what the call carries, and launches (the rule: api.cpp)
+int osvos_conv3x3_dispatch(const ConvCall& c, int dtype);
+// f32x3: weights pre-split once per pack (default) or re-split by every workgroup from the fp32 pack (OSVOS_X3_PRESPLIT=0; bit-identical).  Read by
+// the network's pack and by its convolutions' dispatch, nowhere below them: an op-level call uses the pack it is handed
+inline bool osvos_x3_presplit() {
+  static const bool on = [] { const char* e = getenv("OSVOS_X3_PRESPLIT"); return !(e && e[0] == '0'); }();
+  return on;
+}
 
 // One 3x3 weight-gradient launch (dw[co][ci][tap] = sum over pixels of dy[co] * x[ci] shifted by the tap; db = sum of dy), as every launcher below
 // takes it.  Host only, like ConvCall.  Each launcher states which operand formats it takes and rejects the others with an argument error.
@@ -71,6 +95,7 @@ int osvos_wgrad_reduce_launch(const float* slab, const float* bslab, float* dw, 
 
 // exact fp32 (conv3x3_f32.hip): fp32 tensors and fp32 pack, Cin % 8 == 0
 int osvos_conv3x3_f32(const ConvCall& c);
+int osvos_conv3x3_f32_plan(const ConvCall& c, ConvPlan* p);
 size_t osvos_conv3x3_splitk_ws_bytes_f32(int N, int H, int W, int Cout);
 int osvos_conv3x3_splitk_finalize_f32(const float* part, const float* bias, const float* mask, float* y, long npix, int Cout, int y_cs,
                                       int ksplit, int relu, hipStream_t stream);
@@ -81,6 +106,7 @@ int osvos_conv3x3_f32x3_num_tiles(void);
 size_t osvos_conv3x3_f32x3_streamk_ws_bytes(void);
 size_t osvos_conv3x3_f32x3_streamk_ticket_bytes(void);
 int osvos_conv3x3_f32x3(const ConvCall& c);
+int osvos_conv3x3_f32x3_plan(const ConvCall& c, ConvPlan* p);
 // f32x3 weight gradient (wgrad_f32x3.hip): fp32 x / dy, three-way bf16 split, fp32 slabs + the shared reduce
 bool osvos_wgrad_f32x3_applicable(int Cin, int Cin_s, int Cout, int Cout_s);
 bool osvos_wgrad_f32x3_skinny_applicable(int Cin, int Cin_s, int Cout, int Cout_s);
@@ -138,21 +164,25 @@ int osvos_head_generic_param_grads(const float* wup, const float* wf16, const do
 int osvos_head_dw1(const double* G1, float* dw, int k, int accumulate, hipStream_t stream);
 
 // bf16-operand MFMA convolution (conv3x3_bf16.hip): x fp32 or bf16, bf16 pack, fp32 and / or bf16 result.  Tile ids: 0-11 register-staged,
-// 30-37 LDS-DMA staged and 38 persistent (bf16 x only; handed on to the two launchers below), 40-45 two-piece weights
+// 30-37 LDS-DMA staged and 38 persistent (bf16 x only; its plan hands them to the two launchers below), 40-45 two-piece weights
 int osvos_pack_fwd_bf16(const float* w, void* wpk, int Cout, int Cin, hipStream_t stream);
 int osvos_pack_dgrad_bf16(const float* w, void* wpk, int Cout, int Cin, hipStream_t stream);
 int osvos_conv3x3_bf16mfma(const ConvCall& c);
+int osvos_conv3x3_bf16mfma_plan(const ConvCall& c, ConvPlan* p);
 int osvos_conv3x3_bf16mfma_num_tiles(void);
 int osvos_conv3x3_bf16w2_tiles_impl(int* tiles, int max);
 int osvos_conv3x3_bf16mfma_xb_tiles(int* tiles, int max);
 // LDS-DMA staged variant (conv3x3_bf16_dma.hip; bf16 x, single-piece pack): variant = tile id - 30 (0-3: 256 px x 128 / 64 co with 4 waves,
-// 512 px x 128 / 64 co with 8 waves; 4, 5: persistent forms; 6, 7: resident-filter persistent forms for Cin = 64); map: XCD-local block map
+// 512 px x 128 / 64 co with 8 waves; 4, 5: persistent forms; 6, 7: resident-filter persistent forms for Cin = 64).  The bf16 family's choose()
+// names the variant and the map in the plan; *_plan checks the call against them and completes the plan, the launcher takes it as it is
 bool osvos_conv3x3_bf16_dma_applicable(int Cin, int Cout, int y_cs);
-int osvos_conv3x3_bf16_dma(const ConvCall& c, int variant, int map);
-// Cin = 64, bf16 in / out: persistent, resident filter, deferred + skewed packed epilogue (conv3x3_bf16_p64.hip; tile id 38)
-bool osvos_conv3x3_bf16_p64_applicable(int Cin, int Cout, int y_cs, bool has_y_f32, bool has_tensor_mask, bool has_mask_bits, bool has_y_bits, bool has_pool,
-                                       int relu);
-int osvos_conv3x3_bf16_p64(const ConvCall& c, int map);
+int osvos_conv3x3_bf16_dma_num_variants(void);
+int osvos_conv3x3_bf16_dma_plan(const ConvCall& c, ConvPlan* p);
+int osvos_conv3x3_bf16_dma(const ConvCall& c, const ConvPlan& p);
+// Cin = 64, bf16 in / out: persistent, resident filter, deferred + skewed packed epilogue (conv3x3_bf16_p64.hip; tile id 38); plan as above
+bool osvos_conv3x3_bf16_p64_applicable(const ConvCall& c);
+int osvos_conv3x3_bf16_p64_plan(const ConvCall& c, ConvPlan* p);
+int osvos_conv3x3_bf16_p64(const ConvCall& c, const ConvPlan& p);
 
 // bf16-operand weight gradient (fp32 tensors): wgrad_bf16.hip
 bool osvos_wgrad_bf16_applicable(int Cin_s, int Cout);

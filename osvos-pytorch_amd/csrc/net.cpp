@@ -251,12 +251,6 @@ int stream_wait(hipStream_t waiter, hipStream_t on) {
   return 0;
 }
 
-// f32x3: weights pre-split once per pack (default) or re-split by every workgroup from the fp32 pack (OSVOS_X3_PRESPLIT=0; bit-identical)
-inline bool use_presplit() {
-  static const bool on = [] { const char* e = getenv("OSVOS_X3_PRESPLIT"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
 // The convolution of layer l (forward) or its data gradient (dgrad: Cin and Cout swap roles) on an h x w map, as far as the layer table and the
 // packed parameters and the call's f32x3 `pieces` decide it; the caller adds operands, results and workspaces by name.  Precision 'bf16w2':
 // forward packs have two pieces
@@ -277,20 +271,6 @@ ConvCall conv_of(const ConvDesc& dl, int l, bool dgrad, const void* wbuf, const 
 inline void set_x(ConvCall& c, Tensor t) { c.x = t.b ? t.b : t.f; c.x_bf16 = t.b != nullptr; }                // (the bf16 view is preferred when present)
 inline void set_mask(ConvCall& c, Tensor t) { c.mask = t.b ? t.b : t.f; c.mask_bf16 = t.b != nullptr; }
 inline void set_y(ConvCall& c, Tensor t) { c.y = reinterpret_cast<float*>(t.f); c.y_bf16 = t.b; }
-
-// dtype dispatch of a network convolution: fp32 launches may be cut along K (split-K, partial sums in c.part_ws) when the layer is too small to
-// balance across 256 CUs; fused epilogues, bits and stream-K exist in the f32x3 / bf16 families only (fuse_pool() etc. say when the caller may
-// ask for them) and the exact kernels ignore them
-inline int conv_main(ConvCall c, int dtype) {
-  if (dtype == OSVOS_F32_X3 && osvos_conv3x3_f32x3_applicable(c.Cin, c.Cout, c.y_cs)) {    // three-way bf16 split on the bf16 matrix pipe
-    // (with a pre-split pack the fp32 pack of the layer is not even built -- osvos_net_pack -- so it is not handed over either)
-    if (!use_presplit()) c.wpk3 = nullptr;
-    if (c.wpk3 != nullptr) c.wpk = nullptr;
-    return osvos_conv3x3_f32x3(c);
-  }
-  if (dtype == OSVOS_F32 || dtype == OSVOS_F32_X3) return osvos_conv3x3_f32(c);
-  return osvos_conv3x3_bf16mfma(c);
-}
 
 // f32x3 and the bf16-store mode: the forward max-pool of a stage boundary runs as an epilogue of the stage's last convolution (epi.h).
 // Measured at 854x480 batch 1 (profiles/r03_ab_fusions.txt): saves its launch and 20 us (1.473 -> 1.451 ms of forward convolutions +
@@ -399,7 +379,7 @@ int osvos_net_pack(const float* const* params, void* wbuf, int dtype_, int with_
   int ns = 0;
   // f32x3 with pre-split weights: the fp32 packs are read only where no pre-split pack exists (conv1_1 forward: the exact kernel) and by
   // the input-gradient kernel (layer 0's data-gradient pack); all pre-split packs are formed by ONE launch
-  const bool x3ps = dtype == OSVOS_F32_X3 && use_presplit();
+  const bool x3ps = dtype == OSVOS_F32_X3 && osvos_x3_presplit();
   const float* xw[OSVOS_PACK_MAX]; void* xd[OSVOS_PACK_MAX]; int xco[OSVOS_PACK_MAX], xci[OSVOS_PACK_MAX], xdg[OSVOS_PACK_MAX], xhalf[OSVOS_PACK_MAX];
   void* xlo[OSVOS_PACK_MAX];      // precision 'bf16w2': lo planes of the forward packs (NULL: single-piece entry)
   int nx = 0;
@@ -509,7 +489,7 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
         }
         c.part_ws = at(ws, L.conv_part);
         c.sk_ws = sk_ws;
-        rc = conv_main(c, dtype);
+        rc = osvos_conv3x3_dispatch(c, dtype);
         cur = act;
       }
       if (rc) return rc;
@@ -527,7 +507,7 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
         set_x(c, cur);
         c.y = reinterpret_cast<float*>(at(ws, L.prep[i]));
         if (L.side_part[i] != (size_t)-1) c.part_ws = at(ws, L.side_part[i]);
-        rc = conv_main(c, dtype);
+        rc = osvos_conv3x3_dispatch(c, dtype);
       }
       if (rc) return rc;
       float* sc = reinterpret_cast<float*>(at(ws, L.score[i]));
@@ -654,17 +634,10 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
   for (int i = 0; i < 4; ++i) {
     const int si = i + 1;
     const Tensor dprep = L.view(ws, L.dprep[i], L.dprep_b[i]);
-    if (generic)
-      rc = osvos_head_bwd_generic(reinterpret_cast<const float*>(at(ws, L.prep[i])), douts[i], dfused, reinterpret_cast<const float*>(at(wbuf, P.f1[i])),
-                                  reinterpret_cast<const float*>(at(wbuf, P.weff[i])), reinterpret_cast<const float*>(at(wbuf, P.wd[i])),
-                                  reinterpret_cast<float*>(dprep.f), dprep.b, acc + (size_t)i * OSVOS_HEAD_MAX_BLOCKS * 34,
-                                  N, H, W, L.hs[si], L.ws[si], i, stream);
-    else
-      rc = osvos_head_bwd_f32(reinterpret_cast<const float*>(at(ws, L.prep[i])), douts[i], dfused, reinterpret_cast<const float*>(at(wbuf, P.f1[i])),
-                        reinterpret_cast<const float*>(at(wbuf, P.f16[i])), reinterpret_cast<const float*>(at(wbuf, P.wd[i])),
-                        reinterpret_cast<const float*>(at(wbuf, P.wf)) + 16 * i, reinterpret_cast<float*>(dprep.f),
-                        dprep.b, acc + (size_t)i * OSVOS_HEAD_MAX_BLOCKS * 34,
-                        N, H, W, L.hs[si], L.ws[si], i, stream);
+    rc = osvos_head_bwd_generic(reinterpret_cast<const float*>(at(ws, L.prep[i])), douts[i], dfused, reinterpret_cast<const float*>(at(wbuf, P.f1[i])),
+                                reinterpret_cast<const float*>(at(wbuf, P.weff[i])), reinterpret_cast<const float*>(at(wbuf, P.wd[i])),
+                                reinterpret_cast<float*>(dprep.f), dprep.b, acc + (size_t)i * OSVOS_HEAD_MAX_BLOCKS * 34,
+                                N, H, W, L.hs[si], L.ws[si], i, stream);
     if (rc) return rc;
     part[i] = acc + (size_t)i * OSVOS_HEAD_MAX_BLOCKS * 34;
     nblk[i] = osvos_head_bwd_blocks(N, L.hs[si], L.ws[si], i);
@@ -756,7 +729,7 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
       set_mask(c, L.view(ws, L.act[lx]));
       if (L.bits[lx] != (size_t)-1) c.mask_bits = reinterpret_cast<const unsigned*>(at(ws, L.bits[lx]));
     }
-    rc = conv_main(c, dtype);
+    rc = osvos_conv3x3_dispatch(c, dtype);
     if (rc) return rc;
     if (st != stream) {
       side_ev[i] = event_pool().next();
@@ -801,7 +774,7 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
         set_x(c, dy);
         c.y = reinterpret_cast<float*>(at(ws, L.dxin));
         c.y_cs = 4;
-        rc = conv_main(c, dtype);
+        rc = osvos_conv3x3_dispatch(c, dtype);
         if (rc) return rc;
         rc = osvos_nhwc_to_nchw(at(ws, L.dxin), dx_nchw, N, 3, H, W, 4, dtype, stream);
         if (rc) return rc;
@@ -820,7 +793,7 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
     if (first_of_stage) {
       // through the pool into the previous stage's output (+ that stage's side branch, + ReLU mask)
       set_y(c, L.view(ws, L.dpool[si]));
-      if ((rc = conv_main(c, dtype))) return rc;
+      if ((rc = osvos_conv3x3_dispatch(c, dtype))) return rc;
       const int ps2 = si - 1;
       const void* dside = ps2 >= 1 ? at(ws, L.dside[ps2 - 1]) : nullptr;
       if (dbg_skip() & 2) continue;
@@ -840,7 +813,7 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
       set_y(c, L.view(ws, L.dy[l - 1]));
       set_mask(c, L.view(ws, L.act[l - 1]));
       if (L.bits[l - 1] != (size_t)-1) c.mask_bits = reinterpret_cast<const unsigned*>(at(ws, L.bits[l - 1]));
-      if ((rc = conv_main(c, dtype))) return rc;
+      if ((rc = osvos_conv3x3_dispatch(c, dtype))) return rc;
     }
   }
   if ((rc = join())) return rc;         // everything is back on `stream` when the call returns

@@ -618,7 +618,7 @@ struct WbChoice {
 };
 WbChoice choose(int N, int H, int W, int Cin_s, int Cout, int xb) {
   WbChoice ch;
-  static const int form_env = getenv("OSVOS_WGRAD_FORM") ? atoi(getenv("OSVOS_WGRAD_FORM")) : -1;
+  OSVOS_ENV_INT(form_env, "OSVOS_WGRAD_FORM", -1);
 #ifdef OSVOS_WGRAD_ALL_FORMS
   ch.form = xb ? (form_env >= 0 ? form_env : kDefaultForm) : 0;
 #else      // the shipped library holds two forms: 0 (first staging form; the only one for fp32 tensors) and 3 (pixel-major, the default for bf16 tensors)
@@ -627,7 +627,7 @@ WbChoice choose(int N, int H, int W, int Cin_s, int Cout, int xb) {
   ch.wide = ch.form >= kWideForm && Cout % 128 == 0;        // eight-wave form: 128-cout tiles
   ch.p = make_plan(N, H, W, Cin_s, Cout, ch.wide ? 128 : BCO);
   ch.blocks = (long)ch.p.nsplit * ch.p.nco_t * ch.p.nci_t;
-  static const int map_env = getenv("OSVOS_WGRAD_MAP") ? atoi(getenv("OSVOS_WGRAD_MAP")) : -1;
+  OSVOS_ENV_INT(map_env, "OSVOS_WGRAD_MAP", -1);
   ch.map = (map_env >= 0 ? map_env : kDefaultMap) == 1 && ch.blocks % 8 == 0 ? 1 : 0;
   return ch;
 }
@@ -678,54 +678,32 @@ int osvos_conv3x3_wgrad_bf16mfma(const WgradCall& c) {
   const long blocks = ch.blocks;
   a.map = ch.map;
   a.prof = g_wgrad_prof;
-  static const int dbg_env = getenv("OSVOS_WGRAD_DBG") ? atoi(getenv("OSVOS_WGRAD_DBG")) : 0;
+  OSVOS_ENV_INT(dbg_env, "OSVOS_WGRAD_DBG", 0);
   a.dbg = dbg_env;
   constexpr size_t lds = (size_t)DY_BYTES + X_BYTES;
-  static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};      // hipFuncSetAttribute is per device
-  bool& attr_set = attr_set_dev[osvos_current_device()];
-  if (!attr_set) {
-    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16_kernel<0>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16_kernel<1>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16_kernel<0>>(lds)) return rc;
+  if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16_kernel<1>>(lds)) return rc;
 #ifdef OSVOS_WGRAD_ALL_FORMS
   if (phase != WGRAD_REDUCE && form >= 4 && wide) {                // LDS-DMA forms: 4 fragments one stage ahead, 5 ping-pong segments
-    static bool attr4_set_dev[OSVOS_MAX_DEVICES] = {};
-    bool& attr4_set = attr4_set_dev[osvos_current_device()];
     constexpr int lds_dma = (int)DM::LDS;
-    if (!attr4_set) {
-      OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16dma_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_dma));
-      OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16dma_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_dma));
-      attr4_set = true;
-    }
+    if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16dma_kernel<0>>(lds_dma)) return rc;
+    if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16dma_kernel<1>>(lds_dma)) return rc;
     if (form == 5) hipLaunchKernelGGL(wgrad_bf16dma_kernel<1>, dim3((unsigned)blocks), dim3(512), lds_dma, stream, a);
     else hipLaunchKernelGGL(wgrad_bf16dma_kernel<0>, dim3((unsigned)blocks), dim3(512), lds_dma, stream, a);
     OSVOS_LAUNCH_CHECK();
   } else
 #endif
   if (phase != WGRAD_REDUCE && form >= 3) {
-    static bool attr3_set_dev[OSVOS_MAX_DEVICES] = {};      // per device, like every other kernel attribute
-    bool& attr3_set = attr3_set_dev[osvos_current_device()];
     constexpr size_t lds4 = PM<4>::LDS, lds8 = PM<8>::LDS;
-    if (!attr3_set) {
-      OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16pm_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4));
-      OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16pm_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8));
-      attr3_set = true;
-    }
+    if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16pm_kernel<4>>(lds4)) return rc;
+    if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16pm_kernel<8>>(lds8)) return rc;
     if (wide) hipLaunchKernelGGL(wgrad_bf16pm_kernel<8>, dim3((unsigned)blocks), dim3(512), lds8, stream, a);
     else hipLaunchKernelGGL(wgrad_bf16pm_kernel<4>, dim3((unsigned)blocks), dim3(256), lds4, stream, a);
     OSVOS_LAUNCH_CHECK();
 #ifdef OSVOS_WGRAD_ALL_FORMS
   } else if (phase != WGRAD_REDUCE && form != 0) {
-    static bool attr2_set_dev[OSVOS_MAX_DEVICES] = {};
-    bool& attr2_set = attr2_set_dev[osvos_current_device()];
-    if (!attr2_set) {
-      OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16v2_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsV2));
-      OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16v2_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsV2w));
-      attr2_set = true;
-    }
+    if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16v2_kernel<4>>(kLdsV2)) return rc;
+    if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16v2_kernel<8>>(kLdsV2w)) return rc;
     if (wide) hipLaunchKernelGGL(wgrad_bf16v2_kernel<8>, dim3((unsigned)blocks), dim3(512), kLdsV2w, stream, a);
     else hipLaunchKernelGGL(wgrad_bf16v2_kernel<4>, dim3((unsigned)blocks), dim3(256), kLdsV2, stream, a);
     OSVOS_LAUNCH_CHECK();

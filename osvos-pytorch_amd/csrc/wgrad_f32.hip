@@ -414,13 +414,7 @@ WgPlan make_plan(int N, int H, int W, int Cin_s, int Cout) {
 template <int CB, int IB, int PIPE, int DBUF, int OCC, int PWT = 32>
 int launch_wgrad(const WgArgs& a, long blocks, hipStream_t stream) {
   constexpr size_t lds = (size_t)(DBUF ? 2 : 1) * (PPIX * CB * 32 + Geo<PWT>::XPIX * IB * 32) * 4;
-  static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};      // hipFuncSetAttribute is per device
-  bool& attr_set = attr_set_dev[osvos_current_device()];
-  if (!attr_set) {
-    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_f32_kernel<CB, IB, PIPE, DBUF, OCC, PWT>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  if (int rc = osvos_set_dyn_lds_once<&wgrad_f32_kernel<CB, IB, PIPE, DBUF, OCC, PWT>>(lds)) return rc;
   hipLaunchKernelGGL((wgrad_f32_kernel<CB, IB, PIPE, DBUF, OCC, PWT>), dim3((unsigned)blocks), dim3(256), lds, stream, a);
   OSVOS_LAUNCH_CHECK();
   return 0;

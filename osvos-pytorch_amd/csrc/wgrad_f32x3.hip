@@ -464,14 +464,8 @@ int block_map3(long blocks) {
 
 template <int PH, int WAVES, int S16 = 0, int ILV = 0, int NP = 3, int HP = 0, int OA = 0>
 int launch3(const W3Args& a, long blocks, hipStream_t stream) {
-  static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};
-  bool& attr_set = attr_set_dev[osvos_current_device()];
-  if (!attr_set) {
-    OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_f32x3_kernel<PH, WAVES, S16, ILV, NP, HP, OA>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)G3<PH, WAVES, S16>::LDS));
-    attr_set = true;
-  }
   constexpr size_t lds = G3<PH, WAVES, S16>::LDS;
+  if (int rc = osvos_set_dyn_lds_once<&wgrad_f32x3_kernel<PH, WAVES, S16, ILV, NP, HP, OA>>(lds)) return rc;
   hipLaunchKernelGGL((wgrad_f32x3_kernel<PH, WAVES, S16, ILV, NP, HP, OA>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, stream, a);
   OSVOS_LAUNCH_CHECK();
   return 0;

@@ -552,13 +552,7 @@ int osvos_conv3x3_wgrad_small_f32(const WgradCall& c) {
     const C3Args a = c3_args(c, p);
     OSVOS_ARG_CHECK(!c.x_bf16, "wgrad c3: x (3 channels) must be fp32");
     constexpr size_t lds = (size_t)(C3_PPIX * 64 + C3_XPIX * 4) * 4;
-    static bool attr_set_dev[OSVOS_MAX_DEVICES] = {};      // hipFuncSetAttribute is per device
-    bool& attr_set = attr_set_dev[osvos_current_device()];
-    if (!attr_set) {
-      OSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_c3_f32_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      attr_set = true;
-    }
+    if (int rc = osvos_set_dyn_lds_once<&wgrad_c3_f32_kernel>(lds)) return rc;
     if (phase != WGRAD_REDUCE) {
       hipLaunchKernelGGL(wgrad_c3_f32_kernel, dim3(p.nsplit), dim3(256), lds, stream, a);
       OSVOS_LAUNCH_CHECK();

@@ -275,6 +275,15 @@ def wgrad_wide_plan(n, h, w, cin_s, cout, dtype, bf16_tensors=False):
     return dict(zip(("pw", "ph", "npx", "npy", "npatches", "per_split", "nsplit", "nco_t", "nci_t", "blocks", "map", "wide"), [int(v) for v in out]))
 
 
+def conv3x3_plan(n, h, w, cin, cout, dtype, flags, y_cs=None, tile=-1, ksplit=0, sk_grid=0):
+    """What the convolution launchers decide for a call (osvos_conv3x3_plan; host only, needs no GPU): dict of family, tile, map, ksplit,
+    finalize, sk_grid, sk_order, presplit, pipe, pool_after.  dtype: the dtype word (with BF16_W2 / the X3 piece flags); flags: OSVOS_PLAN_* bits
+    of include/osvos_hip.h -- what the call carries."""
+    out = (C.c_int * 10)()
+    check(lib().osvos_conv3x3_plan(n, h, w, cin, cout, cout if y_cs is None else y_cs, dtype, flags, tile, ksplit, sk_grid, out), "conv3x3_plan")
+    return dict(zip(("family", "tile", "map", "ksplit", "finalize", "sk_grid", "sk_order", "presplit", "pipe", "pool_after"), [int(v) for v in out]))
+
+
 def conv3x3_wgrad_c3_bf16dy(x, dy, cout, want_bias=True, accumulate_into=None, ws=None):
     """conv1_1's weight gradient of the bf16-store mode: x fp32 [N,H,W,8] (channels 3..7 zero), dy torch.bfloat16 [N,H,W,Cout_s]
     -> (dW fp32 [cout,3,3,3], db fp32 [cout] | None).  ws: the caller's workspace instead of a fresh one."""
