@@ -255,6 +255,35 @@ int osvos_wgrad_c3_plan(int N, int H, int W, int bf16_dy, int* out);
  * workgroup of split s walks patches [s per_split, min((s + 1) per_split, npatches)), numbered x fastest, then y, then image.  Any other
  * shape / dtype is an argument error. */
 int osvos_wgrad_wide_plan(int N, int H, int W, int Cin_s, int Cout, int dtype, int bf16_tensors, int* out);
+/* host only, launches nothing: what the weight-gradient launchers decide for a call -- which kernel family takes it, which of the family's kernels,
+ * how the pixels are cut into patches and splits, the grid and the reduce behind it -- through the same code the launches go through
+ * (osvos_net_backward builds its calls the same way: Cout_s = Cout, x bf16 in the bf16-store mode except conv1_1's, dy bf16 in that mode).
+ * dtype: as osvos_conv3x3_wgrad, for OSVOS_F32_X3 with the piece flags OSVOS_FLAG_X3_TWO_PIECES / OSVOS_FLAG_X3_HALF_PIECES.  flags: what the call
+ * carries (OSVOS_WGRAD_PLAN_*).  out[OSVOS_WGRAD_PLAN_INTS] = {family (OSVOS_WGRAD_FAMILY_*), kernel (row of the family's kernel table, see below),
+ * patch width, patch height, npx, npy, npatches, per_split, nsplit, nco_t, nci_t, workgroups, 1 if the XCD-local block map is taken, reduce
+ * (OSVOS_WGRAD_REDUCE_*), floats of the weight slabs, floats of the bias partials (the workspace holds both; saturating at 2^31 - 1)}; the
+ * workgroups of split s walk patches [s per_split, min((s + 1) per_split, npatches)), numbered x fastest, then y, then image.
+ * Kernel rows.  F32: 0-3 = wgrad_f32_kernel<1,4,PIPE,DBUF,1> and 5-8 = <2,2,PIPE,DBUF,1> with PIPE + 2 DBUF = row / row - 5; 4 = <2,2,1,0,2,16>
+ * (16 x 4 patches); 9, 10 = <2,2,PIPE,0,2> (two workgroups per CU).  C3_F32 / C3_BF16 / CO16_F32: 0 / 1 / 2, the three skinny kernels.  F32X3:
+ * 3 * form + geometry, form 0 / 1 = two / three bf16 pieces with the staging addresses of OSVOS_WGRAD_X3_OLDADDR=1, 2 = two FP16 pieces, 3 = two
+ * bf16 pieces, 4 = three bf16 pieces; geometry 0 = the Cout 16 form, 1 = 16 x 6 patches, 2 = 16 x 4 patches.  BF16: 0 / 1 = wgrad_bf16_kernel<0 / 1>
+ * (fp32 / bf16 tensors), 2 / 3 = wgrad_bf16pm_kernel<4 / 8> (64- / 128-cout tiles).  A call no launcher takes is the launcher's argument error. */
+#define OSVOS_WGRAD_PLAN_X_BF16 0x1
+#define OSVOS_WGRAD_PLAN_DY_BF16 0x2
+#define OSVOS_WGRAD_PLAN_NO_BIAS 0x4   /* db = NULL */
+#define OSVOS_WGRAD_FAMILY_F32 0        /* exact fp32, the generic kernel */
+#define OSVOS_WGRAD_FAMILY_C3_F32 1     /* conv1_1, exact fp32 (wgrad_c3_f32_kernel) */
+#define OSVOS_WGRAD_FAMILY_C3_BF16 2    /* conv1_1 on the bf16 pipe (wgrad_c3_bf16_kernel) */
+#define OSVOS_WGRAD_FAMILY_CO16_F32 3   /* Cout = 16, exact fp32 (wgrad_co16_f32_kernel) */
+#define OSVOS_WGRAD_FAMILY_F32X3 4
+#define OSVOS_WGRAD_FAMILY_BF16 5
+#define OSVOS_WGRAD_REDUCE_T16 0        /* the transposing reduce, 16 waves per workgroup */
+#define OSVOS_WGRAD_REDUCE_T4 1         /* ... 4 waves */
+#define OSVOS_WGRAD_REDUCE_GENERIC 2    /* the generic reduce */
+#define OSVOS_WGRAD_REDUCE_OIHW 3       /* ... over reference-order slabs (OSVOS_WGRAD_VARIANT bit 3) */
+#define OSVOS_WGRAD_REDUCE_C3 4         /* conv1_1's own */
+#define OSVOS_WGRAD_PLAN_INTS 16
+int osvos_wgrad_plan(int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s, int dtype, int flags, int* out);
 
 /* ---- 2x2/2 max-pool, ceil_mode (aten::max_pool2d_with_indices, vgg_osvos.py:140) ---------- */
 int osvos_maxpool2x2(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream);

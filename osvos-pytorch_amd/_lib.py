@@ -79,6 +79,7 @@ PROTOTYPES = {
     "osvos_conv3x3_wgrad_c3_bf16dy": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "osvos_wgrad_c3_plan": (_i, [_i, _i, _i, _i, _vp]),
     "osvos_wgrad_wide_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp]),
+    "osvos_wgrad_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "osvos_conv3x3_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "osvos_maxpool2x2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "osvos_maxpool2x2_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -7,25 +7,41 @@
 #define NEED_F32(dtype, what)                                                                     \
   OSVOS_ARG_CHECK(osvos_dtype_built(dtype), "%s: dtype %d not built (fp32 tensors only)", what, (int)(dtype))
 
-// Which weight-gradient family takes the launch (kernels.h): two rules, by what the tensors are
-int osvos_wgrad_dispatch(const WgradCall& c, int dtype) {
+// Which weight-gradient family takes the launch (kernels.h): two rules, by what the tensors are.  NULL (and the error set): no kernel takes the call
+struct WgradEntry {
+  bool (*applicable)(const WgradCall&);
+  int (*plan)(const WgradCall&, WgradPlan*);
+  int (*launch)(const WgradCall&);
+};
+static bool wgrad_any(const WgradCall&) { return true; }      // the generic exact kernel: its choose() rejects what it cannot take
+static const WgradEntry* wgrad_family(const WgradCall& c, int dtype) {
+  static const WgradEntry f32 = {wgrad_any, osvos_wgrad_f32_plan, osvos_conv3x3_wgrad_f32},
+                          small = {osvos_wgrad_small_applicable, osvos_wgrad_small_plan, osvos_conv3x3_wgrad_small_f32},
+                          f32x3 = {osvos_wgrad_f32x3_applicable, osvos_wgrad_f32x3_plan, osvos_conv3x3_wgrad_f32x3},
+                          bf16 = {osvos_wgrad_bf16_applicable, osvos_wgrad_bf16_plan, osvos_conv3x3_wgrad_bf16mfma};
   if (!c.x_bf16 && !c.dy_bf16) {      // fp32 tensors: by dtype
     // the wide trunk layers go through the bf16 MFMA kernel; conv1_1 (Cin 3) and side_prep (Cout 16) keep
     // their exact-fp32 skinny kernels (5 % of the weight-gradient FLOPs)
-    if (dtype == OSVOS_F32_BF16MFMA && c.Cin == c.Cin_s && c.Cout % 64 == 0 && osvos_wgrad_bf16_applicable(c.Cin_s, c.Cout))
-      return osvos_conv3x3_wgrad_bf16mfma(c);
+    if (dtype == OSVOS_F32_BF16MFMA && c.Cout % 64 == 0 && bf16.applicable(c)) return &bf16;
     // f32x3: the wide trunk layers and side_prep (the S16 form) on the bf16 matrix pipe with split operands; conv1_1 keeps its exact skinny kernel
-    if (dtype == OSVOS_F32_X3 && (osvos_wgrad_f32x3_applicable(c.Cin, c.Cin_s, c.Cout, c.Cout_s) || osvos_wgrad_f32x3_skinny_applicable(c.Cin, c.Cin_s, c.Cout, c.Cout_s)))
-      return osvos_conv3x3_wgrad_f32x3(c);
-    return osvos_conv3x3_wgrad_f32(c);
+    if (dtype == OSVOS_F32_X3 && f32x3.applicable(c)) return &f32x3;
+    return small.applicable(c) ? &small : &f32;
   }
   // a bf16 tensor (the network's bf16-store mode, osvos_conv3x3_wgrad_bf16act): the wide layers AND side_prep (Cout 16: one 64-cout tile with 16
   // live rows, still 2x faster than the skinny kernel -- wgrad_bf16.hip) read both operands as bf16 on the bf16 MFMA kernel; conv1_1 (Cin 3) takes
   // the skinny kernel with its fp32 input and the bf16 dy.  (The skinny Cout = 16 kernel's bf16-x path is reached by no layer of the network.)
-  if (osvos_wgrad_bf16_applicable(c.Cin_s, c.Cout) && c.Cin == c.Cin_s) return osvos_conv3x3_wgrad_bf16mfma(c);
-  const int r = osvos_conv3x3_wgrad_small_f32(c);
-  if (r == 1) osvos_set_error("net_backward: no bf16-store weight-gradient kernel for layer Cin %d/%d Cout %d", c.Cin, c.Cin_s, c.Cout);
-  return r;
+  if (bf16.applicable(c)) return &bf16;
+  if (small.applicable(c)) return &small;
+  osvos_set_error("net_backward: no bf16-store weight-gradient kernel for layer Cin %d/%d Cout %d", c.Cin, c.Cin_s, c.Cout);
+  return nullptr;
+}
+int osvos_wgrad_dispatch(const WgradCall& c, int dtype) {
+  const WgradEntry* e = wgrad_family(c, dtype);
+  return e ? e->launch(c) : 1;
+}
+int osvos_wgrad_dispatch_plan(const WgradCall& c, int dtype, WgradPlan* p) {
+  const WgradEntry* e = wgrad_family(c, dtype);
+  return e ? e->plan(c, p) : 1;
 }
 
 // Which convolution family takes the launch (kernels.h): by dtype, by the public tile id and by what the call carries.  Edits the call it is
@@ -275,6 +291,7 @@ int osvos_conv3x3_splitk(const void* x, const void* wpk, const float* bias, cons
   return osvos_conv3x3_dispatch(c, dtype);
 }
 
+// the most any family that osvos_wgrad_dispatch can hand this shape to under `dtype` asks for (each from the plans its launches make)
 size_t osvos_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int dtype) {
   const size_t f = osvos_wgrad_ws_bytes_f32(N, H, W, Cin, Cout);
   const size_t b = dtype == OSVOS_F32_BF16MFMA ? osvos_wgrad_bf16_ws_bytes(N, H, W, Cin, Cout) : osvos_wgrad_f32x3_ws_bytes(N, H, W, Cin, Cout);
@@ -287,16 +304,49 @@ int osvos_conv3x3_wgrad(const void* x, const void* dy, void* ws, float* dw, floa
   return osvos_wgrad_dispatch(wgrad_call(x, dy, 0, ws, dw, db, N, H, W, Cin, Cin_s, Cout, Cout_s, accumulate, stream), dtype);
 }
 
-// host only: which wide kernel osvos_wgrad_dispatch hands this shape to, and what that launcher's own plan / form / map selection says
+// host only: what osvos_wgrad_dispatch and the family's choose() decide for a call of this shape that carries what `flags` says
+static char g_some[8];      // any non-null address stands for a tensor the call carries: no choose() reads through one
+static WgradCall wgrad_plan_call(int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s, int dtype_, int flags) {
+  WgradCall c;
+  c.x = c.dy = c.ws = g_some; c.dw = reinterpret_cast<float*>(g_some);
+  if (!(flags & OSVOS_WGRAD_PLAN_NO_BIAS)) c.db = c.dw;
+  c.x_bf16 = (flags & OSVOS_WGRAD_PLAN_X_BF16) != 0; c.dy_bf16 = (flags & OSVOS_WGRAD_PLAN_DY_BF16) != 0;
+  c.N = N; c.H = H; c.W = W; c.Cin = Cin; c.Cin_s = Cin_s; c.Cout = Cout; c.Cout_s = Cout_s;
+  c.pieces = (dtype_ & 0xff) != OSVOS_F32_X3 ? 3 : (dtype_ & OSVOS_FLAG_X3_HALF_PIECES) ? 22 : (dtype_ & OSVOS_FLAG_X3_TWO_PIECES) ? 2 : 3;
+  return c;
+}
+int osvos_wgrad_plan(int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s, int dtype_, int flags, int* out) {
+  OSVOS_ARG_CHECK(out != nullptr, "wgrad_plan: null result array");
+  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "wgrad_plan: bad shape");
+  const int dtype = dtype_ & 0xff;
+  NEED_F32(dtype, "wgrad_plan");
+  WgradPlan p;
+  if (osvos_wgrad_dispatch_plan(wgrad_plan_call(N, H, W, Cin, Cin_s, Cout, Cout_s, dtype_, flags), dtype, &p)) return -1;
+  auto sat = [](size_t v) { return v > 0x7fffffffu ? 0x7fffffff : (int)v; };
+  const int v[OSVOS_WGRAD_PLAN_INTS] = {p.family, p.kernel, p.pw, p.ph, p.npx, p.npy, p.npatches, p.per_split, p.nsplit, p.nco_t, p.nci_t,
+                                        (int)p.blocks, p.map, p.reduce, sat(p.slab_floats), sat(p.bslab_floats)};
+  for (int k = 0; k < OSVOS_WGRAD_PLAN_INTS; ++k) out[k] = v[k];
+  return 0;
+}
+// the two older queries: fields of the same plans
+int osvos_wgrad_c3_plan(int N, int H, int W, int bf16_dy, int* out) {
+  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && out != nullptr, "wgrad_c3_plan: bad arguments");
+  WgradPlan p;
+  osvos_wgrad_c3_split(N, H, W, bf16_dy, &p);
+  out[0] = p.npx; out[1] = p.npy; out[2] = p.npatches; out[3] = p.per_split; out[4] = p.nsplit;
+  return 0;
+}
 int osvos_wgrad_wide_plan(int N, int H, int W, int Cin_s, int Cout, int dtype, int bf16_tensors, int* out) {
   OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && Cin_s > 0 && Cout > 0 && out != nullptr, "wgrad_wide_plan: bad arguments");
-  if (bf16_tensors) {
-    OSVOS_ARG_CHECK(dtype == OSVOS_F32_BF16MFMA, "wgrad_wide_plan: bf16 tensors go with dtype OSVOS_F32_BF16MFMA (got %d)", dtype);
-    return osvos_wgrad_bf16_plan(N, H, W, Cin_s, Cout, 1, out);
-  }
-  if (dtype == OSVOS_F32_X3) return osvos_wgrad_f32x3_plan(N, H, W, Cin_s, Cout, out);
-  OSVOS_ARG_CHECK(dtype == OSVOS_F32_BF16MFMA && Cout % 64 == 0, "wgrad_wide_plan: no wide weight-gradient kernel for dtype %d Cout %d on fp32 tensors", dtype, Cout);
-  return osvos_wgrad_bf16_plan(N, H, W, Cin_s, Cout, 0, out);
+  OSVOS_ARG_CHECK(!bf16_tensors || dtype == OSVOS_F32_BF16MFMA, "wgrad_wide_plan: bf16 tensors go with dtype OSVOS_F32_BF16MFMA (got %d)", dtype);
+  const WgradCall c = wgrad_plan_call(N, H, W, Cin_s, Cin_s, Cout, Cout, dtype, bf16_tensors ? OSVOS_WGRAD_PLAN_X_BF16 | OSVOS_WGRAD_PLAN_DY_BF16 : 0);
+  WgradPlan p;
+  if (osvos_wgrad_dispatch_plan(c, dtype, &p)) return -1;
+  OSVOS_ARG_CHECK(p.family == WGRAD_F32X3 || p.family == WGRAD_BF16, "wgrad_wide_plan: no wide weight-gradient kernel for dtype %d Cin %d Cout %d", dtype, Cin_s, Cout);
+  const int v[12] = {p.pw, p.ph, p.npx, p.npy, p.npatches, p.per_split, p.nsplit, p.nco_t, p.nci_t, (int)p.blocks, p.map,
+                     p.family == WGRAD_BF16 && p.nco_t * 64 < Cout};      // (128-cout tiles)
+  for (int k = 0; k < 12; ++k) out[k] = v[k];
+  return 0;
 }
 
 int osvos_maxpool2x2(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream) {

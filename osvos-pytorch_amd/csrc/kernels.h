@@ -87,11 +87,69 @@ struct WgradCall {
   int pieces = 3;                      // f32x3 family: pieces per operand, as ConvCall::pieces
   hipStream_t stream = nullptr;
 };
-// chooses the family by dtype and by what the tensors are, and launches (the rule: api.cpp)
+// What a launcher decides about one WgradCall before it launches, as ConvPlan above: written by the family's choose() (argument checks, measured
+// rules, environment overrides; host only, no HIP call, no device memory), read by the launcher, which fills its kernel arguments, launches
+// the family's table row `kernel` and then the reduce `reduce`.  osvos_wgrad_plan reports it without launching (tests/test_wgrad_plan_cpu.py pins
+// it for every layer of the network)
+enum WgradFamily {
+  WGRAD_F32 = OSVOS_WGRAD_FAMILY_F32, WGRAD_C3_F32 = OSVOS_WGRAD_FAMILY_C3_F32, WGRAD_C3_BF16 = OSVOS_WGRAD_FAMILY_C3_BF16,
+  WGRAD_CO16_F32 = OSVOS_WGRAD_FAMILY_CO16_F32, WGRAD_F32X3 = OSVOS_WGRAD_FAMILY_F32X3, WGRAD_BF16 = OSVOS_WGRAD_FAMILY_BF16
+};
+// which kernel sums the slabs: the shared transposing reduce with 16 or 4 waves, the shared generic reduce, the same over reference-order (OIHW)
+// slabs (OSVOS_WGRAD_VARIANT bit 3), conv1_1's own
+enum WgradReduce {
+  WGRAD_REDUCE_T16 = OSVOS_WGRAD_REDUCE_T16, WGRAD_REDUCE_T4 = OSVOS_WGRAD_REDUCE_T4, WGRAD_REDUCE_GENERIC = OSVOS_WGRAD_REDUCE_GENERIC,
+  WGRAD_REDUCE_OIHW = OSVOS_WGRAD_REDUCE_OIHW, WGRAD_REDUCE_C3 = OSVOS_WGRAD_REDUCE_C3
+};
+struct WgradPlan {
+  int family = WGRAD_F32;
+  int kernel = 0;                      // row of the family's kernel table
+  int pw = 0, ph = 0;                  // pixel patch
+  int npx = 0, npy = 0, npatches = 0;  // patches along x, along y, in all (x fastest, then y, then image)
+  int per_split = 0, nsplit = 0;       // the workgroups of split s walk patches [s per_split, min((s + 1) per_split, npatches)) and write slab s
+  int nco_t = 1, nci_t = 1;            // channel tiles
+  long blocks = 0;                     // workgroups: nsplit * nco_t * nci_t
+  int map = 0;                         // 1: XCD-local block order
+  size_t slab_floats = 0, bslab_floats = 0;      // the workspace: weight slabs, then the bias partials
+  int reduce = WGRAD_REDUCE_GENERIC;
+};
+// The arithmetic every family's plan shares.  Patches: pw x ph pixels over N frames.
+static inline void wgrad_patches(WgradPlan* p, int N, int H, int W, int pw, int ph) {
+  p->pw = pw; p->ph = ph;
+  p->npx = ceil_div(W, pw);
+  p->npy = ceil_div(H, ph);
+  p->npatches = N * p->npx * p->npy;
+}
+// Splits, from the patches and channel tiles already in the plan: aim at `target_workgroups` workgroups, keep at least `min_patches_per_split`
+// patches in a split and at most `max_splits` splits, then even the splits out.  A split writes slab_per_split + bslab_per_split floats.
+static inline void wgrad_split(WgradPlan* p, int target_workgroups, int min_patches_per_split, int max_splits, size_t slab_per_split,
+                               size_t bslab_per_split) {
+  int want = ceil_div(target_workgroups, p->nco_t * p->nci_t);
+  const int most = p->npatches / min_patches_per_split > 0 ? p->npatches / min_patches_per_split : 1;
+  if (want > most) want = most;
+  if (want > max_splits) want = max_splits;
+  if (want < 1) want = 1;
+  p->per_split = ceil_div(p->npatches, want);
+  p->nsplit = ceil_div(p->npatches, p->per_split);
+  p->blocks = (long)p->nsplit * p->nco_t * p->nci_t;
+  p->slab_floats = (size_t)p->nsplit * slab_per_split;
+  p->bslab_floats = (size_t)p->nsplit * bslab_per_split;
+}
+static inline size_t wgrad_plan_ws_bytes(const WgradPlan& p) { return align_up((p.slab_floats + p.bslab_floats) * sizeof(float), 256); }
+// a dense call of a shape, for the workspace queries (which know no tensors): Cin_s = 8 is conv1_1's padded 3-channel input
+static inline WgradCall wgrad_shape_call(int N, int H, int W, int Cin_s, int Cout) {
+  WgradCall c;
+  c.N = N; c.H = H; c.W = W; c.Cin = Cin_s == 8 ? 3 : Cin_s; c.Cin_s = Cin_s; c.Cout = c.Cout_s = Cout;
+  return c;
+}
+// chooses the family by dtype and by what the tensors are (the rule: api.cpp), and launches / only plans
 int osvos_wgrad_dispatch(const WgradCall& c, int dtype);
-// the slab reduce the families share (wgrad_f32.hip): slab [split][tap][co][ci] -> dw, bslab [split][co] -> db
-int osvos_wgrad_reduce_launch(const float* slab, const float* bslab, float* dw, float* db, int nsplit, int Cout, int Cin,
-                              int Cin_s, int accumulate, hipStream_t stream);
+int osvos_wgrad_dispatch_plan(const WgradCall& c, int dtype, WgradPlan* p);
+// the slab reduces the families share (wgrad_f32.hip): slab [split][tap][co][ci] -> dw, bslab [split][co] -> db.  *_kind: which of them takes a
+// layer (OSVOS_WGRAD_REDUCE_T); *_launch: launches `kind`
+int osvos_wgrad_reduce_kind(int nsplit, int Cout, int Cin, int Cin_s);
+int osvos_wgrad_reduce_launch(int kind, const float* slab, const float* bslab, float* dw, float* db, int nsplit, int Cout, int Cin, int Cin_s,
+                              int accumulate, hipStream_t stream);
 
 // exact fp32 (conv3x3_f32.hip): fp32 tensors and fp32 pack, Cin % 8 == 0
 int osvos_conv3x3_f32(const ConvCall& c);
@@ -108,13 +166,13 @@ size_t osvos_conv3x3_f32x3_streamk_ticket_bytes(void);
 int osvos_conv3x3_f32x3(const ConvCall& c);
 int osvos_conv3x3_f32x3_plan(const ConvCall& c, ConvPlan* p);
 // f32x3 weight gradient (wgrad_f32x3.hip): fp32 x / dy, three-way bf16 split, fp32 slabs + the shared reduce
-bool osvos_wgrad_f32x3_applicable(int Cin, int Cin_s, int Cout, int Cout_s);
-bool osvos_wgrad_f32x3_skinny_applicable(int Cin, int Cin_s, int Cout, int Cout_s);
+// (the wide trunk layers, or side_prep's Cout = 16: the S16 form)
+bool osvos_wgrad_f32x3_wide_applicable(const WgradCall& c);
+bool osvos_wgrad_f32x3_skinny_applicable(const WgradCall& c);
+static inline bool osvos_wgrad_f32x3_applicable(const WgradCall& c) { return osvos_wgrad_f32x3_wide_applicable(c) || osvos_wgrad_f32x3_skinny_applicable(c); }
 size_t osvos_wgrad_f32x3_ws_bytes(int N, int H, int W, int Cin_s, int Cout);
 int osvos_conv3x3_wgrad_f32x3(const WgradCall& c);
-// host only: the launcher's plan, form and block map for a dense dY, as osvos_wgrad_wide_plan lays them out (out[12]); same in wgrad_bf16.hip
-int osvos_wgrad_f32x3_plan(int N, int H, int W, int Cin_s, int Cout, int* out);
-int osvos_wgrad_bf16_plan(int N, int H, int W, int Cin_s, int Cout, int xb, int* out);
+int osvos_wgrad_f32x3_plan(const WgradCall& c, WgradPlan* p);
 size_t osvos_wpack_x3_bytes(int M, int K);
 #define OSVOS_PACK_MAX 40
 // n packs (n <= OSVOS_PACK_MAX) in one launch: ws[k] OIHW fp32 [Couts[k]][Cins[k]][3][3] -> dsts[k]; dgrads[k] != 0: data-gradient form.
@@ -129,9 +187,12 @@ int osvos_pack_x3(const float* w, void* wpk3, int Cout, int Cin, int dgrad, int 
 bool osvos_dgrad_c3_applicable(int Cin, int Cout);
 int osvos_conv3x3_dgrad_c3_f32(const float* dy, const float* wpk_dgrad, float* dx_nchw, int N, int H, int W, int Cout, hipStream_t stream);
 int osvos_conv3x3_dgrad_c3_bf16mfma(const void* dy_bf16, const void* wpk_bf16_dgrad, float* dx_nchw, int N, int H, int W, int Cout, hipStream_t stream);
+// exact fp32 weight gradient, the generic kernel (wgrad_f32.hip): fp32 x and dy.  *_check: the argument checks every fp32-tensor call of the
+// exact kernels meets (the skinny launcher's too)
 size_t osvos_wgrad_ws_bytes_f32(int N, int H, int W, int Cin_s, int Cout);
-// exact fp32 weight gradient (wgrad_f32.hip): fp32 x and dy; hands conv1_1's and side_prep's shapes to the skinny launcher first
+int osvos_wgrad_f32_check(const WgradCall& c);
 int osvos_conv3x3_wgrad_f32(const WgradCall& c);
+int osvos_wgrad_f32_plan(const WgradCall& c, WgradPlan* p);
 int osvos_nchw_to_nhwc_f32(const float* src, float* dst, void* dstbf, int N, int C, int H, int W, int cpad, hipStream_t stream);
 int osvos_nhwc_to_nchw_f32(const float* src, float* dst, int N, int C, int H, int W, int cs, hipStream_t stream);
 int osvos_pack_fwd_f32(const float* w, float* wpk, int Cout, int Cin, hipStream_t stream);
@@ -184,12 +245,15 @@ bool osvos_conv3x3_bf16_p64_applicable(const ConvCall& c);
 int osvos_conv3x3_bf16_p64_plan(const ConvCall& c, ConvPlan* p);
 int osvos_conv3x3_bf16_p64(const ConvCall& c, const ConvPlan& p);
 
-// bf16-operand weight gradient (fp32 tensors): wgrad_bf16.hip
-bool osvos_wgrad_bf16_applicable(int Cin_s, int Cout);
+// bf16-operand weight gradient (wgrad_bf16.hip): x and dy both fp32 or both bf16 (the bf16-store mode of the network)
+bool osvos_wgrad_bf16_applicable(const WgradCall& c);
 size_t osvos_wgrad_bf16_ws_bytes(int N, int H, int W, int Cin_s, int Cout);
-// x and dy both fp32 or both bf16 (the bf16-store mode of the network)
 int osvos_conv3x3_wgrad_bf16mfma(const WgradCall& c);
+int osvos_wgrad_bf16_plan(const WgradCall& c, WgradPlan* p);
 // the skinny fp32 kernels (wgrad_small_f32.hip): Cin = 3 (conv1_1: x fp32, dy fp32 or bf16) and Cout = 16 (side_prep: dy fp32, x fp32 or bf16).
-// Returns 1 when the shape is neither (the caller falls through to another kernel)
+// *_applicable: the shape is one of the two (and OSVOS_WGRAD_GENERIC does not hand an fp32-tensor call to the generic kernel)
+bool osvos_wgrad_small_applicable(const WgradCall& c);
 size_t osvos_wgrad_small_ws_bytes(int N, int H, int W, int Cin_s, int Cout);
 int osvos_conv3x3_wgrad_small_f32(const WgradCall& c);
+int osvos_wgrad_small_plan(const WgradCall& c, WgradPlan* p);
+void osvos_wgrad_c3_split(int N, int H, int W, int bf16_pipe, WgradPlan* p);      // how either conv1_1 kernel cuts a frame (no checks; osvos_wgrad_c3_plan)

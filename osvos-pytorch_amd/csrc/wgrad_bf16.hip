@@ -572,149 +572,108 @@ __global__ __launch_bounds__(64 * WAVES) void wgrad_bf16pm_kernel(WbArgs a) {
 #undef OSVOS_WGRAD_FORMS_PART
 #endif
 
-#ifdef OSVOS_WGRAD_ALL_FORMS
-constexpr size_t kLdsV2 = (size_t)DY_BYTES + X_BYTES, kLdsV2w = (size_t)2 * DY_BYTES + X_BYTES;
-#endif
-
 constexpr int kDefaultMap = 1;      // bf16-input form: XCD-local split order (L2 hit rate 38 % -> 77 %, HBM reads / 3; OSVOS_WGRAD_MAP=0 turns it off)
 constexpr int kDefaultForm = 3;     // bf16-input kernel: 0 = first staging form, 1 = second (wgrad_bf16v2_kernel<4>), 2 = second with eight waves / 128-cout
 constexpr int kWideForm = 2;        // tiles where Cout allows (OSVOS_WGRAD_FORM)
 unsigned long long* g_wgrad_prof = nullptr;
 
-struct WbPlan {
-  int nco_t, nci_t, npx, npy, npatches, nsplit, per_split;
-  size_t slab_floats, bslab_floats;
+template <auto Kernel, int THREADS, size_t LDS>
+int launch_wb(const WbArgs& a, long blocks, hipStream_t stream) {
+  if (int rc = osvos_set_dyn_lds_once<Kernel>(LDS)) return rc;
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)blocks), dim3(THREADS), LDS, stream, a);
+  OSVOS_LAUNCH_CHECK();
+  return 0;
+}
+
+// the kernel table: each row with its workgroup size and its LDS bytes.  form: OSVOS_WGRAD_FORM as choose() reads it; sub: of the first staging
+// form 1 = bf16 tensors, of the others 1 = eight waves on 128-cout tiles.  The shipped library holds two forms: 0 (the only one for fp32 tensors)
+// and 3 (pixel-major, the default for bf16 tensors).  The probe forms (tools/native/wgrad_bf16_forms.inc: 1 item loads inside the k-loop, 4 / 5
+// LDS-DMA plain / ping-pong) stand where their kernels were first named before there was a table: kernels land in the code object in that order
+typedef int (*WbLaunch)(const WbArgs&, long, hipStream_t);
+struct WbRow { int form, sub; WbLaunch launch; };
+constexpr WbRow kKernels[] = {
+    {0, 0, launch_wb<&wgrad_bf16_kernel<0>, 256, (size_t)DY_BYTES + X_BYTES>}, {0, 1, launch_wb<&wgrad_bf16_kernel<1>, 256, (size_t)DY_BYTES + X_BYTES>},
+#ifdef OSVOS_WGRAD_ALL_FORMS
+    {4, 1, launch_wb<&wgrad_bf16dma_kernel<0>, 512, DM::LDS>}, {5, 1, launch_wb<&wgrad_bf16dma_kernel<1>, 512, DM::LDS>},
+#endif
+    {3, 0, launch_wb<&wgrad_bf16pm_kernel<4>, 256, PM<4>::LDS>}, {3, 1, launch_wb<&wgrad_bf16pm_kernel<8>, 512, PM<8>::LDS>},
+#ifdef OSVOS_WGRAD_ALL_FORMS
+    {1, 0, launch_wb<&wgrad_bf16v2_kernel<4>, 256, (size_t)DY_BYTES + X_BYTES>}, {1, 1, launch_wb<&wgrad_bf16v2_kernel<8>, 512, (size_t)2 * DY_BYTES + X_BYTES>},
+#endif
 };
 
-// bco = 128: the eight-wave form (one workgroup per CU: aim at one round of 256 workgroups)
-WbPlan make_plan(int N, int H, int W, int Cin_s, int Cout, int bco = BCO) {
-  WbPlan p;
-  p.nco_t = ceil_div(Cout, bco);
-  p.nci_t = ceil_div(Cin_s, BCI);
-  p.npx = ceil_div(W, PW);
-  p.npy = ceil_div(H, PH);
-  p.npatches = N * p.npx * p.npy;
+// the plan of a shape for 64- or 128-cout tiles, but for the kernel row (no checks: the workspace query asks for shapes without a call)
+void plan_tiles(int N, int H, int W, int Cin_s, int Cout, int bco, WgradPlan* p) {
+  *p = WgradPlan();
+  p->family = WGRAD_BF16;
+  p->nco_t = ceil_div(Cout, bco);
+  p->nci_t = ceil_div(Cin_s, BCI);
+  wgrad_patches(p, N, H, W, PW, PH);
   // workgroups aimed at: 512 for the four-wave form (two per CU), 192 for the eight-wave form (one per CU -- round 5: three quarters of the CUs
   // instead of all of them, the data-gradient chain that runs beside it keeps a share: +0.6-1.0 % on configs[2] on two boxes; 128 / 224 / 256 level
   // to -0.8 %, 384 -1.4 %, 512 -3 %; profiles/r05_ab_small.txt)
-  int want = ceil_div(bco == BCO ? 512 : 192, p.nco_t * p.nci_t);
-  const int max_split = p.npatches / 2 > 0 ? p.npatches / 2 : 1;
-  if (want > max_split) want = max_split;
-  if (want > 256) want = 256;
-  p.per_split = ceil_div(p.npatches, want);
-  p.nsplit = ceil_div(p.npatches, p.per_split);
-  p.slab_floats = (size_t)p.nsplit * 9 * Cout * Cin_s;
-  p.bslab_floats = (size_t)p.nsplit * Cout;
-  return p;
+  wgrad_split(p, bco == BCO ? 512 : 192, 2, 256, (size_t)9 * Cout * Cin_s, Cout);
+  OSVOS_ENV_INT(map_env, "OSVOS_WGRAD_MAP", -1);
+  p->map = (map_env >= 0 ? map_env : kDefaultMap) == 1 && p->blocks % 8 == 0 ? 1 : 0;
+  p->reduce = osvos_wgrad_reduce_kind(p->nsplit, Cout, Cin_s, Cin_s);      // (Cin == Cin_s for every shape of this family)
 }
 
-// which form takes a launch (xb: bf16 tensors), its plan, its grid and its block map
-struct WbChoice {
-  int form;
-  bool wide;
-  WbPlan p;
-  long blocks;
-  int map;
-};
-WbChoice choose(int N, int H, int W, int Cin_s, int Cout, int xb) {
-  WbChoice ch;
+// which form takes a launch, its plan, its grid and its block map
+int choose(const WgradCall& c, WgradPlan* p) {
+  OSVOS_ARG_CHECK(c.x && c.dy && c.ws && c.dw, "wgrad bf16: null pointer");
+  OSVOS_ARG_CHECK(osvos_wgrad_bf16_applicable(c) && c.Cout_s % 4 == 0, "wgrad bf16: unsupported shape");
+  OSVOS_ARG_CHECK((long)c.H * c.W * c.Cin_s < (1L << 29) && (long)c.H * c.W * c.Cout_s < (1L << 29), "wgrad bf16: image too large for 31-bit byte offsets");
+  OSVOS_ARG_CHECK(!c.x_bf16 == !c.dy_bf16, "wgrad bf16: x and dy must both be fp32 or both be bf16");
+  const int xb = c.x_bf16 ? 1 : 0;
   OSVOS_ENV_INT(form_env, "OSVOS_WGRAD_FORM", -1);
 #ifdef OSVOS_WGRAD_ALL_FORMS
-  ch.form = xb ? (form_env >= 0 ? form_env : kDefaultForm) : 0;
-#else      // the shipped library holds two forms: 0 (first staging form; the only one for fp32 tensors) and 3 (pixel-major, the default for bf16 tensors)
-  ch.form = xb ? ((form_env == 0) ? 0 : kDefaultForm) : 0;
+  const int form = xb ? (form_env >= 0 ? form_env : kDefaultForm) : 0;
+#else
+  const int form = xb ? ((form_env == 0) ? 0 : kDefaultForm) : 0;
 #endif
-  ch.wide = ch.form >= kWideForm && Cout % 128 == 0;        // eight-wave form: 128-cout tiles
-  ch.p = make_plan(N, H, W, Cin_s, Cout, ch.wide ? 128 : BCO);
-  ch.blocks = (long)ch.p.nsplit * ch.p.nco_t * ch.p.nci_t;
-  OSVOS_ENV_INT(map_env, "OSVOS_WGRAD_MAP", -1);
-  ch.map = (map_env >= 0 ? map_env : kDefaultMap) == 1 && ch.blocks % 8 == 0 ? 1 : 0;
-  return ch;
+  const bool wide = form >= kWideForm && c.Cout % 128 == 0;        // eight-wave form: 128-cout tiles
+  plan_tiles(c.N, c.H, c.W, c.Cin_s, c.Cout, wide ? 128 : BCO, p);
+  // LDS-DMA forms (4: fragments one stage ahead, 5: ping-pong segments) exist for 128-cout tiles only; forms 1 and 2 are one kernel
+  const int row_form = (form >= 4 && wide) ? (form == 5 ? 5 : 4) : form >= 3 ? 3 : form != 0 ? 1 : 0, sub = row_form == 0 ? xb : wide ? 1 : 0;
+  for (p->kernel = 0; kKernels[p->kernel].form != row_form || kKernels[p->kernel].sub != sub; ++p->kernel) {}
+  return 0;
 }
 
 }  // namespace
 
-// shapes the bf16 kernel takes: the wide trunk layers (Cin_s, Cout multiples of 64); everything else stays on the fp32 kernels
+// shapes the bf16 kernel takes: the wide trunk layers (Cin_s, Cout multiples of 64, no channel padding); everything else stays on the fp32 kernels
 // (Cout = 16, the side_prep layers: one 64-cout tile with 16 live rows -- 75 % of the MFMA rows multiply zeros, still 2x faster than
 //  the exact-fp32 skinny kernel, whose cost is staging the wide X tile either way)
-bool osvos_wgrad_bf16_applicable(int Cin_s, int Cout) { return Cin_s % 64 == 0 && (Cout % 64 == 0 || Cout == 16); }
+bool osvos_wgrad_bf16_applicable(const WgradCall& c) { return c.Cin == c.Cin_s && c.Cin_s % 64 == 0 && (c.Cout % 64 == 0 || c.Cout == 16); }
 
 size_t osvos_wgrad_bf16_ws_bytes(int N, int H, int W, int Cin_s, int Cout) {
-  if (!osvos_wgrad_bf16_applicable(Cin_s, Cout)) return 0;
-  const WbPlan p = make_plan(N, H, W, Cin_s, Cout), pw = make_plan(N, H, W, Cin_s, Cout, 128);      // whichever form runs
-  const size_t f = p.slab_floats + p.bslab_floats, fw = pw.slab_floats + pw.bslab_floats;
-  return align_up((f > fw ? f : fw) * sizeof(float), 256);
+  if (!osvos_wgrad_bf16_applicable(wgrad_shape_call(N, H, W, Cin_s, Cout))) return 0;
+  WgradPlan p, pw;      // whichever form runs
+  plan_tiles(N, H, W, Cin_s, Cout, BCO, &p);
+  plan_tiles(N, H, W, Cin_s, Cout, 128, &pw);
+  const size_t f = wgrad_plan_ws_bytes(p), fw = wgrad_plan_ws_bytes(pw);
+  return f > fw ? f : fw;
 }
 
-// what the launcher below does with this shape (osvos_wgrad_wide_plan): launches nothing
-int osvos_wgrad_bf16_plan(int N, int H, int W, int Cin_s, int Cout, int xb, int* out) {
-  OSVOS_ARG_CHECK(osvos_wgrad_bf16_applicable(Cin_s, Cout), "wgrad_wide_plan: no bf16 weight-gradient kernel for Cin %d Cout %d", Cin_s, Cout);
-  const WbChoice ch = choose(N, H, W, Cin_s, Cout, xb);
-  const WbPlan& p = ch.p;
-  out[0] = PW; out[1] = PH; out[2] = p.npx; out[3] = p.npy; out[4] = p.npatches; out[5] = p.per_split; out[6] = p.nsplit;
-  out[7] = p.nco_t; out[8] = p.nci_t; out[9] = (int)ch.blocks; out[10] = ch.map; out[11] = ch.wide ? 1 : 0;
-  return 0;
-}
+int osvos_wgrad_bf16_plan(const WgradCall& c, WgradPlan* p) { return choose(c, p); }
 
-// x and dy both fp32, or both bf16 (xb)
 int osvos_conv3x3_wgrad_bf16mfma(const WgradCall& c) {
-  float *const dw = c.dw, *const db = c.db;
-  void* const ws = c.ws; hipStream_t stream = c.stream;
-  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cin_s = c.Cin_s, Cout = c.Cout, Cout_s = c.Cout_s, accumulate = c.accumulate, phase = c.phase, xb = c.x_bf16 ? 1 : 0;
-  OSVOS_ARG_CHECK(c.x && c.dy && ws && dw, "wgrad bf16: null pointer");
-  OSVOS_ARG_CHECK(osvos_wgrad_bf16_applicable(Cin_s, Cout) && Cin == Cin_s && Cout_s % 4 == 0, "wgrad bf16: unsupported shape");
-  OSVOS_ARG_CHECK((long)H * W * Cin_s < (1L << 29) && (long)H * W * Cout_s < (1L << 29), "wgrad bf16: image too large for 31-bit byte offsets");
-  OSVOS_ARG_CHECK(!c.x_bf16 == !c.dy_bf16, "wgrad bf16: x and dy must both be fp32 or both be bf16");
-  const WbChoice ch = choose(N, H, W, Cin_s, Cout, xb);
-  const int form = ch.form;
-  const bool wide = ch.wide;
-  const WbPlan& p = ch.p;
+  WgradPlan p;
+  if (int rc = choose(c, &p)) return rc;
   WbArgs a;
   a.x = c.x; a.dy = c.dy;
-  a.slab = reinterpret_cast<float*>(ws);
-  a.bslab = db ? a.slab + p.slab_floats : nullptr;
-  a.N = N; a.H = H; a.W = W; a.Cin_s = Cin_s; a.Cout = Cout; a.Cout_s = Cout_s;
+  a.slab = reinterpret_cast<float*>(c.ws);
+  a.bslab = c.db ? a.slab + p.slab_floats : nullptr;
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cin_s = c.Cin_s; a.Cout = c.Cout; a.Cout_s = c.Cout_s;
   a.npx = p.npx; a.npy = p.npy; a.npatches = p.npatches; a.per_split = p.per_split; a.nco_t = p.nco_t; a.nci_t = p.nci_t;
-  const long blocks = ch.blocks;
-  a.map = ch.map;
+  a.map = p.map;
   a.prof = g_wgrad_prof;
   OSVOS_ENV_INT(dbg_env, "OSVOS_WGRAD_DBG", 0);
   a.dbg = dbg_env;
-  constexpr size_t lds = (size_t)DY_BYTES + X_BYTES;
-  if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16_kernel<0>>(lds)) return rc;
-  if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16_kernel<1>>(lds)) return rc;
-#ifdef OSVOS_WGRAD_ALL_FORMS
-  if (phase != WGRAD_REDUCE && form >= 4 && wide) {                // LDS-DMA forms: 4 fragments one stage ahead, 5 ping-pong segments
-    constexpr int lds_dma = (int)DM::LDS;
-    if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16dma_kernel<0>>(lds_dma)) return rc;
-    if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16dma_kernel<1>>(lds_dma)) return rc;
-    if (form == 5) hipLaunchKernelGGL(wgrad_bf16dma_kernel<1>, dim3((unsigned)blocks), dim3(512), lds_dma, stream, a);
-    else hipLaunchKernelGGL(wgrad_bf16dma_kernel<0>, dim3((unsigned)blocks), dim3(512), lds_dma, stream, a);
-    OSVOS_LAUNCH_CHECK();
-  } else
-#endif
-  if (phase != WGRAD_REDUCE && form >= 3) {
-    constexpr size_t lds4 = PM<4>::LDS, lds8 = PM<8>::LDS;
-    if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16pm_kernel<4>>(lds4)) return rc;
-    if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16pm_kernel<8>>(lds8)) return rc;
-    if (wide) hipLaunchKernelGGL(wgrad_bf16pm_kernel<8>, dim3((unsigned)blocks), dim3(512), lds8, stream, a);
-    else hipLaunchKernelGGL(wgrad_bf16pm_kernel<4>, dim3((unsigned)blocks), dim3(256), lds4, stream, a);
-    OSVOS_LAUNCH_CHECK();
-#ifdef OSVOS_WGRAD_ALL_FORMS
-  } else if (phase != WGRAD_REDUCE && form != 0) {
-    if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16v2_kernel<4>>(kLdsV2)) return rc;
-    if (int rc = osvos_set_dyn_lds_once<&wgrad_bf16v2_kernel<8>>(kLdsV2w)) return rc;
-    if (wide) hipLaunchKernelGGL(wgrad_bf16v2_kernel<8>, dim3((unsigned)blocks), dim3(512), kLdsV2w, stream, a);
-    else hipLaunchKernelGGL(wgrad_bf16v2_kernel<4>, dim3((unsigned)blocks), dim3(256), kLdsV2, stream, a);
-    OSVOS_LAUNCH_CHECK();
-#endif
-  } else if (phase != WGRAD_REDUCE) {
-    if (xb) hipLaunchKernelGGL(wgrad_bf16_kernel<1>, dim3((unsigned)blocks), dim3(256), lds, stream, a);
-    else hipLaunchKernelGGL(wgrad_bf16_kernel<0>, dim3((unsigned)blocks), dim3(256), lds, stream, a);
-    OSVOS_LAUNCH_CHECK();
-  }
-  if (phase == WGRAD_PARTIALS) return 0;
-  return osvos_wgrad_reduce_launch(a.slab, a.bslab, dw, db, p.nsplit, Cout, Cin, Cin_s, accumulate, stream);
+  if (c.phase != WGRAD_REDUCE)
+    if (int rc = kKernels[p.kernel].launch(a, p.blocks, c.stream)) return rc;
+  if (c.phase == WGRAD_PARTIALS) return 0;
+  return osvos_wgrad_reduce_launch(p.reduce, a.slab, a.bslab, c.dw, c.db, p.nsplit, c.Cout, c.Cin, c.Cin_s, c.accumulate, c.stream);
 }
 
 #ifdef OSVOS_WGRAD_PROF

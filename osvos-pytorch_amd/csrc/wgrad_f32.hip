@@ -374,41 +374,24 @@ __global__ __launch_bounds__(64 * NW) void wgrad_reduce_t_kernel(const float* __
   }
 }
 
-struct WgPlan {
-  int cb, ib, pw, nco_t, nci_t, npx, npy, npatches, nsplit, per_split;
-  size_t slab_floats, bslab_floats;
-};
-
-WgPlan make_plan(int N, int H, int W, int Cin_s, int Cout) {
-  WgPlan p;
-  if (Cout <= 32) { p.cb = 1; p.ib = 4; } else { p.cb = 2; p.ib = 2; }
-  p.nco_t = ceil_div(Cout, p.cb * 32);
-  p.nci_t = ceil_div(Cin_s, p.ib * 32);
+// The generic kernel's plan for a shape, but for the kernel row and the reduce (no checks: the workspace query asks for shapes without a call)
+void plan_generic(int N, int H, int W, int Cin_s, int Cout, WgradPlan* p) {
+  *p = WgradPlan();
+  p->family = WGRAD_F32;
+  const int cb = Cout <= 32 ? 1 : 2, ib = Cout <= 32 ? 4 : 2;      // 32 x 128 or 64 x 64 channels per workgroup
+  p->nco_t = ceil_div(Cout, cb * 32);
+  p->nci_t = ceil_div(Cin_s, ib * 32);
   // 16 x 4 patches when they cover the frame with at least 8 % fewer padded pixels (and the generic 64 x 64 kernel is used)
-  p.pw = 32;
-  if (p.cb == 2 && (long)ceil_div(W, 16) * 16 * ceil_div(H, 4) * 4 * 100 < (long)ceil_div(W, 32) * 32 * ceil_div(H, 2) * 2 * 92) p.pw = 16;
-  {
-    OSVOS_ENV_INT(env_pw, "OSVOS_WGRAD_PW", 0);
-    if (env_pw > 0 && p.cb == 2) p.pw = env_pw == 16 ? 16 : 32;
-  }
-  const int PW = p.pw, PH = PPIX / p.pw;
-  p.npx = ceil_div(W, PW);
-  p.npy = ceil_div(H, PH);
-  p.npatches = N * p.npx * p.npy;
+  int pw = 32;
+  if (cb == 2 && (long)ceil_div(W, 16) * 16 * ceil_div(H, 4) * 4 * 100 < (long)ceil_div(W, 32) * 32 * ceil_div(H, 2) * 2 * 92) pw = 16;
+  OSVOS_ENV_INT(env_pw, "OSVOS_WGRAD_PW", 0);
+  if (env_pw > 0 && cb == 2) pw = env_pw == 16 ? 16 : 32;
+  wgrad_patches(p, N, H, W, pw, PPIX / pw);
   OSVOS_ENV_INT(env_blocks, "OSVOS_WGRAD_BLOCKS", 0);
   // ~2 workgroups per CU; small frames (conv5 at 480p: 30 patches) prefer fewer, longer splits
-  int target_blocks = env_blocks > 0 ? env_blocks : (p.npatches >= 100 ? 512 : 256);
-  if (target_blocks < 1) target_blocks = 512;
-  int want = ceil_div(target_blocks, p.nco_t * p.nci_t);
-  int max_split = p.npatches / 4 > 0 ? p.npatches / 4 : 1;
-  p.nsplit = want < max_split ? want : max_split;
-  if (p.nsplit > 256) p.nsplit = 256;       // (512 splits for the one-tile conv1_2: partial kernel -23 us, slab reduce +37 us)
-  if (p.nsplit < 1) p.nsplit = 1;
-  p.per_split = ceil_div(p.npatches, p.nsplit);
-  p.nsplit = ceil_div(p.npatches, p.per_split);
-  p.slab_floats = (size_t)p.nsplit * 9 * Cout * Cin_s;
-  p.bslab_floats = (size_t)p.nsplit * Cout;
-  return p;
+  const int target_blocks = env_blocks > 0 ? env_blocks : (p->npatches >= 100 ? 512 : 256);
+  // (at most 256 splits -- 512 for the one-tile conv1_2: partial kernel -23 us, slab reduce +37 us)
+  wgrad_split(p, target_blocks, 4, 256, (size_t)9 * Cout * Cin_s, Cout);
 }
 
 template <int CB, int IB, int PIPE, int DBUF, int OCC, int PWT = 32>
@@ -426,84 +409,87 @@ int wgrad_variant() {
   return env_variant;     // measured best (tools/tune_wgrad.py): pipelined fetch, one LDS buffer, 2 WGs/CU
 }
 
-template <int CB, int IB>
-int launch_wgrad_variant(const WgArgs& a, long blocks, hipStream_t stream) {
-  switch (wgrad_variant() & 7) {
-    case 0: return launch_wgrad<CB, IB, 0, 0, 1>(a, blocks, stream);
-    case 1: return launch_wgrad<CB, IB, 1, 0, 1>(a, blocks, stream);
-    case 2: return launch_wgrad<CB, IB, 0, 1, 1>(a, blocks, stream);
-    case 3: return launch_wgrad<CB, IB, 1, 1, 1>(a, blocks, stream);
-    case 4: return launch_wgrad<CB, IB, 0, 0, (CB == 2 ? 2 : 1)>(a, blocks, stream);
-    case 5: return launch_wgrad<CB, IB, 1, 0, (CB == 2 ? 2 : 1)>(a, blocks, stream);
-    default: return launch_wgrad<CB, IB, 0, 1, 1>(a, blocks, stream);
+}  // namespace
+
+int osvos_wgrad_reduce_kind(int nsplit, int Cout, int Cin, int Cin_s) {
+  OSVOS_ENV_INT(env_t, "OSVOS_WGRAD_REDUCE_T", 1);
+  if (env_t && Cin == Cin_s && Cin_s % 64 == 0 && Cout <= 65535)      // wide layers: LDS-transposing reduce, contiguous OIHW writes
+    return ((long)(Cin_s / 64) * Cout <= 1024 && nsplit >= 32) ? WGRAD_REDUCE_T16 : WGRAD_REDUCE_T4;      // few workgroups, many splits: 16 waves each
+  return WGRAD_REDUCE_GENERIC;
+}
+
+int osvos_wgrad_reduce_launch(int kind, const float* slab, const float* bslab, float* dw, float* db, int nsplit, int Cout, int Cin, int Cin_s,
+                              int accumulate, hipStream_t stream) {
+  if (kind == WGRAD_REDUCE_T16) {
+    hipLaunchKernelGGL(wgrad_reduce_t_kernel<16>, dim3(Cin_s / 64, Cout), dim3(1024), 0, stream, slab, bslab, dw, db, nsplit, Cout, Cin_s, accumulate);
+  } else if (kind == WGRAD_REDUCE_T4) {
+    hipLaunchKernelGGL(wgrad_reduce_t_kernel<4>, dim3(Cin_s / 64, Cout), dim3(256), 0, stream, slab, bslab, dw, db, nsplit, Cout, Cin_s, accumulate);
+  } else {
+    const int total = Cout * Cin_s * 9;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ceil_div(total, 128) + (db ? ceil_div(Cout, 32) : 0)), dim3(256), 0, stream,
+                       slab, bslab, dw, db, nsplit, Cout, Cin, Cin_s, accumulate, kind == WGRAD_REDUCE_OIHW ? 1 : 0);
   }
+  OSVOS_LAUNCH_CHECK();
+  return 0;
+}
+
+namespace {
+
+// the kernel table, <CB, IB, PIPE, DBUF, OCC, PWT>: the 32 x 128-channel tile of Cout <= 32, the 64 x 64 one on 16 x 4 patches (the measured-best
+// variant only), the 64 x 64 one -- by OSVOS_WGRAD_VARIANT & 7; two workgroups per CU (bit 2) exist for the 64 x 64 tile only
+typedef int (*WgLaunch)(const WgArgs&, long, hipStream_t);
+constexpr WgLaunch kKernels[] = {
+    launch_wgrad<1, 4, 0, 0, 1>, launch_wgrad<1, 4, 1, 0, 1>, launch_wgrad<1, 4, 0, 1, 1>, launch_wgrad<1, 4, 1, 1, 1>,
+    launch_wgrad<2, 2, 1, 0, 2, 16>,
+    launch_wgrad<2, 2, 0, 0, 1>, launch_wgrad<2, 2, 1, 0, 1>, launch_wgrad<2, 2, 0, 1, 1>, launch_wgrad<2, 2, 1, 1, 1>,
+    launch_wgrad<2, 2, 0, 0, 2>, launch_wgrad<2, 2, 1, 0, 2>,
+};
+constexpr int kRowPw16 = 4;
+constexpr int kRowOfVariant[2][8] = {{0, 1, 2, 3, 0, 1, 2, 2}, {5, 6, 7, 8, 9, 10, 7, 7}};      // [Cout > 32][variant & 7]; 6, 7: as 2
+
+int choose(const WgradCall& c, WgradPlan* p) {
+  if (int rc = osvos_wgrad_f32_check(c)) return rc;
+  plan_generic(c.N, c.H, c.W, c.Cin_s, c.Cout, p);
+  p->kernel = p->pw == 16 ? kRowPw16 : kRowOfVariant[c.Cout > 32][wgrad_variant() & 7];
+  p->reduce = ((wgrad_variant() >> 3) & 1) ? WGRAD_REDUCE_OIHW : osvos_wgrad_reduce_kind(p->nsplit, c.Cout, c.Cin, c.Cin_s);
+  return 0;
 }
 
 }  // namespace
 
-int osvos_wgrad_reduce_launch(const float* slab, const float* bslab, float* dw, float* db, int nsplit, int Cout, int Cin,
-                              int Cin_s, int accumulate, hipStream_t stream) {
-  OSVOS_ENV_INT(env_t, "OSVOS_WGRAD_REDUCE_T", 1);
-  if (env_t && Cin == Cin_s && Cin_s % 64 == 0 && Cout <= 65535) {      // wide layers: LDS-transposing reduce, contiguous OIHW writes
-    if ((long)(Cin_s / 64) * Cout <= 1024 && nsplit >= 32)      // few workgroups, many splits: 16 waves each
-      hipLaunchKernelGGL(wgrad_reduce_t_kernel<16>, dim3(Cin_s / 64, Cout), dim3(1024), 0, stream, slab, bslab, dw, db, nsplit, Cout, Cin_s, accumulate);
-    else
-      hipLaunchKernelGGL(wgrad_reduce_t_kernel<4>, dim3(Cin_s / 64, Cout), dim3(256), 0, stream, slab, bslab, dw, db, nsplit, Cout, Cin_s, accumulate);
-    OSVOS_LAUNCH_CHECK();
-    return 0;
-  }
-  const int total = Cout * Cin_s * 9;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ceil_div(total, 128) + (db ? ceil_div(Cout, 32) : 0)), dim3(256), 0, stream,
-                     slab, bslab, dw, db, nsplit, Cout, Cin, Cin_s, accumulate, 0);
-  OSVOS_LAUNCH_CHECK();
+int osvos_wgrad_f32_check(const WgradCall& c) {
+  OSVOS_ARG_CHECK(c.x && c.dy && c.ws && c.dw, "wgrad: null pointer");
+  OSVOS_ARG_CHECK(c.N > 0 && c.H > 0 && c.W > 0 && c.Cin > 0 && c.Cout > 0, "wgrad: bad shape");
+  OSVOS_ARG_CHECK((long)c.H * c.W * c.Cin_s < (1L << 29) && (long)c.H * c.W * c.Cout_s < (1L << 29), "wgrad: image too large for 31-bit byte offsets");
+  OSVOS_ARG_CHECK(c.Cin_s % 4 == 0 && c.Cout_s % 4 == 0 && c.Cout % 4 == 0 && c.Cin <= c.Cin_s && c.Cout <= c.Cout_s,
+                  "wgrad f32: channel strides must be multiples of 4 (Cin %d/%d Cout %d/%d)", c.Cin, c.Cin_s, c.Cout, c.Cout_s);
+  OSVOS_ARG_CHECK(!c.x_bf16 && !c.dy_bf16, "wgrad f32: fp32 tensors only");
   return 0;
 }
 
+// whichever exact kernel takes the shape: the generic one, or a skinny one
 size_t osvos_wgrad_ws_bytes_f32(int N, int H, int W, int Cin_s, int Cout) {
-  WgPlan p = make_plan(N, H, W, Cin_s, Cout);
-  const size_t generic = align_up((p.slab_floats + p.bslab_floats) * sizeof(float), 256);
-  const size_t small = osvos_wgrad_small_ws_bytes(N, H, W, Cin_s, Cout);
+  WgradPlan p;
+  plan_generic(N, H, W, Cin_s, Cout, &p);
+  const size_t generic = wgrad_plan_ws_bytes(p), small = osvos_wgrad_small_ws_bytes(N, H, W, Cin_s, Cout);
   return generic > small ? generic : small;
 }
 
+int osvos_wgrad_f32_plan(const WgradCall& c, WgradPlan* p) { return choose(c, p); }
+
 int osvos_conv3x3_wgrad_f32(const WgradCall& c) {
-  float *const dw = c.dw, *const db = c.db;
-  void* const ws = c.ws; hipStream_t stream = c.stream;
-  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cin_s = c.Cin_s, Cout = c.Cout, Cout_s = c.Cout_s, accumulate = c.accumulate;
-  OSVOS_ARG_CHECK(c.x && c.dy && ws && dw, "wgrad: null pointer");
-  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "wgrad: bad shape");
-  OSVOS_ARG_CHECK((long)H * W * Cin_s < (1L << 29) && (long)H * W * Cout_s < (1L << 29), "wgrad: image too large for 31-bit byte offsets");
-  OSVOS_ARG_CHECK(Cin_s % 4 == 0 && Cout_s % 4 == 0 && Cout % 4 == 0 && Cin <= Cin_s && Cout <= Cout_s,
-                  "wgrad f32: channel strides must be multiples of 4 (Cin %d/%d Cout %d/%d)", Cin, Cin_s, Cout, Cout_s);
-  OSVOS_ARG_CHECK(!c.x_bf16 && !c.dy_bf16, "wgrad f32: fp32 tensors only");
-  {
-    OSVOS_ENV_INT(env_generic, "OSVOS_WGRAD_GENERIC", 0);     // tuning / tests: force the generic kernel
-    if (!env_generic) {
-      const int rc = osvos_conv3x3_wgrad_small_f32(c);
-      if (rc <= 0) return rc;
-    }
-  }
-  WgPlan p = make_plan(N, H, W, Cin_s, Cout);
+  WgradPlan p;
+  if (int rc = choose(c, &p)) return rc;
   WgArgs a;
   a.x = (const float*)c.x; a.dy = (const float*)c.dy;
-  a.slab = reinterpret_cast<float*>(ws);
-  a.bslab = db ? a.slab + p.slab_floats : nullptr;
-  a.N = N; a.H = H; a.W = W; a.Cin_s = Cin_s; a.Cout = Cout; a.Cout_s = Cout_s;
+  a.slab = reinterpret_cast<float*>(c.ws);
+  a.bslab = c.db ? a.slab + p.slab_floats : nullptr;
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cin_s = c.Cin_s; a.Cout = c.Cout; a.Cout_s = c.Cout_s;
   a.npx = p.npx; a.npy = p.npy; a.npatches = p.npatches; a.nsplit = p.nsplit; a.per_split = p.per_split;
   a.nco_t = p.nco_t; a.nci_t = p.nci_t;
-  const long blocks = (long)p.nsplit * p.nco_t * p.nci_t;
-  a.oihw = (wgrad_variant() >> 3) & 1;
-  if (c.phase != WGRAD_REDUCE) {
-    int rc = (p.cb == 1) ? launch_wgrad_variant<1, 4>(a, blocks, stream)
-                         : (p.pw == 16 ? launch_wgrad<2, 2, 1, 0, 2, 16>(a, blocks, stream)      // (the measured-best variant only)
-                                       : launch_wgrad_variant<2, 2>(a, blocks, stream));
-    if (rc) return rc;
-  }
+  a.oihw = p.reduce == WGRAD_REDUCE_OIHW;
+  if (c.phase != WGRAD_REDUCE)
+    if (int rc = kKernels[p.kernel](a, p.blocks, c.stream)) return rc;
   if (c.phase == WGRAD_PARTIALS) return 0;
-  if (!a.oihw) return osvos_wgrad_reduce_launch(a.slab, a.bslab, dw, db, p.nsplit, Cout, Cin, Cin_s, accumulate, stream);
-  const int total = Cout * Cin_s * 9;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ceil_div(total, 128) + (db ? ceil_div(Cout, 32) : 0)), dim3(256), 0, stream,
-                     a.slab, a.bslab, dw, db, p.nsplit, Cout, Cin, Cin_s, accumulate, a.oihw);
-  OSVOS_LAUNCH_CHECK();
-  return 0;
+  return osvos_wgrad_reduce_launch(p.reduce, a.slab, a.bslab, c.dw, c.db, p.nsplit, c.Cout, c.Cin, c.Cin_s, c.accumulate, c.stream);
 }

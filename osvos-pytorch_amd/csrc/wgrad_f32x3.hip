@@ -411,55 +411,27 @@ __global__ __launch_bounds__(64 * WAVES) void wgrad_f32x3_kernel(W3Args a) {
   }
 }
 
-struct W3Plan {
-  int ph, waves, bco, nco_t, nci_t, npx, npy, npatches, nsplit, per_split;
-  size_t slab_floats, bslab_floats;
-};
-
-// one workgroup per CU (124-135 KB of LDS): aim at one round of ~256 workgroups, each with a long patch range
-W3Plan make_plan3(int N, int H, int W, int Cin_s, int Cout) {
-  W3Plan p;
+// the plan of a shape but for the kernel row (no checks: the workspace query asks for shapes without a call).  One workgroup per CU (124-135 KB
+// of LDS): aim at one round of ~256 workgroups, each with a long patch range
+void plan3(int N, int H, int W, int Cin_s, int Cout, WgradPlan* p) {
+  *p = WgradPlan();
+  p->family = WGRAD_F32X3;
   if (Cout == 16) {      // skinny form (S16): 128 cins x 16 couts per workgroup, 16 x 4 pixel patches
-    p.waves = 4; p.bco = 32; p.ph = 4;
-    p.nco_t = 1;
-    p.nci_t = ceil_div(Cin_s, 128);
-    p.npx = ceil_div(W, PW);
-    p.npy = ceil_div(H, p.ph);
-    p.npatches = N * p.npx * p.npy;
-    int want = ceil_div(256, p.nci_t);
-    const int max_split = p.npatches / 2 > 0 ? p.npatches / 2 : 1;
-    if (want > max_split) want = max_split;
-    p.per_split = ceil_div(p.npatches, want);
-    p.nsplit = ceil_div(p.npatches, p.per_split);
-    p.slab_floats = (size_t)p.nsplit * 9 * Cout * Cin_s;
-    p.bslab_floats = (size_t)p.nsplit * Cout;
-    return p;
+    p->nci_t = ceil_div(Cin_s, 128);
+    wgrad_patches(p, N, H, W, PW, 4);
+  } else {
+    // (An eight-wave 128 x 64-channel tile was measured in round 2: 3-4 % faster standalone on conv2_2 / conv3_2, level or slower elsewhere --
+    //  twice the splits = twice the slab traffic -- and the whole step slower beside the data-gradient kernels, 206 vs 210 frames/s: removed.)
+    p->nco_t = ceil_div(Cout, 64);
+    p->nci_t = ceil_div(Cin_s, 64);
+    wgrad_patches(p, N, H, W, PW, (ceil_div(H, 6) * 6 <= ceil_div(H, 4) * 4) ? 6 : 4);
   }
-  // (An eight-wave 128 x 64-channel tile was measured in round 2: 3-4 % faster standalone on conv2_2 / conv3_2, level or slower elsewhere --
-  //  twice the splits = twice the slab traffic -- and the whole step slower beside the data-gradient kernels, 206 vs 210 frames/s: removed.)
-  p.waves = 4;
-  p.bco = 16 * p.waves;
-  p.ph = (ceil_div(H, 6) * 6 <= ceil_div(H, 4) * 4) ? 6 : 4;
-  p.nco_t = ceil_div(Cout, p.bco);
-  p.nci_t = ceil_div(Cin_s, 64);
-  p.npx = ceil_div(W, PW);
-  p.npy = ceil_div(H, p.ph);
-  p.npatches = N * p.npx * p.npy;
-  int want = ceil_div(256, p.nco_t * p.nci_t);      // (round 5 re-check at step level: 192 -0.9 %, 320 -1.5 %, 384 -1.6 %, 512 -4.5 % against 256; profiles/r05_ab_small.txt)
-  const int max_split = p.npatches / 2 > 0 ? p.npatches / 2 : 1;
-  if (want > max_split) want = max_split;
-  if (want > 256) want = 256;
-  p.per_split = ceil_div(p.npatches, want);
-  p.nsplit = ceil_div(p.npatches, p.per_split);
-  p.slab_floats = (size_t)p.nsplit * 9 * Cout * Cin_s;
-  p.bslab_floats = (size_t)p.nsplit * Cout;
-  return p;
-}
-
-// the XCD-local block map: where the switch is on and the grid divides among the eight XCDs
-int block_map3(long blocks) {
+  // (round 5 re-check at step level: 192 -0.9 %, 320 -1.5 %, 384 -1.6 %, 512 -4.5 % against 256; profiles/r05_ab_small.txt)
+  wgrad_split(p, 256, 2, 256, (size_t)9 * Cout * Cin_s, Cout);
+  // the XCD-local block map: where the switch is on and the grid divides among the eight XCDs
   OSVOS_ENV_INT(map_env, "OSVOS_WGRAD_MAP", 1);
-  return (map_env == 1 && blocks % 8 == 0) ? 1 : 0;
+  p->map = (map_env == 1 && p->blocks % 8 == 0) ? 1 : 0;
+  p->reduce = osvos_wgrad_reduce_kind(p->nsplit, Cout, Cin_s, Cin_s);      // (Cin == Cin_s for every shape of this family)
 }
 
 template <int PH, int WAVES, int S16 = 0, int ILV = 0, int NP = 3, int HP = 0, int OA = 0>
@@ -471,77 +443,69 @@ int launch3(const W3Args& a, long blocks, hipStream_t stream) {
   return 0;
 }
 
-}  // namespace
+// the kernel table, <PH, WAVES, S16, ILV, NP, HP, OA>: row = 3 * pieces form + geometry (S16, wide with 6-row patches, wide with 4-row patches).
+// Gathers / staging loads interleaved with the MFMAs of the previous stage (ILV; round 3: 'the block-issue form measured level and is gone' -- in the
+// stages that issue staging loads the two forms were the same code until the staging addresses became branch-free: the kernel's INVARIANT)
+typedef int (*W3Launch)(const W3Args&, long, hipStream_t);
+constexpr W3Launch kKernels[] = {
+    launch3<4, 4, 1, 1, 2, 0, 1>, launch3<6, 4, 0, 1, 2, 0, 1>, launch3<4, 4, 0, 1, 2, 0, 1>,      // two bf16 pieces, the staging addresses before (OSVOS_WGRAD_X3_OLDADDR)
+    launch3<4, 4, 1, 1, 3, 0, 1>, launch3<6, 4, 0, 1, 3, 0, 1>, launch3<4, 4, 0, 1, 3, 0, 1>,      // three bf16 pieces, the same
+    launch3<4, 4, 1, 1, 2, 1>,    launch3<6, 4, 0, 1, 2, 1>,    launch3<4, 4, 0, 1, 2, 1>,         // precision 'fp32h2': two FP16 pieces
+    launch3<4, 4, 1, 1, 2>,       launch3<6, 4, 0, 1, 2>,       launch3<4, 4, 0, 1, 2>,            // precision 'fp32x2': two bf16 pieces
+    launch3<4, 4, 1, 1>,          launch3<6, 4, 0, 1>,          launch3<4, 4, 0, 1>,               // three bf16 pieces
+};
+enum { FORM_OLD2 = 0, FORM_OLD3 = 1, FORM_H2 = 2, FORM_X2 = 3, FORM_X3 = 4 };
 
-// the wide trunk layers (channel counts multiples of 64, no channel padding); conv1_1 and side_prep keep their exact skinny kernels
-bool osvos_wgrad_f32x3_applicable(int Cin, int Cin_s, int Cout, int Cout_s) {
-  return Cin == Cin_s && Cin_s % 64 == 0 && Cout % 64 == 0 && Cout_s % 4 == 0;
-}
-// side_prep's shape (Cout = 16): the S16 form
-bool osvos_wgrad_f32x3_skinny_applicable(int Cin, int Cin_s, int Cout, int Cout_s) {
-  return Cout == 16 && Cout_s == 16 && Cin == Cin_s && Cin_s % 128 == 0;
-}
-
-size_t osvos_wgrad_f32x3_ws_bytes(int N, int H, int W, int Cin_s, int Cout) {
-  if (Cout == 16 && Cin_s % 128 == 0) {
-    const W3Plan p = make_plan3(N, H, W, Cin_s, Cout);
-    return align_up((p.slab_floats + p.bslab_floats) * sizeof(float), 256);
-  }
-  if (Cin_s % 64 != 0 || Cout % 64 != 0) return 0;
-  const W3Plan p = make_plan3(N, H, W, Cin_s, Cout);
-  return align_up((p.slab_floats + p.bslab_floats) * sizeof(float), 256);
-}
-
-// what the launcher below does with a dense dY of this shape (osvos_wgrad_wide_plan): launches nothing
-int osvos_wgrad_f32x3_plan(int N, int H, int W, int Cin_s, int Cout, int* out) {
-  OSVOS_ARG_CHECK(osvos_wgrad_f32x3_applicable(Cin_s, Cin_s, Cout, Cout) || osvos_wgrad_f32x3_skinny_applicable(Cin_s, Cin_s, Cout, Cout),
-                  "wgrad_wide_plan: no f32x3 weight-gradient kernel for Cin %d Cout %d", Cin_s, Cout);
-  const W3Plan p = make_plan3(N, H, W, Cin_s, Cout);
-  const long blocks = (long)p.nsplit * p.nco_t * p.nci_t;
-  out[0] = PW; out[1] = p.ph; out[2] = p.npx; out[3] = p.npy; out[4] = p.npatches; out[5] = p.per_split; out[6] = p.nsplit;
-  out[7] = p.nco_t; out[8] = p.nci_t; out[9] = (int)blocks; out[10] = block_map3(blocks); out[11] = 0;
+int choose(const WgradCall& c, WgradPlan* p) {
+  OSVOS_ARG_CHECK(c.x && c.dy && c.ws && c.dw, "wgrad f32x3: null pointer");
+  OSVOS_ARG_CHECK(c.N > 0 && c.H > 0 && c.W > 0, "wgrad f32x3: bad shape");
+  const bool skinny = osvos_wgrad_f32x3_skinny_applicable(c);      // side_prep
+  OSVOS_ARG_CHECK(skinny || osvos_wgrad_f32x3_wide_applicable(c),
+                  "wgrad f32x3: unsupported shape (Cin %d/%d Cout %d/%d)", c.Cin, c.Cin_s, c.Cout, c.Cout_s);
+  OSVOS_ARG_CHECK((long)c.H * c.W * c.Cin_s < (1L << 28) && (long)c.H * c.W * c.Cout_s < (1L << 28), "wgrad f32x3: image too large for 31-bit byte offsets");
+  OSVOS_ARG_CHECK(!c.x_bf16 && !c.dy_bf16, "wgrad f32x3: fp32 tensors only");
+  plan3(c.N, c.H, c.W, c.Cin_s, c.Cout, p);
+  const bool two = c.pieces == 2;      // precision 'fp32x2'
+  const bool h2 = c.pieces == 22;      // precision 'fp32h2'
+  OSVOS_ENV_INT(oldaddr_env, "OSVOS_WGRAD_X3_OLDADDR", 0);      // 1: the staging-address form before (bf16 pieces only), for one A/B
+  const bool oa = oldaddr_env == 1 && !h2;
+  const int form = oa ? (two ? FORM_OLD2 : FORM_OLD3) : h2 ? FORM_H2 : two ? FORM_X2 : FORM_X3;
+  p->kernel = 3 * form + (skinny ? 0 : p->ph == 6 ? 1 : 2);
   return 0;
 }
 
+}  // namespace
+
+// the wide trunk layers (channel counts multiples of 64, no channel padding); conv1_1 and side_prep keep their exact skinny kernels
+bool osvos_wgrad_f32x3_wide_applicable(const WgradCall& c) {
+  return c.Cin == c.Cin_s && c.Cin_s % 64 == 0 && c.Cout % 64 == 0 && c.Cout_s % 4 == 0;
+}
+// side_prep's shape (Cout = 16): the S16 form
+bool osvos_wgrad_f32x3_skinny_applicable(const WgradCall& c) {
+  return c.Cout == 16 && c.Cout_s == 16 && c.Cin == c.Cin_s && c.Cin_s % 128 == 0;
+}
+
+size_t osvos_wgrad_f32x3_ws_bytes(int N, int H, int W, int Cin_s, int Cout) {
+  if (!osvos_wgrad_f32x3_applicable(wgrad_shape_call(N, H, W, Cin_s, Cout))) return 0;
+  WgradPlan p;
+  plan3(N, H, W, Cin_s, Cout, &p);
+  return wgrad_plan_ws_bytes(p);
+}
+
+int osvos_wgrad_f32x3_plan(const WgradCall& c, WgradPlan* p) { return choose(c, p); }
+
 int osvos_conv3x3_wgrad_f32x3(const WgradCall& c) {
-  float *const dw = c.dw, *const db = c.db;
-  void* const ws = c.ws; hipStream_t stream = c.stream;
-  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cin_s = c.Cin_s, Cout = c.Cout, Cout_s = c.Cout_s, accumulate = c.accumulate;
-  OSVOS_ARG_CHECK(c.x && c.dy && ws && dw, "wgrad f32x3: null pointer");
-  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0, "wgrad f32x3: bad shape");
-  const bool skinny = Cout == 16 && Cout_s == 16 && Cin == Cin_s && Cin_s % 128 == 0;      // side_prep
-  OSVOS_ARG_CHECK(skinny || osvos_wgrad_f32x3_applicable(Cin, Cin_s, Cout, Cout_s),
-                  "wgrad f32x3: unsupported shape (Cin %d/%d Cout %d/%d)", Cin, Cin_s, Cout, Cout_s);
-  OSVOS_ARG_CHECK((long)H * W * Cin_s < (1L << 28) && (long)H * W * Cout_s < (1L << 28), "wgrad f32x3: image too large for 31-bit byte offsets");
-  OSVOS_ARG_CHECK(!c.x_bf16 && !c.dy_bf16, "wgrad f32x3: fp32 tensors only");
-  const W3Plan p = make_plan3(N, H, W, Cin_s, Cout);
+  WgradPlan p;
+  if (int rc = choose(c, &p)) return rc;
   W3Args a;
   a.x = c.x; a.dy = c.dy;
-  a.slab = reinterpret_cast<float*>(ws);
-  a.bslab = db ? a.slab + p.slab_floats : nullptr;
-  a.N = N; a.H = H; a.W = W; a.Cin_s = Cin_s; a.Cout = Cout; a.Cout_s = Cout_s;
+  a.slab = reinterpret_cast<float*>(c.ws);
+  a.bslab = c.db ? a.slab + p.slab_floats : nullptr;
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cin_s = c.Cin_s; a.Cout = c.Cout; a.Cout_s = c.Cout_s;
   a.npx = p.npx; a.npy = p.npy; a.npatches = p.npatches; a.per_split = p.per_split; a.nco_t = p.nco_t; a.nci_t = p.nci_t;
-  const long blocks = (long)p.nsplit * p.nco_t * p.nci_t;
-  a.map = block_map3(blocks);
-  if (c.phase != WGRAD_REDUCE) {
-    // gathers / staging loads interleaved with the MFMAs of the previous stage (round 3: 'the block-issue form measured level and is gone' -- in the
-    // stages that issue staging loads the two forms were the same code until the staging addresses became branch-free: the kernel's INVARIANT)
-    const bool two = c.pieces == 2;      // precision 'fp32x2'
-    const bool h2 = c.pieces == 22;      // precision 'fp32h2'
-    OSVOS_ENV_INT(oldaddr_env, "OSVOS_WGRAD_X3_OLDADDR", 0);      // 1: the staging-address form before (bf16 pieces only), for one A/B
-    const bool oa = oldaddr_env == 1 && !h2;
-    const int rc = oa  ? (two ? (skinny ? launch3<4, 4, 1, 1, 2, 0, 1>(a, blocks, stream)
-                                        : (p.ph == 6 ? launch3<6, 4, 0, 1, 2, 0, 1>(a, blocks, stream) : launch3<4, 4, 0, 1, 2, 0, 1>(a, blocks, stream)))
-                              : (skinny ? launch3<4, 4, 1, 1, 3, 0, 1>(a, blocks, stream)
-                                        : (p.ph == 6 ? launch3<6, 4, 0, 1, 3, 0, 1>(a, blocks, stream) : launch3<4, 4, 0, 1, 3, 0, 1>(a, blocks, stream))))
-                 : h2  ? (skinny ? launch3<4, 4, 1, 1, 2, 1>(a, blocks, stream)
-                                 : (p.ph == 6 ? launch3<6, 4, 0, 1, 2, 1>(a, blocks, stream) : launch3<4, 4, 0, 1, 2, 1>(a, blocks, stream)))
-                 : two ? (skinny ? launch3<4, 4, 1, 1, 2>(a, blocks, stream)
-                                 : (p.ph == 6 ? launch3<6, 4, 0, 1, 2>(a, blocks, stream) : launch3<4, 4, 0, 1, 2>(a, blocks, stream)))
-                       : (skinny ? launch3<4, 4, 1, 1>(a, blocks, stream)
-                                 : (p.ph == 6 ? launch3<6, 4, 0, 1>(a, blocks, stream) : launch3<4, 4, 0, 1>(a, blocks, stream)));
-    if (rc) return rc;
-  }
+  a.map = p.map;
+  if (c.phase != WGRAD_REDUCE)
+    if (int rc = kKernels[p.kernel](a, p.blocks, c.stream)) return rc;
   if (c.phase == WGRAD_PARTIALS) return 0;
-  return osvos_wgrad_reduce_launch(a.slab, a.bslab, dw, db, p.nsplit, Cout, Cin, Cin_s, accumulate, stream);
+  return osvos_wgrad_reduce_launch(p.reduce, a.slab, a.bslab, c.dw, c.db, p.nsplit, c.Cout, c.Cin, c.Cin_s, c.accumulate, c.stream);
 }

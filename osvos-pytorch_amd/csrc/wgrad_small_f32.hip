@@ -441,52 +441,63 @@ __global__ __launch_bounds__(256, 2) void wgrad_co16_f32_kernel(S16Args a) {
   if (do_bias && tid < 16) a.bslab[(size_t)split * 16 + tid] = bsum;
 }
 
-struct SmallPlan {
-  int npx, npy, npatches, nsplit, per_split, nci_t;
-  size_t slab_floats, bslab_floats;
-};
-
-SmallPlan plan_c3(int N, int H, int W) {
-  SmallPlan p;
-  p.npx = ceil_div(W, PW); p.npy = ceil_div(H, C3_PH); p.npatches = N * p.npx * p.npy; p.nci_t = 1;
-  int want = 256;    // runs on the aux stream next to the dgrad chain: fewer, longer splits, smaller slabs
-  if (want > p.npatches) want = p.npatches;
-  p.per_split = ceil_div(p.npatches, want);
-  p.nsplit = ceil_div(p.npatches, p.per_split);
-  p.slab_floats = (size_t)p.nsplit * 64 * 32;
-  p.bslab_floats = (size_t)p.nsplit * 64;
-  return p;
+// the plans of the three kernels but for the checks (the workspace query asks for shapes without a call)
+void plan_c3(int N, int H, int W, WgradPlan* p) {
+  *p = WgradPlan();
+  p->family = WGRAD_C3_F32; p->kernel = 0; p->reduce = WGRAD_REDUCE_C3;
+  wgrad_patches(p, N, H, W, PW, C3_PH);
+  // 256 splits at most: runs on the aux stream next to the dgrad chain: fewer, longer splits, smaller slabs
+  wgrad_split(p, 256, 1, 256, 64 * 32, 64);
 }
-
 // bf16-operand form: 16 x 8 pixel patches, four workgroups per CU
-SmallPlan plan_c3_bf16(int N, int H, int W) {
-  SmallPlan p;
-  p.npx = ceil_div(W, Q_W); p.npy = ceil_div(H, Q_H); p.npatches = N * p.npx * p.npy; p.nci_t = 1;
-  int want = 1024;
-  if (want > p.npatches) want = p.npatches;
-  p.per_split = ceil_div(p.npatches, want);
-  p.nsplit = ceil_div(p.npatches, p.per_split);
-  p.slab_floats = (size_t)p.nsplit * 64 * 32;
-  p.bslab_floats = (size_t)p.nsplit * 64;
-  return p;
+void plan_c3_bf16(int N, int H, int W, WgradPlan* p) {
+  *p = WgradPlan();
+  p->family = WGRAD_C3_BF16; p->kernel = 1; p->reduce = WGRAD_REDUCE_C3;
+  wgrad_patches(p, N, H, W, Q_W, Q_H);
+  wgrad_split(p, 1024, 1, 1024, 64 * 32, 64);
+}
+void plan_co16(int N, int H, int W, int Cin_s, WgradPlan* p) {
+  *p = WgradPlan();
+  p->family = WGRAD_CO16_F32; p->kernel = 2;
+  p->nci_t = ceil_div(Cin_s, S_BCI);
+  wgrad_patches(p, N, H, W, PW, S_PH);
+  wgrad_split(p, 256, 4, 256, (size_t)9 * 16 * Cin_s, 16);
 }
 
-SmallPlan plan_co16(int N, int H, int W, int Cin_s) {
-  SmallPlan p;
-  p.npx = ceil_div(W, PW); p.npy = ceil_div(H, S_PH); p.npatches = N * p.npx * p.npy;
-  p.nci_t = ceil_div(Cin_s, S_BCI);
-  int want = ceil_div(256, p.nci_t);
-  const int max_split = p.npatches / 4 > 0 ? p.npatches / 4 : 1;
-  if (want > max_split) want = max_split;
-  p.per_split = ceil_div(p.npatches, want);
-  p.nsplit = ceil_div(p.npatches, p.per_split);
-  p.slab_floats = (size_t)p.nsplit * 9 * 16 * Cin_s;
-  p.bslab_floats = (size_t)p.nsplit * 16;
-  return p;
+int g_c3_bf16 = 1;      // the bf16-operand conv1_1 weight gradient (osvos_debug_set_c3_bf16: tests compare it with the fp32 kernel)
+
+// the two shapes.  The WIDE operand may be a bf16 tensor (dy of the Cin = 3 layer, x of the Cout = 16 layers); the narrow one is fp32
+bool is_c3(const WgradCall& c) { return c.Cin == 3 && c.Cin_s == 8 && c.Cout <= 64; }
+bool is_co16(const WgradCall& c) { return c.Cout == 16 && c.Cout_s % 4 == 0 && c.Cin_s % 32 == 0 && c.Cin == c.Cin_s; }
+
+int choose(const WgradCall& c, WgradPlan* p) {
+  if (!c.x_bf16 && !c.dy_bf16)      // what an fp32-tensor call of the exact kernels must pass whichever of them takes it
+    if (int rc = osvos_wgrad_f32_check(c)) return rc;
+  OSVOS_ARG_CHECK(c.Cout % 4 == 0, "wgrad small: Cout must be a multiple of 4 (Cout %d)", c.Cout);
+  if (is_c3(c) && c.Cout == 64 && c.Cout_s % 8 == 0 && c.dy_bf16 && g_c3_bf16) {      // bf16-store mode: dY is bf16 -> bf16 matrix pipe
+    plan_c3_bf16(c.N, c.H, c.W, p);
+    OSVOS_ARG_CHECK((long)c.H * c.W * c.Cout_s < (1L << 30), "wgrad c3 bf16: image too large for 31-bit byte offsets");
+    OSVOS_ARG_CHECK(!c.x_bf16, "wgrad c3: x (3 channels) must be fp32");
+  } else if (is_c3(c)) {
+    plan_c3(c.N, c.H, c.W, p);
+    OSVOS_ARG_CHECK(!c.x_bf16, "wgrad c3: x (3 channels) must be fp32");
+  } else {
+    OSVOS_ARG_CHECK(is_co16(c), "wgrad small: neither conv1_1's shape nor Cout 16 (Cin %d/%d Cout %d/%d)", c.Cin, c.Cin_s, c.Cout, c.Cout_s);
+    OSVOS_ARG_CHECK(!c.dy_bf16, "wgrad co16: dy (16 channels) must be fp32");
+    plan_co16(c.N, c.H, c.W, c.Cin_s, p);
+    p->reduce = osvos_wgrad_reduce_kind(p->nsplit, 16, c.Cin, c.Cin_s);
+  }
+  return 0;
 }
+
+int launch_c3_f32(const WgradCall& c, const WgradPlan& p);
+int launch_c3_bf16(const WgradCall& c, const WgradPlan& p);
+int launch_co16(const WgradCall& c, const WgradPlan& p);
+typedef int (*SmallLaunch)(const WgradCall&, const WgradPlan&);
+constexpr SmallLaunch kKernels[] = {launch_c3_f32, launch_c3_bf16, launch_co16};
 
 // conv1_1's argument struct, the same for both of its kernels but for the plan
-C3Args c3_args(const WgradCall& c, const SmallPlan& p) {
+C3Args c3_args(const WgradCall& c, const WgradPlan& p) {
   C3Args a;
   a.x = reinterpret_cast<const float*>(c.x); a.dy = c.dy; a.dy_bf16 = c.dy_bf16 ? 1 : 0;
   a.slab = reinterpret_cast<float*>(c.ws);
@@ -495,8 +506,30 @@ C3Args c3_args(const WgradCall& c, const SmallPlan& p) {
   a.npx = p.npx; a.npy = p.npy; a.npatches = p.npatches; a.per_split = p.per_split;
   return a;
 }
-
-int g_c3_bf16 = 1;      // the bf16-operand conv1_1 weight gradient (osvos_debug_set_c3_bf16: tests compare it with the fp32 kernel)
+int launch_c3_bf16(const WgradCall& c, const WgradPlan& p) {
+  hipLaunchKernelGGL(wgrad_c3_bf16_kernel, dim3(p.nsplit), dim3(256), Q_LDS, c.stream, c3_args(c, p));
+  OSVOS_LAUNCH_CHECK();
+  return 0;
+}
+int launch_c3_f32(const WgradCall& c, const WgradPlan& p) {
+  constexpr size_t lds = (size_t)(C3_PPIX * 64 + C3_XPIX * 4) * 4;
+  if (int rc = osvos_set_dyn_lds_once<&wgrad_c3_f32_kernel>(lds)) return rc;
+  hipLaunchKernelGGL(wgrad_c3_f32_kernel, dim3(p.nsplit), dim3(256), lds, c.stream, c3_args(c, p));
+  OSVOS_LAUNCH_CHECK();
+  return 0;
+}
+int launch_co16(const WgradCall& c, const WgradPlan& p) {
+  S16Args a;
+  a.x = c.x; a.x_bf16 = c.x_bf16 ? 1 : 0; a.dy = reinterpret_cast<const float*>(c.dy);
+  a.slab = reinterpret_cast<float*>(c.ws);
+  a.bslab = c.db ? a.slab + p.slab_floats : nullptr;
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cin_s = c.Cin_s; a.Cout_s = c.Cout_s;
+  a.npx = p.npx; a.npy = p.npy; a.npatches = p.npatches; a.per_split = p.per_split; a.nci_t = p.nci_t;
+  constexpr size_t lds = (size_t)(S_PPIX * S_BCI + S_YPIX * 16) * 4;
+  hipLaunchKernelGGL(wgrad_co16_f32_kernel, dim3((unsigned)p.blocks), dim3(256), lds, c.stream, a);
+  OSVOS_LAUNCH_CHECK();
+  return 0;
+}
 
 }  // namespace
 
@@ -506,79 +539,43 @@ extern "C" int osvos_debug_set_c3_bf16(int on) {
   return prev;
 }
 
-extern "C" int osvos_wgrad_c3_plan(int N, int H, int W, int bf16_dy, int* out) {
-  OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && out != nullptr, "wgrad_c3_plan: bad arguments");
-  const SmallPlan p = bf16_dy ? plan_c3_bf16(N, H, W) : plan_c3(N, H, W);
-  out[0] = p.npx; out[1] = p.npy; out[2] = p.npatches; out[3] = p.per_split; out[4] = p.nsplit;
-  return 0;
+bool osvos_wgrad_small_applicable(const WgradCall& c) {
+  OSVOS_ENV_INT(env_generic, "OSVOS_WGRAD_GENERIC", 0);     // tuning / tests: force the generic kernel (which takes fp32 tensors only)
+  if (env_generic && !c.x_bf16 && !c.dy_bf16) return false;
+  return is_c3(c) || is_co16(c);
 }
 
+// conv1_1: whichever of its two kernels runs (the choice follows the tensors and osvos_debug_set_c3_bf16)
 size_t osvos_wgrad_small_ws_bytes(int N, int H, int W, int Cin_s, int Cout) {
-  if (Cin_s == 8 && Cout <= 64) {
-    SmallPlan p = plan_c3(N, H, W), q = plan_c3_bf16(N, H, W);
-    const size_t a = p.slab_floats + p.bslab_floats, b = q.slab_floats + q.bslab_floats;
-    return align_up((a > b ? a : b) * sizeof(float), 256);
+  const WgradCall c = wgrad_shape_call(N, H, W, Cin_s, Cout);
+  WgradPlan p, q;
+  if (is_c3(c)) {
+    plan_c3(N, H, W, &p);
+    plan_c3_bf16(N, H, W, &q);
+    const size_t a = wgrad_plan_ws_bytes(p), b = wgrad_plan_ws_bytes(q);
+    return a > b ? a : b;
   }
-  if (Cout == 16) {
-    SmallPlan p = plan_co16(N, H, W, Cin_s);
-    return align_up((p.slab_floats + p.bslab_floats) * sizeof(float), 256);
+  if (is_co16(c)) {
+    plan_co16(N, H, W, Cin_s, &p);
+    return wgrad_plan_ws_bytes(p);
   }
   return 0;
 }
 
-// returns 1 if the shape is not one of the two special cases (caller falls through to the generic kernel).  The WIDE operand may be a bf16
-// tensor (dy of the Cin = 3 layer, x of the Cout = 16 layers); the narrow one is fp32
+int osvos_wgrad_small_plan(const WgradCall& c, WgradPlan* p) { return choose(c, p); }
+void osvos_wgrad_c3_split(int N, int H, int W, int bf16_pipe, WgradPlan* p) { bf16_pipe ? plan_c3_bf16(N, H, W, p) : plan_c3(N, H, W, p); }
+
 int osvos_conv3x3_wgrad_small_f32(const WgradCall& c) {
-  float *const dw = c.dw, *const db = c.db;
-  void* const ws = c.ws; hipStream_t stream = c.stream;
-  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cin_s = c.Cin_s, Cout = c.Cout, Cout_s = c.Cout_s, accumulate = c.accumulate, phase = c.phase;
-  if (Cin == 3 && Cin_s == 8 && Cout == 64 && Cout_s % 8 == 0 && c.dy_bf16 && g_c3_bf16) {      // bf16-store mode: dY is bf16 -> bf16 matrix pipe
-    SmallPlan p = plan_c3_bf16(N, H, W);
-    const C3Args a = c3_args(c, p);
-    OSVOS_ARG_CHECK((long)H * W * Cout_s < (1L << 30), "wgrad c3 bf16: image too large for 31-bit byte offsets");
-    OSVOS_ARG_CHECK(!c.x_bf16, "wgrad c3: x (3 channels) must be fp32");
-    if (phase != WGRAD_REDUCE) {
-      hipLaunchKernelGGL(wgrad_c3_bf16_kernel, dim3(p.nsplit), dim3(256), Q_LDS, stream, a);
-      OSVOS_LAUNCH_CHECK();
-    }
-    if (phase == WGRAD_PARTIALS) return 0;
-    hipLaunchKernelGGL(wgrad_c3_reduce_kernel, dim3(ceil_div(Cout * 28, 4)), dim3(256), 0, stream,
-                       a.slab, a.bslab, dw, db, p.nsplit, Cout, accumulate);
-    OSVOS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (Cin == 3 && Cin_s == 8 && Cout <= 64 && Cout % 4 == 0) {
-    SmallPlan p = plan_c3(N, H, W);
-    const C3Args a = c3_args(c, p);
-    OSVOS_ARG_CHECK(!c.x_bf16, "wgrad c3: x (3 channels) must be fp32");
-    constexpr size_t lds = (size_t)(C3_PPIX * 64 + C3_XPIX * 4) * 4;
-    if (int rc = osvos_set_dyn_lds_once<&wgrad_c3_f32_kernel>(lds)) return rc;
-    if (phase != WGRAD_REDUCE) {
-      hipLaunchKernelGGL(wgrad_c3_f32_kernel, dim3(p.nsplit), dim3(256), lds, stream, a);
-      OSVOS_LAUNCH_CHECK();
-    }
-    if (phase == WGRAD_PARTIALS) return 0;
-    hipLaunchKernelGGL(wgrad_c3_reduce_kernel, dim3(ceil_div(Cout * 28, 4)), dim3(256), 0, stream,
-                       a.slab, a.bslab, dw, db, p.nsplit, Cout, accumulate);
-    OSVOS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (Cout == 16 && Cout_s % 4 == 0 && Cin_s % 32 == 0 && Cin == Cin_s) {
-    OSVOS_ARG_CHECK(!c.dy_bf16, "wgrad co16: dy (16 channels) must be fp32");
-    SmallPlan p = plan_co16(N, H, W, Cin_s);
-    S16Args a;
-    a.x = c.x; a.x_bf16 = c.x_bf16 ? 1 : 0; a.dy = reinterpret_cast<const float*>(c.dy);
-    a.slab = reinterpret_cast<float*>(ws);
-    a.bslab = db ? a.slab + p.slab_floats : nullptr;
-    a.N = N; a.H = H; a.W = W; a.Cin_s = Cin_s; a.Cout_s = Cout_s;
-    a.npx = p.npx; a.npy = p.npy; a.npatches = p.npatches; a.per_split = p.per_split; a.nci_t = p.nci_t;
-    constexpr size_t lds = (size_t)(S_PPIX * S_BCI + S_YPIX * 16) * 4;
-    if (phase != WGRAD_REDUCE) {
-      hipLaunchKernelGGL(wgrad_co16_f32_kernel, dim3(p.nsplit * p.nci_t), dim3(256), lds, stream, a);
-      OSVOS_LAUNCH_CHECK();
-    }
-    if (phase == WGRAD_PARTIALS) return 0;
-    return osvos_wgrad_reduce_launch(a.slab, a.bslab, dw, db, p.nsplit, 16, Cin, Cin_s, accumulate, stream);
-  }
-  return 1;
+  WgradPlan p;
+  if (int rc = choose(c, &p)) return rc;
+  float* const slab = reinterpret_cast<float*>(c.ws);
+  float* const bslab = c.db ? slab + p.slab_floats : nullptr;
+  if (c.phase != WGRAD_REDUCE)
+    if (int rc = kKernels[p.kernel](c, p)) return rc;
+  if (c.phase == WGRAD_PARTIALS) return 0;
+  if (p.reduce != WGRAD_REDUCE_C3)
+    return osvos_wgrad_reduce_launch(p.reduce, slab, bslab, c.dw, c.db, p.nsplit, 16, c.Cin, c.Cin_s, c.accumulate, c.stream);
+  hipLaunchKernelGGL(wgrad_c3_reduce_kernel, dim3(ceil_div(c.Cout * 28, 4)), dim3(256), 0, c.stream, slab, bslab, c.dw, c.db, p.nsplit, c.Cout, c.accumulate);
+  OSVOS_LAUNCH_CHECK();
+  return 0;
 }

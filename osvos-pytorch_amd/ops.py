@@ -275,6 +275,18 @@ def wgrad_wide_plan(n, h, w, cin_s, cout, dtype, bf16_tensors=False):
     return dict(zip(("pw", "ph", "npx", "npy", "npatches", "per_split", "nsplit", "nco_t", "nci_t", "blocks", "map", "wide"), [int(v) for v in out]))
 
 
+WGRAD_PLAN_FIELDS = ("family", "kernel", "pw", "ph", "npx", "npy", "npatches", "per_split", "nsplit", "nco_t", "nci_t", "blocks", "map", "reduce",
+                     "slab_floats", "bslab_floats")
+
+
+def wgrad_plan(n, h, w, cin, cin_s, cout, dtype, flags=0, cout_s=None):
+    """What the weight-gradient launchers decide for a call (osvos_wgrad_plan; host only, needs no GPU): dict of WGRAD_PLAN_FIELDS.  dtype: the
+    dtype word (with the X3 piece flags); flags: OSVOS_WGRAD_PLAN_* bits of include/osvos_hip.h -- 1 x is bf16, 2 dy is bf16, 4 no bias gradient."""
+    out = (C.c_int * len(WGRAD_PLAN_FIELDS))()
+    check(lib().osvos_wgrad_plan(n, h, w, cin, cin_s, cout, cout if cout_s is None else cout_s, dtype, flags, out), "wgrad_plan")
+    return dict(zip(WGRAD_PLAN_FIELDS, [int(v) for v in out]))
+
+
 def conv3x3_plan(n, h, w, cin, cout, dtype, flags, y_cs=None, tile=-1, ksplit=0, sk_grid=0):
     """What the convolution launchers decide for a call (osvos_conv3x3_plan; host only, needs no GPU): dict of family, tile, map, ksplit,
     finalize, sk_grid, sk_order, presplit, pipe, pool_after.  dtype: the dtype word (with BF16_W2 / the X3 piece flags); flags: OSVOS_PLAN_* bits
