@@ -541,6 +541,42 @@ size_t osvos_crf_ws_bytes(int N, int H, int W, int iters);
 int osvos_crf_refine(const float* unary, const float* init, const unsigned char* bgr, float* out, void* ws, int N, int H, int W, int iters,
                      int radius, int dilation, float w_a, float w_s, float a_s, float a_c, float g_s, void* stream);
 
+/* ---- motion compensation: a block-matching motion field between two decoded frames, and the integer warp that applies it ----
+ * Integer arithmetic throughout; division is floor division; results are exact (tests compare bit for bit).
+ * Luma of a BGR byte triple: Y = (29 B + 150 G + 77 R + 128) >> 8, in 0..255.
+ * Grid: step S, block B, search R.  GH = ceil(H / S) by GW = ceil(W / S) cells; cell (i, j) owns the pixels y in [i S, min((i + 1) S, H)),
+ *   x in [j S, min((j + 1) S, W)).  Its matching block is the B x B square with top-left corner (i S + floor((S - B) / 2),
+ *   j S + floor((S - B) / 2)): for B > S the blocks overlap and are centred on their cells.
+ * Cost of a candidate d = (dx, dy), |dx|, |dy| <= R:
+ *     cost(d) = sum over the block's B * B pixels p of |Ycur(clamp(p)) - Yprev(clamp(p + d))| + penalty * (|dx| + |dy|)
+ *   clamp brings each coordinate into the frame (edge replication), applied to p and to p + d separately.
+ * Choice: the cell's vector is the candidate that minimises (cost, dx * dx + dy * dy, dy, dx) lexicographically -- every tie is decided; a
+ *   constant frame gives all-zero vectors.  The vector points from a pixel of the CURRENT frame to where it was in the PREVIOUS frame (a
+ *   backward field).
+ * Median: `median` passes over the vector grid, each replacing each component by the median of its 3 x 3 grid neighbourhood (grid indices
+ *   clamped).  cost stays the pre-median minimum of the cell.
+ * osvos_flow_block_match: prev_bgr, cur_bgr [N][H][W][3] uint8 -> vec [N][GH][GW][2] int32 = (dx, dy), cost [N][GH][GW] int32 (may be NULL).
+ *   Frames of a batch are independent.  2 + median launches on `stream` (luma planes; one workgroup per tile of cells with the tile's luma
+ *   staged in LDS, candidates walked four at a time with v_qsad_pk_u16_u8, the minimum taken as an integer min of packed keys; the median passes), no atomics on
+ *   global memory, every element of vec and cost written.  ws: osvos_flow_ws_bytes(...) bytes, 4-byte aligned, contents irrelevant on entry
+ *   (0 for arguments the call refuses).
+ * osvos_flow_warp: out(n, y, x) = src(n, y + dy, x + dx) with (dx, dy) the vector of cell (min(y / S, GH - 1), min(x / S, GW - 1)), `fill`
+ *   where the source coordinate leaves the frame.  src, out [N][H][W] of dtype 0 = uint8 or 1 = float32 (moved as 32-bit words: NaN payloads
+ *   and -0 survive); vec [N][GH][GW][2] int32 with any values.  With dtype 0, fill must be an integer in 0..255.  out must not be src.  One
+ *   launch.  Zero vectors (search = 0) make the warp the identity.
+ * Limits: block 1..32, step 1..32, search 0..48, penalty 0..65535, median 0..8, sides 1..16384, N 1..65535.  The largest cost,
+ *   255 * 1024 + 65535 * 96, fits int.  Every argument error returns < 0 before any device call. */
+#define OSVOS_FLOW_MAX_BLOCK 32
+#define OSVOS_FLOW_MAX_STEP 32
+#define OSVOS_FLOW_MAX_SEARCH 48
+#define OSVOS_FLOW_MAX_PENALTY 65535
+#define OSVOS_FLOW_MAX_MEDIAN 8
+#define OSVOS_FLOW_MAX_SIDE 16384
+size_t osvos_flow_ws_bytes(int N, int H, int W, int block, int step, int search, int median);
+int osvos_flow_block_match(const unsigned char* prev_bgr, const unsigned char* cur_bgr, int* vec, int* cost, void* ws, int N, int H, int W,
+                           int block, int step, int search, int penalty, int median, void* stream);
+int osvos_flow_warp(const void* src, int dtype, const int* vec, void* out, int N, int H, int W, int step, float fill, void* stream);
+
 /* ---- online adaptation: exact squared Euclidean distance maps and the adaptation targets made from them ----
  * osvos_mask_sqdist: mask [N][H][W] uint8 -> sqdist [N][H][W] int32.  A pixel q is a SOURCE when (mask[q] != 0) != (invert != 0);
  *   sqdist[n][y][x] = min over the sources q of image n of |p - q|^2, an exact integer, OSVOS_SQDIST_NONE everywhere in an image without a

@@ -30,6 +30,12 @@ TTA_MAX_VIEWS = 16          # OSVOS_TTA_MAX_VIEWS: logit maps per osvos_tta_fuse
 CRF_MAX_RADIUS = 7          # OSVOS_CRF_MAX_RADIUS: largest window radius of osvos_crf_refine
 CRF_MAX_REACH = 16          # OSVOS_CRF_MAX_REACH: largest radius * dilation
 CRF_MAX_ITERS = 64          # OSVOS_CRF_MAX_ITERS: mean-field iterations per osvos_crf_refine call
+FLOW_MAX_BLOCK = 32         # OSVOS_FLOW_MAX_BLOCK: largest matching block side of osvos_flow_block_match
+FLOW_MAX_STEP = 32          # OSVOS_FLOW_MAX_STEP: largest grid step (osvos_flow_block_match, osvos_flow_warp)
+FLOW_MAX_SEARCH = 48        # OSVOS_FLOW_MAX_SEARCH: largest search range, pixels on every side
+FLOW_MAX_PENALTY = 65535    # OSVOS_FLOW_MAX_PENALTY: largest cost per pixel of |dx| + |dy|
+FLOW_MAX_MEDIAN = 8         # OSVOS_FLOW_MAX_MEDIAN: median passes over the vector grid
+FLOW_MAX_SIDE = 16384       # OSVOS_FLOW_MAX_SIDE: largest H / W of the flow calls
 SQDIST_NONE = 2147483647    # OSVOS_SQDIST_NONE: osvos_mask_sqdist's value in an image without a source pixel
 SQDIST_MAX_SIDE = 4096      # OSVOS_SQDIST_MAX_SIDE: largest H / W of osvos_mask_sqdist and osvos_adapt_targets
 GENERIC_DECONV = 0x100      # OSVOS_FLAG_GENERIC_DECONV: OR-ed into the dtype of the osvos_net_* calls
@@ -124,6 +130,9 @@ PROTOTYPES = {
     "osvos_tta_fuse": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
     "osvos_crf_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "osvos_crf_refine": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _vp]),
+    "osvos_flow_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "osvos_flow_block_match": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "osvos_flow_warp": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "osvos_mask_sqdist_ws_bytes": (_sz, [_i, _i, _i]),
     "osvos_mask_sqdist": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "osvos_adapt_ws_bytes": (_sz, [_i, _i, _i]),

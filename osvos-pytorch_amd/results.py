@@ -453,7 +453,8 @@ class ComponentTracker(object):
     frame 0 (``first_mask`` [H,W] or [1,H,W], non-zero = object); when nothing was kept the next frame passes whole, so the object can be
     found again.  ``__call__`` takes a batch of consecutive frames and returns the filtered logits (dropped pixels at -inf); it enqueues
     only.  The last kept map, the workspace and the running counts live on the device; ``summary`` reads the counts back, once.  Call it on
-    one stream (or order the streams yourself): one workspace serves every call."""
+    one stream (or order the streams yourself): one workspace serves every call.  ``seed`` is the kept map the next call starts from, uint8
+    [1,H,W]: read it, move it (``flow.MotionCompensator.warp``) and assign it back when the object moves farther than ``radius`` a frame."""
 
     def __init__(self, first_mask, radius, threshold=0.5, connectivity=8, min_area=0):
         if not torch.is_tensor(first_mask) or not first_mask.is_cuda:
@@ -490,6 +491,18 @@ class ComponentTracker(object):
         self._counts[2] += n
         self._host = None
         return out.view(logits.shape)
+
+    @property
+    def seed(self):
+        """the uint8 [1,H,W] map (non-zero = kept) the next frame's components are tested against"""
+        return self._seed
+
+    @seed.setter
+    def seed(self, value):
+        if not torch.is_tensor(value) or tuple(value.shape) != (1, self.h, self.w) or value.device != self._seed.device:
+            raise ValueError("seed must be a [1,%d,%d] tensor on %s, got %r" % (self.h, self.w, self._seed.device,
+                                                                              tuple(value.shape) if torch.is_tensor(value) else value))
+        self._seed = _seed_bytes(value, value.device, 1, self.h, self.w).view(1, self.h, self.w)
 
     def summary(self):
         """{'seen', 'kept', 'frames'}: components met, components kept, frames passed so far (one device-to-host copy)."""

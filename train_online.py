@@ -22,6 +22,10 @@ running on the MI355X-native OSVOS path.  Differences by design:
   * ``--crf-iters N``: edge-aware refinement of every test frame's logit map against the decoded frame -- N mean-field steps of a local
     dense CRF on the device (osvos_pytorch_amd.refine.CrfRefiner), after the forward / test-time augmentation / adapter and before
     --track-components; parameters --crf-radius, --crf-dilation, --crf-weights, --crf-thetas (starting values, not tuned on DAVIS)
+  * ``--flow-search R``: motion compensation of what the test loop carries from frame to frame -- a block-matching motion field from the
+    previous decoded frame to the current one on the device (osvos_pytorch_amd.flow.MotionCompensator) moves the previous mask of
+    --adapt-steps and the seed of --track-components to where the object is now; parameters --flow-block, --flow-step, --flow-penalty,
+    --flow-median (starting values, not tuned on DAVIS)
   * launched under torchrun with N processes, rank r fine-tunes sequences r, r+N, ... of the
     comma-separated SEQ_NAME list (independent replicas: online training has no exchange step)
 """
@@ -271,6 +275,33 @@ def make_crf(args):
     return CrfRefiner(**args.crf) if args.crf else None
 
 
+def check_flow_args(args):
+    """the --flow-* rules; SystemExit on values or combinations the motion compensation does not take -- checked before any GPU work.  Sets
+    args.flow to the keyword arguments of flow.MotionCompensator, or None with --flow-search 0"""
+    from osvos_pytorch_amd import flow
+    args.flow = None
+    try:
+        flow.check_flow(args.flow_search, args.flow_block, args.flow_step, args.flow_penalty, args.flow_median)
+    except ValueError as e:
+        raise SystemExit('--flow-*: %s' % e)
+    if not args.flow_search:
+        return
+    if args.multi_object:
+        raise SystemExit('--flow-search runs in the single-object loop only: the per-object trackers of --multi-object run over 64-frame chunks, '
+                         'the motion field moves one frame\'s state to the next')
+    if not args.device_augment:
+        raise SystemExit('--flow-search needs --device-augment: the motion field is made from the decoded uint8 frames on the device (the other '
+                         'loaders deliver no frame_u8, and only this one is known to deliver one frame per batch)')
+    if not args.adapt_steps and args.track_components is None:
+        raise SystemExit('--flow-search needs --adapt-steps or --track-components: it moves the previous mask of the one and the seed of the other')
+    args.flow = dict(search=args.flow_search, block=args.flow_block, step=args.flow_step, penalty=args.flow_penalty, median=args.flow_median)
+
+
+def make_flow(args):
+    from osvos_pytorch_amd.flow import MotionCompensator
+    return MotionCompensator(**args.flow) if args.flow else None
+
+
 def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, nEpochs, nAveGrad):
     """DAVIS 2017 recipe for one sequence: one fine-tuning per object id of the first annotation on that object's binary mask, every frame
     through each network, the K logit stacks merged into label maps, indexed PNGs, J and F per object -- one read-back for the PNGs, one for
@@ -416,10 +447,20 @@ def parse_args(argv=None):
                     help='--crf-iters: weights of the appearance and the smoothness kernel, in logits (each normalised by its kernel\'s mass)')
     ap.add_argument('--crf-thetas', default='8,13,3', metavar='A,B,G',
                     help='--crf-iters: standard deviations -- appearance kernel in pixels, in grey levels, smoothness kernel in pixels')
+    ap.add_argument('--flow-search', type=int, default=0, metavar='R',
+                    help='motion compensation (0 = off): before every test frame a block-matching motion field from the previous decoded frame '
+                         'to this one is made on the device, over +-R pixels (at most 48), and the previous mask of --adapt-steps and the seed '
+                         'of --track-components are moved along it.  Needs --device-augment and at least one of those two; single-object loop '
+                         'only.  The default parameters are starting values, not tuned on DAVIS')
+    ap.add_argument('--flow-block', type=int, default=16, help='--flow-search: side of the matched block, 1..32 pixels, centred on its cell')
+    ap.add_argument('--flow-step', type=int, default=4, help='--flow-search: side of a cell, 1..32 pixels: one vector per cell')
+    ap.add_argument('--flow-penalty', type=int, default=4, help='--flow-search: cost per pixel of |dx| + |dy|, in grey levels summed over the block')
+    ap.add_argument('--flow-median', type=int, default=1, help='--flow-search: 3 x 3 median passes over the vector grid, 0..8')
     args = ap.parse_args(argv)
     args.tta = tta_scales(args)
     check_adapt_args(args)
     check_crf_args(args)
+    check_flow_args(args)
     if args.tta and not (args.device_augment or (args.multi_object and args.synthetic)):
         raise SystemExit('--tta-scales / --tta-flip need --device-augment (or --multi-object --synthetic): test-time augmentation makes its views '
                          'from the decoded uint8 frame on the device')
@@ -466,10 +507,19 @@ def main():
         tta = make_tta(args, net)
         adapter = make_adapter(args, net, trainloader)
         crf = make_crf(args)
+        mc = make_flow(args)
         prev_mask = None                     # --adapt-steps: the previous frame's final mask (frame 0: its annotation)
         with torch.no_grad():
             for sample in testloader:
                 fname = sample['fname']
+                if mc is not None:                   # the field from the previous frame to this one moves what is carried over
+                    if sample['frame_u8'].dim() != 3:
+                        raise SystemExit('--flow-search: the test loader delivered %d frames in one batch; it takes one' % int(sample['frame_u8'].shape[0]))
+                    mc.update(sample['frame_u8'])
+                    if prev_mask is not None:
+                        prev_mask = mc.warp(prev_mask)
+                    if tracker is not None:
+                        tracker.seed = mc.warp(tracker.seed)
                 if tta is not None:
                     fused = tta(sample['frame_u8'])
                 elif adapter is not None and prev_mask is not None:
