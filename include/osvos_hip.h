@@ -577,6 +577,47 @@ int osvos_flow_block_match(const unsigned char* prev_bgr, const unsigned char* c
                            int block, int step, int search, int penalty, int median, void* stream);
 int osvos_flow_warp(const void* src, int dtype, const int* vec, void* out, int N, int H, int W, int step, float fill, void* stream);
 
+/* ---- superpixel snapping: an integer grid-SLIC on the decoded frame, and logit pooling over a labelling ----
+ * Integer arithmetic throughout; division is floor division; results are exact and do not depend on tile shape, schedule or the order in
+ *   which atomics arrive (tests compare bit for bit).
+ * Superpixels (osvos_superpixels_slic): frames [N][H][W][3] uint8 BGR, cell S, compactness m, iters T.
+ *   Grid: GH = ceil(H / S), GW = ceil(W / S), K = GH * GW clusters per frame, cluster k = gy * GW + gx; a pixel's home cell is (y / S, x / S).
+ *   update(labels, prev), per cluster, with count the number of pixels that carry label k: each of the five centre components (x, y, b, g, r)
+ *     becomes floor((2 sum + count) / (2 count)) over those pixels; a cluster with count == 0 keeps prev.
+ *   assign(centres), per pixel: of the clusters of the 3 x 3 cells around its home cell that lie inside the grid, the minimiser of (D, k),
+ *     D = S * S * dc + m * m * ds, dc the squared BGR distance to the centre colour, ds the squared pixel distance to the centre position.
+ *   labels_0 = home cell; centres_0 = update(labels_0, -); for t = 1..T: labels_t = assign(centres_(t-1)), centres_t = update(labels_t,
+ *     centres_(t-1)).  Out: labels [N][H][W] int32 = labels_T; centres [N][K][6] int32 = (x, y, b, g, r, count) of centres_T (may be NULL).
+ *   32 bits suffice: a cluster's pixels lie in the 3 x 3 cells around it, so does its centre; hence |dx|, |dy| < 3 S and
+ *     D < 4096 * 195075 + 4096 * 73728 < 2^31; a cluster has at most 9 S S = 36864 pixels and its x or y sum is below 16384 * 36864 < 2^32.
+ *   Deliberately left out: there is NO connectivity enforcement (a superpixel may be disconnected; pooling does not mind), and colour is
+ *     plain BGR, not CIELAB.  Frames of a batch are independent.
+ *   Launches on `stream`: one memset, then 2 (T + 1) kernels -- per step one tile kernel (labels_0, or assign from the tile's ring of
+ *     centres in LDS, fused with the sums of the next update: LDS integer atomics, at most one global atomic per non-zero accumulator and
+ *     workgroup) and one per-cluster update that divides and re-zeroes the sums.  No workgroup waits for another.
+ *   ws: osvos_superpixels_ws_bytes(N, H, W, cell) bytes (the sums and the working centres), 4-byte aligned, contents irrelevant on entry;
+ *     0 for arguments the call refuses.  frames, labels, centres and ws must not overlap.
+ * Pooling (osvos_superpixels_pool): logits [N][H][W] float32, labels [N][H][W] int32 (ANY labelling, not only SLIC's), K.
+ *   Per pixel q = (int) rint(clamp(x, -16384, 16384) * 65536), half to even; NaN maps to the lower clamp (a NaN is background).  Per frame
+ *   and label: the int64 sum of q and the int32 count; mean_q = floor((2 sum + count) / (2 count)) -- floor, not C truncation: sums are
+ *   negative; out = (float) mean_q * 2^-16.  A pixel whose label is outside [0, K) passes its logit through bit for bit and contributes
+ *   to nothing.  One memset and two launches: an accumulate pass (per workgroup an LDS table over the 2048 labels from the tile's smallest
+ *   one, 64-bit integer global atomics for its non-empty slots and for labels beyond it) and an apply pass (one gather per pixel).
+ *   ws: osvos_superpixels_pool_ws_bytes(N, K) bytes, 8-byte aligned, contents irrelevant on entry; 0 for arguments the call refuses.
+ *   out must not overlap logits or labels; ws must not overlap any of the three.
+ * Limits: cell 2..64, compactness 0..64, iters 0..16, K 1..2^28, sides 1..16384, N 1..65535, N * H * W <= 2^38.  Every argument error
+ *   returns < 0 before any device call, with a text that names the bad parameter. */
+#define OSVOS_SUPERPIXELS_MAX_CELL 64
+#define OSVOS_SUPERPIXELS_MAX_COMPACTNESS 64
+#define OSVOS_SUPERPIXELS_MAX_ITERS 16
+#define OSVOS_SUPERPIXELS_MAX_SIDE 16384
+#define OSVOS_SUPERPIXELS_MAX_K 268435456
+size_t osvos_superpixels_ws_bytes(int N, int H, int W, int cell);
+int osvos_superpixels_slic(const unsigned char* frames, int* labels, int* centres, void* ws, int N, int H, int W, int cell, int compactness,
+                           int iters, void* stream);
+size_t osvos_superpixels_pool_ws_bytes(int N, int K);
+int osvos_superpixels_pool(const float* logits, const int* labels, float* out, void* ws, int N, int H, int W, int K, void* stream);
+
 /* ---- online adaptation: exact squared Euclidean distance maps and the adaptation targets made from them ----
  * osvos_mask_sqdist: mask [N][H][W] uint8 -> sqdist [N][H][W] int32.  A pixel q is a SOURCE when (mask[q] != 0) != (invert != 0);
  *   sqdist[n][y][x] = min over the sources q of image n of |p - q|^2, an exact integer, OSVOS_SQDIST_NONE everywhere in an image without a

@@ -36,6 +36,11 @@ FLOW_MAX_SEARCH = 48        # OSVOS_FLOW_MAX_SEARCH: largest search range, pixel
 FLOW_MAX_PENALTY = 65535    # OSVOS_FLOW_MAX_PENALTY: largest cost per pixel of |dx| + |dy|
 FLOW_MAX_MEDIAN = 8         # OSVOS_FLOW_MAX_MEDIAN: median passes over the vector grid
 FLOW_MAX_SIDE = 16384       # OSVOS_FLOW_MAX_SIDE: largest H / W of the flow calls
+SUPERPIXELS_MAX_CELL = 64   # OSVOS_SUPERPIXELS_MAX_CELL: largest cell side of osvos_superpixels_slic (the smallest is 2)
+SUPERPIXELS_MAX_COMPACTNESS = 64  # OSVOS_SUPERPIXELS_MAX_COMPACTNESS: largest weight of the pixel distance
+SUPERPIXELS_MAX_ITERS = 16  # OSVOS_SUPERPIXELS_MAX_ITERS: assign / update steps per osvos_superpixels_slic call
+SUPERPIXELS_MAX_SIDE = 16384  # OSVOS_SUPERPIXELS_MAX_SIDE: largest H / W of the superpixel calls
+SUPERPIXELS_MAX_K = 268435456  # OSVOS_SUPERPIXELS_MAX_K: most labels per frame of osvos_superpixels_pool
 SQDIST_NONE = 2147483647    # OSVOS_SQDIST_NONE: osvos_mask_sqdist's value in an image without a source pixel
 SQDIST_MAX_SIDE = 4096      # OSVOS_SQDIST_MAX_SIDE: largest H / W of osvos_mask_sqdist and osvos_adapt_targets
 GENERIC_DECONV = 0x100      # OSVOS_FLAG_GENERIC_DECONV: OR-ed into the dtype of the osvos_net_* calls
@@ -133,6 +138,10 @@ PROTOTYPES = {
     "osvos_flow_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "osvos_flow_block_match": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "osvos_flow_warp": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "osvos_superpixels_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "osvos_superpixels_slic": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "osvos_superpixels_pool_ws_bytes": (_sz, [_i, _i]),
+    "osvos_superpixels_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "osvos_mask_sqdist_ws_bytes": (_sz, [_i, _i, _i]),
     "osvos_mask_sqdist": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "osvos_adapt_ws_bytes": (_sz, [_i, _i, _i]),

@@ -26,6 +26,9 @@ running on the MI355X-native OSVOS path.  Differences by design:
     previous decoded frame to the current one on the device (osvos_pytorch_amd.flow.MotionCompensator) moves the previous mask of
     --adapt-steps and the seed of --track-components to where the object is now; parameters --flow-block, --flow-step, --flow-penalty,
     --flow-median (starting values, not tuned on DAVIS)
+  * ``--snap-cell S``: superpixel snapping of every test frame's logit map, as in the OSVOS paper -- an integer grid-SLIC of cell S on the
+    decoded frame and the mean of the logits over each superpixel, on the device (osvos_pytorch_amd.superpixels.SuperpixelSnapper), after
+    --crf-iters and before --track-components; parameters --snap-compactness, --snap-iters (starting values, not tuned on DAVIS)
   * launched under torchrun with N processes, rank r fine-tunes sequences r, r+N, ... of the
     comma-separated SEQ_NAME list (independent replicas: online training has no exchange step)
 """
@@ -302,6 +305,28 @@ def make_flow(args):
     return MotionCompensator(**args.flow) if args.flow else None
 
 
+def check_snap_args(args):
+    """the --snap-* rules; SystemExit on values the snapping does not take -- checked before any GPU work.  Sets args.snap to the keyword
+    arguments of superpixels.SuperpixelSnapper, or None with --snap-cell 0"""
+    from osvos_pytorch_amd import superpixels
+    args.snap = None
+    try:
+        superpixels.check_superpixels(args.snap_cell or 2, args.snap_compactness, args.snap_iters)
+    except ValueError as e:
+        raise SystemExit('--snap-*: %s' % e)
+    if not args.snap_cell:
+        return
+    if not (args.device_augment or (args.multi_object and args.synthetic)):
+        raise SystemExit('--snap-cell needs --device-augment (or --multi-object --synthetic): the superpixels are made from the decoded uint8 '
+                         'frame on the device')
+    args.snap = dict(cell=args.snap_cell, compactness=args.snap_compactness, iters=args.snap_iters)
+
+
+def make_snap(args):
+    from osvos_pytorch_amd.superpixels import SuperpixelSnapper
+    return SuperpixelSnapper(**args.snap) if args.snap else None
+
+
 def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, nEpochs, nAveGrad):
     """DAVIS 2017 recipe for one sequence: one fine-tuning per object id of the first annotation on that object's binary mask, every frame
     through each network, the K logit stacks merged into label maps, indexed PNGs, J and F per object -- one read-back for the PNGs, one for
@@ -361,6 +386,12 @@ def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, n
             stacked = torch.stack(frames[s0:s0 + 64])
             for k in range(K):
                 logits[k, s0:s0 + 64] = crf(logits[k, s0:s0 + 64], stacked)
+    snap = make_snap(args)
+    if snap is not None:
+        for s0 in range(0, len(frames), 64):                                  # (enqueued: nothing is read back)
+            spx = snap.labels(torch.stack(frames[s0:s0 + 64]))                # one labelling per chunk, shared by the K objects
+            for k in range(K):
+                logits[k, s0:s0 + 64] = snap(logits[k, s0:s0 + 64], labels=spx)
     trackers = []
     if args.track_components is not None:
         for k in range(1, K + 1):
@@ -456,11 +487,20 @@ def parse_args(argv=None):
     ap.add_argument('--flow-step', type=int, default=4, help='--flow-search: side of a cell, 1..32 pixels: one vector per cell')
     ap.add_argument('--flow-penalty', type=int, default=4, help='--flow-search: cost per pixel of |dx| + |dy|, in grey levels summed over the block')
     ap.add_argument('--flow-median', type=int, default=1, help='--flow-search: 3 x 3 median passes over the vector grid, 0..8')
+    ap.add_argument('--snap-cell', type=int, default=0, metavar='S',
+                    help='superpixel snapping (0 = off): every test frame\'s logit map is averaged over the superpixels of the decoded frame '
+                         '-- an integer grid-SLIC with cells of S pixels (2..64) on the device -- after --crf-iters and before '
+                         '--track-components, so that a region the image shows as one piece answers as one piece.  Needs --device-augment, '
+                         'or --multi-object --synthetic.  With --multi-object the superpixels of a frame are computed once and shared by '
+                         'the objects.  The default parameters are starting values, not tuned on DAVIS')
+    ap.add_argument('--snap-compactness', type=int, default=10, help='--snap-cell: weight of the pixel distance against the colour distance, 0..64')
+    ap.add_argument('--snap-iters', type=int, default=5, help='--snap-cell: assign / update steps, 0..16 (0: the grid cells themselves)')
     args = ap.parse_args(argv)
     args.tta = tta_scales(args)
     check_adapt_args(args)
     check_crf_args(args)
     check_flow_args(args)
+    check_snap_args(args)
     if args.tta and not (args.device_augment or (args.multi_object and args.synthetic)):
         raise SystemExit('--tta-scales / --tta-flip need --device-augment (or --multi-object --synthetic): test-time augmentation makes its views '
                          'from the decoded uint8 frame on the device')
@@ -508,6 +548,7 @@ def main():
         adapter = make_adapter(args, net, trainloader)
         crf = make_crf(args)
         mc = make_flow(args)
+        snap = make_snap(args)
         prev_mask = None                     # --adapt-steps: the previous frame's final mask (frame 0: its annotation)
         with torch.no_grad():
             for sample in testloader:
@@ -529,6 +570,8 @@ def main():
                     fused = outputs[-1]
                 if crf is not None:
                     fused = crf(fused, sample['frame_u8'])
+                if snap is not None:
+                    fused = snap(fused, sample['frame_u8'])
                 if args.track_components is not None:
                     if tracker is None:
                         if 'gt' not in sample:
