@@ -645,6 +645,52 @@ size_t osvos_adapt_ws_bytes(int N, int H, int W);
 int osvos_adapt_targets(const float* logits, const unsigned char* prev_mask, float pos_logit, int erosion, int distance, float* label,
                         void* counts, int N, int H, int W, void* ws, void* stream);
 
+/* ---- lucid first-frame synthesis: inpaint the background once, then move, re-light and re-composite object and background ----
+ * Integer arithmetic throughout; division is floor division; results are exact (tests compare bit for bit).  Colours are BGR bytes.
+ * osvos_lucid_inpaint (once per sequence): bgr [H][W][3] uint8, hole [H][W] uint8 (non-zero = to be filled) -> out_bgr [H][W][3].
+ *   Fill: a hole pixel p takes the colour of the non-hole pixel q that minimises the key (|p - q|^2, qy, qx) lexicographically -- every tie
+ *     is decided; a non-hole pixel keeps its colour; a frame without a non-hole pixel is copied unchanged (the call still returns 0).
+ *   Smooth, `passes` times: every hole pixel becomes floor((2 sum + n) / (2 n)) per channel, the sum over the (2 radius + 1)^2 window around
+ *     it clipped to the image, n the number of pixels in the clipped window; the window is read from the previous pass's state (hole and
+ *     non-hole pixels alike); non-hole pixels never change.  passes = 0 gives the pure fill.
+ *   Launches on `stream`: a column pass (one lane per column: the row of the column's nearest non-hole pixel, the smaller row on a tie), a
+ *     row pass (one workgroup per row with the row of column answers in LDS; a hole pixel walks outwards from its own column and stops once
+ *     dx^2 > best -- strictly, so that an equally distant candidate with a smaller (qy, qx) is still seen; exact, because within a column the
+ *     key is monotone in |dy|), and one launch per smoothing pass, alternating between ws and out_bgr so that the last writes out_bgr.  No
+ *     atomics; no workgroup waits for another.
+ *   ws: osvos_lucid_inpaint_ws_bytes(H, W, passes) bytes, 4-byte aligned, contents irrelevant on entry; 0 for arguments the call refuses.
+ *     out_bgr must not overlap bgr or hole; ws must not overlap any of the three.
+ *   Limits: sides 1..OSVOS_SQDIST_MAX_SIDE (the largest distance stays inside int32), radius 1..8, passes 0..8.
+ * osvos_lucid_compose (once per training sample): N samples out of one source frame in one launch.  bgr [H][W][3], mask [H][W] (non-zero =
+ *   object), bg [H][W][3] (the inpainted frame) are device pointers; M [N][2][6] doubles, tone [N][2][6] ints and mean3 are HOST pointers and
+ *   travel as kernel arguments: nothing is uploaded and there is no workspace.  Layer 0 is the foreground (colours from bgr, alpha from
+ *   mask != 0), layer 1 the background (colours from bg).  Per sample n, layer L and destination pixel (x, y):
+ *   Coordinates: M[n][L] is a dst -> src affine; exactly as osvos_augment_frame forms them (doubles, no fused multiply-add, rn = round half to
+ *     even): Xb = rn((M1 y + M2) 1024), adelta = rn(M0 x 1024), X = (Xb + adelta + 16) >> 5, ix = X >> 5 (arithmetic), fx = X & 31; Y, iy, fy
+ *     the same with M3, M4, M5.  A flip is just an affine.
+ *   Sample: the four taps (iy + j, ix + i), i, j in {0, 1}, with integer weights (32 - fx, fx) x (32 - fy, fy), which sum to 1024.  A colour
+ *     sample S is the weighted sum of bytes, 0..255 * 1024; a colour tap outside the frame reads the clamped index (edge replication) in BOTH
+ *     layers.  a = the weighted sum of (mask != 0) over the taps, 0..1024; a foreground tap outside the frame has alpha 0.
+ *   Tone: tone[n][L] = (g_b, g_g, g_r, o_b, o_g, o_r), gains Q8 in 0..1024 (256 = 1), offsets -255..255:
+ *     S' = clamp(((S g + 128) >> 8) + (o << 10), 0, 255 << 10).
+ *   Composite: C = a F' + (1024 - a) B' (at most 1024 * 261120 < 2^31); out_img[n][c][y][x] = (float) C * 2^-20 - mean3[c], channel order BGR
+ *     as osvos_augment_frame; out_gt[n][0][y][x] = a >= 512 ? 1.0f : 0.0f.  (Foreground colours are not premultiplied.)
+ *   With identity matrices, gain 256 and offset 0: S' = 1024 v, so wherever mask is set or bg equals bgr the image is (float) v - mean, what
+ *     osvos_augment_frame gives for the identity transform, and the label is the mask.
+ *   Refused (< 0) before any device call: N outside 1..OSVOS_LUCID_MAX_BATCH; sides outside 1..OSVOS_LUCID_MAX_SIDE; a non-finite matrix
+ *     entry; |M0|, |M1|, |M3|, |M4| > 64 or |M2|, |M5| > 2^18 (this keeps every fixed-point coordinate inside int32); gains or offsets out of
+ *     range; a null pointer. */
+#define OSVOS_LUCID_MAX_BATCH 16
+#define OSVOS_LUCID_MAX_SIDE 4096
+#define OSVOS_LUCID_MAX_RADIUS 8
+#define OSVOS_LUCID_MAX_PASSES 8
+#define OSVOS_LUCID_MAX_GAIN 1024
+size_t osvos_lucid_inpaint_ws_bytes(int H, int W, int passes);
+int osvos_lucid_inpaint(const unsigned char* bgr, const unsigned char* hole, unsigned char* out_bgr, int H, int W, int radius, int passes,
+                        void* ws, void* stream);
+int osvos_lucid_compose(const unsigned char* bgr, const unsigned char* mask, const unsigned char* bg, const double* M, const int* tone,
+                        const float* mean3, float* out_img, float* out_gt, int N, int H, int W, void* stream);
+
 /* ---- fused SGD (torch.optim.SGD semantics, train_online.py:79-88,147) ----------------------
  * for each i: d = g + wd*p; buf = first ? d : momentum*buf + d; p -= lr*buf      (flat tensors) */
 int osvos_sgd_step(float* p, const float* g, float* buf, long count, float lr, float momentum,

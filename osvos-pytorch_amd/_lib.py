@@ -43,7 +43,12 @@ SUPERPIXELS_MAX_SIDE = 16384  # OSVOS_SUPERPIXELS_MAX_SIDE: largest H / W of the
 SUPERPIXELS_MAX_K = 268435456  # OSVOS_SUPERPIXELS_MAX_K: most labels per frame of osvos_superpixels_pool
 SQDIST_NONE = 2147483647    # OSVOS_SQDIST_NONE: osvos_mask_sqdist's value in an image without a source pixel
 SQDIST_MAX_SIDE = 4096      # OSVOS_SQDIST_MAX_SIDE: largest H / W of osvos_mask_sqdist and osvos_adapt_targets
-GENERIC_DECONV = 0x100      # OSVOS_FLAG_GENERIC_DECONV: OR-ed into the dtype of the osvos_net_* calls
+LUCID_MAX_BATCH = 16        # OSVOS_LUCID_MAX_BATCH: samples per osvos_lucid_compose launch
+LUCID_MAX_SIDE = 4096       # OSVOS_LUCID_MAX_SIDE: largest H / W of osvos_lucid_compose (osvos_lucid_inpaint: SQDIST_MAX_SIDE)
+LUCID_MAX_RADIUS = 8        # OSVOS_LUCID_MAX_RADIUS: largest smoothing window radius of osvos_lucid_inpaint (the smallest is 1)
+LUCID_MAX_PASSES = 8        # OSVOS_LUCID_MAX_PASSES: smoothing passes per osvos_lucid_inpaint call
+LUCID_MAX_GAIN = 1024       # OSVOS_LUCID_MAX_GAIN: largest Q8 tone gain of osvos_lucid_compose (256 = 1)
+GENERIC_DECONV = 0x100     # OSVOS_FLAG_GENERIC_DECONV: OR-ed into the dtype of the osvos_net_* calls
 NPARAMS = 52
 
 _vp, _i, _l, _sz, _f = C.c_void_p, C.c_int, C.c_long, C.c_size_t, C.c_float
@@ -142,6 +147,9 @@ PROTOTYPES = {
     "osvos_superpixels_slic": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "osvos_superpixels_pool_ws_bytes": (_sz, [_i, _i]),
     "osvos_superpixels_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "osvos_lucid_inpaint_ws_bytes": (_sz, [_i, _i, _i]),
+    "osvos_lucid_inpaint": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "osvos_lucid_compose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "osvos_mask_sqdist_ws_bytes": (_sz, [_i, _i, _i]),
     "osvos_mask_sqdist": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "osvos_adapt_ws_bytes": (_sz, [_i, _i, _i]),

@@ -1,0 +1,215 @@
+"""Lucid first-frame synthesis ("lucid data dreaming"): more training samples out of the one annotated frame, on the device
+(``osvos_lucid_inpaint`` / ``osvos_lucid_compose``, csrc/lucid.hip; the rule: include/osvos_hip.h).
+
+    cut the object out, fill the hole (once per sequence), then per training sample move object and background by affines of their own,
+    re-light both, and composite them again
+
+Online fine-tuning otherwise sees its one frame only flipped, rotated and scaled as a whole (``augment.DeviceAugment``): the object never
+moves against its background, is never lit differently from it, and what lies behind it is never seen.  Integers only: the samples are
+exact and repeat bit for bit.  Everything stays on the device; ``LucidDream`` reads back four numbers (the object's bounding box) once.
+
+Left out: void bands around the pasted edge, non-rigid deformation, occluders, premultiplied foreground colours.  The default parameters are
+STARTING VALUES, NOT TUNED ON DAVIS (no dataset was at hand when this was written), and no accuracy claim is made for them.
+"""
+import ctypes as C
+import math
+import random
+
+import numpy as np
+import torch
+
+from ._lib import LUCID_MAX_BATCH, LUCID_MAX_GAIN, LUCID_MAX_PASSES, LUCID_MAX_RADIUS, LUCID_MAX_SIDE, SQDIST_MAX_SIDE, check, lib
+from .augment import MEANVAL
+
+MAX_GROW = 64               # largest --lucid-grow: pixels the hole reaches beyond the mask
+IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+NEUTRAL = (256, 256, 256, 0, 0, 0)
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _is_num(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(v)
+
+
+def check_lucid(p=0.0, grow=5, radius=2, passes=3, fg_shift=0.25, bg_shift=0.05, gain=0.2, offset=20):
+    """ValueError unless the parameters of ``LucidDream`` (and the probability ``p`` of train_online.py --lucid) are inside their limits
+    (host only)"""
+    for name, v, lo, hi in (("grow", grow, 0, MAX_GROW), ("radius", radius, 1, LUCID_MAX_RADIUS), ("passes", passes, 0, LUCID_MAX_PASSES),
+                            ("offset", offset, 0, 255)):
+        if not _is_int(v):
+            raise ValueError("lucid: %s must be an integer, got %r" % (name, v))
+        if not lo <= v <= hi:
+            raise ValueError("lucid: %s %d (%d..%d)" % (name, v, lo, hi))
+    for name, v, hi in (("p", p, 1.0), ("fg_shift", fg_shift, 4.0), ("bg_shift", bg_shift, 1.0), ("gain", gain, 1.0)):
+        if not _is_num(v) or not 0.0 <= v <= hi:
+            raise ValueError("lucid: %s %r (a number in 0..%g)" % (name, v, hi))
+
+
+def affine_inverse(cx, cy, rot=0.0, sc=1.0, dx=0.0, dy=0.0, mirror=False):
+    """The 6 float64 of the dst -> src affine of: (mirror about the vertical line through the pivot,) rotate by ``rot`` degrees and scale by
+    ``sc`` about the pivot (cx, cy) -- the sense of cv2.getRotationMatrix2D, as ``augment.rotation_matrix_inverse`` -- then shift by (dx, dy).
+    Identity arguments give exactly (1, 0, 0, 0, 1, 0); a pure integer shift gives exactly (1, 0, -dx, 0, 1, -dy)."""
+    if not sc > 0:
+        raise ValueError("lucid: scale %r (> 0)" % (sc,))
+    a = float(rot) * math.pi / 180.0
+    c, s = math.cos(a) / float(sc), math.sin(a) / float(sc)
+    m0, m1, m3, m4 = c, -s, s, c
+    if mirror:
+        m0, m1 = -m0, -m1
+    tx, ty = float(cx) + float(dx), float(cy) + float(dy)
+    m = [m0, m1, float(cx) - m0 * tx - m1 * ty, m3, m4, float(cy) - m3 * tx - m4 * ty]
+    return [v + 0.0 for v in m]                    # (-0.0 -> 0.0)
+
+
+def _need_cuda(t, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("osvos_pytorch_amd.lucid needs CUDA (ROCm) tensors (%s); there is no CPU fallback" % what)
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _frame(t, what, max_side):
+    _need_cuda(t, what)
+    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError("%s must be a uint8 [H,W,3] tensor, got %s %s" % (what, t.dtype, tuple(t.shape)))
+    h, w = int(t.shape[0]), int(t.shape[1])
+    if not (1 <= h <= max_side and 1 <= w <= max_side):
+        raise ValueError("%s of %s: sides 1..%d" % (what, tuple(t.shape), max_side))
+    return t.contiguous()
+
+
+def _plane(t, like, what):
+    _need_cuda(t, what)
+    if t.dtype != torch.uint8 or tuple(t.shape) != tuple(like.shape[:2]) or t.device != like.device:
+        raise ValueError("%s must be a uint8 %s tensor on the device of the frame, got %s %s" % (what, tuple(like.shape[:2]), t.dtype, tuple(t.shape)))
+    return t.contiguous()
+
+
+def inpaint(frame_u8, hole_u8, radius=2, passes=3, ws=None):
+    """frame_u8: uint8 CUDA tensor [H,W,3] (BGR); hole_u8: uint8 [H,W], non-zero = to be filled -> uint8 [H,W,3]: every hole pixel filled
+    with the colour of its nearest non-hole pixel (ties: the smaller row, then the smaller column), then ``passes`` box means of radius
+    ``radius`` over the hole pixels.  Enqueued only."""
+    check_lucid(radius=radius, passes=passes)
+    f = _frame(frame_u8, "frame_u8", SQDIST_MAX_SIDE)
+    hole = _plane(hole_u8, f, "hole_u8")
+    h, w = int(f.shape[0]), int(f.shape[1])
+    need = int(lib().osvos_lucid_inpaint_ws_bytes(h, w, int(passes)))
+    if need == 0:
+        raise ValueError("lucid: no workspace size for %d x %d with %d passes" % (h, w, passes))
+    if ws is None or ws.numel() * ws.element_size() < need or ws.device != f.device:
+        ws = torch.empty((need + 3) // 4, device=f.device, dtype=torch.int32)
+    out = torch.empty_like(f)
+    vp = C.c_void_p
+    with torch.cuda.device(f.device):
+        check(lib().osvos_lucid_inpaint(vp(f.data_ptr()), vp(hole.data_ptr()), vp(out.data_ptr()), h, w, int(radius), int(passes), vp(ws.data_ptr()),
+                                        _stream()), "lucid_inpaint")
+    return out
+
+
+def compose(frame_u8, mask_u8, bg_u8, matrices, tones, meanval=MEANVAL):
+    """frame_u8, bg_u8: uint8 CUDA tensors [H,W,3]; mask_u8: uint8 [H,W] (non-zero = object); matrices: [N][2][6] numbers, the dst -> src
+    affines of (foreground, background) per sample (``affine_inverse``); tones: [N][2][6] integers (g_b, g_g, g_r, o_b, o_g, o_r), gains in Q8
+    (256 = 1, 0..1024), offsets -255..255 -> (image float32 [N,3,H,W], gt float32 [N,1,H,W]) from one launch.  Enqueued only."""
+    f = _frame(frame_u8, "frame_u8", LUCID_MAX_SIDE)
+    bg = _frame(bg_u8, "bg_u8", LUCID_MAX_SIDE)
+    if bg.shape != f.shape or bg.device != f.device:
+        raise ValueError("bg_u8 must match frame_u8, got %s and %s" % (tuple(bg.shape), tuple(f.shape)))
+    mask = _plane(mask_u8, f, "mask_u8")
+    m = np.ascontiguousarray(np.asarray(matrices, dtype=np.float64))
+    t = np.asarray(tones)
+    if m.ndim != 3 or m.shape[1:] != (2, 6) or not 1 <= m.shape[0] <= LUCID_MAX_BATCH:
+        raise ValueError("lucid: matrices must be [N][2][6] with N 1..%d, got %s" % (LUCID_MAX_BATCH, m.shape))
+    if t.shape != m.shape or not np.issubdtype(t.dtype, np.integer):
+        raise ValueError("lucid: tones must be integers [%d][2][6], got %s %s" % (m.shape[0], t.dtype, t.shape))
+    if not np.isfinite(m).all() or (np.abs(m[..., [0, 1, 3, 4]]) > 64).any() or (np.abs(m[..., [2, 5]]) > 2 ** 18).any():
+        raise ValueError("lucid: matrix entries must be finite, |M0|, |M1|, |M3|, |M4| <= 64 and |M2|, |M5| <= 2^18")
+    if (t[..., :3] < 0).any() or (t[..., :3] > LUCID_MAX_GAIN).any() or (np.abs(t[..., 3:]) > 255).any():
+        raise ValueError("lucid: gains 0..%d (Q8), offsets -255..255" % LUCID_MAX_GAIN)
+    t = np.ascontiguousarray(t.astype(np.int32))
+    n, h, w = int(m.shape[0]), int(f.shape[0]), int(f.shape[1])
+    image = torch.empty((n, 3, h, w), device=f.device, dtype=torch.float32)
+    gt = torch.empty((n, 1, h, w), device=f.device, dtype=torch.float32)
+    mean = (C.c_float * 3)(*meanval)
+    vp = C.c_void_p
+    with torch.cuda.device(f.device):
+        check(lib().osvos_lucid_compose(vp(f.data_ptr()), vp(mask.data_ptr()), vp(bg.data_ptr()), vp(m.ctypes.data), vp(t.ctypes.data), mean,
+                                        vp(image.data_ptr()), vp(gt.data_ptr()), n, h, w, _stream()), "lucid_compose")
+    return image, gt
+
+
+class LucidDream(object):
+    """Lucid samples of one annotated frame.  At construction: the hole is ``results.distance_map(mask) <= grow^2`` (the mask grown by
+    ``grow`` pixels), the frame is inpainted once, and the mask's bounding box is read back once (the foreground pivots about its centre;
+    an empty mask pivots about the frame's centre).  Frame, mask and inpainted background stay on the device.
+
+    ``draw()`` takes 13 numbers from Python's ``random``, in this order: ``random.random() < 0.5`` (mirror: both layers, each about its own
+    pivot); foreground rotation, scale, shift x, shift y; background rotation, scale, shift x, shift y; foreground gain, foreground offset,
+    background gain, background offset.  Rotation and scale are drawn as ``DeviceAugment`` draws them from ``rots`` / ``scales``; a shift is
+    uniform in +-``fg_shift`` times the object box's side (+-``bg_shift`` times the frame's side); a gain is uniform in 1 +-``gain`` (all three
+    channels alike, rounded to Q8), an offset a uniform integer in +-``offset`` grey levels.
+
+    ``dream()`` -> {'image': [3,H,W], 'gt': [1,H,W]} as ``DeviceAugment``; ``dream.batch(n)`` -> n samples [n,3,H,W] / [n,1,H,W] from one
+    launch.  The defaults are starting values, NOT tuned on DAVIS."""
+
+    def __init__(self, frame_u8, mask_u8, grow=5, radius=2, passes=3, rots=(-30, 30), scales=(.75, 1.25), fg_shift=0.25, bg_shift=0.05, gain=0.2,
+                 offset=20, meanval=MEANVAL):
+        from .results import distance_map
+        check_lucid(0.0, grow, radius, passes, fg_shift, bg_shift, gain, offset)
+        if not (isinstance(rots, tuple) and isinstance(scales, tuple) and len(rots) == 2 and len(scales) == 2):
+            raise ValueError("LucidDream takes continuous (tuple) ranges of rotation and scale")
+        if not (-90 <= rots[0] <= rots[1] <= 90 and 0.25 <= scales[0] <= scales[1] <= 4):
+            raise ValueError("LucidDream: rots inside -90..90 degrees, scales inside 0.25..4, got %r and %r" % (rots, scales))
+        self.frame = _frame(frame_u8, "frame_u8", LUCID_MAX_SIDE)
+        self.mask = _plane(mask_u8, self.frame, "mask_u8")
+        self.grow, self.radius, self.passes = int(grow), int(radius), int(passes)
+        self.rots, self.scales, self.fg_shift, self.bg_shift, self.gain, self.offset = rots, scales, float(fg_shift), float(bg_shift), float(gain), int(offset)
+        self.meanval = meanval
+        self.h, self.w = int(self.frame.shape[0]), int(self.frame.shape[1])
+        self.hole = (distance_map(self.mask)[0] <= self.grow * self.grow).to(torch.uint8)
+        self.bg = inpaint(self.frame, self.hole, self.radius, self.passes)
+        cols, rows = torch.arange(self.w, device=self.frame.device), torch.arange(self.h, device=self.frame.device)
+        on_c, on_r = (self.mask != 0).any(0), (self.mask != 0).any(1)
+        box = torch.stack([torch.where(on_c, cols, self.w).min(), torch.where(on_c, cols, -1).max(), torch.where(on_r, rows, self.h).min(),
+                           torch.where(on_r, rows, -1).max()]).tolist()                       # the one read-back
+        if box[1] < 0:                                                                         # an empty mask
+            self.box = None
+            self.pivot, self.box_w, self.box_h = (self.w / 2, self.h / 2), 0, 0
+        else:
+            self.box = tuple(int(v) for v in box)                                              # (x0, x1, y0, y1), inclusive
+            self.pivot = ((box[0] + box[1] + 1) / 2, (box[2] + box[3] + 1) / 2)
+            self.box_w, self.box_h = box[1] - box[0] + 1, box[3] - box[2] + 1
+
+    def _layer(self):
+        rot = (self.rots[1] - self.rots[0]) * random.random() + self.rots[0]
+        sc = (self.scales[1] - self.scales[0]) * random.random() + self.scales[0]
+        return rot, sc, 2 * random.random() - 1, 2 * random.random() - 1
+
+    def _tone(self):
+        g = int(round(256 * (1 + self.gain * (2 * random.random() - 1))))
+        o = int(round(self.offset * (2 * random.random() - 1)))
+        return [g, g, g, o, o, o]
+
+    def draw(self):
+        """-> (matrices [2][6], tones [2][6]) of one sample; the 13 draws in the order of the class text"""
+        mirror = random.random() < 0.5
+        rot, sc, ux, uy = self._layer()
+        fg = affine_inverse(self.pivot[0], self.pivot[1], rot, sc, ux * self.fg_shift * self.box_w, uy * self.fg_shift * self.box_h, mirror)
+        rot, sc, ux, uy = self._layer()
+        bg = affine_inverse(self.w / 2, self.h / 2, rot, sc, ux * self.bg_shift * self.w, uy * self.bg_shift * self.h, mirror)
+        return [fg, bg], [self._tone(), self._tone()]
+
+    def batch(self, n):
+        if not _is_int(n) or not 1 <= n <= LUCID_MAX_BATCH:
+            raise ValueError("lucid: batch of %r (1..%d)" % (n, LUCID_MAX_BATCH))
+        draws = [self.draw() for _ in range(n)]
+        image, gt = compose(self.frame, self.mask, self.bg, [d[0] for d in draws], [d[1] for d in draws], self.meanval)
+        return {'image': image, 'gt': gt}
+
+    def __call__(self):
+        s = self.batch(1)
+        return {'image': s['image'][0], 'gt': s['gt'][0]}

@@ -29,6 +29,10 @@ running on the MI355X-native OSVOS path.  Differences by design:
   * ``--snap-cell S``: superpixel snapping of every test frame's logit map, as in the OSVOS paper -- an integer grid-SLIC of cell S on the
     decoded frame and the mean of the logits over each superpixel, on the device (osvos_pytorch_amd.superpixels.SuperpixelSnapper), after
     --crf-iters and before --track-components; parameters --snap-compactness, --snap-iters (starting values, not tuned on DAVIS)
+  * ``--lucid P``: lucid first-frame synthesis -- with probability P a training sample is not the flipped / rotated / scaled frame but a
+    re-composition of it: the object cut out, the hole inpainted once per sequence, object and background moved by affines of their own,
+    re-lit and composited again on the device (osvos_pytorch_amd.lucid.LucidDream); parameters --lucid-grow, --lucid-smooth, --lucid-shift,
+    --lucid-tone (starting values, not tuned on DAVIS).  With P = 0 not one random draw and not one byte changes
   * launched under torchrun with N processes, rank r fine-tunes sequences r, r+N, ... of the
     comma-separated SEQ_NAME list (independent replicas: online training has no exchange step)
 """
@@ -86,16 +90,28 @@ class DeviceTrainFrame(object):
     """train_online.py:92-97 on the device: the sequence's first frame + annotation live on the GPU as uint8; every pass through
     the 'loader' draws the reference's random flip / rotation / scale (same order, Python's random module) and runs one HIP kernel."""
 
-    def __init__(self, img_u8, lab_u8, device):
+    def __init__(self, img_u8, lab_u8, device, lucid=None):
+        """lucid: None, or the keyword arguments of lucid.LucidDream plus 'p' (--lucid): per pass random.random() is drawn first, and below p
+        the sample is a lucid one; with None nothing new is drawn and nothing new is built"""
         from osvos_pytorch_amd.augment import DeviceAugment
         self.img, self.lab = torch.as_tensor(img_u8).to(device), torch.as_tensor(lab_u8).to(device)
         self.aug = DeviceAugment(rots=(-30, 30), scales=(.75, 1.25))
+        self.lucid_p, self.dream = 0.0, None
+        if lucid:
+            from osvos_pytorch_amd.lucid import LucidDream
+            kw = dict(lucid)
+            self.lucid_p = kw.pop('p')
+            self.dream = LucidDream(self.img, self.lab, rots=self.aug.rots, scales=self.aug.scales, **kw)
 
     def __len__(self):
         return 1
 
     def __iter__(self):
-        s = self.aug(self.img, self.lab)
+        if self.dream is not None:
+            import random
+            s = self.dream() if random.random() < self.lucid_p else self.aug(self.img, self.lab)
+        else:
+            s = self.aug(self.img, self.lab)
         yield {'image': s['image'][None], 'gt': s['gt'][None]}
 
 
@@ -139,7 +155,7 @@ def device_loaders(args, seq_name, device, seed):
     else:
         train, test = DavisFrames(True, Path.db_root_dir(), seq_name=seq_name), DavisFrames(False, Path.db_root_dir(), seq_name=seq_name)
     img, lab = train[0]
-    return DeviceTrainFrame(img, lab, device), DeviceTestFrames(test, device, args.prefetch, raw_only=bool(args.tta))
+    return DeviceTrainFrame(img, lab, device, args.lucid), DeviceTestFrames(test, device, args.prefetch, raw_only=bool(args.tta))
 
 
 def synthetic_objects(h, w):
@@ -327,6 +343,35 @@ def make_snap(args):
     return SuperpixelSnapper(**args.snap) if args.snap else None
 
 
+def check_lucid_args(args):
+    """the --lucid* rules; SystemExit on values the synthesis does not take -- checked before any GPU work.  Sets args.lucid to the keyword
+    arguments of DeviceTrainFrame's lucid (those of lucid.LucidDream, and p), or None with --lucid 0"""
+    from osvos_pytorch_amd import lucid
+    args.lucid = None
+
+    def pair(text, kinds, what):
+        parts = text.split(',')
+        if len(parts) != 2:
+            raise ValueError('%s takes two comma-separated numbers, got %r' % (what, text))
+        try:
+            return [kind(v) for kind, v in zip(kinds, parts)]
+        except ValueError:
+            raise ValueError('%s takes two comma-separated numbers, got %r' % (what, text))
+    try:
+        radius, passes = pair(args.lucid_smooth, (int, int), '--lucid-smooth RADIUS,PASSES')
+        fg_shift, bg_shift = pair(args.lucid_shift, (float, float), '--lucid-shift FG,BG')
+        gain, offset = pair(args.lucid_tone, (float, int), '--lucid-tone GAIN,OFFSET')
+        lucid.check_lucid(args.lucid_p, args.lucid_grow, radius, passes, fg_shift, bg_shift, gain, offset)
+    except ValueError as e:
+        raise SystemExit('--lucid*: %s' % e)
+    if not args.lucid_p:
+        return
+    if not args.device_augment:
+        raise SystemExit('--lucid needs --device-augment: the samples are made from the decoded uint8 frame and its annotation on the device')
+    args.lucid = dict(p=args.lucid_p, grow=args.lucid_grow, radius=radius, passes=passes, fg_shift=fg_shift, bg_shift=bg_shift, gain=gain,
+                      offset=offset)
+
+
 def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, nEpochs, nAveGrad):
     """DAVIS 2017 recipe for one sequence: one fine-tuning per object id of the first annotation on that object's binary mask, every frame
     through each network, the K logit stacks merged into label maps, indexed PNGs, J and F per object -- one read-back for the PNGs, one for
@@ -359,7 +404,7 @@ def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, n
     for k in range(1, K + 1):
         net, optimizer = load_parent(args, save_dir, parentEpoch, device)
         random.seed(seed)                      # every object sees the augmentation draws of a single-object run
-        trainloader = DeviceTrainFrame(frames[0], (gts[0] == k).to(torch.uint8) * 255, device)
+        trainloader = DeviceTrainFrame(frames[0], (gts[0] == k).to(torch.uint8) * 255, device, args.lucid)
         print('Object %d of %d' % (k, K))
         fine_tune(args, net, optimizer, trainloader, device, nEpochs, nAveGrad, seed, os.path.join(save_dir, '%s_object-%d' % (seq_name, k)))
         start_time = timeit.default_timer()
@@ -495,12 +540,27 @@ def parse_args(argv=None):
                          'the objects.  The default parameters are starting values, not tuned on DAVIS')
     ap.add_argument('--snap-compactness', type=int, default=10, help='--snap-cell: weight of the pixel distance against the colour distance, 0..64')
     ap.add_argument('--snap-iters', type=int, default=5, help='--snap-cell: assign / update steps, 0..16 (0: the grid cells themselves)')
+    ap.add_argument('--lucid', dest='lucid_p', type=float, default=0.0, metavar='P',
+                    help='lucid first-frame synthesis (0 = off): with probability P (0..1) a training sample is a re-composition of the '
+                         'annotated frame -- the object cut out, the hole inpainted once per sequence, object and background moved by affines '
+                         'of their own, re-lit and composited again on the device -- and otherwise the flipped / rotated / scaled frame as '
+                         'before.  Needs --device-augment.  With --multi-object every object is handled as its own binary mask.  The '
+                         'default parameters are starting values, not tuned on DAVIS')
+    ap.add_argument('--lucid-grow', type=int, default=5, help='--lucid: the inpainted hole is the mask grown by this many pixels, 0..64')
+    ap.add_argument('--lucid-smooth', default='2,3', metavar='RADIUS,PASSES',
+                    help='--lucid: box smoothing of the filled hole -- window radius 1..8 and passes 0..8')
+    ap.add_argument('--lucid-shift', default='0.25,0.05', metavar='FG,BG',
+                    help='--lucid: largest shift of the object as a fraction of its bounding box (0..4) and of the background as a fraction of '
+                         'the frame (0..1)')
+    ap.add_argument('--lucid-tone', default='0.2,20', metavar='GAIN,OFFSET',
+                    help='--lucid: each layer is re-lit with a gain of 1 +- GAIN (0..1) and an offset of +- OFFSET grey levels (0..255)')
     args = ap.parse_args(argv)
     args.tta = tta_scales(args)
     check_adapt_args(args)
     check_crf_args(args)
     check_flow_args(args)
     check_snap_args(args)
+    check_lucid_args(args)
     if args.tta and not (args.device_augment or (args.multi_object and args.synthetic)):
         raise SystemExit('--tta-scales / --tta-flip need --device-augment (or --multi-object --synthetic): test-time augmentation makes its views '
                          'from the decoded uint8 frame on the device')
