@@ -679,7 +679,35 @@ int osvos_adapt_targets(const float* logits, const unsigned char* prev_mask, flo
  *     osvos_augment_frame gives for the identity transform, and the label is the mask.
  *   Refused (< 0) before any device call: N outside 1..OSVOS_LUCID_MAX_BATCH; sides outside 1..OSVOS_LUCID_MAX_SIDE; a non-finite matrix
  *     entry; |M0|, |M1|, |M3|, |M4| > 64 or |M2|, |M5| > 2^18 (this keeps every fixed-point coordinate inside int32); gains or offsets out of
- *     range; a null pointer. */
+ *     range; a null pointer.
+ * osvos_lucid_compose_ex: osvos_lucid_compose with a non-rigid deformation of the foreground, an occluder and a void band around the label's
+ *   edges.  Everything not named here (coordinates, taps, tone, composite, the limits on M and tone) is osvos_lucid_compose's rule unchanged.
+ *   Deformation: D is a DEVICE pointer, null = none: short [N][GH][GW][2] = (dx, dy) in 1/32 pixel on a lattice of `cell` pixels, 4-byte
+ *     aligned (a pair is loaded as one 32-bit word).  cell is a power of two in OSVOS_LUCID_MIN_CELL..OSVOS_LUCID_MAX_CELL, s = log2(cell),
+ *     GW = ((W - 1) >> s) + 2, GH = ((H - 1) >> s) + 2.  For the destination pixel (x, y): gx = x >> s, tx = x & (cell - 1), gy and ty alike,
+ *     dX = ((cell - tx)(cell - ty) D00.x + tx (cell - ty) D01.x + (cell - tx) ty D10.x + tx ty D11.x + (1 << (2 s - 1))) >> 2 s (arithmetic
+ *     shift), D00 = D[n][gy][gx], D01 = D[n][gy][gx + 1], D10 = D[n][gy + 1][gx], D11 = D[n][gy + 1][gx + 1]; dY the same from the .y
+ *     components.  The weights are >= 0 and sum to 2^(2 s) <= 2^16, so every partial sum lies in -2^31 .. 2^31 - 2^15: inside int32.  The
+ *     FOREGROUND layer only uses X = ((Xb + adelta + 16) >> 5) + dX, and Y alike; the background layer is untouched.  The field is indexed
+ *     by the destination pixel and added to the source coordinate; it is bilinear in the lattice (C0).  No bound on D beyond short (every
+ *     coordinate stays inside int32); that the map does not fold is the caller's business.
+ *   Occluder: occ is a HOST pointer, null = none: int [N][6] = (cx, cy, rx, ry, sx, sy), carried in the kernel arguments like M and tone.
+ *     rx == 0 or ry == 0: no occluder in that sample.  Pixel (x, y) is covered iff, in 64-bit integers,
+ *     (x - cx)^2 ry^2 + (y - cy)^2 rx^2 <= rx^2 ry^2.  A covered pixel shows the inpainted background at an integer offset through the
+ *     background's tone: S = 1024 bg[clamp(y + sy, 0, H - 1)][clamp(x + sx, 0, W - 1)][c], S' = tone[n][1] applied to S, C = 1024 S'.
+ *   Label and void band: L(p) = (a >= 512) && !covered.  band in 0..OSVOS_LUCID_MAX_BAND.  p is void iff some pixel q INSIDE the image has
+ *     |p - q|^2 <= band^2 and L(q) != L(p) (the image border is not an edge).  out_gt is -1.0f at a void pixel and (float) L elsewhere;
+ *     out_img does not depend on band.  band == 0: nothing is void, there is no second launch and ws may be null.
+ *   Launches on `stream`: the composition (with band >= 1 each wave also stores the ballot of its 64 labels as one word of a 1-bit label
+ *     plane [N][H][ceil(W / 64)] in ws -- an ordinary vector store), then with band >= 1 one launch that reads only that plane: per row
+ *     offset dy the row's word and its two neighbours, the columns x - hw .. x + hw, hw = isqrt(band^2 - dy^2), clipped to the image, XOR-ed
+ *     with the pixel's own bit; it overwrites out_gt with -1.0f where any bit is left.  No atomics; no workgroup waits for another.
+ *   ws: osvos_lucid_compose_ex_ws_bytes(N, H, W, band) = 8 N H ceil(W / 64) bytes with band >= 1; 0 with band == 0 and for arguments the
+ *     call refuses.  8-byte aligned, contents irrelevant on entry; it must not overlap an input or an output.
+ *   Refused (< 0) before any device call: everything osvos_lucid_compose refuses; with D given, a cell that is not a power of two in
+ *     range or a misaligned D; band out of range; band > 0 with a null, misaligned or overlapping ws; rx or ry outside 0..4096; |cx|, |cy|,
+ *     |sx| or |sy| above 8192.
+ *   With D null (or all zero), occ null and band 0 out_img and out_gt are osvos_lucid_compose's bit for bit (the same kernel is launched). */
 #define OSVOS_LUCID_MAX_BATCH 16
 #define OSVOS_LUCID_MAX_SIDE 4096
 #define OSVOS_LUCID_MAX_RADIUS 8
@@ -690,6 +718,15 @@ int osvos_lucid_inpaint(const unsigned char* bgr, const unsigned char* hole, uns
                         void* ws, void* stream);
 int osvos_lucid_compose(const unsigned char* bgr, const unsigned char* mask, const unsigned char* bg, const double* M, const int* tone,
                         const float* mean3, float* out_img, float* out_gt, int N, int H, int W, void* stream);
+#define OSVOS_LUCID_MAX_BAND        16
+#define OSVOS_LUCID_MIN_CELL        8
+#define OSVOS_LUCID_MAX_CELL        256
+#define OSVOS_LUCID_MAX_OCC_RADIUS  4096
+#define OSVOS_LUCID_MAX_OCC_OFFSET  8192
+size_t osvos_lucid_compose_ex_ws_bytes(int N, int H, int W, int band);
+int osvos_lucid_compose_ex(const unsigned char* bgr, const unsigned char* mask, const unsigned char* bg, const double* M, const int* tone,
+                           const int* occ, const short* D, int cell, int band, const float* mean3, float* out_img, float* out_gt, int N, int H,
+                           int W, void* ws, void* stream);
 
 /* ---- fused SGD (torch.optim.SGD semantics, train_online.py:79-88,147) ----------------------
  * for each i: d = g + wd*p; buf = first ? d : momentum*buf + d; p -= lr*buf      (flat tensors) */

@@ -48,7 +48,12 @@ LUCID_MAX_SIDE = 4096       # OSVOS_LUCID_MAX_SIDE: largest H / W of osvos_lucid
 LUCID_MAX_RADIUS = 8        # OSVOS_LUCID_MAX_RADIUS: largest smoothing window radius of osvos_lucid_inpaint (the smallest is 1)
 LUCID_MAX_PASSES = 8        # OSVOS_LUCID_MAX_PASSES: smoothing passes per osvos_lucid_inpaint call
 LUCID_MAX_GAIN = 1024       # OSVOS_LUCID_MAX_GAIN: largest Q8 tone gain of osvos_lucid_compose (256 = 1)
-GENERIC_DECONV = 0x100     # OSVOS_FLAG_GENERIC_DECONV: OR-ed into the dtype of the osvos_net_* calls
+LUCID_MAX_BAND = 16         # OSVOS_LUCID_MAX_BAND: widest void band of osvos_lucid_compose_ex, pixels
+LUCID_MIN_CELL = 8          # OSVOS_LUCID_MIN_CELL: smallest lattice cell of the deformation field (a power of two)
+LUCID_MAX_CELL = 256        # OSVOS_LUCID_MAX_CELL: largest lattice cell
+LUCID_MAX_OCC_RADIUS = 4096  # OSVOS_LUCID_MAX_OCC_RADIUS: largest occluder semi-axis
+LUCID_MAX_OCC_OFFSET = 8192  # OSVOS_LUCID_MAX_OCC_OFFSET: largest |centre| and |source offset| of an occluder
+GENERIC_DECONV = 0x100    # OSVOS_FLAG_GENERIC_DECONV: OR-ed into the dtype of the osvos_net_* calls
 NPARAMS = 52
 
 _vp, _i, _l, _sz, _f = C.c_void_p, C.c_int, C.c_long, C.c_size_t, C.c_float
@@ -150,6 +155,8 @@ PROTOTYPES = {
     "osvos_lucid_inpaint_ws_bytes": (_sz, [_i, _i, _i]),
     "osvos_lucid_inpaint": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "osvos_lucid_compose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "osvos_lucid_compose_ex_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "osvos_lucid_compose_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "osvos_mask_sqdist_ws_bytes": (_sz, [_i, _i, _i]),
     "osvos_mask_sqdist": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "osvos_adapt_ws_bytes": (_sz, [_i, _i, _i]),

@@ -13,6 +13,13 @@
 // Composition: one workgroup per 64 x 4 destination tile, a lane is a column, N samples in grid z; the 2 N affines and tone sets travel as
 // kernel arguments.  Taps are read through the cache: staging a tile's source footprint in LDS first was timed and lost, other tile shapes
 // made no difference (profiles/lucid_timing.txt).
+//
+//   osvos_lucid_compose_ex  the same kernel body, templated on three options: a displacement field bilinear in a coarse lattice added to the
+// foreground's source coordinate, an ellipse of displaced background over the composite, and a void band around the label's edges.  The band
+// needs the neighbours' labels, which no lane has: each wave stores the ballot of its 64 labels -- one word of a 1-bit label plane [N][H][W / 64]
+// -- and a second launch reads only that plane (about 54 KB per 854x480 sample): per row of the disc three words (fetched a row per lane, handed
+// round as scalars), a funnel shift to the lane's window, an XOR with the lane's own bit and a mask.  No in-place hazard, no atomics
+// (profiles/lucid_deform_timing.txt).
 #include <limits.h>
 #include <math.h>
 
@@ -119,6 +126,14 @@ struct ComposeArgs {
   int tone[OSVOS_LUCID_MAX_BATCH][2][6];
 };
 
+// osvos_lucid_compose_ex's additions ride behind the plain arguments, so that the plain kernel's argument block stays what it was
+struct ComposeExArgs : ComposeArgs {
+  const int* D;                  // [N][GH][GW] (dx, dy) shorts in 1/32 pixel, a pair per word; only read with DEFORM
+  unsigned long long* plane;     // [N][H][ceil(W / 64)] the 1-bit label plane; only written with BAND
+  int shift, GH, GW;             // log2(cell) and the lattice
+  int occ[OSVOS_LUCID_MAX_BATCH][6];      // (cx, cy, rx, ry, sx, sy); only read with OCCLUDE
+};
+
 // fixed-point source coordinates exactly as augment_kernel forms them (doubles, no fused multiply-add, round half to even)
 __device__ __forceinline__ void lucid_coords(const double* M, int x, int y, int& X, int& Y) {
 #pragma clang fp contract(off)
@@ -128,17 +143,39 @@ __device__ __forceinline__ void lucid_coords(const double* M, int x, int y, int&
   Y = (Yb + bdelta + 16) >> 5;
 }
 
-// block (64, 4), grid (ceil(W / 64), ceil(H / 4), N): a wave is 64 consecutive columns of one row
-__global__ __launch_bounds__(256) void lucid_compose_kernel(const ComposeArgs a) {
-  const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, n = blockIdx.z;
+// block (64, 4), grid (ceil(W / 64), ceil(H / 4), N): a wave is 64 consecutive columns of one row.  One body: osvos_lucid_compose launches
+// <false, false, false, ComposeArgs>, which compiles to what it was before the options existed.
+template <bool DEFORM, bool OCCLUDE, bool BAND, typename Args>
+__global__ __launch_bounds__(256) void lucid_compose_kernel(const Args a) {
+  const int xl = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, n = blockIdx.z;
   const int H = a.H, W = a.W;
-  if (x >= W || y >= H) return;
+  // With BAND the wave's ballot is a word of the label plane, so lanes past the row's end must NOT leave before it: they stay active, work on
+  // the row's last pixel (every read in bounds), vote 0 and store nothing.  Nothing relies on how inactive lanes vote.  (A row past the
+  // frame's end is a whole wave: y is uniform in it.)
+  if constexpr (BAND) {
+    if (y >= H) return;
+  } else {
+    if (xl >= W || y >= H) return;
+  }
+  const bool live = xl < W;
+  const int x = BAND ? min(xl, W - 1) : xl;
   int alpha = 0;
   int col[2][3];
 #pragma unroll
   for (int L = 0; L < 2; ++L) {
     int X, Y;
     lucid_coords(a.M[n][L], x, y, X, Y);
+    if constexpr (DEFORM) {
+      if (L == 0) {
+        const int s = a.shift, cell = 1 << s, gx = x >> s, gy = y >> s, tx = x & (cell - 1), ty = y & (cell - 1);
+        const int* d = a.D + ((size_t)n * a.GH + gy) * a.GW + gx;              // gy + 1 < GH and gx + 1 < GW by the lattice's size
+        const int d00 = d[0], d01 = d[1], d10 = d[a.GW], d11 = d[a.GW + 1];
+        const int w00 = (cell - tx) * (cell - ty), w01 = tx * (cell - ty), w10 = (cell - tx) * ty, w11 = tx * ty, half = 1 << (2 * s - 1);
+        // (short)(d) = .x, d >> 16 = .y; weights >= 0 summing to 2^(2 s) <= 2^16 times shorts: every partial sum inside int32
+        X += (w00 * (short)d00 + w01 * (short)d01 + w10 * (short)d10 + w11 * (short)d11 + half) >> (2 * s);
+        Y += (w00 * (d00 >> 16) + w01 * (d01 >> 16) + w10 * (d10 >> 16) + w11 * (d11 >> 16) + half) >> (2 * s);
+      }
+    }
     const int ix = X >> 5, iy = Y >> 5, fx = X & 31, fy = Y & 31;
     const int cx0 = min(max(ix, 0), W - 1), cx1 = min(max(ix + 1, 0), W - 1), cy0 = min(max(iy, 0), H - 1), cy1 = min(max(iy + 1, 0), H - 1);
     const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;
@@ -157,14 +194,90 @@ __global__ __launch_bounds__(256) void lucid_compose_kernel(const ComposeArgs a)
               (x1in && y1in && a.mask[o11] ? w11 : 0);
     }
   }
-  const size_t hw = (size_t)H * W, o = (size_t)y * W + x;
-  float* img = a.out_img + (size_t)n * 3 * hw;
+  if constexpr (OCCLUDE) {
+    const int* e = a.occ[n];
+    const long long rx2 = (long long)e[2] * e[2], ry2 = (long long)e[3] * e[3], dx = x - e[0], dy = y - e[1];
+    if (rx2 != 0 && ry2 != 0 && dx * dx * ry2 + dy * dy * rx2 <= rx2 * ry2) {      // at most 12288^2 * 4096^2 * 2 < 2^52
+      const size_t o = ((size_t)min(max(y + e[5], 0), H - 1) * W + min(max(x + e[4], 0), W - 1)) * 3;
+      const int* t = a.tone[n][1];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int C = alpha * col[0][c] + (1024 - alpha) * col[1][c];      // <= 1024 * 261120 < 2^31
-    img[c * hw + o] = (float)C * (1.0f / 1048576.0f) - a.mean[c];
+      for (int c = 0; c < 3; ++c) {
+        const int v = ((a.bg[o + c] * 1024 * t[c] + 128) >> 8) + t[3 + c] * 1024;
+        col[1][c] = min(max(v, 0), 255 << 10);
+      }
+      alpha = 0;                                             // C = 1024 S', label 0
+    }
   }
-  a.out_gt[(size_t)n * hw + o] = alpha >= 512 ? 1.0f : 0.0f;
+  const size_t hw = (size_t)H * W, o = (size_t)y * W + x;
+  const bool label = alpha >= 512;
+  if (live) {
+    float* img = a.out_img + (size_t)n * 3 * hw;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int C = alpha * col[0][c] + (1024 - alpha) * col[1][c];      // <= 1024 * 261120 < 2^31
+      img[c * hw + o] = (float)C * (1.0f / 1048576.0f) - a.mean[c];
+    }
+    a.out_gt[(size_t)n * hw + o] = label ? 1.0f : 0.0f;
+  }
+  if constexpr (BAND) {
+    const unsigned long long word = __ballot(live && label);                 // all 64 lanes are here: bit i = column 64 blockIdx.x + i
+    if (threadIdx.x == 0) a.plane[((size_t)n * H + y) * gridDim.x + blockIdx.x] = word;
+  }
+}
+
+struct BandArgs {
+  const unsigned long long* plane;      // [N][H][ceil(W / 64)]
+  float* out_gt;                        // [N][1][H][W]
+  int H, W, band;
+  int hw[OSVOS_LUCID_MAX_BAND + 1];     // isqrt(band^2 - dy^2) by |dy|
+};
+
+__device__ __forceinline__ unsigned long long lane_word(unsigned long long v, int lane) {      // lane: uniform
+  const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)v, lane), hi = __builtin_amdgcn_readlane((int)(unsigned)(v >> 32), lane);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// block (64, 4), grid (ceil(W / 64), ceil(H / 4), N), after the composition on the same stream.  A wave needs the word of its 64 columns
+// and the two next to it from the 2 band + 1 <= 33 rows of the disc: lane i fetches those of row y - band + i (three loads per wave, all in
+// flight at once; a loop of uniform loads was timed first and waited on every row), and the loop takes row after row out of that lane -- as
+// scalars, so that a row of three zero words is skipped by the whole wave.  Every lane stays to the end for that: lanes past the row's end
+// work on the last pixel and store nothing.  A lane looks at the 64 columns x - 32 .. x + 31 funnelled out of two of the words; columns
+// outside the image are masked, never read as 0.
+__global__ __launch_bounds__(256) void lucid_band_kernel(const BandArgs a) {
+  const int lane = threadIdx.x, xl = blockIdx.x * 64 + lane, y = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.y), n = blockIdx.z;
+  const int H = a.H, W = a.W, band = a.band, words = gridDim.x, wi = blockIdx.x;      // (y: a wave is one row of the block, so the row is scalar)
+  if (y >= H) return;                                                        // (the whole wave)
+  const int x = min(xl, W - 1);
+  const unsigned long long* rows = a.plane + (size_t)n * H * words;
+  unsigned long long wl = 0, wm = 0, wh = 0;
+  const int fetch = y - band + lane;
+  const int half_width = a.hw[min(lane < band ? band - lane : lane - band, OSVOS_LUCID_MAX_BAND)];      // of the row this lane fetches
+  if (lane <= 2 * band && fetch >= 0 && fetch < H) {
+    const unsigned long long* r = rows + (size_t)fetch * words;
+    wm = r[wi];
+    if (wi > 0) wl = r[wi - 1];
+    if (wi + 1 < words) wh = r[wi + 1];
+  }
+  const unsigned long long own = (lane_word(wm, band) >> lane) & 1 ? ~0ull : 0ull;      // (for a lane past the row's end: 0, unused)
+  const int left = min(band, x), right = min(band, W - 1 - x);               // the disc's columns clipped to the image, for hw = band
+  const bool low = lane < 32;
+  const int k = low ? lane + 32 : lane - 32;                                 // window bit j = column x - 32 + j
+  unsigned long long differ = 0;
+  for (int dy = -band; dy <= band; ++dy) {
+    const int yy = y + dy;
+    if (yy < 0 || yy >= H) continue;                                         // (uniform in the wave)
+    const unsigned long long mid = lane_word(wm, dy + band), lo = lane_word(wl, dy + band), hi = lane_word(wh, dy + band);
+    if ((lo | mid | hi) == 0) {                                              // (uniform) a row of background: it differs from every set pixel --
+      differ |= own;                                                         // the row is inside the image and holds at least column x
+      continue;
+    }
+    const unsigned long long A = low ? lo : mid, B = low ? mid : hi;
+    const unsigned long long win = k == 0 ? A : (A >> k) | (B << (64 - k));
+    const int h = __builtin_amdgcn_readlane(half_width, dy + band), l = min(h, left), rr = min(h, right);
+    const unsigned long long m = ((2ull << (l + rr)) - 1) << (32 - l);       // l + rr + 1 <= 33 bits from bit 32 - l >= 16
+    differ |= (win ^ own) & m;
+  }
+  if (differ && xl < W) a.out_gt[((size_t)n * H + y) * W + x] = -1.0f;
 }
 
 inline bool inpaint_ok(int H, int W, int passes) {
@@ -216,16 +329,15 @@ extern "C" int osvos_lucid_inpaint(const unsigned char* bgr, const unsigned char
   return 0;
 }
 
-extern "C" int osvos_lucid_compose(const unsigned char* bgr, const unsigned char* mask, const unsigned char* bg, const double* M, const int* tone,
-                                   const float* mean3, float* out_img, float* out_gt, int N, int H, int W, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+// the checks and the argument block that osvos_lucid_compose and osvos_lucid_compose_ex share; 0 or the refusal
+static int compose_fill(ComposeArgs& args, const unsigned char* bgr, const unsigned char* mask, const unsigned char* bg, const double* M,
+                        const int* tone, const float* mean3, float* out_img, float* out_gt, int N, int H, int W) {
   OSVOS_ARG_CHECK(bgr && mask && bg && M && tone && mean3 && out_img && out_gt, "lucid_compose: null pointer");
   OSVOS_ARG_CHECK(N >= 1 && N <= OSVOS_LUCID_MAX_BATCH, "lucid_compose: N %d (1..%d)", N, OSVOS_LUCID_MAX_BATCH);
   OSVOS_ARG_CHECK(H >= 1 && H <= OSVOS_LUCID_MAX_SIDE && W >= 1 && W <= OSVOS_LUCID_MAX_SIDE, "lucid_compose: size H %d, W %d (sides 1..%d)", H, W,
                   OSVOS_LUCID_MAX_SIDE);
   OSVOS_ARG_CHECK((reinterpret_cast<size_t>(out_img) & 3) == 0 && (reinterpret_cast<size_t>(out_gt) & 3) == 0,
                   "lucid_compose: float pointers must be 4-byte aligned");
-  ComposeArgs args;          // (2.4 KB of kernel arguments: nothing is uploaded)
   for (int i = 0; i < N * 12; ++i) {
     const double v = M[i];
     const int k = i % 6;
@@ -244,7 +356,101 @@ extern "C" int osvos_lucid_compose(const unsigned char* bgr, const unsigned char
   for (int i = N * 12; i < OSVOS_LUCID_MAX_BATCH * 12; ++i) { (&args.M[0][0][0])[i] = 0.0; (&args.tone[0][0][0])[i] = 0; }
   args.bgr = bgr; args.mask = mask; args.bg = bg; args.out_img = out_img; args.out_gt = out_gt; args.H = H; args.W = W;
   for (int c = 0; c < 3; ++c) args.mean[c] = mean3[c];
-  hipLaunchKernelGGL(lucid_compose_kernel, dim3((unsigned)ceil_div(W, 64), (unsigned)ceil_div(H, 4), (unsigned)N), dim3(64, 4), 0, stream, args);
+  return 0;
+}
+
+static inline dim3 compose_grid(int N, int H, int W) { return dim3((unsigned)ceil_div(W, 64), (unsigned)ceil_div(H, 4), (unsigned)N); }
+
+extern "C" int osvos_lucid_compose(const unsigned char* bgr, const unsigned char* mask, const unsigned char* bg, const double* M, const int* tone,
+                                   const float* mean3, float* out_img, float* out_gt, int N, int H, int W, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ComposeArgs args;          // (2.4 KB of kernel arguments: nothing is uploaded)
+  if (const int rc = compose_fill(args, bgr, mask, bg, M, tone, mean3, out_img, out_gt, N, H, W)) return rc;
+  hipLaunchKernelGGL((lucid_compose_kernel<false, false, false, ComposeArgs>), compose_grid(N, H, W), dim3(64, 4), 0, stream, args);
   OSVOS_LAUNCH_CHECK();
+  return 0;
+}
+
+static inline bool compose_ex_sizes_ok(int N, int H, int W, int band) {
+  return N >= 1 && N <= OSVOS_LUCID_MAX_BATCH && H >= 1 && H <= OSVOS_LUCID_MAX_SIDE && W >= 1 && W <= OSVOS_LUCID_MAX_SIDE && band >= 0 &&
+         band <= OSVOS_LUCID_MAX_BAND;
+}
+
+// ws: the 1-bit label plane [N][H][ceil(W / 64)] of 64-bit words
+extern "C" size_t osvos_lucid_compose_ex_ws_bytes(int N, int H, int W, int band) {
+  if (!compose_ex_sizes_ok(N, H, W, band) || band == 0) return 0;
+  return sizeof(unsigned long long) * (size_t)N * H * ceil_div(W, 64);
+}
+
+typedef void (*ComposeExKernel)(const ComposeExArgs);
+// [deform][occlude][band]; the entry without any option is never launched from here: that call goes to the plain kernel
+static const ComposeExKernel kComposeEx[2][2][2] = {
+    {{nullptr, lucid_compose_kernel<false, false, true, ComposeExArgs>},
+     {lucid_compose_kernel<false, true, false, ComposeExArgs>, lucid_compose_kernel<false, true, true, ComposeExArgs>}},
+    {{lucid_compose_kernel<true, false, false, ComposeExArgs>, lucid_compose_kernel<true, false, true, ComposeExArgs>},
+     {lucid_compose_kernel<true, true, false, ComposeExArgs>, lucid_compose_kernel<true, true, true, ComposeExArgs>}}};
+
+extern "C" int osvos_lucid_compose_ex(const unsigned char* bgr, const unsigned char* mask, const unsigned char* bg, const double* M, const int* tone,
+                                      const int* occ, const short* D, int cell, int band, const float* mean3, float* out_img, float* out_gt, int N,
+                                      int H, int W, void* ws, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ComposeExArgs args;        // (under 3 KB of kernel arguments: only D is read from device memory)
+  if (const int rc = compose_fill(args, bgr, mask, bg, M, tone, mean3, out_img, out_gt, N, H, W)) return rc;
+  const size_t px = (size_t)H * W;
+  int shift = 0;
+  if (D) {
+    OSVOS_ARG_CHECK(cell >= OSVOS_LUCID_MIN_CELL && cell <= OSVOS_LUCID_MAX_CELL && (cell & (cell - 1)) == 0,
+                    "lucid_compose_ex: cell %d (a power of two in %d..%d)", cell, OSVOS_LUCID_MIN_CELL, OSVOS_LUCID_MAX_CELL);
+    OSVOS_ARG_CHECK((reinterpret_cast<size_t>(D) & 3) == 0, "lucid_compose_ex: D must be 4-byte aligned");
+    while ((1 << shift) < cell) ++shift;
+  }
+  OSVOS_ARG_CHECK(band >= 0 && band <= OSVOS_LUCID_MAX_BAND, "lucid_compose_ex: band %d (0..%d)", band, OSVOS_LUCID_MAX_BAND);
+  const size_t need = osvos_lucid_compose_ex_ws_bytes(N, H, W, band);
+  if (band > 0) {
+    OSVOS_ARG_CHECK(ws, "lucid_compose_ex: band %d needs ws (null pointer)", band);
+    OSVOS_ARG_CHECK((reinterpret_cast<size_t>(ws) & 7) == 0, "lucid_compose_ex: ws must be 8-byte aligned");
+    OSVOS_ARG_CHECK(!overlap(ws, need, bgr, 3 * px) && !overlap(ws, need, mask, px) && !overlap(ws, need, bg, 3 * px) &&
+                        !overlap(ws, need, out_img, sizeof(float) * 3 * N * px) && !overlap(ws, need, out_gt, sizeof(float) * N * px),
+                    "lucid_compose_ex: ws overlaps an input or an output");
+  }
+  bool occlude = false;
+  for (int i = 0; i < OSVOS_LUCID_MAX_BATCH * 6; ++i) (&args.occ[0][0])[i] = 0;
+  if (occ) {
+    for (int i = 0; i < N * 6; ++i) {
+      const int v = occ[i], k = i % 6;
+      if (k == 2 || k == 3)
+        OSVOS_ARG_CHECK(v >= 0 && v <= OSVOS_LUCID_MAX_OCC_RADIUS, "lucid_compose_ex: occluder radius %d of sample %d (0..%d)", v, i / 6,
+                        OSVOS_LUCID_MAX_OCC_RADIUS);
+      else
+        OSVOS_ARG_CHECK(v >= -OSVOS_LUCID_MAX_OCC_OFFSET && v <= OSVOS_LUCID_MAX_OCC_OFFSET,
+                        "lucid_compose_ex: occluder %s %d of sample %d (|.| <= %d)", k < 2 ? "centre" : "offset", v, i / 6, OSVOS_LUCID_MAX_OCC_OFFSET);
+      (&args.occ[0][0])[i] = v;
+    }
+    for (int n = 0; n < N; ++n) occlude = occlude || (args.occ[n][2] != 0 && args.occ[n][3] != 0);
+  }
+  if (!D && !occlude && band == 0) {                         // nothing asked for: osvos_lucid_compose's own kernel, its bits and its cost
+    hipLaunchKernelGGL((lucid_compose_kernel<false, false, false, ComposeArgs>), compose_grid(N, H, W), dim3(64, 4), 0, stream,
+                       static_cast<const ComposeArgs&>(args));
+    OSVOS_LAUNCH_CHECK();
+    return 0;
+  }
+  args.D = reinterpret_cast<const int*>(D);
+  args.plane = reinterpret_cast<unsigned long long*>(ws);
+  args.shift = shift;
+  args.GH = D ? ((H - 1) >> shift) + 2 : 0;
+  args.GW = D ? ((W - 1) >> shift) + 2 : 0;
+  hipLaunchKernelGGL(kComposeEx[D != nullptr][occlude][band > 0], compose_grid(N, H, W), dim3(64, 4), 0, stream, args);
+  OSVOS_LAUNCH_CHECK();
+  if (band > 0) {
+    BandArgs b;
+    b.plane = args.plane; b.out_gt = out_gt; b.H = H; b.W = W; b.band = band;
+    for (int dy = 0; dy <= OSVOS_LUCID_MAX_BAND; ++dy) {
+      int h = 0;
+      while (dy <= band && (h + 1) * (h + 1) <= band * band - dy * dy) ++h;
+      b.hw[dy] = h;
+    }
+    hipLaunchKernelGGL(lucid_band_kernel, compose_grid(N, H, W), dim3(64, 4), 0, stream, b);
+    OSVOS_LAUNCH_CHECK();
+  }
   return 0;
 }

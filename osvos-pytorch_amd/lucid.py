@@ -1,15 +1,17 @@
 """Lucid first-frame synthesis ("lucid data dreaming"): more training samples out of the one annotated frame, on the device
-(``osvos_lucid_inpaint`` / ``osvos_lucid_compose``, csrc/lucid.hip; the rule: include/osvos_hip.h).
+(``osvos_lucid_inpaint`` / ``osvos_lucid_compose`` / ``osvos_lucid_compose_ex``, csrc/lucid.hip; the rule: include/osvos_hip.h).
 
     cut the object out, fill the hole (once per sequence), then per training sample move object and background by affines of their own,
-    re-light both, and composite them again
+    re-light both, and composite them again -- optionally with the object bent by a smooth displacement field (non-rigid deformation),
+    partly hidden behind an ellipse of displaced background (an occluder), and with a band of void labels (-1) around the label's edges
 
 Online fine-tuning otherwise sees its one frame only flipped, rotated and scaled as a whole (``augment.DeviceAugment``): the object never
-moves against its background, is never lit differently from it, and what lies behind it is never seen.  Integers only: the samples are
-exact and repeat bit for bit.  Everything stays on the device; ``LucidDream`` reads back four numbers (the object's bounding box) once.
+moves against its background, is never lit differently from it, never changes shape, is never hidden, and what lies behind it is never
+seen.  Integers only: the samples are exact and repeat bit for bit.  Everything stays on the device; ``LucidDream`` reads back four numbers
+(the object's bounding box) once.
 
-Left out: void bands around the pasted edge, non-rigid deformation, occluders, premultiplied foreground colours.  The default parameters are
-STARTING VALUES, NOT TUNED ON DAVIS (no dataset was at hand when this was written), and no accuracy claim is made for them.
+Left out: cubic lattices, premultiplied foreground colours.  The default parameters are STARTING VALUES, NOT TUNED ON DAVIS (no dataset
+was at hand when this was written), and no accuracy claim is made for them.
 """
 import ctypes as C
 import math
@@ -18,7 +20,8 @@ import random
 import numpy as np
 import torch
 
-from ._lib import LUCID_MAX_BATCH, LUCID_MAX_GAIN, LUCID_MAX_PASSES, LUCID_MAX_RADIUS, LUCID_MAX_SIDE, SQDIST_MAX_SIDE, check, lib
+from ._lib import (LUCID_MAX_BAND, LUCID_MAX_BATCH, LUCID_MAX_CELL, LUCID_MAX_GAIN, LUCID_MAX_OCC_OFFSET, LUCID_MAX_OCC_RADIUS, LUCID_MAX_PASSES,
+                   LUCID_MAX_RADIUS, LUCID_MAX_SIDE, LUCID_MIN_CELL, SQDIST_MAX_SIDE, check, lib)
 from .augment import MEANVAL
 
 MAX_GROW = 64               # largest --lucid-grow: pixels the hole reaches beyond the mask
@@ -34,18 +37,31 @@ def _is_num(v):
     return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(v)
 
 
-def check_lucid(p=0.0, grow=5, radius=2, passes=3, fg_shift=0.25, bg_shift=0.05, gain=0.2, offset=20):
+def check_lucid(p=0.0, grow=5, radius=2, passes=3, fg_shift=0.25, bg_shift=0.05, gain=0.2, offset=20, deform=0.0, occlude=0.0, band=0, cell=128):
     """ValueError unless the parameters of ``LucidDream`` (and the probability ``p`` of train_online.py --lucid) are inside their limits
     (host only)"""
     for name, v, lo, hi in (("grow", grow, 0, MAX_GROW), ("radius", radius, 1, LUCID_MAX_RADIUS), ("passes", passes, 0, LUCID_MAX_PASSES),
-                            ("offset", offset, 0, 255)):
+                            ("offset", offset, 0, 255), ("band", band, 0, LUCID_MAX_BAND), ("cell", cell, LUCID_MIN_CELL, LUCID_MAX_CELL)):
         if not _is_int(v):
             raise ValueError("lucid: %s must be an integer, got %r" % (name, v))
         if not lo <= v <= hi:
             raise ValueError("lucid: %s %d (%d..%d)" % (name, v, lo, hi))
-    for name, v, hi in (("p", p, 1.0), ("fg_shift", fg_shift, 4.0), ("bg_shift", bg_shift, 1.0), ("gain", gain, 1.0)):
+    if cell & (cell - 1):
+        raise ValueError("lucid: cell %d (a power of two in %d..%d)" % (cell, LUCID_MIN_CELL, LUCID_MAX_CELL))
+    for name, v, hi in (("p", p, 1.0), ("fg_shift", fg_shift, 4.0), ("bg_shift", bg_shift, 1.0), ("gain", gain, 1.0), ("deform", deform, 1.0),
+                        ("occlude", occlude, 1.0)):
         if not _is_num(v) or not 0.0 <= v <= hi:
             raise ValueError("lucid: %s %r (a number in 0..%g)" % (name, v, hi))
+
+
+def field_shape(h, w, cell):
+    """(GH, GW) of the deformation lattice of an h x w frame: control points every ``cell`` pixels, one row and one column past the last
+    pixel's cell"""
+    check_lucid(cell=cell)
+    if not (_is_int(h) and _is_int(w) and h >= 1 and w >= 1):
+        raise ValueError("lucid: field_shape of %r x %r" % (h, w))
+    s = int(cell).bit_length() - 1
+    return ((int(h) - 1) >> s) + 2, ((int(w) - 1) >> s) + 2
 
 
 def affine_inverse(cx, cy, rot=0.0, sc=1.0, dx=0.0, dy=0.0, mirror=False):
@@ -111,10 +127,16 @@ def inpaint(frame_u8, hole_u8, radius=2, passes=3, ws=None):
     return out
 
 
-def compose(frame_u8, mask_u8, bg_u8, matrices, tones, meanval=MEANVAL):
+def compose(frame_u8, mask_u8, bg_u8, matrices, tones, meanval=MEANVAL, occluders=None, field=None, cell=64, band=0, ws=None):
     """frame_u8, bg_u8: uint8 CUDA tensors [H,W,3]; mask_u8: uint8 [H,W] (non-zero = object); matrices: [N][2][6] numbers, the dst -> src
     affines of (foreground, background) per sample (``affine_inverse``); tones: [N][2][6] integers (g_b, g_g, g_r, o_b, o_g, o_r), gains in Q8
-    (256 = 1, 0..1024), offsets -255..255 -> (image float32 [N,3,H,W], gt float32 [N,1,H,W]) from one launch.  Enqueued only."""
+    (256 = 1, 0..1024), offsets -255..255 -> (image float32 [N,3,H,W], gt float32 [N,1,H,W]) from one launch.  Enqueued only.
+
+    The options go through ``osvos_lucid_compose_ex``; without any of them the call is ``osvos_lucid_compose`` as before.  ``occluders``:
+    [N][6] integers (cx, cy, rx, ry, sx, sy) -- inside the ellipse the sample shows the background from (sx, sy) further on, label 0;
+    rx = 0 or ry = 0: none in that sample.  ``field``: the foreground's displacement, int16 [N,GH,GW,2] = (dx, dy) in 1/32 pixel on a lattice
+    of ``cell`` pixels (``field_shape``), a CUDA tensor or an array-like that is uploaded in one copy.  ``band`` 1..16: labels within that many
+    pixels of a label edge are -1 (void; one more launch); ``ws``: a CUDA tensor to hold the label plane, allocated when missing or small."""
     f = _frame(frame_u8, "frame_u8", LUCID_MAX_SIDE)
     bg = _frame(bg_u8, "bg_u8", LUCID_MAX_SIDE)
     if bg.shape != f.shape or bg.device != f.device:
@@ -136,9 +158,45 @@ def compose(frame_u8, mask_u8, bg_u8, matrices, tones, meanval=MEANVAL):
     gt = torch.empty((n, 1, h, w), device=f.device, dtype=torch.float32)
     mean = (C.c_float * 3)(*meanval)
     vp = C.c_void_p
+    if occluders is None and field is None and band == 0:
+        with torch.cuda.device(f.device):
+            check(lib().osvos_lucid_compose(vp(f.data_ptr()), vp(mask.data_ptr()), vp(bg.data_ptr()), vp(m.ctypes.data), vp(t.ctypes.data), mean,
+                                            vp(image.data_ptr()), vp(gt.data_ptr()), n, h, w, _stream()), "lucid_compose")
+        return image, gt
+    if not _is_int(band) or not 0 <= band <= LUCID_MAX_BAND:
+        raise ValueError("lucid: band %r (an integer in 0..%d)" % (band, LUCID_MAX_BAND))
+    occ = None
+    if occluders is not None:
+        occ = np.asarray(occluders)
+        if occ.shape != (n, 6) or not np.issubdtype(occ.dtype, np.integer):
+            raise ValueError("lucid: occluders must be integers [%d][6], got %s %s" % (n, occ.dtype, occ.shape))
+        if (occ[:, 2:4] < 0).any() or (occ[:, 2:4] > LUCID_MAX_OCC_RADIUS).any() or (np.abs(occ[:, [0, 1, 4, 5]]) > LUCID_MAX_OCC_OFFSET).any():
+            raise ValueError("lucid: occluder radii 0..%d, |centre| and |offset| <= %d" % (LUCID_MAX_OCC_RADIUS, LUCID_MAX_OCC_OFFSET))
+        occ = np.ascontiguousarray(occ.astype(np.int32))
+    d = None
+    if field is not None:
+        check_lucid(cell=cell)
+        want = (n,) + field_shape(h, w, cell) + (2,)
+        if isinstance(field, torch.Tensor):
+            if field.dtype != torch.int16 or tuple(field.shape) != want or field.device != f.device:
+                raise ValueError("lucid: field must be an int16 %s tensor on the device of the frame, got %s %s" % (want, field.dtype, tuple(field.shape)))
+            d = field.contiguous()
+        else:
+            a = np.asarray(field)
+            if a.shape != want or not np.issubdtype(a.dtype, np.integer) or (a < -32768).any() or (a > 32767).any():
+                raise ValueError("lucid: field must be int16 values %s, got %s %s" % (want, a.dtype, a.shape))
+            d = torch.from_numpy(np.ascontiguousarray(a.astype(np.int16))).to(f.device)      # the one copy
+        if d.data_ptr() % 4:
+            raise ValueError("lucid: field must be 4-byte aligned")
+    need = int(lib().osvos_lucid_compose_ex_ws_bytes(n, h, w, int(band)))
+    if need and (ws is None or not isinstance(ws, torch.Tensor) or ws.device != f.device or ws.data_ptr() % 8
+                 or ws.numel() * ws.element_size() < need):
+        ws = torch.empty((need + 7) // 8, device=f.device, dtype=torch.int64)
     with torch.cuda.device(f.device):
-        check(lib().osvos_lucid_compose(vp(f.data_ptr()), vp(mask.data_ptr()), vp(bg.data_ptr()), vp(m.ctypes.data), vp(t.ctypes.data), mean,
-                                        vp(image.data_ptr()), vp(gt.data_ptr()), n, h, w, _stream()), "lucid_compose")
+        check(lib().osvos_lucid_compose_ex(vp(f.data_ptr()), vp(mask.data_ptr()), vp(bg.data_ptr()), vp(m.ctypes.data), vp(t.ctypes.data),
+                                           vp(occ.ctypes.data) if occ is not None else None, vp(d.data_ptr()) if d is not None else None, int(cell),
+                                           int(band), mean, vp(image.data_ptr()), vp(gt.data_ptr()), n, h, w,
+                                           vp(ws.data_ptr()) if need else None, _stream()), "lucid_compose_ex")
     return image, gt
 
 
@@ -151,15 +209,26 @@ class LucidDream(object):
     pivot); foreground rotation, scale, shift x, shift y; background rotation, scale, shift x, shift y; foreground gain, foreground offset,
     background gain, background offset.  Rotation and scale are drawn as ``DeviceAugment`` draws them from ``rots`` / ``scales``; a shift is
     uniform in +-``fg_shift`` times the object box's side (+-``bg_shift`` times the frame's side); a gain is uniform in 1 +-``gain`` (all three
-    channels alike, rounded to Q8), an offset a uniform integer in +-``offset`` grey levels.
+    channels alike, rounded to Q8), an offset a uniform integer in +-``offset`` grey levels.  With ``deform``, ``occlude`` and ``band`` off
+    not one further number is drawn.
+
+    Then, with ``deform`` > 0, 2 GH GW numbers (``field_shape(H, W, deform_cell)``), in the order lattice row gy, lattice column gx, dx then
+    dy: a control point's displacement is ``round(4 deform_cell deform (2 u - 1))`` in 1/32 pixel, that is at most ``deform * deform_cell / 8``
+    pixels -- neighbouring control points differ by at most a quarter of their spacing, so the bilinear map cannot fold.  Then, with
+    ``occlude`` > 0, 7 numbers, always all seven: presence (``u < occlude``); the centre's x and y, ``round(x0 + u box_w)`` and
+    ``round(y0 + u box_h)`` over the object's box; the semi-axes ``round((0.1 + 0.2 u) box_w)`` and ``round((0.1 + 0.2 u) box_h)``; the
+    offset of the background shown in the ellipse, ``round((2 u - 1) W / 4)`` and ``round((2 u - 1) H / 4)``.  An absent occluder, or an
+    empty mask, gives rx = 0 (all six numbers 0).  ``band`` > 0 draws nothing: labels within ``band`` pixels of a label edge are -1 (void).
 
     ``dream()`` -> {'image': [3,H,W], 'gt': [1,H,W]} as ``DeviceAugment``; ``dream.batch(n)`` -> n samples [n,3,H,W] / [n,1,H,W] from one
-    launch.  The defaults are starting values, NOT tuned on DAVIS."""
+    ``compose`` call.  The defaults are starting values, NOT tuned on DAVIS."""
 
     def __init__(self, frame_u8, mask_u8, grow=5, radius=2, passes=3, rots=(-30, 30), scales=(.75, 1.25), fg_shift=0.25, bg_shift=0.05, gain=0.2,
-                 offset=20, meanval=MEANVAL):
+                 offset=20, meanval=MEANVAL, deform=0.0, deform_cell=128, occlude=0.0, band=0):
         from .results import distance_map
-        check_lucid(0.0, grow, radius, passes, fg_shift, bg_shift, gain, offset)
+        check_lucid(0.0, grow, radius, passes, fg_shift, bg_shift, gain, offset, deform, occlude, band, deform_cell)
+        self.deform, self.deform_cell, self.occlude, self.band = float(deform), int(deform_cell), float(occlude), int(band)
+        self.ws = None                                                                         # the label plane of the void band, kept between calls
         if not (isinstance(rots, tuple) and isinstance(scales, tuple) and len(rots) == 2 and len(scales) == 2):
             raise ValueError("LucidDream takes continuous (tuple) ranges of rotation and scale")
         if not (-90 <= rots[0] <= rots[1] <= 90 and 0.25 <= scales[0] <= scales[1] <= 4):
@@ -195,19 +264,43 @@ class LucidDream(object):
         return [g, g, g, o, o, o]
 
     def draw(self):
-        """-> (matrices [2][6], tones [2][6]) of one sample; the 13 draws in the order of the class text"""
+        """-> (matrices [2][6], tones [2][6], field [GH][GW][2] or None, occluder [6] or None) of one sample; the draws in the order of the
+        class text"""
         mirror = random.random() < 0.5
         rot, sc, ux, uy = self._layer()
         fg = affine_inverse(self.pivot[0], self.pivot[1], rot, sc, ux * self.fg_shift * self.box_w, uy * self.fg_shift * self.box_h, mirror)
         rot, sc, ux, uy = self._layer()
         bg = affine_inverse(self.w / 2, self.h / 2, rot, sc, ux * self.bg_shift * self.w, uy * self.bg_shift * self.h, mirror)
-        return [fg, bg], [self._tone(), self._tone()]
+        tones = [self._tone(), self._tone()]
+        field = occ = None
+        if self.deform > 0:
+            gh, gw = field_shape(self.h, self.w, self.deform_cell)
+            amp = 4 * self.deform_cell * self.deform
+            field = [[[int(round(amp * (2 * random.random() - 1))) for _ in range(2)] for _ in range(gw)] for _ in range(gh)]
+        if self.occlude > 0:
+            u = [random.random() for _ in range(7)]
+            occ = [0] * 6
+            if u[0] < self.occlude and self.box is not None:
+                occ = [int(round(self.box[0] + u[1] * self.box_w)), int(round(self.box[2] + u[2] * self.box_h)),
+                       int(round((0.1 + 0.2 * u[3]) * self.box_w)), int(round((0.1 + 0.2 * u[4]) * self.box_h)),
+                       int(round((2 * u[5] - 1) * self.w / 4)), int(round((2 * u[6] - 1) * self.h / 4))]
+        return [fg, bg], tones, field, occ
 
     def batch(self, n):
         if not _is_int(n) or not 1 <= n <= LUCID_MAX_BATCH:
             raise ValueError("lucid: batch of %r (1..%d)" % (n, LUCID_MAX_BATCH))
         draws = [self.draw() for _ in range(n)]
-        image, gt = compose(self.frame, self.mask, self.bg, [d[0] for d in draws], [d[1] for d in draws], self.meanval)
+        M, T = [d[0] for d in draws], [d[1] for d in draws]
+        if not (self.deform > 0 or self.occlude > 0 or self.band):
+            image, gt = compose(self.frame, self.mask, self.bg, M, T, self.meanval)
+            return {'image': image, 'gt': gt}
+        if self.band and self.ws is None:
+            need = int(lib().osvos_lucid_compose_ex_ws_bytes(LUCID_MAX_BATCH, self.h, self.w, self.band))
+            self.ws = torch.empty((need + 7) // 8, device=self.frame.device, dtype=torch.int64)
+        image, gt = compose(self.frame, self.mask, self.bg, M, T, self.meanval,
+                            occluders=[d[3] for d in draws] if self.occlude > 0 else None,
+                            field=np.asarray([d[2] for d in draws], np.int16) if self.deform > 0 else None, cell=self.deform_cell,
+                            band=self.band, ws=self.ws)
         return {'image': image, 'gt': gt}
 
     def __call__(self):

@@ -32,7 +32,10 @@ running on the MI355X-native OSVOS path.  Differences by design:
   * ``--lucid P``: lucid first-frame synthesis -- with probability P a training sample is not the flipped / rotated / scaled frame but a
     re-composition of it: the object cut out, the hole inpainted once per sequence, object and background moved by affines of their own,
     re-lit and composited again on the device (osvos_pytorch_amd.lucid.LucidDream); parameters --lucid-grow, --lucid-smooth, --lucid-shift,
-    --lucid-tone (starting values, not tuned on DAVIS).  With P = 0 not one random draw and not one byte changes
+    --lucid-tone (starting values, not tuned on DAVIS).  With P = 0 not one random draw and not one byte changes.  ``--lucid-deform A[,CELL]``
+    bends the object by a smooth displacement field, ``--lucid-occlude P`` hides part of it behind an ellipse of displaced background,
+    ``--lucid-band R`` labels the pixels within R of a label edge void (-1: no count, no loss, no gradient; not with --window-fused); all
+    three are off by default, and off they change no draw and no byte
   * launched under torchrun with N processes, rank r fine-tunes sequences r, r+N, ... of the
     comma-separated SEQ_NAME list (independent replicas: online training has no exchange step)
 """
@@ -198,7 +201,10 @@ def fine_tune(args, net, optimizer, trainloader, device, nEpochs, nAveGrad, seed
                     window = []
                 continue
             inputs = inputs.detach().requires_grad_()      # (a fresh leaf: a frame the loader hands out again must not accumulate a .grad)
-            loop.micro_batch(inputs, gts)
+            if args.lucid_void:      # --lucid with --lucid-band: labels below 0 are void
+                loop.micro_batch(inputs, gts, void_labels=True)
+            else:
+                loop.micro_batch(inputs, gts)
         if epoch % max(1, nEpochs // 20) == max(1, nEpochs // 20) - 1:
             running = loop.pop_running()[0] / (num_img_tr * max(1, nEpochs // 20))
             print('[Epoch: %d, numImages: %5d]' % (epoch + 1, num_img_tr))
@@ -361,15 +367,35 @@ def check_lucid_args(args):
         radius, passes = pair(args.lucid_smooth, (int, int), '--lucid-smooth RADIUS,PASSES')
         fg_shift, bg_shift = pair(args.lucid_shift, (float, float), '--lucid-shift FG,BG')
         gain, offset = pair(args.lucid_tone, (float, int), '--lucid-tone GAIN,OFFSET')
-        lucid.check_lucid(args.lucid_p, args.lucid_grow, radius, passes, fg_shift, bg_shift, gain, offset)
+        parts = args.lucid_deform.split(',')
+        if len(parts) not in (1, 2):
+            raise ValueError('--lucid-deform takes A or A,CELL, got %r' % args.lucid_deform)
+        try:
+            deform, cell = float(parts[0]), int(parts[1]) if len(parts) == 2 else 128
+        except ValueError:
+            raise ValueError('--lucid-deform takes A or A,CELL, got %r' % args.lucid_deform)
+        lucid.check_lucid(args.lucid_p, args.lucid_grow, radius, passes, fg_shift, bg_shift, gain, offset, deform, args.lucid_occlude,
+                          args.lucid_band, cell)
     except ValueError as e:
         raise SystemExit('--lucid*: %s' % e)
+    args.lucid_void = False          # fine_tune: the samples carry void labels
+    if args.lucid_band > 0 and args.window_fused:
+        raise SystemExit('--lucid-band does not combine with --window-fused: window_batch has no void rule')
+    if args.lucid_band > 0 and os.environ.get('OSVOS_FUSED_LOSS_STEP', '1') == '0':
+        raise SystemExit('--lucid-band needs the fused loss step (OSVOS_FUSED_LOSS_STEP is 0): the void rule lives in the HIP loss kernel')
     if not args.lucid_p:
         return
     if not args.device_augment:
         raise SystemExit('--lucid needs --device-augment: the samples are made from the decoded uint8 frame and its annotation on the device')
     args.lucid = dict(p=args.lucid_p, grow=args.lucid_grow, radius=radius, passes=passes, fg_shift=fg_shift, bg_shift=bg_shift, gain=gain,
                       offset=offset)
+    if deform > 0:                   # (an option that is off adds nothing: LucidDream is built exactly as before)
+        args.lucid.update(deform=deform, deform_cell=cell)
+    if args.lucid_occlude > 0:
+        args.lucid.update(occlude=args.lucid_occlude)
+    if args.lucid_band > 0:
+        args.lucid.update(band=args.lucid_band)
+        args.lucid_void = True
 
 
 def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, nEpochs, nAveGrad):
@@ -554,6 +580,15 @@ def parse_args(argv=None):
                          'the frame (0..1)')
     ap.add_argument('--lucid-tone', default='0.2,20', metavar='GAIN,OFFSET',
                     help='--lucid: each layer is re-lit with a gain of 1 +- GAIN (0..1) and an offset of +- OFFSET grey levels (0..255)')
+    ap.add_argument('--lucid-deform', default='0', metavar='A[,CELL]',
+                    help='--lucid: non-rigid deformation of the object (0 = off) -- a displacement field on a lattice of CELL pixels (a power of '
+                         'two in 8..256, default 128), bilinear in between, each control point moved by up to A * CELL / 8 pixels (A in 0..1)')
+    ap.add_argument('--lucid-occlude', type=float, default=0.0, metavar='P',
+                    help='--lucid: with probability P (0..1, 0 = off) a lucid sample hides part of the object behind an ellipse of displaced '
+                         'background, labelled background')
+    ap.add_argument('--lucid-band', type=int, default=0, metavar='R',
+                    help='--lucid: labels within R pixels (0..16, 0 = off) of a label edge of a lucid sample are void -- no count, no loss, '
+                         'gradient 0.  Needs the fused loss step; not with --window-fused')
     args = ap.parse_args(argv)
     args.tta = tta_scales(args)
     check_adapt_args(args)
