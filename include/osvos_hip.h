@@ -728,6 +728,37 @@ int osvos_lucid_compose_ex(const unsigned char* bgr, const unsigned char* mask, 
                            const int* occ, const short* D, int cell, int band, const float* mean3, float* out_img, float* out_gt, int N, int H,
                            int W, void* ws, void* stream);
 
+/* ---- appearance matching to the first frame: int8 features and a labelled nearest-neighbour search on the integer matrix pipe ----
+ * Every float operation below is ONE IEEE fp32 operation (no fused multiply-add); the dot products are integers.  Results are exact and do
+ *   not depend on tiling, slicing or schedule (tests compare bit for bit against a numpy restatement).
+ * Quantise (osvos_match_quantize): feat [P][C], format 0 = fp32 or 1 = bf16 (the value of osvos_net_ws_format; bf16 widens exactly).
+ *   Per pixel: m = max_c |f_c|.  If m is zero, or any f_c is not finite, q_c = 0 for every c and rinv = 0.  Otherwise s = 127.0f / m and
+ *   q_c = (int8) clamp(rintf(f_c * s), -127, 127), half to even, a NaN product (0 * inf, when s overflows) counting as 0;
+ *   n = sum_c q_c^2 (int32, at most 127^2 * 1024 < 2^24, so (float) n is exact); rinv = n ? 1.0f / sqrtf((float) n) : 0.  The two quotients
+ *   and the square root are correctly rounded: the kernel forms them in double and rounds once more, which is the correctly rounded fp32
+ *   result because 53 >= 2 * 24 + 2.  Out: q int8 [P][C], rinv fp32 [P].  One launch, one wave per pixel.
+ * Cell labels (osvos_match_cell_labels): mask uint8 [N][H][W], nonzero = object; the feature grid h x w = ceil(H / S) x ceil(W / S), S the
+ *   stride (2^stage under ceil-mode pooling).  Cell (i, j) covers rows S i .. min(S i + S, H) - 1 and the same for columns; a = its area,
+ *   k = its object pixels.  label = 1 if 4 k >= 3 a, 0 if 4 k <= a, 255 (void: in neither bank) otherwise.  Out: uint8 [N][h][w].  One launch.
+ * Nearest (osvos_match_nearest): query Q int8 [N][Pq][C] with rinv_q [N][Pq]; reference R int8 [NR][Pr][C] with rinv_r and label_r [NR][Pr];
+ *   NR is N, or 1 (every frame searches the same bank).  For class c in {1 foreground, 0 background}:
+ *     t_ab = (float) dot(Q_a, R_b) * rinv_r[b]                  (|dot| <= 127^2 C < 2^24 for C <= 1024: the conversion is exact)
+ *     best_c[a] = max of t_ab over the b with label_r[b] == c;  idx_c[a] = the smallest such b that attains it;  sim_c[a] = best_c[a] * rinv_q[a]
+ *   a class without a reference row gives sim = -2.0f and idx = -1; rows with any other label are in neither class.
+ *   Out: sim fp32 [N][2][Pq] (foreground first), idx int32 [N][2][Pq] (may be NULL).  Two launches: a tile kernel on
+ *   v_mfma_i32_32x32x32_i8 (a workgroup owns 128 query rows, staged once in LDS, and walks a slice of R through LDS; the scores are reduced
+ *   in registers and never stored; per-slice partial (value, index) pairs go to ws) and a small kernel that merges the slices.  Rows past
+ *   Pq / Pr are masked by the kernel, not padded by the caller.  No atomics; deterministic.
+ *   ws: osvos_match_ws_bytes(N, Pq, Pr, C) bytes, 8-byte aligned, contents irrelevant on entry; 0 for arguments the call refuses.
+ * Limits: C a multiple of 64 in 64..1024, Pq and Pr 1..2^20, P 1..2^30, N 1..65535, sides 1..16384, stride a power of two 1..64.  q, Q and R
+ *   are 16-byte aligned.  Outputs (and ws) must not overlap inputs or each other.  Every argument error returns < 0 before any device
+ *   call, with a text that names the bad parameter. */
+int osvos_match_quantize(const void* feat, int format, signed char* q, float* rinv, long P, int C, void* stream);
+int osvos_match_cell_labels(const unsigned char* mask, unsigned char* label, int N, int H, int W, int h, int w, int stride, void* stream);
+size_t osvos_match_ws_bytes(int N, int Pq, int Pr, int C);
+int osvos_match_nearest(const signed char* Q, const float* rinv_q, const signed char* R, const float* rinv_r, const unsigned char* label_r, float* sim,
+                        int* idx, void* ws, int N, int NR, int Pq, int Pr, int C, void* stream);
+
 /* ---- fused SGD (torch.optim.SGD semantics, train_online.py:79-88,147) ----------------------
  * for each i: d = g + wd*p; buf = first ? d : momentum*buf + d; p -= lr*buf      (flat tensors) */
 int osvos_sgd_step(float* p, const float* g, float* buf, long count, float lr, float momentum,

@@ -41,6 +41,8 @@ SUPERPIXELS_MAX_COMPACTNESS = 64  # OSVOS_SUPERPIXELS_MAX_COMPACTNESS: largest w
 SUPERPIXELS_MAX_ITERS = 16  # OSVOS_SUPERPIXELS_MAX_ITERS: assign / update steps per osvos_superpixels_slic call
 SUPERPIXELS_MAX_SIDE = 16384  # OSVOS_SUPERPIXELS_MAX_SIDE: largest H / W of the superpixel calls
 SUPERPIXELS_MAX_K = 268435456  # OSVOS_SUPERPIXELS_MAX_K: most labels per frame of osvos_superpixels_pool
+MATCH_MAX_C = 1024          # osvos_match_*: most channels (a multiple of 64, from 64)
+MATCH_MAX_P = 1 << 20       # osvos_match_nearest: most query / reference rows per frame
 SQDIST_NONE = 2147483647    # OSVOS_SQDIST_NONE: osvos_mask_sqdist's value in an image without a source pixel
 SQDIST_MAX_SIDE = 4096      # OSVOS_SQDIST_MAX_SIDE: largest H / W of osvos_mask_sqdist and osvos_adapt_targets
 LUCID_MAX_BATCH = 16        # OSVOS_LUCID_MAX_BATCH: samples per osvos_lucid_compose launch
@@ -152,6 +154,10 @@ PROTOTYPES = {
     "osvos_superpixels_slic": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "osvos_superpixels_pool_ws_bytes": (_sz, [_i, _i]),
     "osvos_superpixels_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "osvos_match_quantize": (_i, [_vp, _i, _vp, _vp, _l, _i, _vp]),
+    "osvos_match_cell_labels": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "osvos_match_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "osvos_match_nearest": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "osvos_lucid_inpaint_ws_bytes": (_sz, [_i, _i, _i]),
     "osvos_lucid_inpaint": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "osvos_lucid_compose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -76,11 +76,12 @@ class OnlineAdapter(object):
         self.steps, self.mix, self.weight = int(steps), int(mix), float(weight)
         self.prob, self.erosion, self.distance = float(prob), int(erosion), int(distance)
         self.loop = TrainLoop(net, optimizer, mode='online', n_ave_grad=1)
+        self.forward = None          # a callable image -> logit maps to use in place of net.forward for the two plain forwards (match.AppearanceMatcher)
         self.adapted = self.skipped = self.steps_taken = 0
 
     def _forward(self, image):
         with torch.no_grad():
-            return self.net.forward(image)[-1]
+            return (self.forward or self.net.forward)(image)[-1]
 
     def __call__(self, image, prev_mask):
         if self.steps == 0:

@@ -282,6 +282,49 @@ class OSVOSNetFunction(torch.autograd.Function):
         return (None, dx) + tuple(grads)
 
 
+FEATURE_LAYERS = (3, 6, 9, 12)      # osvos_net_ws_query indices of conv2_2, conv3_3, conv4_3, conv5_3: what the side branches read
+
+
+def net_forward_features(rt, x, params, layer=9):
+    """A forward without a graph that keeps its workspace: ``(outs, feat, fmt)`` -- ``outs`` the five logit maps of ``OSVOSNetFunction`` under
+    ``torch.no_grad()`` bit for bit (the same library call with the same flags), ``feat`` trunk tensor ``layer`` (one of FEATURE_LAYERS: the last convolution of stages
+    1-4, always materialised because a side branch reads it) as a VIEW of the workspace shaped [N,h,w,C], float32 or bfloat16, and ``fmt``
+    its ``osvos_net_ws_format`` (0 fp32, 1 bf16).  The view keeps the workspace alive; nothing is copied."""
+    if isinstance(layer, bool) or not isinstance(layer, int) or layer not in FEATURE_LAYERS:
+        raise ValueError("forward_features: layer %r is not one of %s (conv2_2, conv3_3, conv4_3, conv5_3)" % (layer, FEATURE_LAYERS))
+    if not x.is_cuda:
+        raise RuntimeError("OSVOS (osvos_pytorch_amd) runs on the GPU only: move the module and the input to 'cuda'; there is no CPU fallback")
+    if len(params) != NPARAMS:
+        raise RuntimeError("expected %d parameters, got %d" % (NPARAMS, len(params)))
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError("expected input of shape [N,3,H,W], got %s" % (tuple(x.shape),))
+    l = lib()
+    with torch.no_grad():
+        xin = x.detach().contiguous().float()
+        ps = [p.detach().contiguous() for p in params]
+        for p in ps:
+            if p.dtype != torch.float32 or p.device != xin.device:
+                raise RuntimeError("parameters must be float32 on the input's device")
+        with torch.cuda.device(xin.device):
+            rt.ensure_packed(ps)
+            n, _, h, w = (int(v) for v in xin.shape)
+            # the same choice of forward as OSVOSNetFunction makes (autograd reports needs_input_grad for a parameter that requires grad under
+            # torch.no_grad() too, so a module with trainable parameters runs the full-workspace forward there as well): same call, same bits
+            need_bwd = bool(x.requires_grad or any(p.requires_grad for p in params))
+            nbytes = l.osvos_net_ws_bytes(n, h, w, rt.dtype) if need_bwd else l.osvos_net_ws_bytes_infer(n, h, w, rt.dtype)
+            ws = torch.empty(nbytes, device=xin.device, dtype=torch.uint8)
+            outs = [torch.empty((n, 1, h, w), device=xin.device, dtype=torch.float32) for _ in range(5)]
+            check(l.osvos_net_forward(C.c_void_p(xin.data_ptr()), C.c_void_p(rt.wbuf.data_ptr()), C.c_void_p(ws.data_ptr()),
+                                      ptr_array([o.data_ptr() for o in outs]), n, h, w, rt.cdtype_fwd() | (0 if need_bwd else INFERENCE), _stream(),
+                                      rt.auxf(xin.device)), "net_forward")
+        off, el, ch, hh, ww = C.c_size_t(), C.c_size_t(), C.c_int(), C.c_int(), C.c_int()
+        check(l.osvos_net_ws_query(n, h, w, rt.dtype, layer, C.byref(off), C.byref(el), C.byref(ch), C.byref(hh), C.byref(ww)), "net_ws_query")
+        fmt = int(l.osvos_net_ws_format(rt.dtype, layer))
+        dt, size = (torch.bfloat16, 2) if fmt == 1 else (torch.float32, 4)
+        feat = ws[off.value:off.value + size * el.value].view(dt).view(n, hh.value, ww.value, ch.value)
+    return outs, feat, fmt
+
+
 class CBCELossFunction(torch.autograd.Function):
     """class_balanced_cross_entropy_loss (osvos_layers.py:19-48); loss and dLoss/dOutput come out
     of the same kernel pass, the backward only scales by the (device-resident) upstream gradient."""

@@ -1,0 +1,222 @@
+"""Appearance matching to the annotated first frame (PML / VideoMatch / FEELVOS style), on the device: every pixel's trunk feature is
+quantised to int8 and compared with the features of the first frame -- and optionally of the previous frame -- by a labelled
+nearest-neighbour search on the integer matrix pipe (``osvos_match_quantize`` / ``osvos_match_cell_labels`` / ``osvos_match_nearest``,
+csrc/match.hip; the rule: include/osvos_hip.h).
+
+    quantise: q = clamp(rint(f * 127 / max|f|), -127, 127) per pixel, rinv = 1 / sqrt(sum q^2)
+    labels:   a feature cell is object when 3/4 of its pixels are, background when at most 1/4 are, void (in neither bank) otherwise
+    nearest:  per query pixel and class, the largest cosine dot(Q_a, R_b) * rinv_r[b] * rinv_q[a] over the bank's rows of that class
+    map:      cosine to the nearest foreground feature minus cosine to the nearest background feature, on the feature grid
+
+The network's logits are the only evidence every other stage has; when the network fires on a distractor that merely looks like the object
+to its classifier, the map is a second opinion from the features themselves.  ``AppearanceMatcher`` adds ``gain * map`` to the fused logits
+with ``tta.fuse_views`` (bilinear, on the device).  Integer dot products: the result is exact and repeats bit for bit.
+
+The default parameters are STARTING VALUES, NOT TUNED ON DAVIS (no dataset was at hand when this was written), and no accuracy claim is
+made for them: tune them on a validation split before quoting a score.
+"""
+import ctypes as C
+import math
+import sys
+
+import numpy as np
+import torch
+
+from . import tta
+from ._lib import MATCH_MAX_C, MATCH_MAX_P, check, lib
+from .autograd import FEATURE_LAYERS
+
+_STRIDE = {3: 2, 6: 4, 9: 8, 12: 16}      # conv2_2, conv3_3, conv4_3, conv5_3: 2^stage under ceil-mode pooling
+
+
+def stride_of(layer):
+    """pixels per feature cell of trunk tensor ``layer`` (3, 6, 9 or 12)"""
+    if isinstance(layer, bool) or not isinstance(layer, (int, np.integer)) or int(layer) not in FEATURE_LAYERS:
+        raise ValueError("match: layer %r is not one of %s (conv2_2, conv3_3, conv4_3, conv5_3)" % (layer, FEATURE_LAYERS))
+    return _STRIDE[int(layer)]
+
+
+def check_match(layer, gain):
+    """ValueError unless ``layer`` is one of the four feature layers and ``gain`` a finite number >= 0 (host only)"""
+    stride_of(layer)
+    if isinstance(gain, bool) or not isinstance(gain, (int, float, np.integer, np.floating)) or not math.isfinite(gain) or gain < 0:
+        raise ValueError("match: gain %r (a finite number >= 0; 0 = off)" % (gain,))
+
+
+def _need_cuda(t, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("osvos_pytorch_amd.match needs CUDA (ROCm) tensors (%s); there is no CPU fallback" % what)
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _channels_ok(c):
+    return 64 <= c <= MATCH_MAX_C and c % 64 == 0
+
+
+def quantize(feat):
+    """feat: float32 or bfloat16 CUDA tensor [..., C] (C a multiple of 64, 64..1024; e.g. the [N,h,w,C] view of ``OSVOS.forward_features``)
+    -> (q int8 [..., C], rinv float32 [...]).  Enqueued only."""
+    _need_cuda(feat, "feat")
+    if feat.dtype not in (torch.float32, torch.bfloat16) or feat.dim() < 2:
+        raise ValueError("feat must be a float32 or bfloat16 [..., C] tensor, got %s %s" % (feat.dtype, tuple(feat.shape)))
+    c = int(feat.shape[-1])
+    if not _channels_ok(c) or feat.numel() == 0:
+        raise ValueError("feat of %s: C must be a multiple of 64 in 64..%d and no dimension empty" % (tuple(feat.shape), MATCH_MAX_C))
+    f = feat.contiguous()
+    p = f.numel() // c
+    q = torch.empty(f.shape, device=f.device, dtype=torch.int8)
+    rinv = torch.empty(f.shape[:-1], device=f.device, dtype=torch.float32)
+    vp = C.c_void_p
+    with torch.cuda.device(f.device):
+        check(lib().osvos_match_quantize(vp(f.data_ptr()), 1 if f.dtype == torch.bfloat16 else 0, vp(q.data_ptr()), vp(rinv.data_ptr()), p, c, _stream()),
+              "match_quantize")
+    return q, rinv
+
+
+def cell_labels(mask, stride):
+    """mask: uint8 or bool CUDA tensor [N,H,W], [N,1,H,W] or [H,W], nonzero = object -> uint8 [N,h,w] on the ceil(H / stride) x ceil(W / stride)
+    grid: 1 object, 0 background, 255 void.  Enqueued only."""
+    _need_cuda(mask, "mask")
+    if mask.dim() == 4 and mask.shape[1] == 1:
+        mask = mask[:, 0]
+    if mask.dim() == 2:
+        mask = mask[None]
+    if mask.dtype == torch.bool:
+        mask = mask.to(torch.uint8)
+    if mask.dtype != torch.uint8 or mask.dim() != 3 or mask.numel() == 0:
+        raise ValueError("mask must be a uint8 or bool [N,H,W], [N,1,H,W] or [H,W] tensor, got %s %s" % (mask.dtype, tuple(mask.shape)))
+    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or not 1 <= stride <= 64 or stride & (stride - 1):
+        raise ValueError("match: stride %r (a power of two, 1..64)" % (stride,))
+    m = mask.contiguous()
+    n, H, W = (int(v) for v in m.shape)
+    h, w = -(-H // int(stride)), -(-W // int(stride))
+    label = torch.empty((n, h, w), device=m.device, dtype=torch.uint8)
+    vp = C.c_void_p
+    with torch.cuda.device(m.device):
+        check(lib().osvos_match_cell_labels(vp(m.data_ptr()), vp(label.data_ptr()), n, H, W, h, w, int(stride), _stream()), "match_cell_labels")
+    return label
+
+
+def nearest_workspace(n, pq, pr, c, device, ws=None):
+    """a uint8 CUDA tensor of at least osvos_match_ws_bytes: ``ws`` when it is large enough and on ``device``, else a new one"""
+    need = int(lib().osvos_match_ws_bytes(n, pq, pr, c))
+    if need == 0:
+        raise ValueError("match: no workspace size for N %d Pq %d Pr %d C %d" % (n, pq, pr, c))
+    if ws is None or ws.numel() < need or ws.device != device:
+        ws = torch.empty(need, device=device, dtype=torch.uint8)
+    return ws
+
+
+def nearest(q, rinv_q, r, rinv_r, label_r, ws=None, with_idx=False):
+    """q int8 [N,Pq,C] with rinv_q float32 [N,Pq]; r int8 [NR,Pr,C] with rinv_r float32 and label_r uint8 [NR,Pr], NR = N or 1 (one bank for
+    every frame) -> sim float32 [N,2,Pq]: per query row the cosine to the nearest reference row labelled 1 (row 0 of the class axis) and to
+    the nearest labelled 0 (row 1); -2 for a class the bank does not hold.  ``with_idx``: also idx int32 [N,2,Pq], the smallest reference
+    row that attains it (-1 for an empty class).  Enqueued only."""
+    for t, what in ((q, "q"), (rinv_q, "rinv_q"), (r, "r"), (rinv_r, "rinv_r"), (label_r, "label_r")):
+        _need_cuda(t, what)
+    if q.dtype != torch.int8 or r.dtype != torch.int8 or q.dim() != 3 or r.dim() != 3 or q.shape[2] != r.shape[2]:
+        raise ValueError("q and r must be int8 [N,Pq,C] and [NR,Pr,C] tensors with the same C, got %s %s and %s %s" % (q.dtype, tuple(q.shape), r.dtype, tuple(r.shape)))
+    n, pq, c = (int(v) for v in q.shape)
+    nr, pr = int(r.shape[0]), int(r.shape[1])
+    if not _channels_ok(c) or nr not in (1, n) or not (1 <= pq <= MATCH_MAX_P and 1 <= pr <= MATCH_MAX_P) or n < 1:
+        raise ValueError("match: N %d NR %d Pq %d Pr %d C %d: NR is N or 1, rows 1..%d, C a multiple of 64 in 64..%d" % (n, nr, pq, pr, c, MATCH_MAX_P, MATCH_MAX_C))
+    if rinv_q.dtype != torch.float32 or tuple(rinv_q.shape) != (n, pq) or rinv_r.dtype != torch.float32 or tuple(rinv_r.shape) != (nr, pr):
+        raise ValueError("rinv_q and rinv_r must be float32 [%d,%d] and [%d,%d] tensors" % (n, pq, nr, pr))
+    if label_r.dtype != torch.uint8 or tuple(label_r.shape) != (nr, pr):
+        raise ValueError("label_r must be a uint8 [%d,%d] tensor, got %s %s" % (nr, pr, label_r.dtype, tuple(label_r.shape)))
+    if any(t.device != q.device for t in (rinv_q, r, rinv_r, label_r)):
+        raise ValueError("match: the five tensors must be on one device")
+    q, rinv_q, r, rinv_r, label_r = (t.contiguous() for t in (q, rinv_q, r, rinv_r, label_r))
+    sim = torch.empty((n, 2, pq), device=q.device, dtype=torch.float32)
+    idx = torch.empty((n, 2, pq), device=q.device, dtype=torch.int32) if with_idx else None
+    ws = nearest_workspace(n, pq, pr, c, q.device, ws)
+    vp = C.c_void_p
+    with torch.cuda.device(q.device):
+        check(lib().osvos_match_nearest(vp(q.data_ptr()), vp(rinv_q.data_ptr()), vp(r.data_ptr()), vp(rinv_r.data_ptr()), vp(label_r.data_ptr()),
+                                        vp(sim.data_ptr()), vp(idx.data_ptr()) if with_idx else None, vp(ws.data_ptr()), n, nr, pq, pr, c, _stream()),
+              "match_nearest")
+    return (sim, idx) if with_idx else sim
+
+
+class AppearanceMatcher(object):
+    """A second opinion on the fused logits from the trunk features themselves, on the device.
+
+    ``matcher.set_reference(x0, mask0)`` runs the annotated first frame ``x0`` [1,3,H,W] through ``net`` and keeps the int8 features of
+    trunk tensor ``layer`` with the cell labels of ``mask0`` (uint8 or bool [H,W], [1,H,W] or [1,1,H,W]) as the first-frame bank.  ONE
+    read-back checks that the bank holds both classes; if it does not, the matcher is inert -- it says so once and returns plain forwards.
+
+    ``matcher(x, prev_mask=None)`` runs ``net.forward_features(x)``, quantises the features, searches the bank, and returns the five logit
+    maps of the forward with the last one replaced by ``tta.fuse_views([fused, map], .., weights=[1, gain])``, map = cosine to the nearest
+    foreground feature minus cosine to the nearest background feature.  With ``previous=True`` the features of the previous call and
+    ``prev_mask`` (that frame's final mask [N,H,W] or [N,1,H,W]) form a second bank, and each class takes the larger of its two cosines.
+    ``gain == 0`` is ``net.forward`` under ``torch.no_grad()`` and nothing else.  The banks and workspaces stay on the device.
+
+    The defaults are starting values, NOT tuned on DAVIS."""
+
+    def __init__(self, net, layer=9, gain=4.0, previous=False):
+        check_match(layer, gain)
+        self.net, self.layer, self.gain, self.previous = net, int(layer), float(gain), bool(previous)
+        self.stride = stride_of(layer)
+        self.inert = False
+        self._bank = None            # (r [1,P,C], rinv_r [1,P], label [1,P]) of the first frame
+        self._last = None            # (q, rinv_q) of the previous call
+        self._ws = self._ws_prev = None
+
+    @property
+    def has_reference(self):
+        """True once set_reference has run (or when gain is 0 and there is nothing to build)"""
+        return self.gain == 0 or self._bank is not None
+
+    def _features(self, x):
+        outs, feat, _ = self.net.forward_features(x, self.layer)
+        n, h, w, c = (int(v) for v in feat.shape)
+        q, rinv = quantize(feat)
+        return outs, q.view(n, h * w, c), rinv.view(n, h * w), (h, w)
+
+    def set_reference(self, x0, mask0):
+        if self.gain == 0:
+            return self
+        if x0.dim() != 4 or x0.shape[0] != 1:
+            raise ValueError("set_reference takes ONE annotated frame [1,3,H,W], got %s" % (tuple(x0.shape),))
+        _, r, rinv_r, (h, w) = self._features(x0)
+        label = cell_labels(mask0, self.stride)
+        if tuple(label.shape) != (1, h, w):
+            raise ValueError("mask0 of %s does not belong to a frame of %s" % (tuple(mask0.shape), tuple(x0.shape)))
+        label = label.view(1, h * w)
+        n_fg, n_bg = (int(v) for v in torch.stack([(label == 1).sum(), (label == 0).sum()]).cpu().numpy())      # the one read-back
+        self.inert = n_fg == 0 or n_bg == 0
+        if self.inert:
+            print("AppearanceMatcher: the first frame gives %d foreground and %d background cells at layer %d (stride %d): no matching, plain forwards"
+                  % (n_fg, n_bg, self.layer, self.stride), file=sys.stderr)
+        self._bank, self._last = (r, rinv_r, label), None
+        return self
+
+    def __call__(self, x, prev_mask=None):
+        if self.gain == 0:
+            with torch.no_grad():
+                return self.net.forward(x)
+        if self._bank is None:
+            raise RuntimeError("AppearanceMatcher: set_reference(first frame, its mask) comes first")
+        if self.inert:
+            return self.net.forward_features(x, self.layer)[0]
+        outs, q, rinv_q, (h, w) = self._features(x)
+        n, p, c = (int(v) for v in q.shape)
+        r, rinv_r, label = self._bank
+        if int(r.shape[1]) != p:
+            raise ValueError("AppearanceMatcher: the frame's %d x %d feature grid is not the first frame's" % (h, w))
+        self._ws = nearest_workspace(n, p, p, c, q.device, self._ws)
+        sim = nearest(q, rinv_q, r, rinv_r, label, ws=self._ws)
+        if self.previous:
+            if prev_mask is not None and self._last is not None and self._last[0].shape == q.shape:
+                plabel = cell_labels(prev_mask, self.stride)
+                if tuple(plabel.shape) != (n, h, w):
+                    raise ValueError("prev_mask of %s does not belong to frames of %s" % (tuple(prev_mask.shape), tuple(x.shape)))
+                self._ws_prev = nearest_workspace(n, p, p, c, q.device, self._ws_prev)
+                sim = torch.maximum(sim, nearest(q, rinv_q, self._last[0], self._last[1], plabel.view(n, p), ws=self._ws_prev))
+            self._last = (q, rinv_q)
+        mp = (sim[:, 0] - sim[:, 1]).view(n, h, w)
+        fused = tta.fuse_views([outs[-1], mp], [False, False], (int(x.shape[2]), int(x.shape[3])), weights=[1.0, self.gain])
+        return list(outs[:4]) + [fused]

@@ -15,7 +15,7 @@ import os
 import torch
 import torch.nn as nn
 
-from ..autograd import NetRuntime, OSVOSNetFunction
+from ..autograd import NetRuntime, OSVOSNetFunction, net_forward_features
 from ..layers.osvos_layers import interp_surgery
 
 try:  # the path config is a top-level module in the reference (mypath.py); same here
@@ -72,6 +72,13 @@ class OSVOS(nn.Module):
         [N,1,H,W] (reference vgg_osvos.py:59-74)."""
         outs = OSVOSNetFunction.apply(self._runtime, x, *self.parameters())
         return list(outs)
+
+    def forward_features(self, x, layer=9):
+        """An inference forward that also hands out a trunk feature: ``(outs, feat, fmt)`` with ``outs`` the five logit maps of ``forward``
+        under ``torch.no_grad()`` bit for bit, ``feat`` the output of conv2_2 / conv3_3 / conv4_3 / conv5_3 (``layer`` 3, 6, 9 or 12; any
+        other value raises) as a view [N,h,w,C] of the forward's workspace, float32 or bfloat16, and ``fmt`` its storage format (0 fp32,
+        1 bf16: ``osvos_net_ws_format``).  Appearance matching reads it (osvos_pytorch_amd.match).  Not part of the reference's API."""
+        return net_forward_features(self._runtime, x, list(self.parameters()), layer)
 
     def set_precision(self, name):
         """'fp32x3' (default: fp32 tensors, fp32-grade results -- the wide 3x3 convolutions run on the bf16 matrix pipe with three-way split

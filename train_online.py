@@ -29,6 +29,12 @@ running on the MI355X-native OSVOS path.  Differences by design:
   * ``--snap-cell S``: superpixel snapping of every test frame's logit map, as in the OSVOS paper -- an integer grid-SLIC of cell S on the
     decoded frame and the mean of the logits over each superpixel, on the device (osvos_pytorch_amd.superpixels.SuperpixelSnapper), after
     --crf-iters and before --track-components; parameters --snap-compactness, --snap-iters (starting values, not tuned on DAVIS)
+  * ``--match-gain G``: appearance matching to the annotated first frame -- every test frame's trunk features (``--match-layer`` 3, 6, 9 or
+    12: conv2_2 .. conv5_3) are quantised to int8 and searched against the first frame's on the integer matrix pipe; G times (cosine to the
+    nearest foreground feature minus cosine to the nearest background feature) is added to the fused logits on the device
+    (osvos_pytorch_amd.match.AppearanceMatcher), in the test forward itself: before --adapt-steps uses it, before --crf-iters, --snap-cell
+    and --track-components.  ``--match-previous`` also searches the previous frame's features under its final mask.  Not with --tta-*.
+    Starting values, not tuned on DAVIS; with G = 0 nothing is built and not one byte changes
   * ``--lucid P``: lucid first-frame synthesis -- with probability P a training sample is not the flipped / rotated / scaled frame but a
     re-composition of it: the object cut out, the hole inpainted once per sequence, object and background moved by affines of their own,
     re-lit and composited again on the device (osvos_pytorch_amd.lucid.LucidDream); parameters --lucid-grow, --lucid-smooth, --lucid-shift,
@@ -349,6 +355,31 @@ def make_snap(args):
     return SuperpixelSnapper(**args.snap) if args.snap else None
 
 
+def check_match_args(args):
+    """the --match-* rules; SystemExit on values the matching does not take -- checked before any GPU work.  Sets args.match to the keyword
+    arguments of match.AppearanceMatcher, or None with --match-gain 0"""
+    from osvos_pytorch_amd import match
+    args.match = None
+    try:
+        match.check_match(args.match_layer, args.match_gain)
+    except ValueError as e:
+        raise SystemExit('--match-*: %s' % e)
+    if not args.match_gain:
+        return
+    if args.tta:
+        raise SystemExit('--match-gain is not run together with --tta-scales / --tta-flip: matching under test-time augmentation is not built')
+    if not (args.device_augment or (args.multi_object and args.synthetic)):
+        raise SystemExit('--match-gain needs --device-augment (or --multi-object --synthetic): the first-frame bank is made on the device input pipeline')
+    if args.match_previous and args.adapt_steps:
+        raise SystemExit('--match-previous is not run together with --adapt-steps: the adapter forwards every frame twice')
+    args.match = dict(layer=args.match_layer, gain=args.match_gain, previous=args.match_previous)
+
+
+def make_match(args, net):
+    from osvos_pytorch_amd.match import AppearanceMatcher
+    return AppearanceMatcher(net, **args.match) if args.match else None
+
+
 def check_lucid_args(args):
     """the --lucid* rules; SystemExit on values the synthesis does not take -- checked before any GPU work.  Sets args.lucid to the keyword
     arguments of DeviceTrainFrame's lucid (those of lucid.LucidDream, and p), or None with --lucid 0"""
@@ -437,15 +468,23 @@ def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, n
         if args.test_precision:
             net.set_precision(args.test_precision)
         tta = make_tta(args, net)
+        matcher = make_match(args, net)                 # one matcher per object's network: its own first-frame bank
+        match_prev = None
         with torch.no_grad():
+            if matcher is not None:
+                matcher.set_reference(augment_frame(frames[0], None, flip=False, rot=None)[0][None], gts[0] == k)
             for f, img in enumerate(frames):
                 if tta is not None:
                     logits[k - 1, f].copy_(tta(img)[0, 0])
+                elif matcher is not None:
+                    out = matcher(augment_frame(img, None, flip=False, rot=None)[0][None], match_prev)[-1]
+                    logits[k - 1, f].copy_(out[0, 0])
+                    match_prev = out > 0 if matcher.previous else None
                 else:
                     logits[k - 1, f].copy_(net.forward(augment_frame(img, None, flip=False, rot=None)[0][None])[-1][0, 0])
         torch.cuda.synchronize()
         test_time += timeit.default_timer() - start_time
-        del net, optimizer, trainloader, tta
+        del net, optimizer, trainloader, tta, matcher
 
     save_dir_res = os.path.join(save_dir, 'Results', seq_name)
     os.makedirs(save_dir_res, exist_ok=True)
@@ -566,6 +605,17 @@ def parse_args(argv=None):
                          'the objects.  The default parameters are starting values, not tuned on DAVIS')
     ap.add_argument('--snap-compactness', type=int, default=10, help='--snap-cell: weight of the pixel distance against the colour distance, 0..64')
     ap.add_argument('--snap-iters', type=int, default=5, help='--snap-cell: assign / update steps, 0..16 (0: the grid cells themselves)')
+    ap.add_argument('--match-gain', type=float, default=0.0, metavar='G',
+                    help='appearance matching to the first frame (0 = off): the trunk features of every test frame are quantised to int8 and '
+                         'searched against those of the annotated first frame on the device; G times (cosine to the nearest foreground feature '
+                         'minus cosine to the nearest background feature) is added to the fused logits of the test forward, before '
+                         '--adapt-steps uses them and before --crf-iters, --snap-cell and --track-components.  Needs --device-augment, or '
+                         '--multi-object --synthetic; not with --tta-*.  With --multi-object one matcher per object\'s network.  The default '
+                         'parameters are starting values, not tuned on DAVIS')
+    ap.add_argument('--match-layer', type=int, default=9, help='--match-gain: the trunk tensor matched -- 3, 6, 9 or 12 (conv2_2, conv3_3, conv4_3, conv5_3)')
+    ap.add_argument('--match-previous', action='store_true',
+                    help='--match-gain: also search the previous frame\'s features under its final mask; each class takes the larger cosine.  '
+                         'Not with --adapt-steps')
     ap.add_argument('--lucid', dest='lucid_p', type=float, default=0.0, metavar='P',
                     help='lucid first-frame synthesis (0 = off): with probability P (0..1) a training sample is a re-composition of the '
                          'annotated frame -- the object cut out, the hole inpainted once per sequence, object and background moved by affines '
@@ -596,6 +646,7 @@ def parse_args(argv=None):
     check_flow_args(args)
     check_snap_args(args)
     check_lucid_args(args)
+    check_match_args(args)
     if args.tta and not (args.device_augment or (args.multi_object and args.synthetic)):
         raise SystemExit('--tta-scales / --tta-flip need --device-augment (or --multi-object --synthetic): test-time augmentation makes its views '
                          'from the decoded uint8 frame on the device')
@@ -644,6 +695,10 @@ def main():
         crf = make_crf(args)
         mc = make_flow(args)
         snap = make_snap(args)
+        matcher = make_match(args, net)
+        match_prev = [None]                  # --match-previous: the previous frame's final mask
+        if matcher is not None and adapter is not None:
+            adapter.forward = lambda image: matcher(image, match_prev[0])      # both of the adapter's forwards are matched ones
         prev_mask = None                     # --adapt-steps: the previous frame's final mask (frame 0: its annotation)
         with torch.no_grad():
             for sample in testloader:
@@ -656,10 +711,16 @@ def main():
                         prev_mask = mc.warp(prev_mask)
                     if tracker is not None:
                         tracker.seed = mc.warp(tracker.seed)
+                if matcher is not None and not matcher.has_reference:
+                    if 'gt' not in sample:
+                        raise SystemExit('--match-gain: sequence %s has no first annotation to build the bank from' % seq_name)
+                    matcher.set_reference(sample['image'].to(device), sample['gt'].to(device)[:, 0] > 0.5)
                 if tta is not None:
                     fused = tta(sample['frame_u8'])
                 elif adapter is not None and prev_mask is not None:
                     fused = adapter(sample['image'].to(device), prev_mask)      # (turns gradients on for its own training steps)
+                elif matcher is not None:
+                    fused = matcher(sample['image'].to(device), match_prev[0])[-1]
                 else:
                     outputs = net.forward(sample['image'].to(device))
                     fused = outputs[-1]
@@ -677,6 +738,8 @@ def main():
                     if prev_mask is None and 'gt' not in sample:
                         raise SystemExit('--adapt-steps: sequence %s has no first annotation to start from' % seq_name)
                     prev_mask = sample['gt'].to(device) > 0.5 if prev_mask is None else fused > 0
+                if matcher is not None and matcher.previous:
+                    match_prev[0] = fused > 0
                 # sigmoid + scipy<=1.1 imsave byte scaling on the device, PNG written by osvos_pytorch_amd.results (reference :181-187)
                 save_masks(fused, [os.path.join(save_dir_res, os.path.basename(fname[jj]) + '.png') for jj in range(int(fused.size()[0]))])
                 if 'gt' in sample:
