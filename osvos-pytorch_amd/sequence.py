@@ -1,0 +1,182 @@
+"""The test phase of train_online.py: everything between "the network is fine-tuned" and "the masks are scored", for both recipes.
+
+The stages arrive built (results.ComponentTracker as a factory ``first_mask -> tracker``, because its seed is the first annotation), or as
+None for an option that is off.  THE ORDER OF THE STAGES LIVES HERE, and tests/test_sequence_cpu.py asserts it with recording stand-ins:
+
+  ``FrameForward``          one frame -> fused logits: tta > adapter (once a previous mask exists) > matcher > net.forward
+  ``post_chain``            crf -> snap -> tracker on a logit stack and its decoded frames (one frame or a chunk of frames)
+  ``SingleObjectSequence``  per frame: motion compensation of what is carried over, matcher reference, FrameForward, post_chain, then the
+                            state of the next frame (SingleObjectSequence.step)
+  ``multi_object_sequence`` per object: fine-tuning (the caller's) and FrameForward over every frame into a [K,F,H,W] stack; then post_chain
+                            stage by stage over chunks of frames; ``score_objects`` merges, scores and writes
+
+The two recipes differ in ONE rule.  The mask that --match-previous hands to the next frame (FrameForward.remember) is the FINAL mask in
+the single-object recipe -- after crf, snap and tracker -- and the RAW output of the matched forward in the multi-object recipe, whose post
+chain runs only after every forward of every object is done."""
+import timeit
+
+import torch
+
+from .results import MultiObjectEvaluator, merge_objects, save_label_maps
+
+
+class FrameForward(object):
+    """``forward(frame_u8, image, prev_mask)`` -> the fused logits [1,1,H,W] of one frame, from the first of: ``tta(frame_u8)``;
+    ``adapter(image, prev_mask)`` once there is a previous mask (so never on frame 0); ``matcher(image, match_prev)[-1]``;
+    ``net.forward(image)[-1]``.  With an adapter and a matcher both of the adapter's plain forwards are matched ones that read the current
+    ``match_prev``.  One per network: the multi-object recipe builds one per object, without adapter."""
+
+    def __init__(self, net, tta=None, adapter=None, matcher=None):
+        self.net, self.tta, self.adapter, self.matcher = net, tta, adapter, matcher
+        self.match_prev = None               # --match-previous: the previous frame's mask (which one: see the module docstring)
+        if matcher is not None and adapter is not None:
+            adapter.forward = lambda image: matcher(image, self.match_prev)
+
+    @property
+    def needs_reference(self):
+        return self.matcher is not None and not self.matcher.has_reference
+
+    @property
+    def needs_image(self):
+        """False under test-time augmentation, which makes its own views from frame_u8"""
+        return self.tta is None
+
+    def set_reference(self, image, mask):
+        if self.needs_reference:
+            self.matcher.set_reference(image, mask)
+
+    def __call__(self, frame_u8, image, prev_mask=None):
+        if self.tta is not None:
+            return self.tta(frame_u8)
+        if self.adapter is not None and prev_mask is not None:
+            return self.adapter(image, prev_mask)           # (turns gradients on for its own training steps)
+        if self.matcher is not None:
+            return self.matcher(image, self.match_prev)[-1]
+        return self.net.forward(image)[-1]
+
+    def remember(self, logits):
+        if self.matcher is not None and self.matcher.previous:
+            self.match_prev = logits > 0
+
+
+def post_chain(fused, frames_u8, crf=None, snap=None, tracker=None, labels=None):
+    """crf -> snap -> tracker on ``fused`` ([1,1,H,W] with the frame [H,W,3], or [n,H,W] with n consecutive frames [n,H,W,3]); a stage that
+    is None is left out.  ``labels``: ``snap.labels(frames_u8)`` made by the caller, for several objects over the same frames."""
+    if crf is not None:
+        fused = crf(fused, frames_u8)
+    if snap is not None:
+        fused = snap(fused, frames_u8) if labels is None else snap(fused, labels=labels)
+    if tracker is not None:
+        fused = tracker(fused)
+    return fused
+
+
+class SingleObjectSequence(object):
+    """Iterating yields ``(fname, fused, gt or None)`` for every sample of ``loader``, in order; the caller writes and scores.  ``prev_mask``
+    (--adapt-steps: the previous frame's final mask; for frame 1 the annotation of frame 0), ``tracker`` and ``forward.match_prev`` are the
+    state carried from frame to frame; ``flow`` (flow.MotionCompensator) moves the first two to where the object is now."""
+
+    def __init__(self, loader, forward, device, seq_name, flow=None, crf=None, snap=None, make_tracker=None):
+        self.loader, self.forward, self.device, self.seq_name = loader, forward, device, seq_name
+        self.flow, self.crf, self.snap, self.make_tracker = flow, crf, snap, make_tracker
+        self.prev_mask = self.tracker = None
+
+    def __iter__(self):
+        for sample in self.loader:
+            yield self.step(sample)
+
+    @torch.no_grad()
+    def step(self, sample):
+        forward, seq_name = self.forward, self.seq_name
+        frame_u8, gt = sample.get('frame_u8'), sample.get('gt')
+        image = sample['image'].to(self.device) if 'image' in sample else None
+        if self.flow is not None:                # the field from the previous frame to this one moves what is carried over
+            if frame_u8.dim() != 3:
+                raise SystemExit('--flow-search: the test loader delivered %d frames in one batch; it takes one' % int(frame_u8.shape[0]))
+            self.flow.update(frame_u8)
+            if self.prev_mask is not None:
+                self.prev_mask = self.flow.warp(self.prev_mask)
+            if self.tracker is not None:
+                self.tracker.seed = self.flow.warp(self.tracker.seed)
+        if forward.needs_reference:
+            if gt is None:
+                raise SystemExit('--match-gain: sequence %s has no first annotation to build the bank from' % seq_name)
+            forward.set_reference(image, gt.to(self.device)[:, 0] > 0.5)
+        fused = forward(frame_u8, image, self.prev_mask)
+        fused = post_chain(fused, frame_u8, self.crf, self.snap)
+        if self.make_tracker is not None:
+            if self.tracker is None:             # (built here, after crf and snap of frame 0, as it always was)
+                if gt is None:
+                    raise SystemExit('--track-components: sequence %s has no first annotation to seed the tracker' % seq_name)
+                self.tracker = self.make_tracker(gt.to(self.device)[0, 0] > 0.5)
+            fused = self.tracker(fused)
+        if forward.adapter is not None:
+            if self.prev_mask is None and gt is None:
+                raise SystemExit('--adapt-steps: sequence %s has no first annotation to start from' % seq_name)
+            self.prev_mask = gt.to(self.device) > 0.5 if self.prev_mask is None else fused > 0
+        forward.remember(fused)                  # the FINAL mask
+        return sample['fname'], fused, gt
+
+
+def multi_object_sequence(frames, gts, K, fine_tuned, forward_of, image_of, crf=None, snap=None, make_tracker=None, chunk=64):
+    """The DAVIS 2017 recipe on the decoded frames [H,W,3] and the indexed annotations ``gts`` (gts[0] holds ids 1..K) of one sequence.
+
+    Per object k: ``fine_tuned(k)`` -> its network, ``forward_of(net)`` -> its FrameForward, the matcher's reference from frame 0 under
+    ``gts[0] == k``, then every frame (``image_of(frame)``: the network's input) into row k - 1 of the logit stack; the RAW output is what
+    --match-previous remembers.  Then, over chunks of ``chunk`` consecutive frames, stage by stage as post_chain orders them: crf for every
+    object; one superpixel labelling per chunk, shared by the objects; one tracker per object, seeded with ``gts[0] == k``, walking its
+    chunks in order.  Everything is enqueued; nothing is read back.  -> (logits [K,F,H,W], trackers, the timer value the test phase would
+    have started at had its parts run back to back)."""
+    h, w = int(frames[0].shape[0]), int(frames[0].shape[1])
+    logits = torch.empty((K, len(frames), h, w), device=frames[0].device, dtype=torch.float32)
+    test_time = 0.0
+    for k in range(1, K + 1):
+        net = fine_tuned(k)
+        start_time = timeit.default_timer()
+        forward = forward_of(net)                # one matcher per object's network: its own first-frame bank
+        with torch.no_grad():
+            if forward.needs_reference:
+                forward.set_reference(image_of(frames[0]), gts[0] == k)
+            for f, img in enumerate(frames):
+                out = forward(img, image_of(img) if forward.needs_image else None)
+                logits[k - 1, f].copy_(out[0, 0])
+                forward.remember(out)            # the RAW output
+        if logits.is_cuda:
+            torch.cuda.synchronize()
+        test_time += timeit.default_timer() - start_time
+        del net, forward
+
+    print('Testing Network')
+    started = timeit.default_timer() - test_time
+    chunks = [slice(s0, s0 + chunk) for s0 in range(0, len(frames), chunk)]
+    if crf is not None:
+        for c in chunks:
+            stacked = torch.stack(frames[c])
+            for k in range(K):
+                logits[k, c] = post_chain(logits[k, c], stacked, crf=crf)
+    if snap is not None:
+        for c in chunks:
+            spx = snap.labels(torch.stack(frames[c]))
+            for k in range(K):
+                logits[k, c] = post_chain(logits[k, c], None, snap=snap, labels=spx)
+    trackers = []
+    for k in range(K if make_tracker is not None else 0):
+        trackers.append(make_tracker(gts[0] == k + 1))
+        for c in chunks:
+            logits[k, c] = post_chain(logits[k, c], None, tracker=trackers[k])
+    return logits, trackers, started
+
+
+def score_objects(logits, gts, paths):
+    """merge the K logit stacks into label maps, score the annotated frames per object, write the indexed PNGs -> the evaluator's summary;
+    one read-back for the PNGs, one for the counts"""
+    K = int(logits.shape[0])
+    labels = merge_objects(logits)
+    evaluator = MultiObjectEvaluator(K)
+    scored = [f for f, g in enumerate(gts) if g is not None]
+    step = max(1, min(64, 65535 // K))
+    for s0 in range(0, len(scored), step):
+        at = scored[s0:s0 + step]
+        evaluator.add(labels[at], torch.stack([gts[f] for f in at]))      # (enqueued: nothing is read back here)
+    save_label_maps(labels, paths)
+    return evaluator.summary()

@@ -7,17 +7,15 @@ test_gpu_ops.test_cbce_loss_and_grad (rtol 1e-5 on the loss, rtol 2e-5 / atol 2e
 +0.0 bit for bit.  Outputs are pre-filled with garbage; the osvos_* calls go through _lib."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import adapt_cases as ac
+import script_runner
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GARBAGE = 7.25e33
 VOID, PER_IMAGE, ZEROED = 4, 1, 2          # OSVOS_CBCE_VOID, OSVOS_CBCE_PER_IMAGE, OSVOS_CBCE_SCRATCH_ZEROED
 vp = C.c_void_p
@@ -472,9 +470,7 @@ def test_adapter_around_the_real_network_with_two_steps_trains():
 
 
 def _run_script(tmp_path, extra):
-    env = dict(os.environ, OSVOS_SAVE_ROOT=str(tmp_path), OSVOS_MODELS_DIR=str(tmp_path), PYTHONPATH=REPO, SEQ_NAME="blackswan")
-    return subprocess.run([sys.executable, "train_online.py", "--synthetic", "--device-augment", "--synthetic-frames", "3", "--height", "64", "--width", "96",
-                           "--epochs", "5"] + extra, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
+    return script_runner.train_online(tmp_path, "--device-augment", "--synthetic-frames", "3", *extra, height=64, width=96)
 
 
 def test_train_online_with_online_adaptation(tmp_path):

@@ -2,19 +2,16 @@
 against the committed fixture tests/golden/components.npz, every comparison exact (integers and bytes); results.components,
 results.filter_components, results.ComponentTracker; train_online.py --track-components."""
 import ctypes as C
-import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import component_cases as cc
+import script_runner
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = cc.load()
 BY_NAME = {c["name"]: c for c in CASES}
 LOGITS = {c["name"]: cc.logits(c) for c in CASES}          # made once, shared, never written to
@@ -301,9 +298,7 @@ def test_argument_errors_are_errors_not_answers():
 
 @pytest.mark.parametrize("multi", [False, True], ids=["single", "multi_object"])
 def test_train_online_track_components(tmp_path, multi):
-    env = dict(os.environ, OSVOS_SAVE_ROOT=str(tmp_path), OSVOS_MODELS_DIR=str(tmp_path), PYTHONPATH=REPO, SEQ_NAME="blackswan")
-    cmd = [sys.executable, "train_online.py", "--synthetic", "--epochs", "10", "--height", "48", "--width", "64", "--track-components", "8"]
-    r = subprocess.run(cmd + (["--multi-object"] if multi else []), cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
+    r = script_runner.train_online(tmp_path, "--track-components", "8", *(["--multi-object"] if multi else []), epochs=10, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = r.stdout.splitlines()
     if multi:

@@ -7,18 +7,15 @@ upper bound on a pixel's summed kernel weights -- 9e-6 .. 1.3e-4 for the cases h
 Decisions: out > 0 equals reference > 0 wherever |reference| exceeds the bound used, and the pixels excluded that way are at most 0.5 % of a
 case (test_crf_cpu.py shows the reference alone meets that cap).  Outputs and workspaces are pre-filled with garbage."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import crf_cases as cc
+import script_runner
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GARBAGE = 7.25e33
 
 
@@ -213,15 +210,8 @@ def test_wrappers_match_the_direct_call():
 
 
 def _train_online(tmp, *extra):
-    env = dict(os.environ, OSVOS_SAVE_ROOT=str(tmp), OSVOS_MODELS_DIR=str(tmp), PYTHONPATH=REPO, SEQ_NAME="blackswan")
-    os.makedirs(str(tmp), exist_ok=True)
-    r = subprocess.run([sys.executable, "train_online.py", "--synthetic", "--epochs", "5", "--height", "48", "--width", "64"] + list(extra),
-                       cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    png = os.path.join(str(tmp), "Results", "blackswan", "00000.png")
-    assert os.path.exists(png)
-    with open(png, "rb") as f:
-        return r.stdout, f.read()
+    r = script_runner.train_online(tmp, *extra, frames=1)
+    return r.stdout, r.masks[0]
 
 
 def test_train_online_with_refinement(tmp_path):

@@ -3,18 +3,15 @@ rule in tests/flow_cases.py, bit for bit (the rule is integer arithmetic: every 
 exact properties, the wrappers of osvos_pytorch_amd.flow, the tracking scenario through results.ComponentTracker, and train_online.py
 --flow-search.  vec, cost, out and the workspace are pre-filled with garbage before every call."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import flow_cases as fc
+import script_runner
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GARBAGE_INT = 0x5a5a5a5a
 GARBAGE_BYTE = 0xa5
 GUARD = 256
@@ -334,18 +331,8 @@ def test_tracking_scenario_through_the_tracker():
 
 
 def _train_online(tmp, *extra):
-    env = dict(os.environ, OSVOS_SAVE_ROOT=str(tmp), OSVOS_MODELS_DIR=str(tmp), PYTHONPATH=REPO, SEQ_NAME="blackswan")
-    os.makedirs(str(tmp), exist_ok=True)
-    r = subprocess.run([sys.executable, "train_online.py", "--synthetic", "--epochs", "5", "--height", "48", "--width", "64", "--device-augment",
-                        "--synthetic-frames", "3"] + list(extra), cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    masks = []
-    for f in range(3):
-        png = os.path.join(str(tmp), "Results", "blackswan", "%05d.png" % f)
-        assert os.path.exists(png), png
-        with open(png, "rb") as fh:
-            masks.append(fh.read())
-    return r.stdout, masks
+    r = script_runner.train_online(tmp, "--device-augment", "--synthetic-frames", "3", *extra, frames=3)
+    return r.stdout, r.masks
 
 
 def test_train_online_with_motion_compensation(tmp_path):

@@ -3,19 +3,16 @@ restatement of the rule in tests/lucid_cases.py, bit for bit (the rule is intege
 tolerance), the refusals, the wrappers of osvos_pytorch_amd.lucid, the scenario through LucidDream, and train_online.py --lucid.  Outputs
 and the workspace are pre-filled with garbage before every call."""
 import ctypes as C
-import os
 import random
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import lucid_cases as lc
+import script_runner
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GARBAGE_BYTE = 0xa5
 GUARD = 256
 
@@ -300,20 +297,12 @@ def test_scenario_through_lucid_dream():
 
 
 def _run_script(tmp, *args):
-    env = dict(os.environ, OSVOS_SAVE_ROOT=str(tmp), OSVOS_MODELS_DIR=str(tmp), PYTHONPATH=REPO, SEQ_NAME="blackswan")
-    os.makedirs(str(tmp), exist_ok=True)
-    r = subprocess.run([sys.executable, "train_online.py", "--synthetic", "--epochs", "5", "--height", "48", "--width", "64"] + list(args),
-                       cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r.stdout
+    return script_runner.train_online(tmp, *args).stdout
 
 
 def _train_online(tmp, *extra):
-    out = _run_script(tmp, "--device-augment", *extra)
-    png = os.path.join(str(tmp), "Results", "blackswan", "00000.png")
-    assert os.path.exists(png), png
-    with open(png, "rb") as fh:
-        return out, fh.read()
+    r = script_runner.train_online(tmp, "--device-augment", *extra, frames=1)
+    return r.stdout, r.masks[0]
 
 
 def _losses(out):

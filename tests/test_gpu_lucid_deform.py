@@ -6,8 +6,6 @@ before every call, and a guard region after the workspace must keep it."""
 import ctypes as C
 import os
 import random
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,9 +13,9 @@ import torch
 
 import lucid_cases as lc
 import lucid_deform_cases as ld
+import script_runner
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GARBAGE_BYTE = 0xa5
 GUARD = 256
 
@@ -311,12 +309,7 @@ def test_lucid_dream_with_the_options():
 
 
 def _run_script(tmp, *args):
-    env = dict(os.environ, OSVOS_SAVE_ROOT=str(tmp), OSVOS_MODELS_DIR=str(tmp), PYTHONPATH=REPO, SEQ_NAME="blackswan")
-    os.makedirs(str(tmp), exist_ok=True)
-    r = subprocess.run([sys.executable, "train_online.py", "--synthetic", "--epochs", "5", "--height", "48", "--width", "64", "--device-augment"] + list(args),
-                       cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r.stdout
+    return script_runner.train_online(tmp, "--device-augment", *args).stdout
 
 
 def _png(tmp):

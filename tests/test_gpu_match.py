@@ -4,17 +4,15 @@ equality, there is no tolerance), OSVOS.forward_features, the wrappers of osvos_
 and train_online.py --match-gain.  Outputs and workspaces are pre-filled with garbage before every call; a guard band after ws is checked."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import match_cases as mc
+import script_runner
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GARBAGE_BYTE = 0xa5
 GARBAGE_INT = 0x5a5a5a5a
 GUARD = 256
@@ -386,23 +384,12 @@ def test_scenario_on_the_device():
 
 
 def _run_script(tmp, *args):
-    env = dict(os.environ, OSVOS_SAVE_ROOT=str(tmp), OSVOS_MODELS_DIR=str(tmp), PYTHONPATH=REPO, SEQ_NAME="blackswan")
-    os.makedirs(str(tmp), exist_ok=True)
-    r = subprocess.run([sys.executable, "train_online.py", "--synthetic", "--epochs", "5", "--height", "48", "--width", "64"] + list(args),
-                       cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r.stdout
+    return script_runner.train_online(tmp, *args).stdout
 
 
 def _train_online(tmp, *extra):
-    out = _run_script(tmp, "--device-augment", "--synthetic-frames", "3", *extra)
-    masks = []
-    for f in range(3):
-        png = os.path.join(str(tmp), "Results", "blackswan", "%05d.png" % f)
-        assert os.path.exists(png), png
-        with open(png, "rb") as fh:
-            masks.append(fh.read())
-    return out, masks
+    r = script_runner.train_online(tmp, "--device-augment", "--synthetic-frames", "3", *extra, frames=3)
+    return r.stdout, r.masks
 
 
 def test_train_online_with_matching(tmp_path):

@@ -4,17 +4,15 @@ entry point osvos_mask_jf_counts on the object's two binary maps; results.MultiO
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import object_cases as oc
+import script_runner
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = oc.load()
 IDS = [c["name"] for c in CASES]
 
@@ -239,9 +237,7 @@ def test_multi_object_evaluator_matches_the_single_object_functions_without_touc
 
 def test_train_online_multi_object(tmp_path):
     from PIL import Image
-    env = dict(os.environ, OSVOS_SAVE_ROOT=str(tmp_path), OSVOS_MODELS_DIR=str(tmp_path), PYTHONPATH=REPO, SEQ_NAME="blackswan")
-    r = subprocess.run([sys.executable, "train_online.py", "--synthetic", "--multi-object", "--epochs", "10", "--height", "48", "--width", "64"],
-                       cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
+    r = script_runner.train_online(tmp_path, "--multi-object", epochs=10, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = r.stdout.splitlines()
     num = r"(-?\d+\.\d{4})"

@@ -4,17 +4,15 @@ is no tolerance), their exact properties, the wrappers of osvos_pytorch_amd.supe
 and train_online.py --snap-cell.  labels, centres, out and both workspaces are pre-filled with garbage before every call."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import superpixel_cases as sc
+import script_runner
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GARBAGE_INT = 0x5a5a5a5a
 GARBAGE_BYTE = 0xa5
 GUARD = 256
@@ -333,23 +331,12 @@ def test_snapping_scenario_on_the_device():
 
 
 def _run_script(tmp, *args):
-    env = dict(os.environ, OSVOS_SAVE_ROOT=str(tmp), OSVOS_MODELS_DIR=str(tmp), PYTHONPATH=REPO, SEQ_NAME="blackswan")
-    os.makedirs(str(tmp), exist_ok=True)
-    r = subprocess.run([sys.executable, "train_online.py", "--synthetic", "--epochs", "5", "--height", "48", "--width", "64"] + list(args),
-                       cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r.stdout
+    return script_runner.train_online(tmp, *args).stdout
 
 
 def _train_online(tmp, *extra):
-    out = _run_script(tmp, "--device-augment", "--synthetic-frames", "3", *extra)
-    masks = []
-    for f in range(3):
-        png = os.path.join(str(tmp), "Results", "blackswan", "%05d.png" % f)
-        assert os.path.exists(png), png
-        with open(png, "rb") as fh:
-            masks.append(fh.read())
-    return out, masks
+    r = script_runner.train_online(tmp, "--device-augment", "--synthetic-frames", "3", *extra, frames=3)
+    return r.stdout, r.masks
 
 
 def test_train_online_with_snapping(tmp_path):

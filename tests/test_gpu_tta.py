@@ -10,8 +10,6 @@ Fuse: |diff| <= (8 + 2 V) * 2^-23 * M with M the case's largest |logit|: twice a
 accumulated view.  Outputs are pre-filled with garbage; the osvos_* calls go through _lib."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,9 +17,9 @@ import torch
 
 import tta_cases as tc
 import trained_fixture as tf
+import script_runner
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GARBAGE = 7.25e33
 SIZE_IDS = ["%dx%dx%d" % s for s in tc.FRAME_SIZES]
 
@@ -248,9 +246,7 @@ def test_test_time_augment_around_the_real_network(trained_net):
 
 
 def test_train_online_with_test_time_augmentation(tmp_path):
-    env = dict(os.environ, OSVOS_SAVE_ROOT=str(tmp_path), OSVOS_MODELS_DIR=str(tmp_path), PYTHONPATH=REPO, SEQ_NAME="blackswan")
-    r = subprocess.run([sys.executable, "train_online.py", "--synthetic", "--device-augment", "--epochs", "5", "--height", "48", "--width", "64",
-                        "--tta-scales", "0.75,1,1.25", "--tta-flip"], cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
+    r = script_runner.train_online(tmp_path, "--device-augment", "--tta-scales", "0.75,1,1.25", "--tta-flip")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "Online training time" in r.stdout and "J&F on blackswan:" in r.stdout, r.stdout[-2000:]
     assert os.path.exists(os.path.join(str(tmp_path), "Results", "blackswan", "00000.png"))
@@ -258,9 +254,7 @@ def test_train_online_with_test_time_augmentation(tmp_path):
 
 def test_train_online_multi_object_with_test_time_augmentation(tmp_path):
     """the --multi-object loop takes tta(frame) per object network: two objects, mirrored views, merged label map, J and F per object"""
-    env = dict(os.environ, OSVOS_SAVE_ROOT=str(tmp_path), OSVOS_MODELS_DIR=str(tmp_path), PYTHONPATH=REPO, SEQ_NAME="blackswan")
-    r = subprocess.run([sys.executable, "train_online.py", "--multi-object", "--synthetic", "--epochs", "5", "--height", "48", "--width", "64",
-                        "--tta-flip"], cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
+    r = script_runner.train_online(tmp_path, "--multi-object", "--tta-flip")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "J&F on blackswan (2 objects):" in r.stdout and "J&F on blackswan object 2:" in r.stdout, r.stdout[-2000:]
     assert os.path.exists(os.path.join(str(tmp_path), "Results", "blackswan", "00000.png"))

@@ -4,6 +4,7 @@ must leave the list unchanged: kernel names carry the template arguments, so an 
 
     rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python tools/launch_list.py run --precision fp32x3 [--repo OTHER_CHECKOUT]
     python tools/launch_list.py report DIR > list.txt        # one line per launch, in dispatch order: kernel | grid | workgroup | LDS bytes
+    python tools/launch_list.py report DIR --after sgd       # ... of any traced program, from the first launch whose kernel name holds "sgd" on
 
 `run` does ONE forward + loss + backward of the network at 1 x 480 x 854 after the packs are written (no warm-up pass: every launch counts)."""
 import argparse
@@ -39,7 +40,10 @@ def report(args):
             rows.append((int(r["dispatch_id"]), r["kernel_name"], "x".join(r["grid_size_" + a] for a in "xyz"),
                          "x".join(r["workgroup_size_" + a] for a in "xyz"), r["lds_block_size"]))
     assert rows, "no kernel trace under " + args.dir
-    for _, name, grid, wg, lds in sorted(rows):
+    rows.sort()
+    if args.after:
+        rows = rows[min(i for i, r in enumerate(rows) if args.after in r[1]) + 1:]
+    for _, name, grid, wg, lds in rows:
         print("%s | %s | %s | %s" % (name, grid, wg, lds))
 
 
@@ -53,5 +57,6 @@ if __name__ == "__main__":
     r.add_argument("--repo", default=None, help="the checkout whose package runs (default: this one)")
     p = sub.add_parser("report")
     p.add_argument("dir")
+    p.add_argument("--after", default="", help="leave out everything up to and including the first launch whose kernel name contains this")
     a = ap.parse_args()
     run(a) if a.cmd == "run" else report(a)

@@ -20,20 +20,17 @@ running on the MI355X-native OSVOS path.  Differences by design:
     interleave the annotated first frame with the frame itself, trained against targets made on the device from the network's own confident
     output and the previous frame's mask, the rest void (osvos_pytorch_amd.adapt.OnlineAdapter)
   * ``--crf-iters N``: edge-aware refinement of every test frame's logit map against the decoded frame -- N mean-field steps of a local
-    dense CRF on the device (osvos_pytorch_amd.refine.CrfRefiner), after the forward / test-time augmentation / adapter and before
-    --track-components; parameters --crf-radius, --crf-dilation, --crf-weights, --crf-thetas (starting values, not tuned on DAVIS)
+    dense CRF on the device (osvos_pytorch_amd.refine.CrfRefiner); parameters --crf-radius, --crf-dilation, --crf-weights, --crf-thetas (starting values, not tuned on DAVIS)
   * ``--flow-search R``: motion compensation of what the test loop carries from frame to frame -- a block-matching motion field from the
     previous decoded frame to the current one on the device (osvos_pytorch_amd.flow.MotionCompensator) moves the previous mask of
     --adapt-steps and the seed of --track-components to where the object is now; parameters --flow-block, --flow-step, --flow-penalty,
     --flow-median (starting values, not tuned on DAVIS)
   * ``--snap-cell S``: superpixel snapping of every test frame's logit map, as in the OSVOS paper -- an integer grid-SLIC of cell S on the
-    decoded frame and the mean of the logits over each superpixel, on the device (osvos_pytorch_amd.superpixels.SuperpixelSnapper), after
-    --crf-iters and before --track-components; parameters --snap-compactness, --snap-iters (starting values, not tuned on DAVIS)
+    decoded frame and the mean of the logits over each superpixel, on the device (osvos_pytorch_amd.superpixels.SuperpixelSnapper); parameters --snap-compactness, --snap-iters (starting values, not tuned on DAVIS)
   * ``--match-gain G``: appearance matching to the annotated first frame -- every test frame's trunk features (``--match-layer`` 3, 6, 9 or
     12: conv2_2 .. conv5_3) are quantised to int8 and searched against the first frame's on the integer matrix pipe; G times (cosine to the
     nearest foreground feature minus cosine to the nearest background feature) is added to the fused logits on the device
-    (osvos_pytorch_amd.match.AppearanceMatcher), in the test forward itself: before --adapt-steps uses it, before --crf-iters, --snap-cell
-    and --track-components.  ``--match-previous`` also searches the previous frame's features under its final mask.  Not with --tta-*.
+    (osvos_pytorch_amd.match.AppearanceMatcher), in the test forward itself.  ``--match-previous`` also searches the previous frame's features under its final mask.  Not with --tta-*.
     Starting values, not tuned on DAVIS; with G = 0 nothing is built and not one byte changes
   * ``--lucid P``: lucid first-frame synthesis -- with probability P a training sample is not the flipped / rotated / scaled frame but a
     re-composition of it: the object cut out, the hole inpainted once per sequence, object and background moved by affines of their own,
@@ -42,6 +39,9 @@ running on the MI355X-native OSVOS path.  Differences by design:
     bends the object by a smooth displacement field, ``--lucid-occlude P`` hides part of it behind an ellipse of displaced background,
     ``--lucid-band R`` labels the pixels within R of a label edge void (-1: no count, no loss, no gradient; not with --window-fused); all
     three are off by default, and off they change no draw and no byte
+  * the test phase -- which stage runs when, and what is carried from frame to frame -- is osvos_pytorch_amd.sequence for both recipes: the
+    order is stated there, once, and asserted by tests/test_sequence_cpu.py; this file parses the options, fine-tunes, builds the stages
+    (build_forward, build_post) and prints
   * launched under torchrun with N processes, rank r fine-tunes sequences r, r+N, ... of the
     comma-separated SEQ_NAME list (independent replicas: online training has no exchange step)
 """
@@ -66,7 +66,8 @@ import torch
 
 import networks.vgg_osvos as vo
 from layers.osvos_layers import sigmoid_np  # noqa: F401  (kept importable like the reference)
-from osvos_pytorch_amd.results import ComponentTracker, MultiObjectEvaluator, SequenceEvaluator, merge_objects, save_label_maps, save_masks
+from osvos_pytorch_amd import sequence
+from osvos_pytorch_amd.results import ComponentTracker, SequenceEvaluator, save_masks
 from mypath import Path
 from osvos_pytorch_amd.parallel import shard_indices
 from osvos_pytorch_amd.train_common import TrainLoop, init_distributed, make_sgd
@@ -222,6 +223,12 @@ def fine_tune(args, net, optimizer, trainloader, device, nEpochs, nAveGrad, seed
     print('Online training time: ' + str(timeit.default_timer() - start_time))
 
 
+def need_decoded_frames(args, what, why):
+    """the rule of every option that reads 'frame_u8': only the device input pipeline and the synthetic multi-object recipe deliver it"""
+    if not (args.device_augment or (args.multi_object and args.synthetic)):
+        raise SystemExit('%s --device-augment (or --multi-object --synthetic): %s' % (what, why))
+
+
 def check_adapt_args(args):
     """the --adapt-* / --synthetic-frames rules; SystemExit on a combination the script does not run -- checked before any GPU work"""
     if args.synthetic_frames < 1:
@@ -249,16 +256,6 @@ def check_adapt_args(args):
         raise SystemExit('--adapt-lr takes a learning rate > 0, got %r' % args.adapt_lr)
 
 
-def make_adapter(args, net, trainloader):
-    """the online adapter of --adapt-steps on a FRESH optimizer (no momentum carried over from the first-frame fine-tuning), or None"""
-    if not args.adapt_steps:
-        return None
-    from osvos_pytorch_amd.adapt import OnlineAdapter, first_frame_source
-    optimizer = make_sgd(net, 'online', lr=args.adapt_lr) if args.adapt_lr is not None else make_sgd(net, 'online')
-    return OnlineAdapter(net, optimizer, first_frame_source(trainloader), steps=args.adapt_steps, mix=args.adapt_mix, weight=args.adapt_weight,
-                         prob=args.adapt_prob, erosion=args.adapt_erosion, distance=args.adapt_distance)
-
-
 def tta_scales(args):
     """the scales of --tta-scales / --tta-flip (() = test-time augmentation off); SystemExit on a bad list -- checked before any GPU work"""
     from osvos_pytorch_amd import tta
@@ -271,11 +268,6 @@ def tta_scales(args):
     except ValueError as e:
         raise SystemExit('--tta-scales: %s' % e)
     return scales
-
-
-def make_tta(args, net):
-    from osvos_pytorch_amd.tta import TestTimeAugment
-    return TestTimeAugment(net.forward, args.tta, args.tta_flip) if args.tta else None
 
 
 def check_crf_args(args):
@@ -294,16 +286,9 @@ def check_crf_args(args):
         raise SystemExit('--crf-*: %s' % e)
     if not args.crf_iters:
         return
-    if not (args.device_augment or (args.multi_object and args.synthetic)):
-        raise SystemExit('--crf-iters needs --device-augment (or --multi-object --synthetic): the refinement reads the decoded uint8 frame '
-                         'on the device')
+    need_decoded_frames(args, '--crf-iters needs', 'the refinement reads the decoded uint8 frame on the device')
     args.crf = dict(iters=args.crf_iters, radius=args.crf_radius, dilation=args.crf_dilation, w_appearance=w_a, w_smooth=w_s, theta_alpha=t_a,
                     theta_beta=t_b, theta_gamma=t_g)
-
-
-def make_crf(args):
-    from osvos_pytorch_amd.refine import CrfRefiner
-    return CrfRefiner(**args.crf) if args.crf else None
 
 
 def check_flow_args(args):
@@ -328,11 +313,6 @@ def check_flow_args(args):
     args.flow = dict(search=args.flow_search, block=args.flow_block, step=args.flow_step, penalty=args.flow_penalty, median=args.flow_median)
 
 
-def make_flow(args):
-    from osvos_pytorch_amd.flow import MotionCompensator
-    return MotionCompensator(**args.flow) if args.flow else None
-
-
 def check_snap_args(args):
     """the --snap-* rules; SystemExit on values the snapping does not take -- checked before any GPU work.  Sets args.snap to the keyword
     arguments of superpixels.SuperpixelSnapper, or None with --snap-cell 0"""
@@ -344,15 +324,8 @@ def check_snap_args(args):
         raise SystemExit('--snap-*: %s' % e)
     if not args.snap_cell:
         return
-    if not (args.device_augment or (args.multi_object and args.synthetic)):
-        raise SystemExit('--snap-cell needs --device-augment (or --multi-object --synthetic): the superpixels are made from the decoded uint8 '
-                         'frame on the device')
+    need_decoded_frames(args, '--snap-cell needs', 'the superpixels are made from the decoded uint8 frame on the device')
     args.snap = dict(cell=args.snap_cell, compactness=args.snap_compactness, iters=args.snap_iters)
-
-
-def make_snap(args):
-    from osvos_pytorch_amd.superpixels import SuperpixelSnapper
-    return SuperpixelSnapper(**args.snap) if args.snap else None
 
 
 def check_match_args(args):
@@ -368,16 +341,10 @@ def check_match_args(args):
         return
     if args.tta:
         raise SystemExit('--match-gain is not run together with --tta-scales / --tta-flip: matching under test-time augmentation is not built')
-    if not (args.device_augment or (args.multi_object and args.synthetic)):
-        raise SystemExit('--match-gain needs --device-augment (or --multi-object --synthetic): the first-frame bank is made on the device input pipeline')
+    need_decoded_frames(args, '--match-gain needs', 'the first-frame bank is made on the device input pipeline')
     if args.match_previous and args.adapt_steps:
         raise SystemExit('--match-previous is not run together with --adapt-steps: the adapter forwards every frame twice')
     args.match = dict(layer=args.match_layer, gain=args.match_gain, previous=args.match_previous)
-
-
-def make_match(args, net):
-    from osvos_pytorch_amd.match import AppearanceMatcher
-    return AppearanceMatcher(net, **args.match) if args.match else None
 
 
 def check_lucid_args(args):
@@ -429,6 +396,38 @@ def check_lucid_args(args):
         args.lucid_void = True
 
 
+def build_forward(args, net, trainloader=None):
+    """the sequence.FrameForward of a fine-tuned network: the --test-precision re-pack, then the stages that belong to one network, each None
+    when its option is off -- test-time augmentation, the online adapter (with ``trainloader``: the single-object recipe) on a FRESH optimizer
+    (no momentum carried over from the first-frame fine-tuning), the appearance matcher"""
+    if args.test_precision:
+        net.set_precision(args.test_precision)      # (re-packs the weights once: the FP16-pair packs are another format)
+    tta = adapter = matcher = None
+    if args.tta:
+        from osvos_pytorch_amd.tta import TestTimeAugment
+        tta = TestTimeAugment(net.forward, args.tta, args.tta_flip)
+    if args.adapt_steps and trainloader is not None:
+        from osvos_pytorch_amd.adapt import OnlineAdapter, first_frame_source
+        optimizer = make_sgd(net, 'online', lr=args.adapt_lr) if args.adapt_lr is not None else make_sgd(net, 'online')
+        adapter = OnlineAdapter(net, optimizer, first_frame_source(trainloader), steps=args.adapt_steps, mix=args.adapt_mix, weight=args.adapt_weight,
+                                prob=args.adapt_prob, erosion=args.adapt_erosion, distance=args.adapt_distance)
+    if args.match:
+        from osvos_pytorch_amd.match import AppearanceMatcher
+        matcher = AppearanceMatcher(net, **args.match)
+    return sequence.FrameForward(net, tta, adapter, matcher)
+
+
+def build_post(args):
+    """the stages that belong to no network, as keyword arguments of the sequences, each None when its option is off: flow, crf, snap,
+    make_tracker (first_mask -> tracker: the tracker is seeded with the first annotation)"""
+    from osvos_pytorch_amd.flow import MotionCompensator
+    from osvos_pytorch_amd.refine import CrfRefiner
+    from osvos_pytorch_amd.superpixels import SuperpixelSnapper
+    return dict(flow=MotionCompensator(**args.flow) if args.flow else None, crf=CrfRefiner(**args.crf) if args.crf else None,
+                snap=SuperpixelSnapper(**args.snap) if args.snap else None,
+                make_tracker=(lambda first_mask: ComponentTracker(first_mask, args.track_components)) if args.track_components is not None else None)
+
+
 def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, nEpochs, nAveGrad):
     """DAVIS 2017 recipe for one sequence: one fine-tuning per object id of the first annotation on that object's binary mask, every frame
     through each network, the K logit stacks merged into label maps, indexed PNGs, J and F per object -- one read-back for the PNGs, one for
@@ -454,76 +453,30 @@ def multi_object_sequence(args, seq_name, device, seed, save_dir, parentEpoch, n
     K = n_objects(gts[0].cpu().numpy())
     if not 1 <= K <= MAX_OBJECTS:
         raise SystemExit('--multi-object: the first annotation of %s holds %d object ids (1..%d are supported)' % (seq_name, K, MAX_OBJECTS))
-    h, w = int(frames[0].shape[0]), int(frames[0].shape[1])
-    logits = torch.empty((K, len(frames), h, w), device=device, dtype=torch.float32)
     print('Start of Online Training, sequence: %s (%d objects)' % (seq_name, K))
-    test_time = 0.0
-    for k in range(1, K + 1):
+
+    def fine_tuned(k):
         net, optimizer = load_parent(args, save_dir, parentEpoch, device)
         random.seed(seed)                      # every object sees the augmentation draws of a single-object run
         trainloader = DeviceTrainFrame(frames[0], (gts[0] == k).to(torch.uint8) * 255, device, args.lucid)
         print('Object %d of %d' % (k, K))
         fine_tune(args, net, optimizer, trainloader, device, nEpochs, nAveGrad, seed, os.path.join(save_dir, '%s_object-%d' % (seq_name, k)))
-        start_time = timeit.default_timer()
-        if args.test_precision:
-            net.set_precision(args.test_precision)
-        tta = make_tta(args, net)
-        matcher = make_match(args, net)                 # one matcher per object's network: its own first-frame bank
-        match_prev = None
-        with torch.no_grad():
-            if matcher is not None:
-                matcher.set_reference(augment_frame(frames[0], None, flip=False, rot=None)[0][None], gts[0] == k)
-            for f, img in enumerate(frames):
-                if tta is not None:
-                    logits[k - 1, f].copy_(tta(img)[0, 0])
-                elif matcher is not None:
-                    out = matcher(augment_frame(img, None, flip=False, rot=None)[0][None], match_prev)[-1]
-                    logits[k - 1, f].copy_(out[0, 0])
-                    match_prev = out > 0 if matcher.previous else None
-                else:
-                    logits[k - 1, f].copy_(net.forward(augment_frame(img, None, flip=False, rot=None)[0][None])[-1][0, 0])
-        torch.cuda.synchronize()
-        test_time += timeit.default_timer() - start_time
-        del net, optimizer, trainloader, tta, matcher
+        return net
 
     save_dir_res = os.path.join(save_dir, 'Results', seq_name)
     os.makedirs(save_dir_res, exist_ok=True)
-    print('Testing Network')
-    start_time = timeit.default_timer()
-    crf = make_crf(args)
-    if crf is not None:
-        for s0 in range(0, len(frames), 64):                                  # (enqueued: nothing is read back)
-            stacked = torch.stack(frames[s0:s0 + 64])
-            for k in range(K):
-                logits[k, s0:s0 + 64] = crf(logits[k, s0:s0 + 64], stacked)
-    snap = make_snap(args)
-    if snap is not None:
-        for s0 in range(0, len(frames), 64):                                  # (enqueued: nothing is read back)
-            spx = snap.labels(torch.stack(frames[s0:s0 + 64]))                # one labelling per chunk, shared by the K objects
-            for k in range(K):
-                logits[k, s0:s0 + 64] = snap(logits[k, s0:s0 + 64], labels=spx)
-    trackers = []
-    if args.track_components is not None:
-        for k in range(1, K + 1):
-            trackers.append(ComponentTracker(gts[0] == k, args.track_components))
-            for s0 in range(0, len(frames), 64):                              # consecutive frames, in order (enqueued: nothing is read back)
-                logits[k - 1, s0:s0 + 64] = trackers[-1](logits[k - 1, s0:s0 + 64])
-    labels = merge_objects(logits)
-    evaluator = MultiObjectEvaluator(K)
-    scored = [f for f, g in enumerate(gts) if g is not None]
-    step = max(1, min(64, 65535 // K))
-    for s0 in range(0, len(scored), step):
-        at = scored[s0:s0 + step]
-        evaluator.add(labels[at], torch.stack([gts[f] for f in at]))      # (enqueued: nothing is read back here)
-    save_label_maps(labels, [os.path.join(save_dir_res, n + '.png') for n in names])
-    res = evaluator.summary()
+    post = build_post(args)
+    assert post.pop('flow') is None            # (parse_args refuses --flow-search with --multi-object)
+    logits, trackers, started = sequence.multi_object_sequence(
+        frames, gts, K, fine_tuned, lambda net: build_forward(args, net), lambda img: augment_frame(img, None, flip=False, rot=None)[0][None], **post)
+    res = sequence.score_objects(logits, gts, [os.path.join(save_dir_res, n + '.png') for n in names])
     for k, o in enumerate(res['objects']):
         print('J&F on %s object %d: J %.4f F %.4f' % (seq_name, k + 1, o['J']['mean'], o['F']['mean']))
     print('J&F on %s (%d objects): %.4f' % (seq_name, K, res['J&F']))
     for k, t in enumerate(trackers):
         c = t.summary()
         print('Components kept on %s object %d: %d of %d over %d frames' % (seq_name, k + 1, c['kept'], c['seen'], c['frames']))
-    print('Testing time multi-object: ' + str(test_time + timeit.default_timer() - start_time))
+    print('Testing time multi-object: ' + str(timeit.default_timer() - started))
 
 
 def parse_args(argv=None):
@@ -647,9 +600,8 @@ def parse_args(argv=None):
     check_snap_args(args)
     check_lucid_args(args)
     check_match_args(args)
-    if args.tta and not (args.device_augment or (args.multi_object and args.synthetic)):
-        raise SystemExit('--tta-scales / --tta-flip need --device-augment (or --multi-object --synthetic): test-time augmentation makes its views '
-                         'from the decoded uint8 frame on the device')
+    if args.tta:
+        need_decoded_frames(args, '--tta-scales / --tta-flip need', 'test-time augmentation makes its views from the decoded uint8 frame on the device')
     if args.track_components is not None and not 0 <= args.track_components <= 64:
         raise SystemExit('--track-components takes a radius of 0..64 pixels, got %d' % args.track_components)
     if args.multi_object and not (args.device_augment or args.synthetic):
@@ -687,63 +639,14 @@ def main():
         os.makedirs(save_dir_res, exist_ok=True)
         print('Testing Network')
         evaluator = SequenceEvaluator()      # J and F counts stay on the device: one read-back after the last frame
-        tracker = None
-        if args.test_precision:
-            net.set_precision(args.test_precision)      # (re-packs the weights once: the FP16-pair packs are another format)
-        tta = make_tta(args, net)
-        adapter = make_adapter(args, net, trainloader)
-        crf = make_crf(args)
-        mc = make_flow(args)
-        snap = make_snap(args)
-        matcher = make_match(args, net)
-        match_prev = [None]                  # --match-previous: the previous frame's final mask
-        if matcher is not None and adapter is not None:
-            adapter.forward = lambda image: matcher(image, match_prev[0])      # both of the adapter's forwards are matched ones
-        prev_mask = None                     # --adapt-steps: the previous frame's final mask (frame 0: its annotation)
-        with torch.no_grad():
-            for sample in testloader:
-                fname = sample['fname']
-                if mc is not None:                   # the field from the previous frame to this one moves what is carried over
-                    if sample['frame_u8'].dim() != 3:
-                        raise SystemExit('--flow-search: the test loader delivered %d frames in one batch; it takes one' % int(sample['frame_u8'].shape[0]))
-                    mc.update(sample['frame_u8'])
-                    if prev_mask is not None:
-                        prev_mask = mc.warp(prev_mask)
-                    if tracker is not None:
-                        tracker.seed = mc.warp(tracker.seed)
-                if matcher is not None and not matcher.has_reference:
-                    if 'gt' not in sample:
-                        raise SystemExit('--match-gain: sequence %s has no first annotation to build the bank from' % seq_name)
-                    matcher.set_reference(sample['image'].to(device), sample['gt'].to(device)[:, 0] > 0.5)
-                if tta is not None:
-                    fused = tta(sample['frame_u8'])
-                elif adapter is not None and prev_mask is not None:
-                    fused = adapter(sample['image'].to(device), prev_mask)      # (turns gradients on for its own training steps)
-                elif matcher is not None:
-                    fused = matcher(sample['image'].to(device), match_prev[0])[-1]
-                else:
-                    outputs = net.forward(sample['image'].to(device))
-                    fused = outputs[-1]
-                if crf is not None:
-                    fused = crf(fused, sample['frame_u8'])
-                if snap is not None:
-                    fused = snap(fused, sample['frame_u8'])
-                if args.track_components is not None:
-                    if tracker is None:
-                        if 'gt' not in sample:
-                            raise SystemExit('--track-components: sequence %s has no first annotation to seed the tracker' % seq_name)
-                        tracker = ComponentTracker(sample['gt'].to(device)[0, 0] > 0.5, args.track_components)
-                    fused = tracker(fused)
-                if adapter is not None:
-                    if prev_mask is None and 'gt' not in sample:
-                        raise SystemExit('--adapt-steps: sequence %s has no first annotation to start from' % seq_name)
-                    prev_mask = sample['gt'].to(device) > 0.5 if prev_mask is None else fused > 0
-                if matcher is not None and matcher.previous:
-                    match_prev[0] = fused > 0
-                # sigmoid + scipy<=1.1 imsave byte scaling on the device, PNG written by osvos_pytorch_amd.results (reference :181-187)
-                save_masks(fused, [os.path.join(save_dir_res, os.path.basename(fname[jj]) + '.png') for jj in range(int(fused.size()[0]))])
-                if 'gt' in sample:
-                    evaluator.add(fused, sample['gt'].to(device))
+        forward = build_forward(args, net, trainloader)
+        frames = sequence.SingleObjectSequence(testloader, forward, device, seq_name, **build_post(args))
+        for fname, fused, gt in frames:
+            # sigmoid + scipy<=1.1 imsave byte scaling on the device, PNG written by osvos_pytorch_amd.results (reference :181-187)
+            save_masks(fused, [os.path.join(save_dir_res, os.path.basename(fname[jj]) + '.png') for jj in range(int(fused.size()[0]))])
+            if gt is not None:
+                evaluator.add(fused, gt.to(device))
+        tracker, adapter = frames.tracker, forward.adapter
         if evaluator.frames:
             res = evaluator.summary()
             st = res['J']
