@@ -516,6 +516,37 @@ int osvos_tta_view(const unsigned char* bgr, const float* mean3, float* out, int
 int osvos_tta_fuse(const float* const* views, const int* Hv, const int* Wv, const int* flip, const float* weight, int V, float* out, int N,
                    int H, int W, void* stream);
 
+/* ---- object-centred zoom: a box from a mask, the box's window as a network input of fixed size, the canvas's logits pasted back ----
+ * A box is int32 (x0, y0, bw, bh) in DEVICE memory, one per frame: the window of columns x0 .. x0 + bw - 1 and rows y0 .. y0 + bh - 1.
+ * osvos_roi_box: mask [N][H][W] bytes (device; non-zero = object) -> box [N][4].  Per frame, in signed 64-bit integers, `/` rounding down
+ *   (every operand it meets is >= 0):
+ *     1. xa, xb, ya, yb = the smallest and largest column and row of a set pixel; no set pixel: box = (0, 0, W, H), done
+ *     2. bw = xb - xa + 1, bh = yb - ya + 1, pad = (max(bw, bh) * margin_pct + 99) / 100 + margin_px;
+ *        x0 = xa - pad, y0 = ya - pad, bw += 2 pad, bh += 2 pad
+ *     3. bw < min_w: x0 -= (min_w - bw) / 2, bw = min_w;  bh < min_h: y0 -= (min_h - bh) / 2, bh = min_h
+ *     4. bw * Hc < bh * Wc: nw = (bh * Wc + Hc - 1) / Hc, x0 -= (nw - bw) / 2, bw = nw;
+ *        else bh * Wc < bw * Hc: nh = (bw * Hc + Wc - 1) / Wc, y0 -= (nh - bh) / 2, bh = nh          (the canvas's aspect)
+ *     5. bw = min(bw, W), x0 = min(max(x0, 0), W - bw);  bh = min(bh, H), y0 = min(max(y0, 0), H - bh)
+ *   The box lies in the frame and holds the tight box; one capped by the frame loses the aspect.  margin_pct, margin_px >= 0,
+ *   0 <= min_w <= W, 0 <= min_h <= H.  ws: OSVOS_ROI_BOX_WS_BYTES(N) bytes, 16-byte aligned, contents irrelevant on entry and worthless
+ *   afterwards: the call keeps no state in it.  Two launches on `stream`; frames are independent.
+ * osvos_roi_view: bgr [N][H][W][3] uint8 -> out [N][3][Hc][Wc] fp32 = the sampling rule above (test-time augmentation) with n_src = bw
+ *   (bh), n_dst = Wc (Hc), source indices offset by x0 (y0) and clamped to the box, minus mean3[c] (HOST pointer): osvos_tta_view of the
+ *   cropped frame.  The box (0, 0, W, H) with Hc == H, Wc == W gives osvos_tta_view's same-size unflipped output bit for bit.
+ * osvos_roi_paste: logits [N][Hc][Wc] fp32 -> out [N][H][W] fp32: inside the box the same rule with n_src = Wc (Hc), n_dst = bw (bh) at
+ *   destination index x - x0 (y - y0); `outside` everywhere else.  A canvas of the box's size passes through bit for bit, inf and NaN
+ *   included.  out must not be logits.
+ * Both read the box from device memory -- only sizes are arguments, nothing is read back -- and force it into the frame first
+ *   (1 <= bw <= W, 0 <= x0 <= W - bw, likewise y), which leaves a box of osvos_roi_box as it is.  One launch each on `stream`.
+ * Every side 1..16384, N 1..65535; pointers to floats and ints 4-byte aligned.  A refused call returns a negative code, sets
+ *   osvos_last_error and launches nothing. */
+#define OSVOS_ROI_BOX_PARTS 64
+#define OSVOS_ROI_BOX_WS_BYTES(N) ((size_t)(N) * OSVOS_ROI_BOX_PARTS * 16)
+int osvos_roi_box(const unsigned char* mask, int* box, int N, int H, int W, int Hc, int Wc, int margin_pct, int margin_px, int min_w, int min_h,
+                  void* ws, void* stream);
+int osvos_roi_view(const unsigned char* bgr, const int* box, const float* mean3, float* out, int N, int H, int W, int Hc, int Wc, void* stream);
+int osvos_roi_paste(const float* logits, const int* box, float* out, int N, int Hc, int Wc, int H, int W, float outside, void* stream);
+
 /* ---- mask refinement: mean field of a local two-label dense CRF (Potts compatibility, ConvCRF-style window), logits in, logits out ----
  * Per image: unary [H][W] fp32 logits u, bgr [H][W][3] uint8 (the decoded frame I), a start state z^0 = init (NULL: unary).  For t = 0..iters-1
  *     s_j       = 2 sigmoid(z_j^t) - 1

@@ -27,6 +27,7 @@ INFERENCE = 0x400           # OSVOS_FLAG_INFERENCE: osvos_net_forward writes not
 MAX_OBJECTS = 16            # OSVOS_MAX_OBJECTS: object ids per label map (osvos_merge_objects, osvos_labels_jf_counts)
 BOUNDARY_MAX_RADIUS = 64    # OSVOS_BOUNDARY_MAX_RADIUS: largest disk radius (osvos_mask_jf_counts, osvos_components_select)
 TTA_MAX_VIEWS = 16          # OSVOS_TTA_MAX_VIEWS: logit maps per osvos_tta_fuse call
+ROI_BOX_PARTS = 64          # OSVOS_ROI_BOX_PARTS: osvos_roi_box takes 16 * ROI_BOX_PARTS bytes of workspace per frame
 CRF_MAX_RADIUS = 7          # OSVOS_CRF_MAX_RADIUS: largest window radius of osvos_crf_refine
 CRF_MAX_REACH = 16          # OSVOS_CRF_MAX_REACH: largest radius * dilation
 CRF_MAX_ITERS = 64          # OSVOS_CRF_MAX_ITERS: mean-field iterations per osvos_crf_refine call
@@ -145,6 +146,9 @@ PROTOTYPES = {
     "osvos_components_select": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "osvos_tta_view": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "osvos_tta_fuse": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "osvos_roi_box": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "osvos_roi_view": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "osvos_roi_paste": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "osvos_crf_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "osvos_crf_refine": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _vp]),
     "osvos_flow_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),

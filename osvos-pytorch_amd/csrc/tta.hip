@@ -5,7 +5,7 @@
 //   osvos_tta_fuse   V logit maps [N][Hv[v]][Wv[v]] of different sizes -> out [N][H][W] = sum_v weight[v] * sample_v(y, x): each view resampled
 //                    onto the H x W grid, read through column Wv - 1 - c when it came from a mirrored input.  Logits, never sigmoids.
 //
-// Sampling rule (tta_tap, the one place it is written): separable bilinear with half-pixel centres -- F.interpolate(mode='bilinear',
+// Sampling rule (tta_tap in tta_tap.h, the one place it is written): separable bilinear with half-pixel centres -- F.interpolate(mode='bilinear',
 // align_corners=False)'s geometry -- with the taps in INTEGERS: for destination i of n_dst over n_src,
 //   num = max((2 i + 1) n_src - n_dst, 0), den = 2 n_dst, i0 = min(num / den, n_src - 1), i1 = min(i0 + 1, n_src - 1), f = (num % den) / den
 // (sizes <= 16384 keep num inside int32; num % den and den are exact in fp32, so f carries one rounding and is 0 exactly when the tap falls on
@@ -21,53 +21,9 @@
 // sources are gathered with 1- and 4-byte loads (neighbouring lanes read neighbouring or equal addresses), so views need 4-byte alignment
 // only.  The fuse kernel takes its table of views BY VALUE in the kernel arguments: no device upload, nothing to free.
 #include "common.h"
+#include "tta_tap.h"      // Tap, tta_tap, tta_lerp, tta_column, tta_store4 (shared with roi.hip)
 
 namespace {
-
-struct Tap {
-  int i0, i1;
-  float f;      // weight of i1; the weight of i0 is 1 - f
-};
-
-__device__ __forceinline__ Tap tta_tap(int i, int n_dst, int n_src) {
-  const int t = (2 * i + 1) * n_src - n_dst;
-  const unsigned num = t > 0 ? (unsigned)t : 0u, den = 2u * (unsigned)n_dst;
-  const unsigned q = num / den;
-  Tap tap;
-  tap.i0 = min((int)q, n_src - 1);
-  tap.i1 = min(tap.i0 + 1, n_src - 1);
-  tap.f = (float)(num - q * den) / (float)den;
-  return tap;
-}
-
-__device__ __forceinline__ float tta_lerp(float a, float b, float f) {
-#pragma clang fp contract(off)
-  return f == 0.f ? a : (1.f - f) * a + f * b;
-}
-
-// column of pixel j of this thread
-template <bool VEC>
-__device__ __forceinline__ int tta_column(int j) {
-  return VEC ? (int)(blockIdx.x * 64 + threadIdx.x) * 4 + j : (int)(blockIdx.x * 256 + j * 64 + threadIdx.x);
-}
-
-template <bool VEC>
-__device__ __forceinline__ void tta_store4(float* __restrict__ row, int W, const float* v) {
-  if constexpr (VEC) {
-    const int x = tta_column<true>(0);
-    if (x < W) {
-      f32x4 q;
-      q[0] = v[0]; q[1] = v[1]; q[2] = v[2]; q[3] = v[3];
-      *reinterpret_cast<f32x4*>(row + x) = q;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int x = tta_column<false>(j);
-      if (x < W) row[x] = v[j];
-    }
-  }
-}
 
 struct ViewArgs {
   const unsigned char* bgr;      // [N][H][W][3]

@@ -3,7 +3,7 @@
 The stages arrive built (results.ComponentTracker as a factory ``first_mask -> tracker``, because its seed is the first annotation), or as
 None for an option that is off.  THE ORDER OF THE STAGES LIVES HERE, and tests/test_sequence_cpu.py asserts it with recording stand-ins:
 
-  ``FrameForward``          one frame -> fused logits: tta > adapter (once a previous mask exists) > matcher > net.forward
+  ``FrameForward``          one frame -> fused logits: roi > tta > adapter (once a previous mask exists) > matcher > net.forward
   ``post_chain``            crf -> snap -> tracker on a logit stack and its decoded frames (one frame or a chunk of frames)
   ``SingleObjectSequence``  per frame: motion compensation of what is carried over, matcher reference, FrameForward, post_chain, then the
                             state of the next frame (SingleObjectSequence.step)
@@ -12,7 +12,8 @@ None for an option that is off.  THE ORDER OF THE STAGES LIVES HERE, and tests/t
 
 The two recipes differ in ONE rule.  The mask that --match-previous hands to the next frame (FrameForward.remember) is the FINAL mask in
 the single-object recipe -- after crf, snap and tracker -- and the RAW output of the matched forward in the multi-object recipe, whose post
-chain runs only after every forward of every object is done."""
+chain runs only after every forward of every object is done.  The mask the object-centred zoom takes its box from (FrameForward.roi_prev)
+is remembered by the same call, so it follows the same rule."""
 import timeit
 
 import torch
@@ -21,14 +22,16 @@ from .results import MultiObjectEvaluator, merge_objects, save_label_maps
 
 
 class FrameForward(object):
-    """``forward(frame_u8, image, prev_mask)`` -> the fused logits [1,1,H,W] of one frame, from the first of: ``tta(frame_u8)``;
+    """``forward(frame_u8, image, prev_mask)`` -> the fused logits [1,1,H,W] of one frame, from the first of: ``roi(frame_u8, roi_prev)``
+    (roi.RoiZoom: the network on a crop around the mask ``remember`` was handed last; None on frame 0: the full frame); ``tta(frame_u8)``;
     ``adapter(image, prev_mask)`` once there is a previous mask (so never on frame 0); ``matcher(image, match_prev)[-1]``;
     ``net.forward(image)[-1]``.  With an adapter and a matcher both of the adapter's plain forwards are matched ones that read the current
     ``match_prev``.  One per network: the multi-object recipe builds one per object, without adapter."""
 
-    def __init__(self, net, tta=None, adapter=None, matcher=None):
-        self.net, self.tta, self.adapter, self.matcher = net, tta, adapter, matcher
+    def __init__(self, net, tta=None, adapter=None, matcher=None, roi=None):
+        self.net, self.tta, self.adapter, self.matcher, self.roi = net, tta, adapter, matcher, roi
         self.match_prev = None               # --match-previous: the previous frame's mask (which one: see the module docstring)
+        self.roi_prev = None                 # --zoom: the previous frame's mask, by the same rule
         if matcher is not None and adapter is not None:
             adapter.forward = lambda image: matcher(image, self.match_prev)
 
@@ -38,14 +41,16 @@ class FrameForward(object):
 
     @property
     def needs_image(self):
-        """False under test-time augmentation, which makes its own views from frame_u8"""
-        return self.tta is None
+        """False under test-time augmentation and under the zoom, which make their own views from frame_u8"""
+        return self.tta is None and self.roi is None
 
     def set_reference(self, image, mask):
         if self.needs_reference:
             self.matcher.set_reference(image, mask)
 
     def __call__(self, frame_u8, image, prev_mask=None):
+        if self.roi is not None:
+            return self.roi(frame_u8, self.roi_prev)
         if self.tta is not None:
             return self.tta(frame_u8)
         if self.adapter is not None and prev_mask is not None:
@@ -57,6 +62,8 @@ class FrameForward(object):
     def remember(self, logits):
         if self.matcher is not None and self.matcher.previous:
             self.match_prev = logits > 0
+        if self.roi is not None:
+            self.roi_prev = logits > 0
 
 
 def post_chain(fused, frames_u8, crf=None, snap=None, tracker=None, labels=None):
@@ -74,7 +81,8 @@ def post_chain(fused, frames_u8, crf=None, snap=None, tracker=None, labels=None)
 class SingleObjectSequence(object):
     """Iterating yields ``(fname, fused, gt or None)`` for every sample of ``loader``, in order; the caller writes and scores.  ``prev_mask``
     (--adapt-steps: the previous frame's final mask; for frame 1 the annotation of frame 0), ``tracker`` and ``forward.match_prev`` are the
-    state carried from frame to frame; ``flow`` (flow.MotionCompensator) moves the first two to where the object is now."""
+    state carried from frame to frame, and so is ``forward.roi_prev``; ``flow`` (flow.MotionCompensator) moves the first two and the last to
+    where the object is now."""
 
     def __init__(self, loader, forward, device, seq_name, flow=None, crf=None, snap=None, make_tracker=None):
         self.loader, self.forward, self.device, self.seq_name = loader, forward, device, seq_name
@@ -98,6 +106,8 @@ class SingleObjectSequence(object):
                 self.prev_mask = self.flow.warp(self.prev_mask)
             if self.tracker is not None:
                 self.tracker.seed = self.flow.warp(self.tracker.seed)
+            if forward.roi_prev is not None:
+                forward.roi_prev = self.flow.warp(forward.roi_prev)
         if forward.needs_reference:
             if gt is None:
                 raise SystemExit('--match-gain: sequence %s has no first annotation to build the bank from' % seq_name)

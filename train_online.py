@@ -39,6 +39,12 @@ running on the MI355X-native OSVOS path.  Differences by design:
     bends the object by a smooth displacement field, ``--lucid-occlude P`` hides part of it behind an ellipse of displaced background,
     ``--lucid-band R`` labels the pixels within R of a label edge void (-1: no count, no loss, no gradient; not with --window-fused); all
     three are off by default, and off they change no draw and no byte
+  * ``--zoom MAXZOOM``: object-centred zoom of the test forwards -- on the device, a box around the previous frame's mask (a margin, at most
+    MAXZOOM-fold enlargement, the canvas's aspect), the box's window of the decoded frame resampled onto one fixed canvas (``--zoom-canvas``,
+    default the frame's size: the network keeps one input shape), the network on that, and its logits pasted back into the frame with
+    ``--zoom-outside`` around them (osvos_pytorch_amd.roi.RoiZoom); frame 0 runs on the full frame.  Before --crf-iters, --snap-cell and
+    --track-components, which keep running on the frame's grid.  Not with --tta-*, --match-gain or --adapt-steps.  ``--zoom-margin PCT,PX``.
+    Starting values, not tuned on DAVIS; with MAXZOOM = 0 nothing is built and not one byte changes
   * the test phase -- which stage runs when, and what is carried from frame to frame -- is osvos_pytorch_amd.sequence for both recipes: the
     order is stated there, once, and asserted by tests/test_sequence_cpu.py; this file parses the options, fine-tunes, builds the stages
     (build_forward, build_post) and prints
@@ -165,7 +171,7 @@ def device_loaders(args, seq_name, device, seed):
     else:
         train, test = DavisFrames(True, Path.db_root_dir(), seq_name=seq_name), DavisFrames(False, Path.db_root_dir(), seq_name=seq_name)
     img, lab = train[0]
-    return DeviceTrainFrame(img, lab, device, args.lucid), DeviceTestFrames(test, device, args.prefetch, raw_only=bool(args.tta))
+    return DeviceTrainFrame(img, lab, device, args.lucid), DeviceTestFrames(test, device, args.prefetch, raw_only=bool(args.tta or args.roi))
 
 
 def synthetic_objects(h, w):
@@ -270,6 +276,47 @@ def tta_scales(args):
     return scales
 
 
+def check_zoom_args(args):
+    """the --zoom* rules; SystemExit on values or combinations the zoom does not take -- checked before any GPU work.  Sets args.roi to the
+    keyword arguments of roi.RoiZoom, or None with --zoom 0"""
+    from osvos_pytorch_amd import roi
+    args.roi = None
+    try:
+        parts = args.zoom_margin.split(',')
+        try:
+            pct, px = [int(v) for v in parts] if len(parts) == 2 else [None, None]
+        except ValueError:
+            pct = None
+        if pct is None:
+            raise ValueError('--zoom-margin takes PCT,PX, two integers >= 0, got %r' % args.zoom_margin)
+        canvas = None
+        if args.zoom_canvas:
+            parts = args.zoom_canvas.lower().split('x')
+            try:
+                canvas = tuple(int(v) for v in parts) if len(parts) == 2 else None
+            except ValueError:
+                canvas = None
+            if canvas is None or not all(1 <= v <= roi.MAX_SIDE for v in canvas):
+                raise ValueError('--zoom-canvas takes HxW with sides of 1..%d, got %r' % (roi.MAX_SIDE, args.zoom_canvas))
+        if args.zoom != 0 and not args.zoom >= 1:
+            raise ValueError('--zoom takes the largest enlargement, a number >= 1 (0 = off), got %r' % args.zoom)
+        roi.check_zoom(pct, px, args.zoom or 1.0)
+        if args.zoom_outside != args.zoom_outside:
+            raise ValueError('--zoom-outside takes a logit, got %r' % args.zoom_outside)
+    except ValueError as e:
+        raise SystemExit('--zoom*: %s' % e)
+    if not args.zoom:
+        return
+    if args.tta:
+        raise SystemExit('--zoom is not run together with --tta-scales / --tta-flip: the views of a crop are not built')
+    if args.match_gain:
+        raise SystemExit('--zoom is not run together with --match-gain: matching needs the crop of the trunk features, which is not built')
+    if args.adapt_steps:
+        raise SystemExit('--zoom is not run together with --adapt-steps: the adapter trains on the whole frame and returns its own final forward')
+    need_decoded_frames(args, '--zoom needs', 'the crop is made from the decoded uint8 frame on the device')
+    args.roi = dict(canvas=canvas, margin_pct=pct, margin_px=px, max_zoom=args.zoom, outside=args.zoom_outside)
+
+
 def check_crf_args(args):
     """the --crf-* rules; SystemExit on values the refinement does not take -- checked before any GPU work.  Sets args.crf to the
     keyword arguments of refine.CrfRefiner, or None with --crf-iters 0"""
@@ -308,7 +355,7 @@ def check_flow_args(args):
     if not args.device_augment:
         raise SystemExit('--flow-search needs --device-augment: the motion field is made from the decoded uint8 frames on the device (the other '
                          'loaders deliver no frame_u8, and only this one is known to deliver one frame per batch)')
-    if not args.adapt_steps and args.track_components is None:
+    if not args.adapt_steps and args.track_components is None and not args.roi:
         raise SystemExit('--flow-search needs --adapt-steps or --track-components: it moves the previous mask of the one and the seed of the other')
     args.flow = dict(search=args.flow_search, block=args.flow_block, step=args.flow_step, penalty=args.flow_penalty, median=args.flow_median)
 
@@ -402,7 +449,10 @@ def build_forward(args, net, trainloader=None):
     (no momentum carried over from the first-frame fine-tuning), the appearance matcher"""
     if args.test_precision:
         net.set_precision(args.test_precision)      # (re-packs the weights once: the FP16-pair packs are another format)
-    tta = adapter = matcher = None
+    tta = adapter = matcher = roi = None
+    if args.roi:
+        from osvos_pytorch_amd.roi import RoiZoom
+        roi = RoiZoom(net.forward, **args.roi)
     if args.tta:
         from osvos_pytorch_amd.tta import TestTimeAugment
         tta = TestTimeAugment(net.forward, args.tta, args.tta_flip)
@@ -414,7 +464,7 @@ def build_forward(args, net, trainloader=None):
     if args.match:
         from osvos_pytorch_amd.match import AppearanceMatcher
         matcher = AppearanceMatcher(net, **args.match)
-    return sequence.FrameForward(net, tta, adapter, matcher)
+    return sequence.FrameForward(net, tta, adapter, matcher, roi)
 
 
 def build_post(args):
@@ -592,9 +642,22 @@ def parse_args(argv=None):
     ap.add_argument('--lucid-band', type=int, default=0, metavar='R',
                     help='--lucid: labels within R pixels (0..16, 0 = off) of a label edge of a lucid sample are void -- no count, no loss, '
                          'gradient 0.  Needs the fused loss step; not with --window-fused')
+    ap.add_argument('--zoom', type=float, default=0.0, metavar='MAXZOOM',
+                    help='object-centred zoom (0 = off): every test frame after the first is segmented on a crop around the previous frame\'s '
+                         'mask -- the mask\'s box grown by --zoom-margin and to the canvas\'s aspect, never smaller than the canvas over MAXZOOM '
+                         '(>= 1) -- resampled onto the canvas on the device, and the logits are pasted back into the frame, before --crf-iters, '
+                         '--snap-cell and --track-components.  The single-object loop takes the box from the final mask, --multi-object from '
+                         'each network\'s raw output.  Needs --device-augment, or --multi-object --synthetic; not with --tta-*, --match-gain '
+                         'or --adapt-steps.  The default parameters are starting values, not tuned on DAVIS')
+    ap.add_argument('--zoom-margin', default='25,8', metavar='PCT,PX',
+                    help='--zoom: the tight box grows on every side by PCT percent of its longer side plus PX pixels')
+    ap.add_argument('--zoom-canvas', default='', metavar='HxW', help='--zoom: the size of the network\'s input (default: the frame\'s size)')
+    ap.add_argument('--zoom-outside', type=float, default=-20.0, metavar='V',
+                    help='--zoom: the logit of every pixel outside the box (finite, so that --crf-iters and --snap-cell keep working on it)')
     args = ap.parse_args(argv)
     args.tta = tta_scales(args)
     check_adapt_args(args)
+    check_zoom_args(args)
     check_crf_args(args)
     check_flow_args(args)
     check_snap_args(args)
