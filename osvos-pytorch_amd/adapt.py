@@ -8,13 +8,12 @@ from the previous frame's mask, made on the device by ``osvos_adapt_targets`` (c
 
 and the steps on the current frame are interleaved with steps on the annotated first frame, so the network does not drift.  Everything is
 enqueued; the only read-back is the 24 bytes of class counts per frame that decide whether the frame is usable at all."""
-import ctypes as C
-
 import numpy as np
 import torch
 
-from ._lib import check, lib
-from .results import _mask_bytes_nhw, _stream
+from . import _glue as g
+from ._lib import lib
+from .results import mask_bytes_nhw
 from .train_common import TrainLoop
 
 
@@ -22,22 +21,20 @@ def adaptation_targets(logits, prev_mask, prob=0.97, erosion=15, distance=220):
     """logits: float32 CUDA tensor [N,1,H,W] or [N,H,W] (the fused output), prev_mask: the previous frame's final mask (uint8, bool or float;
     [N,1,H,W], [N,H,W] or [H,W]; non-zero = object) -> ``(label, counts)``: label float32 [N,1,H,W] with 1 / 0 / -1 = positive / negative /
     void, counts int64 [N,3] = (n_pos, n_neg, n_void), both on the device.  Enqueued only."""
-    if not torch.is_tensor(logits) or not logits.is_cuda:
-        raise RuntimeError("osvos_pytorch_amd.adapt needs CUDA (ROCm) tensors; there is no CPU fallback")
+    g.need_cuda(logits, "logits", "adapt")
     if not 0.0 < prob < 1.0:
         raise ValueError("prob must be a probability in (0, 1), got %r" % (prob,))
     if int(erosion) < 0 or int(distance) < 0:
         raise ValueError("erosion and distance are pixel counts >= 0, got %r and %r" % (erosion, distance))
-    m, n, h, w = _mask_bytes_nhw(prev_mask, "adaptation_targets")
+    m, n, h, w = mask_bytes_nhw(prev_mask, "adaptation_targets", "adapt")
     x = logits.detach().float().contiguous()
     if x.numel() != n * h * w or tuple(x.shape[-2:]) != (h, w) or x.device != m.device:
         raise ValueError("logits of shape %r next to a mask of %d frames of %d x %d" % (tuple(logits.shape), n, h, w))
     label = torch.empty((n, 1, h, w), device=x.device, dtype=torch.float32)
     counts = torch.empty((n, 3), device=x.device, dtype=torch.int64)
-    ws = torch.empty((lib().osvos_adapt_ws_bytes(n, h, w) + 3) // 4, device=x.device, dtype=torch.int32)
-    vp = C.c_void_p
-    check(lib().osvos_adapt_targets(vp(x.data_ptr()), vp(m.data_ptr()), float(np.log(prob / (1.0 - prob))), int(erosion), int(distance),
-                                    vp(label.data_ptr()), vp(counts.data_ptr()), n, h, w, vp(ws.data_ptr()), _stream()), "adapt_targets")
+    ws = g.workspace(lib().osvos_adapt_ws_bytes(n, h, w), x.device, what="%d frames of %d x %d" % (n, h, w), prefix="adapt", dtype=torch.int32)
+    g.call("adapt_targets", x.device, g.ptr(x), g.ptr(m), float(np.log(prob / (1.0 - prob))), int(erosion), int(distance), g.ptr(label), g.ptr(counts),
+           n, h, w, g.ptr(ws))
     return label, counts
 
 

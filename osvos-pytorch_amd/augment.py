@@ -13,7 +13,7 @@ import random
 
 import torch
 
-from ._lib import check, lib
+from . import _glue as g
 
 MEANVAL = (104.00699, 116.66877, 122.67892)          # davis_2016.py default / train_online.py:36
 
@@ -37,12 +37,11 @@ def rotation_matrix_inverse(w, h, rot, sc):
 def augment_frame(img_bgr, label, flip=False, rot=None, sc=None, meanval=MEANVAL):
     """img_bgr: uint8 CUDA tensor [H,W,3]; label: uint8 CUDA tensor [H,W] or None; rot (degrees) / sc: None = no warp.
     Returns (image float32 [3,H,W], gt float32 [1,H,W])."""
-    if not img_bgr.is_cuda or (label is not None and not label.is_cuda):
-        raise RuntimeError("osvos_pytorch_amd.augment needs CUDA (ROCm) tensors; there is no CPU fallback")
-    if img_bgr.dtype != torch.uint8 or img_bgr.dim() != 3 or img_bgr.shape[2] != 3:
-        raise ValueError("img_bgr must be a uint8 [H,W,3] tensor")
-    img_bgr = img_bgr.contiguous()
-    h, w = int(img_bgr.shape[0]), int(img_bgr.shape[1])
+    g.need_cuda(img_bgr, "img_bgr", "augment")
+    if label is not None:
+        g.need_cuda(label, "label", "augment")
+    img_bgr = g.frames(img_bgr, "img_bgr", batch=False)          # ([1,H,W,3]: the same bytes)
+    h, w = int(img_bgr.shape[1]), int(img_bgr.shape[2])
     if label is not None:
         if label.dtype != torch.uint8 or tuple(label.shape) != (h, w):
             raise ValueError("label must be a uint8 [H,W] tensor matching the frame")
@@ -54,10 +53,8 @@ def augment_frame(img_bgr, label, flip=False, rot=None, sc=None, meanval=MEANVAL
     minv = None
     if rot is not None:
         minv = (C.c_double * 6)(*rotation_matrix_inverse(w, h, float(rot), float(sc)))
-    vp = C.c_void_p
-    check(lib().osvos_augment_frame(vp(img_bgr.data_ptr()), vp(label.data_ptr()) if label is not None else None, mean, int(bool(flip)), minv,
-                                    vp(out_img.data_ptr()), vp(out_gt.data_ptr()), vp(scratch.data_ptr()), h, w,
-                                    vp(torch.cuda.current_stream().cuda_stream)), "augment_frame")
+    g.call("augment_frame", img_bgr.device, g.ptr(img_bgr), g.ptr(label), mean, int(bool(flip)), minv, g.ptr(out_img), g.ptr(out_gt), g.ptr(scratch),
+           h, w)
     return out_img, out_gt
 
 

@@ -8,6 +8,7 @@ import os
 
 import torch
 
+from ._glue import stream as _stream
 from ._lib import (BF16_W2, DEFER_JOIN, F32, F32_BF16MFMA, F32_X3, GENERIC_DECONV, INFERENCE, NPARAMS, X3_HALF_PIECES, X3_HALF_PIECES_BWD, X3_TWO_PIECES, check,
                    lib, ptr_array)
 
@@ -21,10 +22,6 @@ _FROZEN = set(range(8))
 PRECISIONS = {"fp32": (F32, 3, 3), "bf16": (F32_BF16MFMA, 3, 3), "fp32x3": (F32_X3, 3, 3), "fp32x2": (F32_X3, 2, 2), "fp32x3b2": (F32_X3, 3, 2),
               "fp32h2": (F32_X3, 22, 22), "fp32x3h2": (F32_X3, 3, 22), "bf16w2": (F32_BF16MFMA, "w2", 3)}
 _PIECE_FLAG = {3: 0, 2: X3_TWO_PIECES, 22: X3_HALF_PIECES, "w2": BF16_W2}
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class NetRuntime:

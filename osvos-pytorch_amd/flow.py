@@ -14,59 +14,30 @@ read back.
 The default parameters are STARTING VALUES, NOT TUNED ON DAVIS (no dataset was at hand when this was written), and no accuracy claim is
 made for them: tune them on a validation split before quoting a score.
 """
-import ctypes as C
-
-import numpy as np
 import torch
 
-from ._lib import (FLOW_MAX_BLOCK, FLOW_MAX_MEDIAN, FLOW_MAX_PENALTY, FLOW_MAX_SEARCH, FLOW_MAX_SIDE, FLOW_MAX_STEP, check, lib)
+from . import _glue as g
+from ._glue import grid_shape  # noqa: F401  (flow.grid_shape: the cells of a frame at a grid step)
+from ._lib import (FLOW_MAX_BLOCK, FLOW_MAX_MEDIAN, FLOW_MAX_PENALTY, FLOW_MAX_SEARCH, FLOW_MAX_SIDE, FLOW_MAX_STEP, lib)
 
 
 def check_flow(search, block, step, penalty, median):
     """ValueError unless the five parameters are integers inside the limits of osvos_flow_block_match (host only)"""
     for name, v, lo, hi in (("search", search, 0, FLOW_MAX_SEARCH), ("block", block, 1, FLOW_MAX_BLOCK), ("step", step, 1, FLOW_MAX_STEP),
                             ("penalty", penalty, 0, FLOW_MAX_PENALTY), ("median", median, 0, FLOW_MAX_MEDIAN)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError("flow: %s must be an integer, got %r" % (name, v))
-        if not lo <= v <= hi:
-            raise ValueError("flow: %s %d (%d..%d)" % (name, v, lo, hi))
-
-
-def grid_shape(h, w, step):
-    """(GH, GW) = (ceil(h / step), ceil(w / step)): the cells of an h x w frame"""
-    return -(-int(h) // int(step)), -(-int(w) // int(step))
-
-
-def _need_cuda(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("osvos_pytorch_amd.flow needs CUDA (ROCm) tensors (%s); there is no CPU fallback" % what)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        g.check_int(name, v, lo, hi, "flow")
 
 
 def _frames(t, what):
     """[N,H,W,3] or [H,W,3] uint8 -> contiguous [N,H,W,3]"""
-    _need_cuda(t, what)
-    if t.dim() == 3:
-        t = t[None]
-    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3:
-        raise ValueError("%s must be a uint8 [N,H,W,3] or [H,W,3] tensor, got %s %s" % (what, t.dtype, tuple(t.shape)))
-    n, h, w = (int(v) for v in t.shape[:3])
-    if n < 1 or not (1 <= h <= FLOW_MAX_SIDE and 1 <= w <= FLOW_MAX_SIDE):
-        raise ValueError("%s of %s: N >= 1 and sides 1..%d" % (what, tuple(t.shape), FLOW_MAX_SIDE))
-    return t.contiguous()
+    g.need_cuda(t, what, "flow")
+    return g.frames(t, what, FLOW_MAX_SIDE)
 
 
 def workspace(n, h, w, block, step, search, median, device, ws=None):
     """a uint8 CUDA tensor of at least osvos_flow_ws_bytes bytes: ``ws`` when it is large enough and on ``device``, else a new one"""
-    need = int(lib().osvos_flow_ws_bytes(n, h, w, block, step, search, median))
-    if need == 0:
-        raise ValueError("flow: no workspace size for %d frames of %d x %d with block %d step %d search %d median %d" % (n, h, w, block, step, search, median))
-    if ws is None or ws.numel() < need or ws.device != device:
-        ws = torch.empty(need, device=device, dtype=torch.uint8)
-    return ws
+    return g.workspace(lib().osvos_flow_ws_bytes(n, h, w, block, step, search, median), device, ws,
+                       "%d frames of %d x %d with block %d step %d search %d median %d" % (n, h, w, block, step, search, median), "flow")
 
 
 def block_match(prev_u8, cur_u8, search=24, block=16, step=4, penalty=4, median=1, ws=None):
@@ -84,10 +55,8 @@ def block_match(prev_u8, cur_u8, search=24, block=16, step=4, penalty=4, median=
     vec = torch.empty((n, gh, gw, 2), device=c.device, dtype=torch.int32)
     cost = torch.empty((n, gh, gw), device=c.device, dtype=torch.int32)
     ws = workspace(n, h, w, block, step, search, median, c.device, ws)
-    vp = C.c_void_p
-    with torch.cuda.device(c.device):
-        check(lib().osvos_flow_block_match(vp(p.data_ptr()), vp(c.data_ptr()), vp(vec.data_ptr()), vp(cost.data_ptr()), vp(ws.data_ptr()), n, h, w,
-                                           int(block), int(step), int(search), int(penalty), int(median), _stream()), "flow_block_match")
+    g.call("flow_block_match", c.device, g.ptr(p), g.ptr(c), g.ptr(vec), g.ptr(cost), g.ptr(ws), n, h, w, int(block), int(step), int(search),
+           int(penalty), int(median))
     return vec, cost
 
 
@@ -95,18 +64,10 @@ def warp(src, vec, step, fill=0):
     """src: uint8, bool or float32 CUDA tensor [N,1,H,W], [N,H,W] or [H,W]; vec: int32 [N,GH,GW,2] of ``block_match`` on the same device
     -> out(n, y, x) = src(n, y + dy, x + dx) with (dx, dy) the vector of the pixel's cell, ``fill`` where the source leaves the frame; the
     shape and dtype of ``src`` (bool goes through bytes).  An exact gather: float32 keeps its bits.  Enqueued only."""
-    _need_cuda(src, "src")
-    _need_cuda(vec, "vec")
-    if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or not 1 <= step <= FLOW_MAX_STEP:
-        raise ValueError("flow: step %r (an integer 1..%d)" % (step, FLOW_MAX_STEP))
-    if src.dtype not in (torch.uint8, torch.bool, torch.float32):
-        raise ValueError("src must be uint8, bool or float32, got %s" % src.dtype)
-    if not (src.dim() in (2, 3) or (src.dim() == 4 and src.shape[1] == 1)):
-        raise ValueError("src must be [N,1,H,W], [N,H,W] or [H,W], got %s" % (tuple(src.shape),))
-    h, w = int(src.shape[-2]), int(src.shape[-1])
-    n = 1 if src.dim() == 2 else int(src.shape[0])
-    if n < 1 or not (1 <= h <= FLOW_MAX_SIDE and 1 <= w <= FLOW_MAX_SIDE):
-        raise ValueError("src of %s: N >= 1 and sides 1..%d" % (tuple(src.shape), FLOW_MAX_SIDE))
+    g.need_cuda(src, "src", "flow")
+    g.need_cuda(vec, "vec", "flow")
+    g.check_int("step", step, 1, FLOW_MAX_STEP, "flow")
+    src, n, h, w = g.planes(src, "src", (torch.uint8, torch.bool, torch.float32), FLOW_MAX_SIDE)
     gh, gw = grid_shape(h, w, step)
     if vec.dtype != torch.int32 or tuple(vec.shape) != (n, gh, gw, 2) or vec.device != src.device:
         raise ValueError("vec must be an int32 [%d,%d,%d,2] tensor on the device of src, got %s %s" % (n, gh, gw, vec.dtype, tuple(vec.shape)))
@@ -114,13 +75,10 @@ def warp(src, vec, step, fill=0):
     fill = float(fill)
     if src.dtype != torch.float32 and not (fill == int(fill) and 0 <= fill <= (1 if as_bool else 255)):
         raise ValueError("fill %r is no %s value" % (fill, "bool" if as_bool else "byte"))
-    x = (src.to(torch.uint8) if as_bool else src).contiguous()
+    x = src.to(torch.uint8) if as_bool else src
     out = torch.empty_like(x)
     v = vec.contiguous()
-    vp = C.c_void_p
-    with torch.cuda.device(x.device):
-        check(lib().osvos_flow_warp(vp(x.data_ptr()), 1 if x.dtype == torch.float32 else 0, vp(v.data_ptr()), vp(out.data_ptr()), n, h, w,
-                                    int(step), fill, _stream()), "flow_warp")
+    g.call("flow_warp", x.device, g.ptr(x), 1 if x.dtype == torch.float32 else 0, g.ptr(v), g.ptr(out), n, h, w, int(step), fill)
     return out.to(torch.bool) if as_bool else out
 
 

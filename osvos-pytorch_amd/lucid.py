@@ -20,8 +20,9 @@ import random
 import numpy as np
 import torch
 
+from . import _glue as g
 from ._lib import (LUCID_MAX_BAND, LUCID_MAX_BATCH, LUCID_MAX_CELL, LUCID_MAX_GAIN, LUCID_MAX_OCC_OFFSET, LUCID_MAX_OCC_RADIUS, LUCID_MAX_PASSES,
-                   LUCID_MAX_RADIUS, LUCID_MAX_SIDE, LUCID_MIN_CELL, SQDIST_MAX_SIDE, check, lib)
+                   LUCID_MAX_RADIUS, LUCID_MAX_SIDE, LUCID_MIN_CELL, SQDIST_MAX_SIDE, lib)
 from .augment import MEANVAL
 
 MAX_GROW = 64               # largest --lucid-grow: pixels the hole reaches beyond the mask
@@ -29,37 +30,25 @@ IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
 NEUTRAL = (256, 256, 256, 0, 0, 0)
 
 
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-
-
-def _is_num(v):
-    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(v)
-
-
 def check_lucid(p=0.0, grow=5, radius=2, passes=3, fg_shift=0.25, bg_shift=0.05, gain=0.2, offset=20, deform=0.0, occlude=0.0, band=0, cell=128):
     """ValueError unless the parameters of ``LucidDream`` (and the probability ``p`` of train_online.py --lucid) are inside their limits
     (host only)"""
     for name, v, lo, hi in (("grow", grow, 0, MAX_GROW), ("radius", radius, 1, LUCID_MAX_RADIUS), ("passes", passes, 0, LUCID_MAX_PASSES),
                             ("offset", offset, 0, 255), ("band", band, 0, LUCID_MAX_BAND), ("cell", cell, LUCID_MIN_CELL, LUCID_MAX_CELL)):
-        if not _is_int(v):
-            raise ValueError("lucid: %s must be an integer, got %r" % (name, v))
-        if not lo <= v <= hi:
-            raise ValueError("lucid: %s %d (%d..%d)" % (name, v, lo, hi))
+        g.check_int(name, v, lo, hi, "lucid")
     if cell & (cell - 1):
         raise ValueError("lucid: cell %d (a power of two in %d..%d)" % (cell, LUCID_MIN_CELL, LUCID_MAX_CELL))
     for name, v, hi in (("p", p, 1.0), ("fg_shift", fg_shift, 4.0), ("bg_shift", bg_shift, 1.0), ("gain", gain, 1.0), ("deform", deform, 1.0),
                         ("occlude", occlude, 1.0)):
-        if not _is_num(v) or not 0.0 <= v <= hi:
-            raise ValueError("lucid: %s %r (a number in 0..%g)" % (name, v, hi))
+        g.check_number(name, v, 0, hi, "lucid")
 
 
 def field_shape(h, w, cell):
     """(GH, GW) of the deformation lattice of an h x w frame: control points every ``cell`` pixels, one row and one column past the last
     pixel's cell"""
     check_lucid(cell=cell)
-    if not (_is_int(h) and _is_int(w) and h >= 1 and w >= 1):
-        raise ValueError("lucid: field_shape of %r x %r" % (h, w))
+    g.check_int("field_shape's h", h, 1, None, "lucid")
+    g.check_int("field_shape's w", w, 1, None, "lucid")
     s = int(cell).bit_length() - 1
     return ((int(h) - 1) >> s) + 2, ((int(w) - 1) >> s) + 2
 
@@ -80,27 +69,14 @@ def affine_inverse(cx, cy, rot=0.0, sc=1.0, dx=0.0, dy=0.0, mirror=False):
     return [v + 0.0 for v in m]                    # (-0.0 -> 0.0)
 
 
-def _need_cuda(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("osvos_pytorch_amd.lucid needs CUDA (ROCm) tensors (%s); there is no CPU fallback" % what)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _frame(t, what, max_side):
-    _need_cuda(t, what)
-    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
-        raise ValueError("%s must be a uint8 [H,W,3] tensor, got %s %s" % (what, t.dtype, tuple(t.shape)))
-    h, w = int(t.shape[0]), int(t.shape[1])
-    if not (1 <= h <= max_side and 1 <= w <= max_side):
-        raise ValueError("%s of %s: sides 1..%d" % (what, tuple(t.shape), max_side))
-    return t.contiguous()
+    """uint8 [H,W,3] -> the contiguous frame, [H,W,3]"""
+    g.need_cuda(t, what, "lucid")
+    return g.frames(t, what, max_side, batch=False)[0]
 
 
 def _plane(t, like, what):
-    _need_cuda(t, what)
+    g.need_cuda(t, what, "lucid")
     if t.dtype != torch.uint8 or tuple(t.shape) != tuple(like.shape[:2]) or t.device != like.device:
         raise ValueError("%s must be a uint8 %s tensor on the device of the frame, got %s %s" % (what, tuple(like.shape[:2]), t.dtype, tuple(t.shape)))
     return t.contiguous()
@@ -114,16 +90,10 @@ def inpaint(frame_u8, hole_u8, radius=2, passes=3, ws=None):
     f = _frame(frame_u8, "frame_u8", SQDIST_MAX_SIDE)
     hole = _plane(hole_u8, f, "hole_u8")
     h, w = int(f.shape[0]), int(f.shape[1])
-    need = int(lib().osvos_lucid_inpaint_ws_bytes(h, w, int(passes)))
-    if need == 0:
-        raise ValueError("lucid: no workspace size for %d x %d with %d passes" % (h, w, passes))
-    if ws is None or ws.numel() * ws.element_size() < need or ws.device != f.device:
-        ws = torch.empty((need + 3) // 4, device=f.device, dtype=torch.int32)
+    ws = g.workspace(lib().osvos_lucid_inpaint_ws_bytes(h, w, int(passes)), f.device, ws, "%d x %d with %d passes" % (h, w, passes), "lucid",
+                     dtype=torch.int32)
     out = torch.empty_like(f)
-    vp = C.c_void_p
-    with torch.cuda.device(f.device):
-        check(lib().osvos_lucid_inpaint(vp(f.data_ptr()), vp(hole.data_ptr()), vp(out.data_ptr()), h, w, int(radius), int(passes), vp(ws.data_ptr()),
-                                        _stream()), "lucid_inpaint")
+    g.call("lucid_inpaint", f.device, g.ptr(f), g.ptr(hole), g.ptr(out), h, w, int(radius), int(passes), g.ptr(ws))
     return out
 
 
@@ -159,12 +129,9 @@ def compose(frame_u8, mask_u8, bg_u8, matrices, tones, meanval=MEANVAL, occluder
     mean = (C.c_float * 3)(*meanval)
     vp = C.c_void_p
     if occluders is None and field is None and band == 0:
-        with torch.cuda.device(f.device):
-            check(lib().osvos_lucid_compose(vp(f.data_ptr()), vp(mask.data_ptr()), vp(bg.data_ptr()), vp(m.ctypes.data), vp(t.ctypes.data), mean,
-                                            vp(image.data_ptr()), vp(gt.data_ptr()), n, h, w, _stream()), "lucid_compose")
+        g.call("lucid_compose", f.device, g.ptr(f), g.ptr(mask), g.ptr(bg), vp(m.ctypes.data), vp(t.ctypes.data), mean, g.ptr(image), g.ptr(gt), n, h, w)
         return image, gt
-    if not _is_int(band) or not 0 <= band <= LUCID_MAX_BAND:
-        raise ValueError("lucid: band %r (an integer in 0..%d)" % (band, LUCID_MAX_BAND))
+    g.check_int("band", band, 0, LUCID_MAX_BAND, "lucid")
     occ = None
     if occluders is not None:
         occ = np.asarray(occluders)
@@ -189,14 +156,9 @@ def compose(frame_u8, mask_u8, bg_u8, matrices, tones, meanval=MEANVAL, occluder
         if d.data_ptr() % 4:
             raise ValueError("lucid: field must be 4-byte aligned")
     need = int(lib().osvos_lucid_compose_ex_ws_bytes(n, h, w, int(band)))
-    if need and (ws is None or not isinstance(ws, torch.Tensor) or ws.device != f.device or ws.data_ptr() % 8
-                 or ws.numel() * ws.element_size() < need):
-        ws = torch.empty((need + 7) // 8, device=f.device, dtype=torch.int64)
-    with torch.cuda.device(f.device):
-        check(lib().osvos_lucid_compose_ex(vp(f.data_ptr()), vp(mask.data_ptr()), vp(bg.data_ptr()), vp(m.ctypes.data), vp(t.ctypes.data),
-                                           vp(occ.ctypes.data) if occ is not None else None, vp(d.data_ptr()) if d is not None else None, int(cell),
-                                           int(band), mean, vp(image.data_ptr()), vp(gt.data_ptr()), n, h, w,
-                                           vp(ws.data_ptr()) if need else None, _stream()), "lucid_compose_ex")
+    ws = g.workspace(need, f.device, ws, dtype=torch.int64, align=8) if need else None      # (0: no band, no label plane)
+    g.call("lucid_compose_ex", f.device, g.ptr(f), g.ptr(mask), g.ptr(bg), vp(m.ctypes.data), vp(t.ctypes.data),
+           vp(occ.ctypes.data) if occ is not None else None, g.ptr(d), int(cell), int(band), mean, g.ptr(image), g.ptr(gt), n, h, w, g.ptr(ws))
     return image, gt
 
 
@@ -287,16 +249,15 @@ class LucidDream(object):
         return [fg, bg], tones, field, occ
 
     def batch(self, n):
-        if not _is_int(n) or not 1 <= n <= LUCID_MAX_BATCH:
-            raise ValueError("lucid: batch of %r (1..%d)" % (n, LUCID_MAX_BATCH))
+        g.check_int("batch", n, 1, LUCID_MAX_BATCH, "lucid")
         draws = [self.draw() for _ in range(n)]
         M, T = [d[0] for d in draws], [d[1] for d in draws]
         if not (self.deform > 0 or self.occlude > 0 or self.band):
             image, gt = compose(self.frame, self.mask, self.bg, M, T, self.meanval)
             return {'image': image, 'gt': gt}
         if self.band and self.ws is None:
-            need = int(lib().osvos_lucid_compose_ex_ws_bytes(LUCID_MAX_BATCH, self.h, self.w, self.band))
-            self.ws = torch.empty((need + 7) // 8, device=self.frame.device, dtype=torch.int64)
+            self.ws = g.workspace(lib().osvos_lucid_compose_ex_ws_bytes(LUCID_MAX_BATCH, self.h, self.w, self.band), self.frame.device,
+                                  what="%d x %d with band %d" % (self.h, self.w, self.band), prefix="lucid", dtype=torch.int64)
         image, gt = compose(self.frame, self.mask, self.bg, M, T, self.meanval,
                             occluders=[d[3] for d in draws] if self.occlude > 0 else None,
                             field=np.asarray([d[2] for d in draws], np.int16) if self.deform > 0 else None, cell=self.deform_cell,

@@ -15,15 +15,13 @@ with ``tta.fuse_views`` (bilinear, on the device).  Integer dot products: the re
 The default parameters are STARTING VALUES, NOT TUNED ON DAVIS (no dataset was at hand when this was written), and no accuracy claim is
 made for them: tune them on a validation split before quoting a score.
 """
-import ctypes as C
-import math
 import sys
 
-import numpy as np
 import torch
 
+from . import _glue as g
 from . import tta
-from ._lib import MATCH_MAX_C, MATCH_MAX_P, check, lib
+from ._lib import MATCH_MAX_C, MATCH_MAX_P, lib
 from .autograd import FEATURE_LAYERS
 
 _STRIDE = {3: 2, 6: 4, 9: 8, 12: 16}      # conv2_2, conv3_3, conv4_3, conv5_3: 2^stage under ceil-mode pooling
@@ -31,25 +29,16 @@ _STRIDE = {3: 2, 6: 4, 9: 8, 12: 16}      # conv2_2, conv3_3, conv4_3, conv5_3: 
 
 def stride_of(layer):
     """pixels per feature cell of trunk tensor ``layer`` (3, 6, 9 or 12)"""
-    if isinstance(layer, bool) or not isinstance(layer, (int, np.integer)) or int(layer) not in FEATURE_LAYERS:
+    g.check_int("layer", layer, min(FEATURE_LAYERS), max(FEATURE_LAYERS), "match")
+    if int(layer) not in FEATURE_LAYERS:
         raise ValueError("match: layer %r is not one of %s (conv2_2, conv3_3, conv4_3, conv5_3)" % (layer, FEATURE_LAYERS))
     return _STRIDE[int(layer)]
 
 
 def check_match(layer, gain):
-    """ValueError unless ``layer`` is one of the four feature layers and ``gain`` a finite number >= 0 (host only)"""
+    """ValueError unless ``layer`` is one of the four feature layers and ``gain`` a finite number >= 0 (0 = off; host only)"""
     stride_of(layer)
-    if isinstance(gain, bool) or not isinstance(gain, (int, float, np.integer, np.floating)) or not math.isfinite(gain) or gain < 0:
-        raise ValueError("match: gain %r (a finite number >= 0; 0 = off)" % (gain,))
-
-
-def _need_cuda(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("osvos_pytorch_amd.match needs CUDA (ROCm) tensors (%s); there is no CPU fallback" % what)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    g.check_number("gain", gain, 0, None, "match")
 
 
 def _channels_ok(c):
@@ -59,7 +48,7 @@ def _channels_ok(c):
 def quantize(feat):
     """feat: float32 or bfloat16 CUDA tensor [..., C] (C a multiple of 64, 64..1024; e.g. the [N,h,w,C] view of ``OSVOS.forward_features``)
     -> (q int8 [..., C], rinv float32 [...]).  Enqueued only."""
-    _need_cuda(feat, "feat")
+    g.need_cuda(feat, "feat", "match")
     if feat.dtype not in (torch.float32, torch.bfloat16) or feat.dim() < 2:
         raise ValueError("feat must be a float32 or bfloat16 [..., C] tensor, got %s %s" % (feat.dtype, tuple(feat.shape)))
     c = int(feat.shape[-1])
@@ -69,45 +58,31 @@ def quantize(feat):
     p = f.numel() // c
     q = torch.empty(f.shape, device=f.device, dtype=torch.int8)
     rinv = torch.empty(f.shape[:-1], device=f.device, dtype=torch.float32)
-    vp = C.c_void_p
-    with torch.cuda.device(f.device):
-        check(lib().osvos_match_quantize(vp(f.data_ptr()), 1 if f.dtype == torch.bfloat16 else 0, vp(q.data_ptr()), vp(rinv.data_ptr()), p, c, _stream()),
-              "match_quantize")
+    g.call("match_quantize", f.device, g.ptr(f), 1 if f.dtype == torch.bfloat16 else 0, g.ptr(q), g.ptr(rinv), p, c)
     return q, rinv
 
 
 def cell_labels(mask, stride):
     """mask: uint8 or bool CUDA tensor [N,H,W], [N,1,H,W] or [H,W], nonzero = object -> uint8 [N,h,w] on the ceil(H / stride) x ceil(W / stride)
     grid: 1 object, 0 background, 255 void.  Enqueued only."""
-    _need_cuda(mask, "mask")
-    if mask.dim() == 4 and mask.shape[1] == 1:
-        mask = mask[:, 0]
-    if mask.dim() == 2:
-        mask = mask[None]
-    if mask.dtype == torch.bool:
-        mask = mask.to(torch.uint8)
-    if mask.dtype != torch.uint8 or mask.dim() != 3 or mask.numel() == 0:
-        raise ValueError("mask must be a uint8 or bool [N,H,W], [N,1,H,W] or [H,W] tensor, got %s %s" % (mask.dtype, tuple(mask.shape)))
-    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or not 1 <= stride <= 64 or stride & (stride - 1):
+    g.need_cuda(mask, "mask", "match")
+    m, n, H, W = g.planes(mask, "mask", (torch.uint8, torch.bool))
+    if m.numel() == 0:
+        raise ValueError("mask of %s: no dimension may be empty" % (tuple(mask.shape),))
+    g.check_int("stride", stride, 1, 64, "match")
+    if stride & (stride - 1):
         raise ValueError("match: stride %r (a power of two, 1..64)" % (stride,))
-    m = mask.contiguous()
-    n, H, W = (int(v) for v in m.shape)
-    h, w = -(-H // int(stride)), -(-W // int(stride))
+    if m.dtype == torch.bool:
+        m = m.to(torch.uint8)
+    h, w = g.grid_shape(H, W, stride)
     label = torch.empty((n, h, w), device=m.device, dtype=torch.uint8)
-    vp = C.c_void_p
-    with torch.cuda.device(m.device):
-        check(lib().osvos_match_cell_labels(vp(m.data_ptr()), vp(label.data_ptr()), n, H, W, h, w, int(stride), _stream()), "match_cell_labels")
+    g.call("match_cell_labels", m.device, g.ptr(m), g.ptr(label), n, H, W, h, w, int(stride))
     return label
 
 
 def nearest_workspace(n, pq, pr, c, device, ws=None):
     """a uint8 CUDA tensor of at least osvos_match_ws_bytes: ``ws`` when it is large enough and on ``device``, else a new one"""
-    need = int(lib().osvos_match_ws_bytes(n, pq, pr, c))
-    if need == 0:
-        raise ValueError("match: no workspace size for N %d Pq %d Pr %d C %d" % (n, pq, pr, c))
-    if ws is None or ws.numel() < need or ws.device != device:
-        ws = torch.empty(need, device=device, dtype=torch.uint8)
-    return ws
+    return g.workspace(lib().osvos_match_ws_bytes(n, pq, pr, c), device, ws, "N %d Pq %d Pr %d C %d" % (n, pq, pr, c), "match")
 
 
 def nearest(q, rinv_q, r, rinv_r, label_r, ws=None, with_idx=False):
@@ -116,7 +91,7 @@ def nearest(q, rinv_q, r, rinv_r, label_r, ws=None, with_idx=False):
     the nearest labelled 0 (row 1); -2 for a class the bank does not hold.  ``with_idx``: also idx int32 [N,2,Pq], the smallest reference
     row that attains it (-1 for an empty class).  Enqueued only."""
     for t, what in ((q, "q"), (rinv_q, "rinv_q"), (r, "r"), (rinv_r, "rinv_r"), (label_r, "label_r")):
-        _need_cuda(t, what)
+        g.need_cuda(t, what, "match")
     if q.dtype != torch.int8 or r.dtype != torch.int8 or q.dim() != 3 or r.dim() != 3 or q.shape[2] != r.shape[2]:
         raise ValueError("q and r must be int8 [N,Pq,C] and [NR,Pr,C] tensors with the same C, got %s %s and %s %s" % (q.dtype, tuple(q.shape), r.dtype, tuple(r.shape)))
     n, pq, c = (int(v) for v in q.shape)
@@ -133,11 +108,8 @@ def nearest(q, rinv_q, r, rinv_r, label_r, ws=None, with_idx=False):
     sim = torch.empty((n, 2, pq), device=q.device, dtype=torch.float32)
     idx = torch.empty((n, 2, pq), device=q.device, dtype=torch.int32) if with_idx else None
     ws = nearest_workspace(n, pq, pr, c, q.device, ws)
-    vp = C.c_void_p
-    with torch.cuda.device(q.device):
-        check(lib().osvos_match_nearest(vp(q.data_ptr()), vp(rinv_q.data_ptr()), vp(r.data_ptr()), vp(rinv_r.data_ptr()), vp(label_r.data_ptr()),
-                                        vp(sim.data_ptr()), vp(idx.data_ptr()) if with_idx else None, vp(ws.data_ptr()), n, nr, pq, pr, c, _stream()),
-              "match_nearest")
+    g.call("match_nearest", q.device, g.ptr(q), g.ptr(rinv_q), g.ptr(r), g.ptr(rinv_r), g.ptr(label_r), g.ptr(sim), g.ptr(idx), g.ptr(ws), n, nr, pq,
+           pr, c)
     return (sim, idx) if with_idx else sim
 
 

@@ -9,11 +9,8 @@ import ctypes as C
 
 import torch
 
+from ._glue import stream as _stream
 from ._lib import F32, F32_BF16MFMA, F32_X3, check, lib
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _p(t):

@@ -12,6 +12,7 @@ import ctypes as C
 
 import torch
 
+from . import _glue
 from ._lib import check, lib
 
 
@@ -56,7 +57,7 @@ class FusedSGD(torch.optim.Optimizer):
                 buckets.setdefault((mom, first), []).append((p, g, buf, lr, wd))
         if not buckets:
             return loss
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        stream = _glue.stream()
         vp = C.c_void_p
         for (mom, first), items in buckets.items():
             n = len(items)

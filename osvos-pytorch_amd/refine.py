@@ -11,30 +11,23 @@ keeps its parameters and its workspace.  The result is a logit map of the input'
 The default parameters are STARTING VALUES, NOT TUNED ON DAVIS (no dataset was at hand when this was written): tune them on a validation
 split before quoting a score.
 """
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
-from ._lib import CRF_MAX_ITERS, CRF_MAX_RADIUS, CRF_MAX_REACH, check, lib
+from . import _glue as g
+from ._lib import CRF_MAX_ITERS, CRF_MAX_RADIUS, CRF_MAX_REACH
 
 MAX_SIDE = 16384
 
 
 def check_window(radius, dilation, iters=0):
     """ValueError unless (radius, dilation, iters) is a window osvos_crf_refine takes"""
-    for name, v in (("radius", radius), ("dilation", dilation), ("iters", iters)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError("crf: %s must be an integer, got %r" % (name, v))
-    if not 0 <= radius <= CRF_MAX_RADIUS:
-        raise ValueError("crf: radius %d (0..%d)" % (radius, CRF_MAX_RADIUS))
-    if dilation < 1:
-        raise ValueError("crf: dilation %d (>= 1)" % dilation)
+    for name, v, lo, hi in (("radius", radius, 0, CRF_MAX_RADIUS), ("dilation", dilation, 1, None), ("iters", iters, 0, CRF_MAX_ITERS)):
+        g.check_int(name, v, lo, hi, "crf")
     if radius * dilation > CRF_MAX_REACH:
         raise ValueError("crf: radius %d x dilation %d reaches %d pixels (at most %d)" % (radius, dilation, radius * dilation, CRF_MAX_REACH))
-    if not 0 <= iters <= CRF_MAX_ITERS:
-        raise ValueError("crf: iters %d (0..%d)" % (iters, CRF_MAX_ITERS))
 
 
 def window_offsets(radius, dilation):
@@ -72,64 +65,39 @@ def crf_coefficients(radius, dilation, w_appearance, w_smooth, theta_alpha, thet
     return out
 
 
-def _need_cuda(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("osvos_pytorch_amd.refine needs CUDA (ROCm) tensors (%s); there is no CPU fallback" % what)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _maps(t, what):
-    """[N,1,H,W] or [N,H,W] float32 -> the contiguous tensor (same layout)"""
-    _need_cuda(t, what)
-    if t.dtype != torch.float32 or not (t.dim() == 3 or (t.dim() == 4 and t.shape[1] == 1)):
-        raise ValueError("%s must be a float32 [N,1,H,W] or [N,H,W] tensor, got %s %s" % (what, t.dtype, tuple(t.shape)))
-    return t.contiguous()
-
-
 def refine_raw(logits, frames_u8, coeffs, iters, radius, dilation, init=None, out=None, ws=None):
     """one osvos_crf_refine call with the five coefficients given; ws: a float32 CUDA tensor of at least N H W elements, or None"""
     check_window(radius, dilation, iters)
     coeffs = tuple(float(c) for c in coeffs)
     if len(coeffs) != 5 or not all(math.isfinite(c) and c >= 0 for c in coeffs):
         raise ValueError("crf: five finite coefficients >= 0 (w_a, w_s, a_s, a_c, g_s), got %r" % (coeffs,))
-    u = _maps(logits, "logits")
-    n, h, w = int(u.shape[0]), int(u.shape[-2]), int(u.shape[-1])
-    if n < 1 or not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
-        raise ValueError("logits of %s: N >= 1 and sides 1..%d" % (tuple(u.shape), MAX_SIDE))
-    _need_cuda(frames_u8, "frames_u8")
-    if frames_u8.dim() == 3:
-        frames_u8 = frames_u8[None]
-    if frames_u8.dtype != torch.uint8 or tuple(frames_u8.shape) != (n, h, w, 3) or frames_u8.device != u.device:
+    g.need_cuda(logits, "logits", "refine")
+    u, n, h, w = g.planes(logits, "logits", (torch.float32,), MAX_SIDE, dims=(3, 4))
+    g.need_cuda(frames_u8, "frames_u8", "refine")
+    fr = g.frames(frames_u8, "frames_u8")
+    if tuple(fr.shape) != (n, h, w, 3) or fr.device != u.device:
         raise ValueError("frames_u8 must be a uint8 [%d,%d,%d,3] tensor on the logits' device ([H,W,3] for one image), got %s %s"
-                         % (n, h, w, frames_u8.dtype, tuple(frames_u8.shape)))
-    frames_u8 = frames_u8.contiguous()
+                         % (n, h, w, fr.dtype, tuple(fr.shape)))
     z0 = None
     if init is not None:
-        z0 = _maps(init, "init")
+        g.need_cuda(init, "init", "refine")
+        z0 = g.planes(init, "init", (torch.float32,), dims=(3, 4))[0]
         if z0.numel() != u.numel() or tuple(z0.shape[-2:]) != (h, w) or z0.device != u.device:
             raise ValueError("init must hold one [%d,%d] map per image on the logits' device, got %s" % (h, w, tuple(z0.shape)))
     if out is None:
         out = torch.empty_like(u)
     else:
-        _need_cuda(out, "out")
-        if out.dtype != torch.float32 or tuple(out.shape) != tuple(u.shape) or not out.is_contiguous() or out.device != u.device:
-            raise ValueError("out must be a contiguous float32 tensor of shape %s on the logits' device" % (tuple(u.shape),))
-        if out.data_ptr() == u.data_ptr() or (z0 is not None and out.data_ptr() == z0.data_ptr()):
-            raise ValueError("out must not be logits or init: an iteration reads a neighbourhood of its source")
+        g.need_cuda(out, "out", "refine")
+        # (an iteration reads a neighbourhood of its source: the result cannot be written over it)
+        g.out_buffer(out, torch.float32, u.shape, u.device, "the logits' device", alias=(("logits", u), ("init", z0)))
     if iters >= 2:
         if ws is None:
             ws = torch.empty(n * h * w, device=u.device, dtype=torch.float32)
         elif not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= n * h * w
                   and ws.device == u.device):
             raise ValueError("ws must be a contiguous float32 CUDA tensor of at least %d elements on the logits' device" % (n * h * w))
-    vp = C.c_void_p
-    with torch.cuda.device(u.device):
-        check(lib().osvos_crf_refine(vp(u.data_ptr()), vp(z0.data_ptr()) if z0 is not None else None, vp(frames_u8.data_ptr()), vp(out.data_ptr()),
-                                     vp(ws.data_ptr()) if iters >= 2 else None, n, h, w, int(iters), int(radius), int(dilation), *coeffs,
-                                     _stream()), "crf_refine")
+    g.call("crf_refine", u.device, g.ptr(u), g.ptr(z0), g.ptr(fr), g.ptr(out), g.ptr(ws) if iters >= 2 else None, n, h, w, int(iters), int(radius),
+           int(dilation), *coeffs)
     return out
 
 
@@ -157,25 +125,14 @@ class CrfRefiner(object):
         self._ws = {}
 
     def __call__(self, logits, frames_u8, init=None, out=None):
-        _need_cuda(logits, "logits")
+        g.need_cuda(logits, "logits", "refine")
         ws = None
         if self.iters >= 2:
             key = (logits.device, int(logits.numel()))
-            ws = self._ws.get(key)
-            if ws is None:
-                ws = self._ws[key] = torch.empty(max(1, int(logits.numel())), device=logits.device, dtype=torch.float32)
+            ws = self._ws[key] = g.workspace(4 * max(1, int(logits.numel())), logits.device, self._ws.get(key), dtype=torch.float32)
         return refine_raw(logits, frames_u8, self.coeffs, self.iters, self.radius, self.dilation, init=init, out=out, ws=ws)
 
 
 def parse_pair(text, n, what):
     """'4,1' -> (4.0, 1.0): n comma-separated finite numbers; ValueError otherwise"""
-    parts = [t.strip() for t in (text or "").split(",")]
-    if len(parts) != n:
-        raise ValueError("%s takes %d comma-separated numbers, got %r" % (what, n, text))
-    try:
-        vals = tuple(float(t) for t in parts)
-    except ValueError:
-        raise ValueError("%s takes %d comma-separated numbers, got %r" % (what, n, text))
-    if not all(math.isfinite(v) for v in vals):
-        raise ValueError("%s takes finite numbers, got %r" % (what, text))
-    return vals
+    return g.parse_numbers(text, (float,) * n, what, finite=True)

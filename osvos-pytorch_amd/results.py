@@ -25,24 +25,24 @@ import zlib
 import numpy as np
 import torch
 
-from ._lib import BOUNDARY_MAX_RADIUS, MAX_OBJECTS, SQDIST_MAX_SIDE, check, lib
+from . import _glue as g
+from ._lib import BOUNDARY_MAX_RADIUS, MAX_OBJECTS, SQDIST_MAX_SIDE, lib
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def _threshold_logit(threshold):
+    if not 0.0 < threshold < 1.0:
+        raise ValueError("threshold must be a probability in (0, 1)")
+    return float(np.log(threshold / (1.0 - threshold)))
 
 
 def mask_bytes(logits):
     """logits: float32 CUDA tensor [N,1,H,W] or [N,H,W] -> uint8 CUDA tensor [N,H,W] (imsave's byte image per frame)."""
-    if not logits.is_cuda:
-        raise RuntimeError("osvos_pytorch_amd.results needs CUDA (ROCm) tensors; there is no CPU fallback")
+    g.need_cuda(logits, "logits", "results")
     x = logits.detach().float().contiguous()
     n = x.shape[0]
-    count = x.numel() // n
     out = torch.empty((n,) + tuple(x.shape[-2:]), device=x.device, dtype=torch.uint8)
     scratch = torch.empty(2 * n, device=x.device, dtype=torch.int32)
-    check(lib().osvos_mask_to_bytes(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()), count, n, _stream()),
-          "mask_to_bytes")
+    g.call("mask_to_bytes", x.device, g.ptr(x), g.ptr(out), g.ptr(scratch), x.numel() // n, n)
     return out
 
 
@@ -78,22 +78,35 @@ def save_masks(fused_logits, paths):
         write_png(p, img)
 
 
+def _logits_and_truth(logits, gts, threshold):
+    """-> (logits fp32 contiguous, the ground truth likewise and on their device, the logit of ``threshold``)"""
+    g.need_cuda(logits, "logits", "results")
+    g.need_cuda(gts, "gts", "results")
+    thr = _threshold_logit(threshold)
+    x = logits.detach().float().contiguous()
+    gt = gts.detach().to(device=x.device, dtype=torch.float32).contiguous()
+    if gt.numel() != x.numel():
+        raise ValueError("logits and ground truth differ in size: %r vs %r" % (tuple(x.shape), tuple(gt.shape)))
+    return x, gt, thr
+
+
+def _frames_of(x):
+    """(N, H, W) of a stack of one-channel frames [N,..,H,W]"""
+    if x.dim() < 3:
+        raise ValueError("expected N frames of H x W, got shape %r" % (tuple(x.shape),))
+    n, h, w = int(x.shape[0]), int(x.shape[-2]), int(x.shape[-1])
+    if x.numel() != n * h * w:
+        raise ValueError("expected one channel per frame, got shape %r" % (tuple(x.shape),))
+    return n, h, w
+
+
 def jaccard(logits, gts, threshold=0.5):
     """DAVIS region measure per frame: J = |P & G| / |P | G| with P = sigmoid(logit) > threshold, G = gt > 0.5
     (J = 1 when both are empty).  logits, gts: CUDA tensors of N frames."""
-    if not (logits.is_cuda and gts.is_cuda):
-        raise RuntimeError("osvos_pytorch_amd.results needs CUDA (ROCm) tensors; there is no CPU fallback")
-    if not 0.0 < threshold < 1.0:
-        raise ValueError("threshold must be a probability in (0, 1)")
-    x = logits.detach().float().contiguous()
-    g = gts.detach().to(device=x.device, dtype=torch.float32).contiguous()
-    if g.numel() != x.numel():
-        raise ValueError("logits and ground truth differ in size: %r vs %r" % (tuple(x.shape), tuple(g.shape)))
+    x, gt, thr = _logits_and_truth(logits, gts, threshold)
     n = x.shape[0]
     counts = torch.empty(2 * n, device=x.device, dtype=torch.int64)
-    thr = float(np.log(threshold / (1.0 - threshold)))
-    check(lib().osvos_mask_iou_counts(C.c_void_p(x.data_ptr()), C.c_void_p(g.data_ptr()), C.c_void_p(counts.data_ptr()), x.numel() // n, n, thr,
-                                      _stream()), "mask_iou_counts")
+    g.call("mask_iou_counts", x.device, g.ptr(x), g.ptr(gt), g.ptr(counts), x.numel() // n, n, thr)
     c = counts.cpu().numpy().reshape(n, 2)
     return [1.0 if u == 0 else float(i) / float(u) for i, u in c]
 
@@ -136,25 +149,16 @@ def f_measure(n_fb, n_gb, fb_match, gb_match):
 
 def _jf_inputs(logits, gts, threshold):
     """jaccard's argument handling -> (logits [N,..,H,W] fp32 contiguous, gts likewise, N, H, W, logit threshold)"""
-    if not (logits.is_cuda and gts.is_cuda):
-        raise RuntimeError("osvos_pytorch_amd.results needs CUDA (ROCm) tensors; there is no CPU fallback")
-    if not 0.0 < threshold < 1.0:
-        raise ValueError("threshold must be a probability in (0, 1)")
-    x = logits.detach().float().contiguous()
-    g = gts.detach().to(device=x.device, dtype=torch.float32).contiguous()
-    if g.numel() != x.numel():
-        raise ValueError("logits and ground truth differ in size: %r vs %r" % (tuple(x.shape), tuple(g.shape)))
-    if x.dim() < 3:
-        raise ValueError("expected N frames of H x W, got shape %r" % (tuple(x.shape),))
-    n, h, w = int(x.shape[0]), int(x.shape[-2]), int(x.shape[-1])
-    if x.numel() != n * h * w:
-        raise ValueError("expected one channel per frame, got shape %r" % (tuple(x.shape),))
-    return x, g, n, h, w, float(np.log(threshold / (1.0 - threshold)))
+    x, gt, thr = _logits_and_truth(logits, gts, threshold)
+    return (x, gt) + _frames_of(x) + (thr,)
 
 
-def _enqueue_jf(x, g, n, h, w, thr, radius, ws, counts_ptr):
-    check(lib().osvos_mask_jf_counts(C.c_void_p(x.data_ptr()), C.c_void_p(g.data_ptr()), C.c_void_p(ws.data_ptr()), C.c_void_p(counts_ptr),
-                                     n, h, w, thr, radius, 0, _stream()), "mask_jf_counts")
+def _boundary_ws(n, h, w, device, ws=None):
+    return g.workspace(lib().osvos_boundary_ws_bytes(n, h, w), device, ws, "%d frames of %d x %d" % (n, h, w), "results", dtype=torch.int64)
+
+
+def _enqueue_jf(x, gt, n, h, w, thr, radius, ws, counts_ptr):
+    g.call("mask_jf_counts", x.device, g.ptr(x), g.ptr(gt), g.ptr(ws), C.c_void_p(counts_ptr), n, h, w, thr, radius, 0)
 
 
 def _scores(rows):
@@ -166,10 +170,10 @@ def _scores(rows):
 def boundary_f(logits, gts, threshold=0.5, bound_th=0.008):
     """DAVIS contour accuracy per frame: F of the boundaries of P = sigmoid(logit) > threshold and G = gt > 0.5, matched within
     ``boundary_radius(H, W, bound_th)`` pixels.  logits, gts: CUDA tensors of N frames (the arguments of ``jaccard``)."""
-    x, g, n, h, w, thr = _jf_inputs(logits, gts, threshold)
-    ws = torch.empty(lib().osvos_boundary_ws_bytes(n, h, w) // 8, device=x.device, dtype=torch.int64)
+    x, gt, n, h, w, thr = _jf_inputs(logits, gts, threshold)
+    ws = _boundary_ws(n, h, w, x.device)
     counts = torch.empty((n, 6), device=x.device, dtype=torch.int64)
-    _enqueue_jf(x, g, n, h, w, thr, boundary_radius(h, w, bound_th), ws, counts.data_ptr())
+    _enqueue_jf(x, gt, n, h, w, thr, boundary_radius(h, w, bound_th), ws, counts.data_ptr())
     return _scores(counts.cpu().numpy())[1]
 
 
@@ -181,8 +185,7 @@ class SequenceEvaluator(object):
     CHUNK = 256      # frames the count table grows by
 
     def __init__(self, threshold=0.5, bound_th=0.008):
-        if not 0.0 < threshold < 1.0:
-            raise ValueError("threshold must be a probability in (0, 1)")
+        _threshold_logit(threshold)
         self.threshold, self.bound_th = threshold, bound_th
         self.frames = 0
         self._table = None          # int64 [capacity, 6] on the device
@@ -190,7 +193,7 @@ class SequenceEvaluator(object):
         self._host = None           # (frames, rows) of the last read-back
 
     def add(self, logits, gts):
-        x, g, n, h, w, thr = _jf_inputs(logits, gts, self.threshold)
+        x, gt, n, h, w, thr = _jf_inputs(logits, gts, self.threshold)
         need = self.frames + n
         if self._table is None or self._table.device != x.device or need > self._table.shape[0]:
             if self._table is not None and self._table.device != x.device:
@@ -199,10 +202,8 @@ class SequenceEvaluator(object):
             if self._table is not None:
                 grown[:self.frames].copy_(self._table[:self.frames])      # (device to device, in stream order)
             self._table = grown
-        words = lib().osvos_boundary_ws_bytes(n, h, w) // 8
-        if self._ws is None or self._ws.numel() < words:
-            self._ws = torch.empty(words, device=x.device, dtype=torch.int64)
-        _enqueue_jf(x, g, n, h, w, thr, boundary_radius(h, w, self.bound_th), self._ws, self._table.data_ptr() + 48 * self.frames)
+        self._ws = _boundary_ws(n, h, w, x.device, self._ws)
+        _enqueue_jf(x, gt, n, h, w, thr, boundary_radius(h, w, self.bound_th), self._ws, self._table.data_ptr() + 48 * self.frames)
         self.frames = need
 
     def per_frame(self):
@@ -225,10 +226,8 @@ def merge_objects(logits, threshold=0.5):
     """logits: float32 CUDA tensor [K,N,H,W] or [K,N,1,H,W], the fused outputs of K per-object networks for N frames -> uint8 CUDA tensor
     [N,H,W]: per pixel the object (1..K) with the highest logit -- the lowest index on a tie, a NaN never wins -- or 0 (background) when
     that logit does not exceed the one of ``threshold``.  Decided on the logits: no sigmoid is computed."""
-    if not logits.is_cuda:
-        raise RuntimeError("osvos_pytorch_amd.results needs CUDA (ROCm) tensors; there is no CPU fallback")
-    if not 0.0 < threshold < 1.0:
-        raise ValueError("threshold must be a probability in (0, 1)")
+    g.need_cuda(logits, "logits", "results")
+    thr = _threshold_logit(threshold)
     x = logits.detach().float().contiguous()
     if x.dim() == 5 and x.shape[2] == 1:
         x = x[:, :, 0]
@@ -238,8 +237,7 @@ def merge_objects(logits, threshold=0.5):
     if not 1 <= k <= MAX_OBJECTS:
         raise ValueError("%d objects; the library is built for 1..%d" % (k, MAX_OBJECTS))
     out = torch.empty((n, h, w), device=x.device, dtype=torch.uint8)
-    thr = float(np.log(threshold / (1.0 - threshold)))
-    check(lib().osvos_merge_objects(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), n, k, h, w, thr, _stream()), "merge_objects")
+    g.call("merge_objects", x.device, g.ptr(x), g.ptr(out), n, k, h, w, thr)
     return out
 
 
@@ -295,13 +293,13 @@ class MultiObjectEvaluator(object):
         self._host = None           # (frames, table) of the last read-back
 
     def add(self, pred_labels, gt_labels):
-        if not (pred_labels.is_cuda and gt_labels.is_cuda):
-            raise RuntimeError("osvos_pytorch_amd.results needs CUDA (ROCm) tensors; there is no CPU fallback")
+        g.need_cuda(pred_labels, "pred_labels", "results")
+        g.need_cuda(gt_labels, "gt_labels", "results")
         if pred_labels.dtype != torch.uint8 or gt_labels.dtype != torch.uint8:
             raise ValueError("label maps are uint8 tensors, got %s and %s" % (pred_labels.dtype, gt_labels.dtype))
         p = pred_labels.detach().contiguous()
-        g = gt_labels.detach().to(device=p.device).contiguous()
-        if p.dim() < 2 or g.numel() != p.numel():
+        gt = gt_labels.detach().to(device=p.device).contiguous()
+        if p.dim() < 2 or gt.numel() != p.numel():
             raise ValueError("prediction and ground truth differ in size: %r vs %r" % (tuple(pred_labels.shape), tuple(gt_labels.shape)))
         h, w = int(p.shape[-2]), int(p.shape[-1])
         n = p.numel() // (h * w)
@@ -316,12 +314,10 @@ class MultiObjectEvaluator(object):
             self._table = grown
         if self._table.device != p.device:
             raise ValueError("all frames of a sequence must live on one device")
-        words = lib().osvos_labels_jf_ws_bytes(n, k, h, w) // 8
-        if self._ws is None or self._ws.numel() < words:
-            self._ws = torch.empty(words, device=p.device, dtype=torch.int64)
-        check(lib().osvos_labels_jf_counts(C.c_void_p(p.data_ptr()), C.c_void_p(g.data_ptr()), C.c_void_p(self._ws.data_ptr()),
-                                           C.c_void_p(self._table.data_ptr() + 48 * k * self.frames), n, k, h, w,
-                                           boundary_radius(h, w, self.bound_th), 0, _stream()), "labels_jf_counts")
+        self._ws = g.workspace(lib().osvos_labels_jf_ws_bytes(n, k, h, w), p.device, self._ws, "%d frames x %d objects of %d x %d" % (n, k, h, w),
+                               "results", dtype=torch.int64)
+        g.call("labels_jf_counts", p.device, g.ptr(p), g.ptr(gt), g.ptr(self._ws), C.c_void_p(self._table.data_ptr() + 48 * k * self.frames), n, k, h, w,
+               boundary_radius(h, w, self.bound_th), 0)
         self.frames = need
 
     def _counts(self):
@@ -358,36 +354,24 @@ class MultiObjectEvaluator(object):
 
 def _component_inputs(logits, threshold, connectivity):
     """_jf_inputs' argument handling without a ground truth -> (logits fp32 contiguous, N, H, W, logit threshold)"""
-    if not logits.is_cuda:
-        raise RuntimeError("osvos_pytorch_amd.results needs CUDA (ROCm) tensors; there is no CPU fallback")
-    if not 0.0 < threshold < 1.0:
-        raise ValueError("threshold must be a probability in (0, 1)")
+    thr = _threshold_logit(threshold)
     if connectivity not in (4, 8):
         raise ValueError("connectivity must be 4 or 8, got %r" % (connectivity,))
+    g.need_cuda(logits, "logits", "results")
     x = logits.detach().float().contiguous()
-    if x.dim() < 3:
-        raise ValueError("expected N frames of H x W, got shape %r" % (tuple(x.shape),))
-    n, h, w = int(x.shape[0]), int(x.shape[-2]), int(x.shape[-1])
-    if x.numel() != n * h * w:
-        raise ValueError("expected one channel per frame, got shape %r" % (tuple(x.shape),))
-    return x, n, h, w, float(np.log(threshold / (1.0 - threshold)))
+    return (x,) + _frames_of(x) + (thr,)
 
 
 def _components_ws(n, h, w, device, ws=None):
-    words = (lib().osvos_components_ws_bytes(n, h, w) + 7) // 8
-    if words == 0:
-        raise ValueError("%d frames of %d x %d: the library takes 1..65535 frames of fewer than 2^31 - 1 pixels" % (n, h, w))
-    if ws is None or ws.numel() < words or ws.device != device:
-        ws = torch.empty(words, device=device, dtype=torch.int64)
-    return ws
+    return g.workspace(lib().osvos_components_ws_bytes(n, h, w), device, ws,
+                       "%d frames of %d x %d (the library takes 1..65535 frames of fewer than 2^31 - 1 pixels)" % (n, h, w), "results", dtype=torch.int64)
 
 
 def _enqueue_components(x, n, h, w, thr, connectivity, ws):
     labels = torch.empty((n, h, w), device=x.device, dtype=torch.int32)
     area = torch.empty((n, h, w), device=x.device, dtype=torch.int32)
     stats = torch.empty((n, 4), device=x.device, dtype=torch.int64)
-    check(lib().osvos_mask_components(C.c_void_p(x.data_ptr()), C.c_void_p(labels.data_ptr()), C.c_void_p(area.data_ptr()), C.c_void_p(stats.data_ptr()),
-                                      C.c_void_p(ws.data_ptr()), n, h, w, thr, connectivity, _stream()), "mask_components")
+    g.call("mask_components", x.device, g.ptr(x), g.ptr(labels), g.ptr(area), g.ptr(stats), g.ptr(ws), n, h, w, thr, connectivity)
     return labels, area, stats
 
 
@@ -400,8 +384,7 @@ def components(logits, threshold=0.5, connectivity=8):
 
 
 def _seed_bytes(seed, device, frames, h, w):
-    if not torch.is_tensor(seed) or not seed.is_cuda:
-        raise RuntimeError("osvos_pytorch_amd.results needs CUDA (ROCm) tensors; there is no CPU fallback")
+    g.need_cuda(seed, "seed", "results")
     s = seed.detach().to(device=device)
     s = s.contiguous() if s.dtype == torch.uint8 else (s != 0).to(torch.uint8).contiguous()
     if s.numel() != frames * h * w or tuple(s.shape[-2:]) != (h, w):
@@ -412,10 +395,8 @@ def _seed_bytes(seed, device, frames, h, w):
 def _enqueue_select(x, labels, area, stats, seed, chain, seed_radius, min_area, keep_largest, fill, thr, ws, n, h, w):
     out = torch.empty_like(x)
     kept = torch.empty((n, h, w), device=x.device, dtype=torch.uint8)
-    check(lib().osvos_components_select(C.c_void_p(x.data_ptr()), C.c_void_p(labels.data_ptr()), C.c_void_p(area.data_ptr()), C.c_void_p(stats.data_ptr()),
-                                        C.c_void_p(seed.data_ptr()) if seed is not None else None, 1 if chain else 0, int(seed_radius), int(min_area),
-                                        1 if keep_largest else 0, float(fill), C.c_void_p(out.data_ptr()), C.c_void_p(kept.data_ptr()),
-                                        C.c_void_p(ws.data_ptr()), n, h, w, thr, _stream()), "components_select")
+    g.call("components_select", x.device, g.ptr(x), g.ptr(labels), g.ptr(area), g.ptr(stats), g.ptr(seed), 1 if chain else 0, int(seed_radius),
+           int(min_area), 1 if keep_largest else 0, float(fill), g.ptr(out), g.ptr(kept), g.ptr(ws), n, h, w, thr)
     return out, kept
 
 
@@ -457,10 +438,8 @@ class ComponentTracker(object):
     [1,H,W]: read it, move it (``flow.MotionCompensator.warp``) and assign it back when the object moves farther than ``radius`` a frame."""
 
     def __init__(self, first_mask, radius, threshold=0.5, connectivity=8, min_area=0):
-        if not torch.is_tensor(first_mask) or not first_mask.is_cuda:
-            raise RuntimeError("osvos_pytorch_amd.results needs CUDA (ROCm) tensors; there is no CPU fallback")
-        if not 0.0 < threshold < 1.0:
-            raise ValueError("threshold must be a probability in (0, 1)")
+        g.need_cuda(first_mask, "first_mask", "results")
+        _threshold_logit(threshold)
         if connectivity not in (4, 8):
             raise ValueError("connectivity must be 4 or 8, got %r" % (connectivity,))
         m = first_mask.detach()
@@ -513,30 +492,21 @@ class ComponentTracker(object):
 
 # ---- distance maps ----------------------------------------------------------------------------------------------------------------------
 
-def _mask_bytes_nhw(mask, who):
-    """a mask tensor [N,1,H,W], [N,H,W] or [H,W] (uint8, bool or float; non-zero = set) -> (uint8 contiguous [N,H,W], N, H, W)"""
-    if not torch.is_tensor(mask) or not mask.is_cuda:
-        raise RuntimeError("osvos_pytorch_amd.results needs CUDA (ROCm) tensors; there is no CPU fallback")
-    m = mask.detach()
-    if m.dim() == 2:
-        m = m[None]
-    if m.dim() == 4 and m.shape[1] == 1:
-        m = m[:, 0]
-    if m.dim() != 3:
-        raise ValueError("%s: expected a mask of shape [N,1,H,W], [N,H,W] or [H,W], got %r" % (who, tuple(mask.shape)))
-    m = m.contiguous() if m.dtype == torch.uint8 else (m != 0).to(torch.uint8).contiguous()
-    n, h, w = (int(v) for v in m.shape)
+def mask_bytes_nhw(mask, who, module="results"):
+    """a mask tensor [N,1,H,W], [N,H,W] or [H,W] (uint8, bool or float; non-zero = set) -> (uint8 contiguous [N,H,W], N, H, W), for the
+    distance kernels: 1..65535 frames with sides of 1..SQDIST_MAX_SIDE.  ``who``: the calling function, for the messages"""
+    g.need_cuda(mask, who + "'s mask", module)
+    m, n, h, w = g.planes(mask.detach(), who + "'s mask")
     if not (1 <= n <= 65535 and 1 <= h <= SQDIST_MAX_SIDE and 1 <= w <= SQDIST_MAX_SIDE):
         raise ValueError("%s: %d frames of %d x %d: the library takes 1..65535 frames with sides of 1..%d" % (who, n, h, w, SQDIST_MAX_SIDE))
-    return m, n, h, w
+    return (m if m.dtype == torch.uint8 else (m != 0).to(torch.uint8)).view(n, h, w), n, h, w
 
 
 def distance_map(mask, invert=False):
     """Exact squared Euclidean distance of every pixel to the nearest set pixel of its frame (``invert``: to the nearest pixel that is NOT
     set): int32 CUDA tensor [N,H,W], ``_lib.SQDIST_NONE`` everywhere in a frame without such a pixel (``osvos_mask_sqdist``).  Enqueued only."""
-    m, n, h, w = _mask_bytes_nhw(mask, "distance_map")
+    m, n, h, w = mask_bytes_nhw(mask, "distance_map")
     out = torch.empty((n, h, w), device=m.device, dtype=torch.int32)
-    ws = torch.empty((lib().osvos_mask_sqdist_ws_bytes(n, h, w) + 3) // 4, device=m.device, dtype=torch.int32)
-    check(lib().osvos_mask_sqdist(C.c_void_p(m.data_ptr()), 1 if invert else 0, C.c_void_p(out.data_ptr()), n, h, w, C.c_void_p(ws.data_ptr()),
-                                  _stream()), "mask_sqdist")
+    ws = g.workspace(lib().osvos_mask_sqdist_ws_bytes(n, h, w), m.device, what="%d frames of %d x %d" % (n, h, w), prefix="results", dtype=torch.int32)
+    g.call("mask_sqdist", m.device, g.ptr(m), 1 if invert else 0, g.ptr(out), n, h, w, g.ptr(ws))
     return out

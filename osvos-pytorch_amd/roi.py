@@ -17,19 +17,11 @@ import math
 
 import torch
 
-from ._lib import ROI_BOX_PARTS, check, lib
+from . import _glue as g
+from ._lib import ROI_BOX_PARTS
 from .augment import MEANVAL
 
 MAX_SIDE = 16384          # the integer taps stay inside int32 up to here (csrc/tta_tap.h)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _need_cuda(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("osvos_pytorch_amd.roi needs CUDA (ROCm) tensors (%s); there is no CPU fallback" % what)
 
 
 def _size(size, what):
@@ -44,11 +36,9 @@ def _size(size, what):
 
 def check_zoom(margin_pct, margin_px, max_zoom):
     """ValueError unless the margins are ints >= 0 and max_zoom is a finite number >= 1"""
-    for v, what in ((margin_pct, "margin_pct"), (margin_px, "margin_px")):
-        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 31:
-            raise ValueError("%s takes an int >= 0, got %r" % (what, v))
-    if isinstance(max_zoom, bool) or not isinstance(max_zoom, (int, float)) or not (math.isfinite(max_zoom) and max_zoom >= 1):
-        raise ValueError("max_zoom takes a finite number >= 1, got %r" % (max_zoom,))
+    g.check_int("margin_pct", margin_pct, 0, 2 ** 31 - 1, "zoom", numpy=False)
+    g.check_int("margin_px", margin_px, 0, 2 ** 31 - 1, "zoom", numpy=False)
+    g.check_number("max_zoom", max_zoom, 1, None, "zoom", numpy=False)
 
 
 def min_size(size, canvas, max_zoom):
@@ -57,10 +47,8 @@ def min_size(size, canvas, max_zoom):
 
 
 def _box(box, n, device):
-    _need_cuda(box, "box")
-    if box.dtype != torch.int32 or tuple(box.shape) != (n, 4) or not box.is_contiguous() or box.device != device:
-        raise ValueError("box must be a contiguous int32 [%d,4] tensor on the frames' device" % n)
-    return box
+    g.need_cuda(box, "box", "roi")
+    return g.out_buffer(box, torch.int32, (n, 4), device, "the frames' device", name="box")
 
 
 def full_box(n, size, device):
@@ -72,77 +60,40 @@ def full_box(n, size, device):
 def mask_box(mask, canvas, margin_pct=25, margin_px=8, max_zoom=2.0, out=None):
     """mask: bool or uint8 CUDA tensor [N,H,W], [N,1,H,W] or [H,W] (non-zero = object), canvas: (Hc, Wc) -> int32 [N,4] on the device, one
     (x0, y0, bw, bh) per frame; an empty mask gives the full frame.  out: a contiguous int32 [N,4] tensor to write into."""
-    _need_cuda(mask, "mask")
-    if mask.dim() == 4 and mask.shape[1] == 1:
-        mask = mask[:, 0]
-    elif mask.dim() == 2:
-        mask = mask[None]
-    if mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 3:
-        raise ValueError("mask must be a bool or uint8 [N,H,W], [N,1,H,W] or [H,W] tensor")
-    mask = mask.contiguous()
-    n, (h, w) = int(mask.shape[0]), _size(mask.shape[1:], "the mask")
+    g.need_cuda(mask, "mask", "roi")
+    mask, n, h, w = g.planes(mask, "mask", (torch.bool, torch.uint8))
+    _size((h, w), "the mask")
     hc, wc = _size(canvas, "the canvas")
     check_zoom(margin_pct, margin_px, max_zoom)
     min_h, min_w = min_size((h, w), (hc, wc), max_zoom)
-    if out is None:
-        out = torch.empty((n, 4), device=mask.device, dtype=torch.int32)
-    else:
-        _box(out, n, mask.device)
+    out = torch.empty((n, 4), device=mask.device, dtype=torch.int32) if out is None else _box(out, n, mask.device)
     ws = torch.empty((n * ROI_BOX_PARTS * 4,), device=mask.device, dtype=torch.int32)      # (contents irrelevant: the call keeps no state)
-    vp = C.c_void_p
-    check(lib().osvos_roi_box(vp(mask.data_ptr()), vp(out.data_ptr()), n, h, w, hc, wc, margin_pct, margin_px, min_w, min_h, vp(ws.data_ptr()),
-                              _stream()), "roi_box")
+    g.call("roi_box", mask.device, g.ptr(mask), g.ptr(out), n, h, w, hc, wc, margin_pct, margin_px, min_w, min_h, g.ptr(ws))
     return out
-
-
-def _frames(frames_u8):
-    _need_cuda(frames_u8, "frames_u8")
-    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
-        raise ValueError("frames_u8 must be a uint8 [N,H,W,3] tensor")
-    return frames_u8.contiguous()
 
 
 def crop_view(frames_u8, box, canvas, meanval=MEANVAL, out=None):
     """frames_u8: uint8 CUDA tensor [N,H,W,3] (BGR, as decoded), box: int32 [N,4] on the device, canvas: (Hc, Wc) -> float32 [N,3,Hc,Wc]: the
     bilinear resample of each frame's box minus meanval.  out: a contiguous float32 CUDA tensor of that shape to write into."""
-    frames_u8 = _frames(frames_u8)
-    n, h, w = int(frames_u8.shape[0]), int(frames_u8.shape[1]), int(frames_u8.shape[2])
+    g.need_cuda(frames_u8, "frames_u8", "roi")
+    frames_u8 = g.frames(frames_u8, "frames_u8", single=False)
+    n, h, w = (int(v) for v in frames_u8.shape[:3])
     _box(box, n, frames_u8.device)
     hc, wc = _size(canvas, "the canvas")
-    if out is None:
-        out = torch.empty((n, 3, hc, wc), device=frames_u8.device, dtype=torch.float32)
-    else:
-        _need_cuda(out, "out")
-        if out.dtype != torch.float32 or tuple(out.shape) != (n, 3, hc, wc) or not out.is_contiguous() or out.device != frames_u8.device:
-            raise ValueError("out must be a contiguous float32 [%d,3,%d,%d] tensor on the frames' device" % (n, hc, wc))
-    mean = (C.c_float * 3)(*meanval)
-    vp = C.c_void_p
-    check(lib().osvos_roi_view(vp(frames_u8.data_ptr()), vp(box.data_ptr()), mean, vp(out.data_ptr()), n, h, w, hc, wc, _stream()), "roi_view")
+    out = g.out_buffer(out, torch.float32, (n, 3, hc, wc), frames_u8.device, "the frames' device", module="roi")
+    g.call("roi_view", frames_u8.device, g.ptr(frames_u8), g.ptr(box), (C.c_float * 3)(*meanval), g.ptr(out), n, h, w, hc, wc)
     return out
 
 
 def paste(logits, box, size, outside=-20.0, out=None):
     """logits: float32 CUDA tensor [N,1,Hc,Wc] or [N,Hc,Wc], box: int32 [N,4] on the device, size: (H, W) of the frame -> float32 [N,1,H,W]:
     the map resampled onto each frame's box, ``outside`` elsewhere.  out: a contiguous float32 [N,1,H,W] CUDA tensor to write into."""
-    _need_cuda(logits, "logits")
-    if logits.dim() == 4 and logits.shape[1] == 1:
-        logits = logits[:, 0]
-    if logits.dtype != torch.float32 or logits.dim() != 3:
-        raise ValueError("logits must be a float32 [N,1,Hc,Wc] or [N,Hc,Wc] tensor")
-    logits = logits.contiguous()
-    n, hc, wc = (int(v) for v in logits.shape)
+    g.need_cuda(logits, "logits", "roi")
+    logits, n, hc, wc = g.planes(logits, "logits", (torch.float32,), dims=(3, 4))
     _box(box, n, logits.device)
     h, w = _size(size, "the frame size")
-    if out is None:
-        out = torch.empty((n, 1, h, w), device=logits.device, dtype=torch.float32)
-    else:
-        _need_cuda(out, "out")
-        if out.dtype != torch.float32 or tuple(out.shape) != (n, 1, h, w) or not out.is_contiguous() or out.device != logits.device:
-            raise ValueError("out must be a contiguous float32 [%d,1,%d,%d] tensor on the logits' device" % (n, h, w))
-        if out.data_ptr() == logits.data_ptr():
-            raise ValueError("out must not be the logits")
-    vp = C.c_void_p
-    check(lib().osvos_roi_paste(vp(logits.data_ptr()), vp(box.data_ptr()), vp(out.data_ptr()), n, hc, wc, h, w, float(outside), _stream()), "roi_paste")
+    out = g.out_buffer(out, torch.float32, (n, 1, h, w), logits.device, "the logits' device", alias=(("the logits", logits),), module="roi")
+    g.call("roi_paste", logits.device, g.ptr(logits), g.ptr(box), g.ptr(out), n, hc, wc, h, w, float(outside))
     return out
 
 
@@ -160,11 +111,9 @@ class RoiZoom(object):
         self._full = {}          # (N, H, W, device) -> the full-frame box tensor
 
     def __call__(self, frames_u8, prev_mask=None):
-        _need_cuda(frames_u8, "frames_u8")
-        if frames_u8.dim() == 3:
-            frames_u8 = frames_u8[None]
-        frames_u8 = _frames(frames_u8)
-        n, h, w = int(frames_u8.shape[0]), int(frames_u8.shape[1]), int(frames_u8.shape[2])
+        g.need_cuda(frames_u8, "frames_u8", "roi")
+        frames_u8 = g.frames(frames_u8, "frames_u8")
+        n, h, w = (int(v) for v in frames_u8.shape[:3])
         canvas = self.canvas or (h, w)
         if prev_mask is None:
             key = (n, h, w, frames_u8.device)
@@ -172,7 +121,7 @@ class RoiZoom(object):
                 self._full[key] = full_box(n, (h, w), frames_u8.device)
             box = self._full[key]
         else:
-            _need_cuda(prev_mask, "prev_mask")
+            g.need_cuda(prev_mask, "prev_mask", "roi")
             if tuple(prev_mask.shape[-2:]) != (h, w) or prev_mask.numel() != n * h * w:
                 raise ValueError("prev_mask %s does not fit %d frames of %d x %d" % (tuple(prev_mask.shape), n, h, w))
             box = mask_box(prev_mask.reshape(n, h, w), canvas, self.margin_pct, self.margin_px, self.max_zoom)

@@ -14,66 +14,33 @@ workspaces on the device.  Nothing is read back.
 The default parameters are STARTING VALUES, NOT TUNED ON DAVIS (no dataset was at hand when this was written), and no accuracy claim is
 made for them: tune them on a validation split before quoting a score.
 """
-import ctypes as C
-
-import numpy as np
 import torch
 
-from ._lib import (SUPERPIXELS_MAX_CELL, SUPERPIXELS_MAX_COMPACTNESS, SUPERPIXELS_MAX_ITERS, SUPERPIXELS_MAX_K, SUPERPIXELS_MAX_SIDE, check, lib)
+from . import _glue as g
+from ._glue import grid_shape  # noqa: F401  (superpixels.grid_shape: the cells of a frame; K = GH * GW superpixels)
+from ._lib import (SUPERPIXELS_MAX_CELL, SUPERPIXELS_MAX_COMPACTNESS, SUPERPIXELS_MAX_ITERS, SUPERPIXELS_MAX_K, SUPERPIXELS_MAX_SIDE, lib)
 
 
 def check_superpixels(cell, compactness, iters):
     """ValueError unless the three parameters are integers inside the limits of osvos_superpixels_slic (host only)"""
     for name, v, lo, hi in (("cell", cell, 2, SUPERPIXELS_MAX_CELL), ("compactness", compactness, 0, SUPERPIXELS_MAX_COMPACTNESS),
                             ("iters", iters, 0, SUPERPIXELS_MAX_ITERS)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError("superpixels: %s must be an integer, got %r" % (name, v))
-        if not lo <= v <= hi:
-            raise ValueError("superpixels: %s %d (%d..%d)" % (name, v, lo, hi))
-
-
-def grid_shape(h, w, cell):
-    """(GH, GW) = (ceil(h / cell), ceil(w / cell)): the cells of an h x w frame; K = GH * GW superpixels"""
-    return -(-int(h) // int(cell)), -(-int(w) // int(cell))
-
-
-def _need_cuda(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("osvos_pytorch_amd.superpixels needs CUDA (ROCm) tensors (%s); there is no CPU fallback" % what)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        g.check_int(name, v, lo, hi, "superpixels")
 
 
 def _frames(t, what):
     """[N,H,W,3] or [H,W,3] uint8 -> contiguous [N,H,W,3]"""
-    _need_cuda(t, what)
-    if t.dim() == 3:
-        t = t[None]
-    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3:
-        raise ValueError("%s must be a uint8 [N,H,W,3] or [H,W,3] tensor, got %s %s" % (what, t.dtype, tuple(t.shape)))
-    n, h, w = (int(v) for v in t.shape[:3])
-    if n < 1 or not (1 <= h <= SUPERPIXELS_MAX_SIDE and 1 <= w <= SUPERPIXELS_MAX_SIDE):
-        raise ValueError("%s of %s: N >= 1 and sides 1..%d" % (what, tuple(t.shape), SUPERPIXELS_MAX_SIDE))
-    return t.contiguous()
-
-
-def _workspace(need, what, device, ws):
-    """a uint8 CUDA tensor of at least ``need`` bytes: ``ws`` when it is large enough and on ``device``, else a new one"""
-    if need == 0:
-        raise ValueError("superpixels: no workspace size for %s" % what)
-    if ws is None or ws.numel() < need or ws.device != device:
-        ws = torch.empty(need, device=device, dtype=torch.uint8)
-    return ws
+    g.need_cuda(t, what, "superpixels")
+    return g.frames(t, what, SUPERPIXELS_MAX_SIDE)
 
 
 def slic_workspace(n, h, w, cell, device, ws=None):
-    return _workspace(int(lib().osvos_superpixels_ws_bytes(n, h, w, cell)), "%d frames of %d x %d with cell %d" % (n, h, w, cell), device, ws)
+    return g.workspace(lib().osvos_superpixels_ws_bytes(n, h, w, cell), device, ws, "%d frames of %d x %d with cell %d" % (n, h, w, cell),
+                       "superpixels")
 
 
 def pool_workspace(n, k, device, ws=None):
-    return _workspace(int(lib().osvos_superpixels_pool_ws_bytes(n, k)), "%d frames of %d labels" % (n, k), device, ws)
+    return g.workspace(lib().osvos_superpixels_pool_ws_bytes(n, k), device, ws, "%d frames of %d labels" % (n, k), "superpixels")
 
 
 def slic(frames_u8, cell=8, compactness=10, iters=5, ws=None, with_centres=False):
@@ -89,10 +56,7 @@ def slic(frames_u8, cell=8, compactness=10, iters=5, ws=None, with_centres=False
     labels = torch.empty((n, h, w), device=f.device, dtype=torch.int32)
     centres = torch.empty((n, gh * gw, 6), device=f.device, dtype=torch.int32) if with_centres else None
     ws = slic_workspace(n, h, w, cell, f.device, ws)
-    vp = C.c_void_p
-    with torch.cuda.device(f.device):
-        check(lib().osvos_superpixels_slic(vp(f.data_ptr()), vp(labels.data_ptr()), vp(centres.data_ptr()) if with_centres else None, vp(ws.data_ptr()),
-                                           n, h, w, int(cell), int(compactness), int(iters), _stream()), "superpixels_slic")
+    g.call("superpixels_slic", f.device, g.ptr(f), g.ptr(labels), g.ptr(centres), g.ptr(ws), n, h, w, int(cell), int(compactness), int(iters))
     return (labels, centres) if with_centres else labels
 
 
@@ -101,29 +65,18 @@ def pool(logits, labels, k=None, ws=None):
     -> the logits with every label's pixels replaced by the label's mean (the rule of include/osvos_hip.h: quantised to 2^-16, floor
     division), in the shape of ``logits``.  A pixel whose label is outside [0, k) keeps its logit bit for bit.  ``k`` = None takes
     labels.max() + 1, which READS BACK one number; pass k (``grid_shape``'s GH * GW for SLIC labels) to enqueue only."""
-    _need_cuda(logits, "logits")
-    _need_cuda(labels, "labels")
-    if logits.dtype != torch.float32:
-        raise ValueError("logits must be float32, got %s" % logits.dtype)
-    if not (logits.dim() in (2, 3) or (logits.dim() == 4 and logits.shape[1] == 1)):
-        raise ValueError("logits must be [N,1,H,W], [N,H,W] or [H,W], got %s" % (tuple(logits.shape),))
-    h, w = int(logits.shape[-2]), int(logits.shape[-1])
-    n = 1 if logits.dim() == 2 else int(logits.shape[0])
-    if n < 1 or not (1 <= h <= SUPERPIXELS_MAX_SIDE and 1 <= w <= SUPERPIXELS_MAX_SIDE):
-        raise ValueError("logits of %s: N >= 1 and sides 1..%d" % (tuple(logits.shape), SUPERPIXELS_MAX_SIDE))
+    g.need_cuda(logits, "logits", "superpixels")
+    g.need_cuda(labels, "labels", "superpixels")
+    x, n, h, w = g.planes(logits, "logits", (torch.float32,), SUPERPIXELS_MAX_SIDE)
     if labels.dtype != torch.int32 or labels.numel() != n * h * w or tuple(labels.shape[-2:]) != (h, w) or labels.device != logits.device:
         raise ValueError("labels must be an int32 [%d,%d,%d] tensor on the device of logits, got %s %s" % (n, h, w, labels.dtype, tuple(labels.shape)))
     if k is None:
         k = max(int(labels.max()) + 1, 1)
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= SUPERPIXELS_MAX_K:
-        raise ValueError("superpixels: k %r (an integer 1..%d)" % (k, SUPERPIXELS_MAX_K))
-    x, lab = logits.contiguous(), labels.contiguous()
+    g.check_int("k", k, 1, SUPERPIXELS_MAX_K, "superpixels")
+    lab = labels.contiguous()
     out = torch.empty_like(x)
     ws = pool_workspace(n, int(k), x.device, ws)
-    vp = C.c_void_p
-    with torch.cuda.device(x.device):
-        check(lib().osvos_superpixels_pool(vp(x.data_ptr()), vp(lab.data_ptr()), vp(out.data_ptr()), vp(ws.data_ptr()), n, h, w, int(k), _stream()),
-              "superpixels_pool")
+    g.call("superpixels_pool", x.device, g.ptr(x), g.ptr(lab), g.ptr(out), g.ptr(ws), n, h, w, int(k))
     return out
 
 
@@ -154,7 +107,7 @@ class SuperpixelSnapper(object):
             raise ValueError("SuperpixelSnapper takes the frames or their labels, one of the two")
         if labels is None:
             labels = self.labels(frames_u8)
-        _need_cuda(logits, "logits")
+        g.need_cuda(logits, "logits", "superpixels")
         gh, gw = grid_shape(logits.shape[-2], logits.shape[-1], self.cell)
         n = 1 if logits.dim() == 2 else int(logits.shape[0])
         self._pool_ws = pool_workspace(n, gh * gw, logits.device, self._pool_ws)

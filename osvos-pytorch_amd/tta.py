@@ -15,7 +15,8 @@ import math
 
 import torch
 
-from ._lib import TTA_MAX_VIEWS, check, lib, ptr_array
+from . import _glue as g
+from ._lib import TTA_MAX_VIEWS, ptr_array
 from .augment import MEANVAL
 
 MAX_SIDE = 16384          # the integer taps stay inside int32 up to here (csrc/tta.hip)
@@ -65,33 +66,15 @@ def parse_scales(text):
     return tuple(out)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _need_cuda(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("osvos_pytorch_amd.tta needs CUDA (ROCm) tensors (%s); there is no CPU fallback" % what)
-
-
 def make_view(frames_u8, hv, wv, flip=False, meanval=MEANVAL, out=None):
     """frames_u8: uint8 CUDA tensor [N,H,W,3] (BGR, as decoded) -> float32 [N,3,hv,wv]: bilinear resample minus meanval, mirrored when flip.
     out: a contiguous float32 CUDA tensor of that shape to write into (e.g. one half of a batch)."""
-    _need_cuda(frames_u8, "frames_u8")
-    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
-        raise ValueError("frames_u8 must be a uint8 [N,H,W,3] tensor")
-    frames_u8 = frames_u8.contiguous()
-    n, h, w = int(frames_u8.shape[0]), int(frames_u8.shape[1]), int(frames_u8.shape[2])
+    g.need_cuda(frames_u8, "frames_u8", "tta")
+    frames_u8 = g.frames(frames_u8, "frames_u8", single=False)
+    n, h, w = (int(v) for v in frames_u8.shape[:3])
     hv, wv = int(hv), int(wv)
-    if out is None:
-        out = torch.empty((n, 3, hv, wv), device=frames_u8.device, dtype=torch.float32)
-    else:
-        _need_cuda(out, "out")
-        if out.dtype != torch.float32 or tuple(out.shape) != (n, 3, hv, wv) or not out.is_contiguous() or out.device != frames_u8.device:
-            raise ValueError("out must be a contiguous float32 [%d,3,%d,%d] tensor on the frames' device" % (n, hv, wv))
-    mean = (C.c_float * 3)(*meanval)
-    vp = C.c_void_p
-    check(lib().osvos_tta_view(vp(frames_u8.data_ptr()), mean, vp(out.data_ptr()), n, h, w, hv, wv, int(bool(flip)), _stream()), "tta_view")
+    out = g.out_buffer(out, torch.float32, (n, 3, hv, wv), frames_u8.device, "the frames' device", module="tta")
+    g.call("tta_view", frames_u8.device, g.ptr(frames_u8), (C.c_float * 3)(*meanval), g.ptr(out), n, h, w, hv, wv, int(bool(flip)))
     return out
 
 
@@ -106,31 +89,22 @@ def fuse_views(views, flips, size, weights=None, out=None):
         raise ValueError("fuse_views: one flip flag (and one weight) per view")
     keep, hvs, wvs, n = [], [], [], None
     for v in views:
-        _need_cuda(v, "views")
-        if v.dim() == 4 and v.shape[1] == 1:
-            v = v[:, 0]
-        if v.dtype != torch.float32 or v.dim() != 3:
-            raise ValueError("every view must be a float32 [N,1,h,w] or [N,h,w] tensor")
-        v = v.contiguous()
+        g.need_cuda(v, "views", "tta")
+        v, nv, hv, wv = g.planes(v, "every view", (torch.float32,), dims=(3, 4))
         if n is None:
-            n = int(v.shape[0])
-        if int(v.shape[0]) != n or v.device != views[0].device:
+            n = nv
+        if nv != n or v.device != views[0].device:
             raise ValueError("the views must share the batch size and the device")
         keep.append(v)
-        hvs.append(int(v.shape[1]))
-        wvs.append(int(v.shape[2]))
+        hvs.append(hv)
+        wvs.append(wv)
     h, w = int(size[0]), int(size[1])
-    if out is None:
-        out = torch.empty((n, 1, h, w), device=keep[0].device, dtype=torch.float32)
-    else:
-        _need_cuda(out, "out")
-        if out.dtype != torch.float32 or tuple(out.shape) != (n, 1, h, w) or not out.is_contiguous() or out.device != keep[0].device:
-            raise ValueError("out must be a contiguous float32 [%d,1,%d,%d] tensor on the views' device" % (n, h, w))
+    out = g.out_buffer(out, torch.float32, (n, 1, h, w), keep[0].device, "the views' device", module="tta")
     V = len(keep)
     ia = C.c_int * V
     wt = (C.c_float * V)(*[float(x) for x in weights]) if weights is not None else None
-    check(lib().osvos_tta_fuse(ptr_array([v.data_ptr() for v in keep]), ia(*hvs), ia(*wvs), ia(*[int(f) for f in flips]), wt, V,
-                               C.c_void_p(out.data_ptr()), n, h, w, _stream()), "tta_fuse")
+    g.call("tta_fuse", keep[0].device, ptr_array([v.data_ptr() for v in keep]), ia(*hvs), ia(*wvs), ia(*[int(f) for f in flips]), wt, V, g.ptr(out),
+           n, h, w)
     return out
 
 
@@ -154,13 +128,9 @@ class TestTimeAugment(object):
         self.weights = None if weights is None else [float(x) for x in weights]
 
     def __call__(self, frames_u8, return_views=False):
-        _need_cuda(frames_u8, "frames_u8")
-        if frames_u8.dim() == 3:
-            frames_u8 = frames_u8[None]
-        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
-            raise ValueError("frames_u8 must be a uint8 [H,W,3] or [N,H,W,3] tensor")
-        frames_u8 = frames_u8.contiguous()
-        n, h, w = int(frames_u8.shape[0]), int(frames_u8.shape[1]), int(frames_u8.shape[2])
+        g.need_cuda(frames_u8, "frames_u8", "tta")
+        frames_u8 = g.frames(frames_u8, "frames_u8")
+        n, h, w = (int(v) for v in frames_u8.shape[:3])
         p = plan(h, w, self.scales, self.flip)
         per = 2 if self.flip else 1
         maps = []

@@ -280,24 +280,16 @@ def check_zoom_args(args):
     """the --zoom* rules; SystemExit on values or combinations the zoom does not take -- checked before any GPU work.  Sets args.roi to the
     keyword arguments of roi.RoiZoom, or None with --zoom 0"""
     from osvos_pytorch_amd import roi
+    from osvos_pytorch_amd._glue import parse_numbers
     args.roi = None
     try:
-        parts = args.zoom_margin.split(',')
-        try:
-            pct, px = [int(v) for v in parts] if len(parts) == 2 else [None, None]
-        except ValueError:
-            pct = None
-        if pct is None:
-            raise ValueError('--zoom-margin takes PCT,PX, two integers >= 0, got %r' % args.zoom_margin)
+        pct, px = parse_numbers(args.zoom_margin, (int, int), '--zoom-margin', expect='PCT,PX, two integers >= 0')
         canvas = None
         if args.zoom_canvas:
-            parts = args.zoom_canvas.lower().split('x')
-            try:
-                canvas = tuple(int(v) for v in parts) if len(parts) == 2 else None
-            except ValueError:
-                canvas = None
-            if canvas is None or not all(1 <= v <= roi.MAX_SIDE for v in canvas):
-                raise ValueError('--zoom-canvas takes HxW with sides of 1..%d, got %r' % (roi.MAX_SIDE, args.zoom_canvas))
+            sides = 'HxW with sides of 1..%d' % roi.MAX_SIDE
+            canvas = parse_numbers(args.zoom_canvas, (int, int), '--zoom-canvas', sep='x', expect=sides)
+            if not all(1 <= v <= roi.MAX_SIDE for v in canvas):
+                raise ValueError('--zoom-canvas takes %s, got %r' % (sides, args.zoom_canvas))
         if args.zoom != 0 and not args.zoom >= 1:
             raise ValueError('--zoom takes the largest enlargement, a number >= 1 (0 = off), got %r' % args.zoom)
         roi.check_zoom(pct, px, args.zoom or 1.0)
@@ -398,27 +390,15 @@ def check_lucid_args(args):
     """the --lucid* rules; SystemExit on values the synthesis does not take -- checked before any GPU work.  Sets args.lucid to the keyword
     arguments of DeviceTrainFrame's lucid (those of lucid.LucidDream, and p), or None with --lucid 0"""
     from osvos_pytorch_amd import lucid
+    from osvos_pytorch_amd._glue import parse_numbers
     args.lucid = None
-
-    def pair(text, kinds, what):
-        parts = text.split(',')
-        if len(parts) != 2:
-            raise ValueError('%s takes two comma-separated numbers, got %r' % (what, text))
-        try:
-            return [kind(v) for kind, v in zip(kinds, parts)]
-        except ValueError:
-            raise ValueError('%s takes two comma-separated numbers, got %r' % (what, text))
+    two = 'two comma-separated numbers'
     try:
-        radius, passes = pair(args.lucid_smooth, (int, int), '--lucid-smooth RADIUS,PASSES')
-        fg_shift, bg_shift = pair(args.lucid_shift, (float, float), '--lucid-shift FG,BG')
-        gain, offset = pair(args.lucid_tone, (float, int), '--lucid-tone GAIN,OFFSET')
-        parts = args.lucid_deform.split(',')
-        if len(parts) not in (1, 2):
-            raise ValueError('--lucid-deform takes A or A,CELL, got %r' % args.lucid_deform)
-        try:
-            deform, cell = float(parts[0]), int(parts[1]) if len(parts) == 2 else 128
-        except ValueError:
-            raise ValueError('--lucid-deform takes A or A,CELL, got %r' % args.lucid_deform)
+        radius, passes = parse_numbers(args.lucid_smooth, (int, int), '--lucid-smooth RADIUS,PASSES', expect=two)
+        fg_shift, bg_shift = parse_numbers(args.lucid_shift, (float, float), '--lucid-shift FG,BG', expect=two)
+        gain, offset = parse_numbers(args.lucid_tone, (float, int), '--lucid-tone GAIN,OFFSET', expect=two)
+        deform, cell = (parse_numbers(args.lucid_deform, (float, int) if ',' in args.lucid_deform else (float,), '--lucid-deform',
+                                      expect='A or A,CELL') + (128,))[:2]
         lucid.check_lucid(args.lucid_p, args.lucid_grow, radius, passes, fg_shift, bg_shift, gain, offset, deform, args.lucid_occlude,
                           args.lucid_band, cell)
     except ValueError as e:
