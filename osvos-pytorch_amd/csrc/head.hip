@@ -237,7 +237,11 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restri
   if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-// out[0] = max |w[ci][co]| over ci != co, out[1] = max |w[c][c] - w[0][0]|   (w: [C][C][k][k])
+// fmaxf drops a NaN operand: a NaN tap (or a NaN difference) would report 0 = "diagonal", and the fast head would return finite logits where the
+// reference returns NaN.  NaN counts as +inf here, which the integer max below orders above every finite value.
+__device__ __forceinline__ float nan_as_inf(float v) { return v != v ? __builtin_inff() : v; }
+
+// out[0] = max |w[ci][co]| over ci != co, out[1] = max |w[c][c] - w[0][0]|   (w: [C][C][k][k]); a NaN among them reports +inf
 __global__ void deconv_diag_check_kernel(const float* __restrict__ w, int C, int kk, float* out) {
   float off = 0.f, dev = 0.f;
   const long total = (long)C * C * kk;
@@ -246,8 +250,8 @@ __global__ void deconv_diag_check_kernel(const float* __restrict__ w, int C, int
     const int co = (int)((i / kk) % C);
     const int ci = (int)(i / ((long)kk * C));
     const float v = w[i];
-    if (ci != co) off = fmaxf(off, fabsf(v));
-    else dev = fmaxf(dev, fabsf(v - w[t]));
+    if (ci != co) off = fmaxf(off, nan_as_inf(fabsf(v)));
+    else dev = fmaxf(dev, nan_as_inf(fabsf(v - w[t])));
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
