@@ -781,6 +781,24 @@ int osvos_lucid_compose_ex(const unsigned char* bgr, const unsigned char* mask, 
  *   in registers and never stored; per-slice partial (value, index) pairs go to ws) and a small kernel that merges the slices.  Rows past
  *   Pq / Pr are masked by the kernel, not padded by the caller.  No atomics; deterministic.
  *   ws: osvos_match_ws_bytes(N, Pq, Pr, C) bytes, 8-byte aligned, contents irrelevant on entry; 0 for arguments the call refuses.
+ * Top-K (osvos_match_topk; VideoMatch's averaging): the operands, the scores t_ab and the classes of nearest; K in 1..OSVOS_MATCH_MAX_K.
+ *   Per query row a and class c: T = the multiset of t_ab over the b with label_r[b] == c, n = |T|, k = min(K, n).  n = 0 gives sim = -2.0f.
+ *   Otherwise v_1 >= .. >= v_k are the k largest members of T (duplicated rows are separate members; which of several equal rows is taken
+ *   cannot matter, so no index is kept);  s = v_1, then s = fl32(s + v_i) for i = 2 .. k in that order;  m = s / (float) k, correctly
+ *   rounded (formed in double and rounded once more, as in quantise);  sim_c[a] = fl32(m * rinv_q[a]).  K = 1 is nearest's sim bit for bit.
+ *   For operands made by osvos_match_quantize every t is finite and never -0; the kernels mark an empty slot with -inf.
+ *   Out: sim fp32 [N][2][Pq].  Two launches: nearest's tile kernel with, per lane and class, a descending list of the 4, 8 or 16 best
+ *   values in registers (the smallest length that holds K) in place of the (value, index) pair, and a kernel that merges the slices' lists.
+ *   ws: osvos_match_topk_ws_bytes(N, Pq, Pr, C, K) bytes (K floats per slice, class and query), 8-byte aligned, contents irrelevant on
+ *   entry and meaningless after the call; 0 for arguments the call refuses.
+ * Local window (osvos_match_local; FEELVOS's local map): queries and references live on the SAME h x w grid, row-major, P = h w <= 2^20 rows
+ *   each; radius in 0..OSVOS_MATCH_MAX_RADIUS.  For query cell (i, j) and class c the candidates are the reference cells (i + di, j + dj)
+ *   inside the grid with |di| <= radius, |dj| <= radius and label c.  best = the largest t over them, idx = the smallest reference row
+ *   (i + di) w + (j + dj) that attains it, sim = best * rinv_q; (-2.0f, -1) when the window holds no row of the class.  A window that covers
+ *   the grid is nearest.  Out: sim fp32 [N][2][P], idx int32 [N][2][P] (may be NULL).  One launch, no workspace: four lanes per query cell
+ *   walk the window in ascending row with the 4-byte integer dot instruction.
+ *   The local map a caller forms from it is max(sim_fg, -1) - max(sim_bg, -1), three fp32 operations: an empty class counts as the smallest
+ *   possible cosine.
  * Limits: C a multiple of 64 in 64..1024, Pq and Pr 1..2^20, P 1..2^30, N 1..65535, sides 1..16384, stride a power of two 1..64.  q, Q and R
  *   are 16-byte aligned.  Outputs (and ws) must not overlap inputs or each other.  Every argument error returns < 0 before any device
  *   call, with a text that names the bad parameter. */
@@ -789,6 +807,13 @@ int osvos_match_cell_labels(const unsigned char* mask, unsigned char* label, int
 size_t osvos_match_ws_bytes(int N, int Pq, int Pr, int C);
 int osvos_match_nearest(const signed char* Q, const float* rinv_q, const signed char* R, const float* rinv_r, const unsigned char* label_r, float* sim,
                         int* idx, void* ws, int N, int NR, int Pq, int Pr, int C, void* stream);
+#define OSVOS_MATCH_MAX_K       16
+#define OSVOS_MATCH_MAX_RADIUS  15
+size_t osvos_match_topk_ws_bytes(int N, int Pq, int Pr, int C, int K);
+int osvos_match_topk(const signed char* Q, const float* rinv_q, const signed char* R, const float* rinv_r, const unsigned char* label_r, float* sim,
+                     void* ws, int N, int NR, int Pq, int Pr, int C, int K, void* stream);
+int osvos_match_local(const signed char* Q, const float* rinv_q, const signed char* R, const float* rinv_r, const unsigned char* label_r, float* sim,
+                      int* idx /* may be NULL */, int N, int NR, int h, int w, int C, int radius, void* stream);
 
 /* ---- fused SGD (torch.optim.SGD semantics, train_online.py:79-88,147) ----------------------
  * for each i: d = g + wd*p; buf = first ? d : momentum*buf + d; p -= lr*buf      (flat tensors) */

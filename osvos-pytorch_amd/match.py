@@ -7,6 +7,9 @@ csrc/match.hip; the rule: include/osvos_hip.h).
     labels:   a feature cell is object when 3/4 of its pixels are, background when at most 1/4 are, void (in neither bank) otherwise
     nearest:  per query pixel and class, the largest cosine dot(Q_a, R_b) * rinv_r[b] * rinv_q[a] over the bank's rows of that class
     map:      cosine to the nearest foreground feature minus cosine to the nearest background feature, on the feature grid
+    topk:     in place of the nearest row, the mean cosine to the k best rows of the class (``osvos_match_topk``, csrc/match_ext.hip)
+    local:    nearest over the reference cells within ``radius`` cells of the query cell on the same grid (``osvos_match_local``); its map
+              counts a class the window does not hold as cosine -1
 
 The network's logits are the only evidence every other stage has; when the network fires on a distractor that merely looks like the object
 to its classifier, the map is a second opinion from the features themselves.  ``AppearanceMatcher`` adds ``gain * map`` to the fused logits
@@ -21,7 +24,7 @@ import torch
 
 from . import _glue as g
 from . import tta
-from ._lib import MATCH_MAX_C, MATCH_MAX_P, lib
+from ._lib import MATCH_MAX_C, MATCH_MAX_K, MATCH_MAX_P, MATCH_MAX_RADIUS, lib
 from .autograd import FEATURE_LAYERS
 
 _STRIDE = {3: 2, 6: 4, 9: 8, 12: 16}      # conv2_2, conv3_3, conv4_3, conv5_3: 2^stage under ceil-mode pooling
@@ -80,16 +83,8 @@ def cell_labels(mask, stride):
     return label
 
 
-def nearest_workspace(n, pq, pr, c, device, ws=None):
-    """a uint8 CUDA tensor of at least osvos_match_ws_bytes: ``ws`` when it is large enough and on ``device``, else a new one"""
-    return g.workspace(lib().osvos_match_ws_bytes(n, pq, pr, c), device, ws, "N %d Pq %d Pr %d C %d" % (n, pq, pr, c), "match")
-
-
-def nearest(q, rinv_q, r, rinv_r, label_r, ws=None, with_idx=False):
-    """q int8 [N,Pq,C] with rinv_q float32 [N,Pq]; r int8 [NR,Pr,C] with rinv_r float32 and label_r uint8 [NR,Pr], NR = N or 1 (one bank for
-    every frame) -> sim float32 [N,2,Pq]: per query row the cosine to the nearest reference row labelled 1 (row 0 of the class axis) and to
-    the nearest labelled 0 (row 1); -2 for a class the bank does not hold.  ``with_idx``: also idx int32 [N,2,Pq], the smallest reference
-    row that attains it (-1 for an empty class).  Enqueued only."""
+def _operands(q, rinv_q, r, rinv_r, label_r):
+    """the five tensors of a search, checked -> (the contiguous tensors, N, NR, Pq, Pr, C)"""
     for t, what in ((q, "q"), (rinv_q, "rinv_q"), (r, "r"), (rinv_r, "rinv_r"), (label_r, "label_r")):
         g.need_cuda(t, what, "match")
     if q.dtype != torch.int8 or r.dtype != torch.int8 or q.dim() != 3 or r.dim() != 3 or q.shape[2] != r.shape[2]:
@@ -105,12 +100,77 @@ def nearest(q, rinv_q, r, rinv_r, label_r, ws=None, with_idx=False):
     if any(t.device != q.device for t in (rinv_q, r, rinv_r, label_r)):
         raise ValueError("match: the five tensors must be on one device")
     q, rinv_q, r, rinv_r, label_r = (t.contiguous() for t in (q, rinv_q, r, rinv_r, label_r))
+    return (q, rinv_q, r, rinv_r, label_r), n, nr, pq, pr, c
+
+
+def nearest_workspace(n, pq, pr, c, device, ws=None):
+    """a uint8 CUDA tensor of at least osvos_match_ws_bytes: ``ws`` when it is large enough and on ``device``, else a new one"""
+    return g.workspace(lib().osvos_match_ws_bytes(n, pq, pr, c), device, ws, "N %d Pq %d Pr %d C %d" % (n, pq, pr, c), "match")
+
+
+def nearest(q, rinv_q, r, rinv_r, label_r, ws=None, with_idx=False):
+    """q int8 [N,Pq,C] with rinv_q float32 [N,Pq]; r int8 [NR,Pr,C] with rinv_r float32 and label_r uint8 [NR,Pr], NR = N or 1 (one bank for
+    every frame) -> sim float32 [N,2,Pq]: per query row the cosine to the nearest reference row labelled 1 (row 0 of the class axis) and to
+    the nearest labelled 0 (row 1); -2 for a class the bank does not hold.  ``with_idx``: also idx int32 [N,2,Pq], the smallest reference
+    row that attains it (-1 for an empty class).  Enqueued only."""
+    (q, rinv_q, r, rinv_r, label_r), n, nr, pq, pr, c = _operands(q, rinv_q, r, rinv_r, label_r)
     sim = torch.empty((n, 2, pq), device=q.device, dtype=torch.float32)
     idx = torch.empty((n, 2, pq), device=q.device, dtype=torch.int32) if with_idx else None
     ws = nearest_workspace(n, pq, pr, c, q.device, ws)
     g.call("match_nearest", q.device, g.ptr(q), g.ptr(rinv_q), g.ptr(r), g.ptr(rinv_r), g.ptr(label_r), g.ptr(sim), g.ptr(idx), g.ptr(ws), n, nr, pq,
            pr, c)
     return (sim, idx) if with_idx else sim
+
+
+def topk_workspace(n, pq, pr, c, k, device, ws=None):
+    """a uint8 CUDA tensor of at least osvos_match_topk_ws_bytes: ``ws`` when it is large enough and on ``device``, else a new one"""
+    g.check_int("k", k, 1, MATCH_MAX_K, "match")
+    return g.workspace(lib().osvos_match_topk_ws_bytes(n, pq, pr, c, int(k)), device, ws, "N %d Pq %d Pr %d C %d K %d" % (n, pq, pr, c, k), "match")
+
+
+def topk(q, rinv_q, r, rinv_r, label_r, k, ws=None):
+    """the operands of ``nearest`` -> sim float32 [N,2,Pq]: per query row and class the mean cosine to the ``k`` (1..16) best reference rows
+    of the class -- to all of them when the bank holds fewer, -2 when it holds none; summed from the best down and divided once
+    (VideoMatch's averaging: one mislabelled bank row no longer decides).  ``k`` = 1 gives ``nearest``'s bits.  Enqueued only."""
+    g.check_int("k", k, 1, MATCH_MAX_K, "match")
+    (q, rinv_q, r, rinv_r, label_r), n, nr, pq, pr, c = _operands(q, rinv_q, r, rinv_r, label_r)
+    sim = torch.empty((n, 2, pq), device=q.device, dtype=torch.float32)
+    ws = topk_workspace(n, pq, pr, c, k, q.device, ws)
+    g.call("match_topk", q.device, g.ptr(q), g.ptr(rinv_q), g.ptr(r), g.ptr(rinv_r), g.ptr(label_r), g.ptr(sim), g.ptr(ws), n, nr, pq, pr, c, int(k))
+    return sim
+
+
+def local(q, rinv_q, r, rinv_r, label_r, grid, radius, with_idx=False):
+    """the operands of ``nearest`` with Pq = Pr = h w, both row-major on the ``grid`` = (h, w) -> sim float32 [N,2,P]: per query cell and
+    class the cosine to the nearest reference cell of the class at most ``radius`` (0..15) rows and columns away; -2 when the window holds
+    none.  ``with_idx``: also idx int32 [N,2,P], the smallest reference row that attains it (-1).  FEELVOS's local map.  Enqueued only."""
+    g.check_int("radius", radius, 0, MATCH_MAX_RADIUS, "match")
+    if not isinstance(grid, (tuple, list)) or len(grid) != 2:
+        raise ValueError("match: grid must be (h, w), got %r" % (grid,))
+    h, w = grid
+    g.check_int("grid h", h, 1, MATCH_MAX_P, "match")
+    g.check_int("grid w", w, 1, MATCH_MAX_P, "match")
+    (q, rinv_q, r, rinv_r, label_r), n, nr, pq, pr, c = _operands(q, rinv_q, r, rinv_r, label_r)
+    if pq != h * w or pr != h * w:
+        raise ValueError("match: Pq %d and Pr %d must both be the grid's %d x %d = %d cells" % (pq, pr, h, w, h * w))
+    sim = torch.empty((n, 2, pq), device=q.device, dtype=torch.float32)
+    idx = torch.empty((n, 2, pq), device=q.device, dtype=torch.int32) if with_idx else None
+    g.call("match_local", q.device, g.ptr(q), g.ptr(rinv_q), g.ptr(r), g.ptr(rinv_r), g.ptr(label_r), g.ptr(sim), g.ptr(idx), n, nr, int(h), int(w), c,
+           int(radius))
+    return (sim, idx) if with_idx else sim
+
+
+def local_map(sim):
+    """sim [N,2,P] of ``local`` -> max(sim_fg, -1) - max(sim_bg, -1), float32 [N,P]: a class the window does not hold counts as the smallest
+    possible cosine, so "no object was near here a frame ago" is evidence against the object"""
+    return torch.clamp_min(sim[:, 0], -1.0) - torch.clamp_min(sim[:, 1], -1.0)
+
+
+def check_match_options(topk, local_radius, local_gain):
+    """ValueError unless ``topk`` is in 1..16, ``local_radius`` in 0..15 and ``local_gain`` a finite number >= 0 (0 = off; host only)"""
+    g.check_int("topk", topk, 1, MATCH_MAX_K, "match")
+    g.check_int("local_radius", local_radius, 0, MATCH_MAX_RADIUS, "match")
+    g.check_number("local_gain", local_gain, 0, None, "match")
 
 
 class AppearanceMatcher(object):
@@ -126,11 +186,19 @@ class AppearanceMatcher(object):
     ``prev_mask`` (that frame's final mask [N,H,W] or [N,1,H,W]) form a second bank, and each class takes the larger of its two cosines.
     ``gain == 0`` is ``net.forward`` under ``torch.no_grad()`` and nothing else.  The banks and workspaces stay on the device.
 
+    ``topk`` > 1 searches both banks with ``topk`` in place of ``nearest``: a class's score is the mean cosine to its ``topk`` best rows.
+    ``local_gain`` > 0 adds a THIRD view to the same ``fuse_views`` call, weights ``[1, gain, local_gain]``: ``local_map`` of the search of
+    the previous call's features under ``prev_mask`` within ``local_radius`` cells of each pixel (``local``).  It does not depend on
+    ``previous``; on the first matched frame, or without ``prev_mask``, there is no local view.  ``topk=1, local_gain=0`` is the matcher
+    without these options: the same calls, the same bytes.
+
     The defaults are starting values, NOT tuned on DAVIS."""
 
-    def __init__(self, net, layer=9, gain=4.0, previous=False):
+    def __init__(self, net, layer=9, gain=4.0, previous=False, topk=1, local_radius=0, local_gain=0.0):
         check_match(layer, gain)
+        check_match_options(topk, local_radius, local_gain)
         self.net, self.layer, self.gain, self.previous = net, int(layer), float(gain), bool(previous)
+        self.topk, self.local_radius, self.local_gain = int(topk), int(local_radius), float(local_gain)
         self.stride = stride_of(layer)
         self.inert = False
         self._bank = None            # (r [1,P,C], rinv_r [1,P], label [1,P]) of the first frame
@@ -141,6 +209,22 @@ class AppearanceMatcher(object):
     def has_reference(self):
         """True once set_reference has run (or when gain is 0 and there is nothing to build)"""
         return self.gain == 0 or self._bank is not None
+
+    @property
+    def needs_previous(self):
+        """True when the next call wants this call's features and mask: the previous-frame bank, the local view, or both"""
+        return self.previous or self.local_gain > 0
+
+    def _search(self, q, rinv_q, r, rinv_r, label, which):
+        """one bank: ``nearest``, or ``topk`` when topk > 1; ``which`` names the bank's workspace attribute"""
+        n, p, c = (int(v) for v in q.shape)
+        if self.topk > 1:
+            ws = topk_workspace(n, p, p, c, self.topk, q.device, getattr(self, which))
+            setattr(self, which, ws)
+            return topk(q, rinv_q, r, rinv_r, label, self.topk, ws=ws)
+        ws = nearest_workspace(n, p, p, c, q.device, getattr(self, which))
+        setattr(self, which, ws)
+        return nearest(q, rinv_q, r, rinv_r, label, ws=ws)
 
     def _features(self, x):
         outs, feat, _ = self.net.forward_features(x, self.layer)
@@ -179,16 +263,20 @@ class AppearanceMatcher(object):
         r, rinv_r, label = self._bank
         if int(r.shape[1]) != p:
             raise ValueError("AppearanceMatcher: the frame's %d x %d feature grid is not the first frame's" % (h, w))
-        self._ws = nearest_workspace(n, p, p, c, q.device, self._ws)
-        sim = nearest(q, rinv_q, r, rinv_r, label, ws=self._ws)
-        if self.previous:
+        sim = self._search(q, rinv_q, r, rinv_r, label, "_ws")
+        local_mp = None
+        if self.needs_previous:
             if prev_mask is not None and self._last is not None and self._last[0].shape == q.shape:
                 plabel = cell_labels(prev_mask, self.stride)
                 if tuple(plabel.shape) != (n, h, w):
                     raise ValueError("prev_mask of %s does not belong to frames of %s" % (tuple(prev_mask.shape), tuple(x.shape)))
-                self._ws_prev = nearest_workspace(n, p, p, c, q.device, self._ws_prev)
-                sim = torch.maximum(sim, nearest(q, rinv_q, self._last[0], self._last[1], plabel.view(n, p), ws=self._ws_prev))
+                if self.previous:
+                    sim = torch.maximum(sim, self._search(q, rinv_q, self._last[0], self._last[1], plabel.view(n, p), "_ws_prev"))
+                if self.local_gain > 0:
+                    local_mp = local_map(local(q, rinv_q, self._last[0], self._last[1], plabel.view(n, p), (h, w), self.local_radius)).view(n, h, w)
             self._last = (q, rinv_q)
-        mp = (sim[:, 0] - sim[:, 1]).view(n, h, w)
-        fused = tta.fuse_views([outs[-1], mp], [False, False], (int(x.shape[2]), int(x.shape[3])), weights=[1.0, self.gain])
+        views, weights = [outs[-1], (sim[:, 0] - sim[:, 1]).view(n, h, w)], [1.0, self.gain]
+        if local_mp is not None:
+            views, weights = views + [local_mp], weights + [self.local_gain]
+        fused = tta.fuse_views(views, [False] * len(views), (int(x.shape[2]), int(x.shape[3])), weights=weights)
         return list(outs[:4]) + [fused]

@@ -10,7 +10,7 @@ None for an option that is off.  THE ORDER OF THE STAGES LIVES HERE, and tests/t
   ``multi_object_sequence`` per object: fine-tuning (the caller's) and FrameForward over every frame into a [K,F,H,W] stack; then post_chain
                             stage by stage over chunks of frames; ``score_objects`` merges, scores and writes
 
-The two recipes differ in ONE rule.  The mask that --match-previous hands to the next frame (FrameForward.remember) is the FINAL mask in
+The two recipes differ in ONE rule.  The mask that --match-previous (and --match-local) hands to the next frame (FrameForward.remember) is the FINAL mask in
 the single-object recipe -- after crf, snap and tracker -- and the RAW output of the matched forward in the multi-object recipe, whose post
 chain runs only after every forward of every object is done.  The mask the object-centred zoom takes its box from (FrameForward.roi_prev)
 is remembered by the same call, so it follows the same rule."""
@@ -30,7 +30,7 @@ class FrameForward(object):
 
     def __init__(self, net, tta=None, adapter=None, matcher=None, roi=None):
         self.net, self.tta, self.adapter, self.matcher, self.roi = net, tta, adapter, matcher, roi
-        self.match_prev = None               # --match-previous: the previous frame's mask (which one: see the module docstring)
+        self.match_prev = None               # --match-previous / --match-local: the previous frame's mask (which one: see the module docstring)
         self.roi_prev = None                 # --zoom: the previous frame's mask, by the same rule
         if matcher is not None and adapter is not None:
             adapter.forward = lambda image: matcher(image, self.match_prev)
@@ -60,7 +60,8 @@ class FrameForward(object):
         return self.net.forward(image)[-1]
 
     def remember(self, logits):
-        if self.matcher is not None and self.matcher.previous:
+        # (needs_previous: the local view wants the mask too, with or without --match-previous; a matcher without the attribute has .previous)
+        if self.matcher is not None and getattr(self.matcher, 'needs_previous', self.matcher.previous):
             self.match_prev = logits > 0
         if self.roi is not None:
             self.roi_prev = logits > 0

@@ -31,6 +31,8 @@ running on the MI355X-native OSVOS path.  Differences by design:
     12: conv2_2 .. conv5_3) are quantised to int8 and searched against the first frame's on the integer matrix pipe; G times (cosine to the
     nearest foreground feature minus cosine to the nearest background feature) is added to the fused logits on the device
     (osvos_pytorch_amd.match.AppearanceMatcher), in the test forward itself.  ``--match-previous`` also searches the previous frame's features under its final mask.  Not with --tta-*.
+    ``--match-topk K`` scores a class by the mean cosine to its K best bank rows (VideoMatch), ``--match-local R[,GAIN]`` adds GAIN times a
+    map searched only within R feature cells of each pixel in the previous frame (FEELVOS); both need --match-gain, off they change no byte.
     Starting values, not tuned on DAVIS; with G = 0 nothing is built and not one byte changes
   * ``--lucid P``: lucid first-frame synthesis -- with probability P a training sample is not the flipped / rotated / scaled frame but a
     re-composition of it: the object cut out, the hole inpainted once per sequence, object and background moved by affines of their own,
@@ -371,19 +373,36 @@ def check_match_args(args):
     """the --match-* rules; SystemExit on values the matching does not take -- checked before any GPU work.  Sets args.match to the keyword
     arguments of match.AppearanceMatcher, or None with --match-gain 0"""
     from osvos_pytorch_amd import match
+    from osvos_pytorch_amd._glue import parse_numbers
     args.match = None
     try:
         match.check_match(args.match_layer, args.match_gain)
     except ValueError as e:
         raise SystemExit('--match-*: %s' % e)
+    try:
+        local_radius, local_gain = 0, 0.0
+        if args.match_local:
+            local_radius, local_gain = (parse_numbers(args.match_local, (int, float) if ',' in args.match_local else (int,), '--match-local',
+                                                      expect='R or R,GAIN', finite=True) + (args.match_gain,))[:2]
+        match.check_match_options(args.match_topk, local_radius, local_gain)
+    except ValueError as e:
+        raise SystemExit('--match-*: %s' % e)
     if not args.match_gain:
+        if args.match_topk != 1 or args.match_local:
+            raise SystemExit('--match-topk / --match-local need --match-gain: they are options of the appearance matcher')
         return
     if args.tta:
         raise SystemExit('--match-gain is not run together with --tta-scales / --tta-flip: matching under test-time augmentation is not built')
     need_decoded_frames(args, '--match-gain needs', 'the first-frame bank is made on the device input pipeline')
     if args.match_previous and args.adapt_steps:
         raise SystemExit('--match-previous is not run together with --adapt-steps: the adapter forwards every frame twice')
+    if local_gain > 0 and args.adapt_steps:
+        raise SystemExit('--match-local is not run together with --adapt-steps: the adapter forwards every frame twice')
     args.match = dict(layer=args.match_layer, gain=args.match_gain, previous=args.match_previous)
+    if args.match_topk > 1:          # (an option that is off adds nothing: AppearanceMatcher is built exactly as before)
+        args.match.update(topk=args.match_topk)
+    if local_gain > 0:
+        args.match.update(local_radius=local_radius, local_gain=local_gain)
 
 
 def check_lucid_args(args):
@@ -599,6 +618,14 @@ def parse_args(argv=None):
     ap.add_argument('--match-previous', action='store_true',
                     help='--match-gain: also search the previous frame\'s features under its final mask; each class takes the larger cosine.  '
                          'Not with --adapt-steps')
+    ap.add_argument('--match-topk', type=int, default=1, metavar='K',
+                    help='--match-gain: a class\'s score is the mean cosine to its K best bank rows (1..16; VideoMatch\'s averaging), so that one '
+                         'mislabelled cell of the first frame no longer decides a region.  1 (the default) is the nearest row, as before')
+    ap.add_argument('--match-local', default='', metavar='R[,GAIN]',
+                    help='--match-gain: a third view (FEELVOS\'s local map) -- GAIN (default: G of --match-gain) times the map of a search '
+                         'of the previous frame\'s features under its final mask that looks only R feature cells (0..15) around each '
+                         'pixel; a class the window does not hold counts as cosine -1.  Independent of --match-previous.  Not with '
+                         '--adapt-steps')
     ap.add_argument('--lucid', dest='lucid_p', type=float, default=0.0, metavar='P',
                     help='lucid first-frame synthesis (0 = off): with probability P (0..1) a training sample is a re-composition of the '
                          'annotated frame -- the object cut out, the hole inpainted once per sequence, object and background moved by affines '
