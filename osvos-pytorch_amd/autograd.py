@@ -165,11 +165,20 @@ class NetRuntime:
         return float(res.max().item()) == 0.0
 
 
+def wants_backward(x, params):
+    """Can a backward follow a forward of (x, params) started here?  Read where grad mode is visible, before ``OSVOSNetFunction.apply``: inside
+    ``Function.forward`` grad mode is always off, and ``ctx.needs_input_grad`` reports a parameter that requires grad under ``torch.no_grad()``
+    too.  False -- under ``torch.no_grad()`` / ``torch.inference_mode()``, or with nothing that requires grad -- selects the inference forward
+    (OSVOS_FLAG_INFERENCE: the training forward's logits bit for bit, no sign bits, no pool codes, the forward-only workspace)."""
+    return bool(torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)))
+
+
 class OSVOSNetFunction(torch.autograd.Function):
     """(x [N,3,H,W], 52 parameters) -> 5 logit maps [N,1,H,W]   (vgg_osvos.py:59-74)."""
 
     @staticmethod
-    def forward(ctx, rt, x, *params):
+    def forward(ctx, rt, need_bwd, x, *params):
+        # need_bwd (wants_backward(), decided by the caller): False = the inference forward in the forward-only workspace
         ctx.set_materialize_grads(False)      # unused heads arrive as None, not as zero maps
         if not x.is_cuda:
             raise RuntimeError("OSVOS (osvos_pytorch_amd) runs on the GPU only: move the module and the input to "
@@ -186,7 +195,6 @@ class OSVOSNetFunction(torch.autograd.Function):
                 raise RuntimeError("parameters must be float32 on the input's device")
         rt.ensure_packed(ps)
         n, _, h, w = xin.shape
-        need_bwd = any(ctx.needs_input_grad)       # False under torch.no_grad(): forward-only workspace
         nbytes = l.osvos_net_ws_bytes(n, h, w, rt.dtype) if need_bwd else l.osvos_net_ws_bytes_infer(n, h, w, rt.dtype)
         ctx.cdtype = rt.cdtype()
         ctx.cdtype_bwd = rt.cdtype_bwd()
@@ -223,7 +231,7 @@ class OSVOSNetFunction(torch.autograd.Function):
         for i in range(len(ctx.param_meta)):
             # the deconv weights (params 0..7): frozen by lr 0 in both reference scripts (train_online.py:84-85) -- the commuted head
             # forms no gradient for them; the generic head (non-diagonal weights = somebody trains them) does
-            need = ctx.needs_input_grad[2 + i] and (i not in _FROZEN or bool(ctx.cdtype & GENERIC_DECONV))
+            need = ctx.needs_input_grad[3 + i] and (i not in _FROZEN or bool(ctx.cdtype & GENERIC_DECONV))
             if need and 4 <= i < 8 and d[i - 4] is None:
                 need = False       # upscale_[i] only sees the side head i
             if need and 42 <= i < 50 and all(g is None for g in d[:4]):
@@ -253,7 +261,7 @@ class OSVOSNetFunction(torch.autograd.Function):
         else:
             targets = [scratch(i) if l else None for i, l in enumerate(launch)]
             grads = [t if w else None for t, w in zip(targets, wanted)]
-        dx = torch.empty((n, 3, h, w), device=dev, dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        dx = torch.empty((n, 3, h, w), device=dev, dtype=torch.float32) if ctx.needs_input_grad[2] else None
         ev, rt.grad_events = getattr(rt, "grad_events", None), None
         rt.grad_events_recorded = bool(ev and inplace)
         if ev and inplace:         # data-parallel overlap (parallel.GradientAllReducer.arm): one ready-event per completion group
@@ -276,7 +284,7 @@ class OSVOSNetFunction(torch.autograd.Function):
                         if t is not None:
                             t.record_stream(st)
             rt.pending_join = dev
-        return (None, dx) + tuple(grads)
+        return (None, None, dx) + tuple(grads)
 
 
 FEATURE_LAYERS = (3, 6, 9, 12)      # osvos_net_ws_query indices of conv2_2, conv3_3, conv4_3, conv5_3: what the side branches read
@@ -284,7 +292,7 @@ FEATURE_LAYERS = (3, 6, 9, 12)      # osvos_net_ws_query indices of conv2_2, con
 
 def net_forward_features(rt, x, params, layer=9):
     """A forward without a graph that keeps its workspace: ``(outs, feat, fmt)`` -- ``outs`` the five logit maps of ``OSVOSNetFunction`` under
-    ``torch.no_grad()`` bit for bit (the same library call with the same flags), ``feat`` trunk tensor ``layer`` (one of FEATURE_LAYERS: the last convolution of stages
+    ``torch.no_grad()`` bit for bit (the library call ``OSVOS.forward`` makes in the caller's grad mode, with the same flags), ``feat`` trunk tensor ``layer`` (one of FEATURE_LAYERS: the last convolution of stages
     1-4, always materialised because a side branch reads it) as a VIEW of the workspace shaped [N,h,w,C], float32 or bfloat16, and ``fmt``
     its ``osvos_net_ws_format`` (0 fp32, 1 bf16).  The view keeps the workspace alive; nothing is copied."""
     if isinstance(layer, bool) or not isinstance(layer, int) or layer not in FEATURE_LAYERS:
@@ -296,6 +304,7 @@ def net_forward_features(rt, x, params, layer=9):
     if x.dim() != 4 or x.shape[1] != 3:
         raise RuntimeError("expected input of shape [N,3,H,W], got %s" % (tuple(x.shape),))
     l = lib()
+    need_bwd = wants_backward(x, params)
     with torch.no_grad():
         xin = x.detach().contiguous().float()
         ps = [p.detach().contiguous() for p in params]
@@ -305,9 +314,7 @@ def net_forward_features(rt, x, params, layer=9):
         with torch.cuda.device(xin.device):
             rt.ensure_packed(ps)
             n, _, h, w = (int(v) for v in xin.shape)
-            # the same choice of forward as OSVOSNetFunction makes (autograd reports needs_input_grad for a parameter that requires grad under
-            # torch.no_grad() too, so a module with trainable parameters runs the full-workspace forward there as well): same call, same bits
-            need_bwd = bool(x.requires_grad or any(p.requires_grad for p in params))
+            # the choice of forward OSVOS.forward makes (wants_backward(), read outside this function's own no_grad block): same call, same bits
             nbytes = l.osvos_net_ws_bytes(n, h, w, rt.dtype) if need_bwd else l.osvos_net_ws_bytes_infer(n, h, w, rt.dtype)
             ws = torch.empty(nbytes, device=xin.device, dtype=torch.uint8)
             outs = [torch.empty((n, 1, h, w), device=xin.device, dtype=torch.float32) for _ in range(5)]

@@ -480,14 +480,18 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
         const Tensor act = L.view(ws, L.act[l]);
         set_x(c, cur);
         set_y(c, act);
-        if (L.bits[l] != (size_t)-1 && !infer) c.y_bits = reinterpret_cast<unsigned*>(at(ws, L.bits[l]));
+        const bool has_bits = L.bits[l] != (size_t)-1;
+        if (has_bits && !infer) c.y_bits = reinterpret_cast<unsigned*>(at(ws, L.bits[l]));
         if (fuse_pool(dtype) && si < 4 && j == kStageN[si] - 1) {      // last convolution of stages 0-3: + the pooled tensor
           const Tensor pooled = L.view(ws, L.pooled[si + 1]);
           c.pooled = reinterpret_cast<float*>(pooled.f);
           c.pooled_bf16 = pooled.b;
           if (L.pool_code[si + 1] != (size_t)-1 && !infer) c.pool_code = at(ws, L.pool_code[si + 1]);
         }
-        c.part_ws = at(ws, L.conv_part);
+        // A launch that writes sign bits is never cut along K (f32x3 choose()).  The inference forward writes no bits, so it withholds the
+        // partial-sum workspace from those layers instead: same plan, same summation order, the logits of the training forward bit for bit.
+        // (Stream-K is decided from the K split alone, so with the split gone sk_ws changes nothing between the two forms.)
+        if (!(has_bits && infer)) c.part_ws = at(ws, L.conv_part);
         c.sk_ws = sk_ws;
         rc = osvos_conv3x3_dispatch(c, dtype);
         cur = act;

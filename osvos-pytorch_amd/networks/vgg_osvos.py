@@ -15,7 +15,7 @@ import os
 import torch
 import torch.nn as nn
 
-from ..autograd import NetRuntime, OSVOSNetFunction, net_forward_features
+from ..autograd import NetRuntime, OSVOSNetFunction, net_forward_features, wants_backward
 from ..layers.osvos_layers import interp_surgery
 
 try:  # the path config is a top-level module in the reference (mypath.py); same here
@@ -70,7 +70,10 @@ class OSVOS(nn.Module):
     def forward(self, x):
         """x: [N,3,H,W] float32 on the GPU.  Returns ``[side_out0..3, fused]`` logits, each
         [N,1,H,W] (reference vgg_osvos.py:59-74)."""
-        outs = OSVOSNetFunction.apply(self._runtime, x, *self.parameters())
+        # grad mode is visible here and nowhere below: under torch.no_grad() / torch.inference_mode() the inference forward (same logits bit
+        # for bit, no sign bits, no pool codes, the forward-only workspace)
+        params = list(self.parameters())
+        outs = OSVOSNetFunction.apply(self._runtime, wants_backward(x, params), x, *params)
         return list(outs)
 
     def forward_features(self, x, layer=9):

@@ -48,8 +48,11 @@ def _has_bits(l, dt):
     return is_mask and dt == BF16MFMA
 
 
-def network_calls(dtype_word, h, w):
-    """[(name, (H, W, Cin, Cout, y_cs, dtype word, flags))]: the calls of one training step, as net.cpp's conv_of() and its callers fill them"""
+def network_calls(dtype_word, h, w, infer=False, streamk=False):
+    """[(name, (H, W, Cin, Cout, y_cs, dtype word, flags))]: the calls of one training step, as net.cpp's conv_of() and its callers fill them.
+    infer: the 17 forward calls as osvos_net_forward fills them under OSVOS_FLAG_INFERENCE -- no sign bits, no pool codes, and no partial-sum
+    workspace for a layer whose training call carries sign bits (the data gradients are the training step's: no inference call builds them).
+    streamk: the main-stream forward convolutions also carry the stream-K workspace, as under OSVOS_X3_STREAMK >= 1 (f32x3 only)"""
     dt = dtype_word & 0xff
     store, x3 = dt == BF16MFMA, dt == F32_X3
     act = (X_BF16, Y_BF16) if store else (0, Y_F32)             # a trunk tensor as an operand / as a result
@@ -59,13 +62,17 @@ def network_calls(dtype_word, h, w):
         ws.append((ws[-1] + 1) // 2)
     calls = []
     for l, (name, si, cin, cin_s, cout) in enumerate(TRUNK):    # forward trunk
-        f = act[0] | act[1] | RELU | PART_WS
+        f = act[0] | act[1] | RELU
         if x3 and cin == cin_s:
             f |= WPK3
-        if _has_bits(l, dt):
+        if _has_bits(l, dt) and not infer:
             f |= Y_BITS
+        if not (_has_bits(l, dt) and infer):
+            f |= PART_WS
         if (x3 or store) and si < 4 and _last(l):
-            f |= POOL | (POOL_CODE if store else 0)
+            f |= POOL | (POOL_CODE if store and not infer else 0)
+        if streamk and x3:
+            f |= SK_WS
         calls.append((name, (hs[si], ws[si], cin_s, cout, cout, dtype_word, f)))
     for i in range(4):                                          # forward side branches: fp32 result, cut along K from 256 channels
         c = STAGE_C[i + 1]
@@ -100,19 +107,60 @@ def plan_table(lib):
             for name, dt in DTYPES.items()}
 
 
-_TABLE = []
+# frames at which a K split is in reach of the f32x3 forward (few tiles per layer), beside FRAMES
+SMALL_FRAMES = [(2, 48, 64), (2, 60, 107), (1, 33, 41), (2, 37, 53), (1, 120, 214)]
+FORWARD_LAYERS = [t[0] for t in TRUNK] + ["side_prep%d" % (i + 2) for i in range(4)]
+
+
+def inference_plan_table(lib):
+    """{"dtype": {"N x H x W": {"forward layer": [training plan, inference plan, the two with the stream-K workspace]}}}"""
+    res = {}
+    for name, dt in DTYPES.items():
+        for n, h, w in FRAMES + [f for f in SMALL_FRAMES if f not in FRAMES]:
+            forms = [dict(network_calls(dt, h, w, infer=infer, streamk=sk)) for sk in (False, True) for infer in (False, True)]
+            res.setdefault(name, {})["%dx%dx%d" % (n, h, w)] = {layer: [plan(lib, n, *f[layer]) for f in forms] for layer in FORWARD_LAYERS}
+    return res
+
+
+_TABLE = {}
+
+
+def _fresh(what):
+    """`what`(the library), from a fresh process without any tuning variable (the launchers cache them at first use)"""
+    if what not in _TABLE:
+        env = {k: v for k, v in os.environ.items() if not k.startswith("OSVOS_") or k == "OSVOS_AUTOBUILD"}
+        code = ("import json, sys; sys.path[:0] = [%r, %r]; from osvos_pytorch_amd import _lib; import test_conv_plan_cpu as t; "
+                "print('PLANS ' + json.dumps(t.%s(_lib.lib())))" % (REPO, os.path.join(REPO, "tests"), what))
+        out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=1800)
+        assert out.returncode == 0, out.stderr[-2000:]
+        _TABLE[what] = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("PLANS ")][-1][6:])
+    return _TABLE[what]
 
 
 def table():
-    """the library's plans, from a fresh process without any tuning variable (the launchers cache them at first use)"""
-    if not _TABLE:
-        env = {k: v for k, v in os.environ.items() if not k.startswith("OSVOS_") or k == "OSVOS_AUTOBUILD"}
-        code = ("import json, sys; sys.path[:0] = [%r, %r]; from osvos_pytorch_amd import _lib; import test_conv_plan_cpu as t; "
-                "print('PLANS ' + json.dumps(t.plan_table(_lib.lib())))" % (REPO, os.path.join(REPO, "tests")))
-        out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=1800)
-        assert out.returncode == 0, out.stderr[-2000:]
-        _TABLE.append(json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("PLANS ")][-1][6:]))
-    return _TABLE[0]
+    return _fresh("plan_table")
+
+
+def test_inference_forward_plans_the_launches_of_the_training_forward():
+    """OSVOS_FLAG_INFERENCE promises the training forward's logits bit for bit (include/osvos_hip.h), so every one of its 17 convolutions must
+    get the training forward's launch: family, tile, block order, K split, finalize, stream-K grid and order, loop form, separate pool.  The
+    f32x3 launcher never cuts a launch that writes sign bits along K; an inference call that merely drops the bits but keeps the partial-sum
+    workspace is cut -- conv3_2 / conv4_1 / conv4_2 in 4 / 4 / 8 with a finalize launch at 2x48x64, 2x60x107, 1x33x41, 2x37x53 and 1x120x214 --
+    and sums in another order.  Both sides are planned live; with and without the stream-K workspace (OSVOS_X3_STREAMK)."""
+    t = _fresh("inference_plan_table")
+    assert sorted(t) == sorted(DTYPES)
+    bad = []
+    for dt in t:
+        assert len(t[dt]) == len(FRAMES) + len(SMALL_FRAMES) - 1, dt      # (2x37x53 is in both lists)
+        for frame in t[dt]:
+            assert sorted(t[dt][frame]) == sorted(FORWARD_LAYERS) and len(FORWARD_LAYERS) == 17
+            for layer, (train, infer, train_sk, infer_sk) in t[dt][frame].items():
+                assert len(train) == len(FIELDS) == 10
+                if infer != train:
+                    bad.append((dt, frame, layer, dict(zip(FIELDS, train)), dict(zip(FIELDS, infer))))
+                if infer_sk != train_sk:
+                    bad.append((dt, frame, layer, "stream-K", dict(zip(FIELDS, train_sk)), dict(zip(FIELDS, infer_sk))))
+    assert not bad, bad
 
 
 def test_plans_equal_the_recorded_ones():

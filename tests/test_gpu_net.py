@@ -360,13 +360,16 @@ def test_batch_and_odd_sizes_no_grad_inference():
         assert np.abs(sigmoid_np(got) - sigmoid_np(ref)).max() < 1e-4
 
 
-@pytest.mark.parametrize("precision", ["fp32x3", "bf16", "fp32"])
+@pytest.mark.parametrize("precision", ["fp32x3", "bf16", "fp32", "fp32h2", "fp32x2", "bf16w2"])
 def test_inference_forward_skips_backward_only_outputs_and_keeps_every_logit_bit(precision):
     """OSVOS_FLAG_INFERENCE (round 6): under torch.no_grad() (train_online.py:172-181) the forward writes neither the one-bit ReLU
     masks nor the pool-code bytes -- which only a backward reads -- and runs in the inference-sized workspace; the five logit maps must be
-    bit-identical to the ones of a forward that a backward could follow, at even and odd sizes."""
+    bit-identical to the ones of a forward that a backward could follow, at even and odd sizes.  The module's parameters are trainable, as
+    in the product: OSVOS.forward reads grad mode itself (autograd.wants_backward), so the no_grad forward here IS the flagged one -- until
+    that decision existed both forwards of this test were the training forward.  What the flagged call writes, and the same identity at
+    the library call: tests/test_gpu_inference_forward.py."""
     from oracle import synth
-    for (n, h, w) in [(2, 60, 107), (1, 33, 41)]:
+    for (n, h, w) in [(2, 60, 107), (1, 33, 41), (2, 48, 64)]:
         wts, x, _ = synth.calibrated_problem(n, h, w, seed=12)
         net = build_net(wts).set_precision(precision)
         xs = torch.from_numpy(x).cuda()
