@@ -60,6 +60,12 @@ LUCID_MAX_OCC_RADIUS = 4096  # OSVOS_LUCID_MAX_OCC_RADIUS: largest occluder semi
 LUCID_MAX_OCC_OFFSET = 8192  # OSVOS_LUCID_MAX_OCC_OFFSET: largest |centre| and |source offset| of an occluder
 GENERIC_DECONV = 0x100    # OSVOS_FLAG_GENERIC_DECONV: OR-ed into the dtype of the osvos_net_* calls
 NPARAMS = 52
+# the slot groups of the 52 parameters / gradients in state_dict order (csrc/common.h, namespace slot, names them for the C side)
+SLOTS_UPSCALE = range(0, 4)         # slot::upscale(i): upscale[i].weight, the fused head's deconvolutions
+SLOTS_UPSCALE_SIDE = range(4, 8)    # slot::upscale_(i): upscale_[i].weight, the side heads'
+SLOTS_CONV = range(8, 42)           # slot::conv_w(l), conv_b(l): (weight, bias) pairs of the 13 trunk convolutions, then of side_prep[0..3]
+SLOTS_SCORE_DSN = range(42, 50)     # slot::score_dsn_w(i), score_dsn_b(i)
+SLOTS_FUSE = range(50, 52)          # slot::fuse_w, fuse_b
 
 _vp, _i, _l, _sz, _f = C.c_void_p, C.c_int, C.c_long, C.c_size_t, C.c_float
 

@@ -5,23 +5,55 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import torch
 
 from ._glue import stream as _stream
-from ._lib import (BF16_W2, DEFER_JOIN, F32, F32_BF16MFMA, F32_X3, GENERIC_DECONV, INFERENCE, NPARAMS, X3_HALF_PIECES, X3_HALF_PIECES_BWD, X3_TWO_PIECES, check,
-                   lib, ptr_array)
+from ._lib import (BF16_W2, DEFER_JOIN, F32, F32_BF16MFMA, F32_X3, GENERIC_DECONV, INFERENCE, NPARAMS, SLOTS_CONV, SLOTS_SCORE_DSN, SLOTS_UPSCALE,
+                   SLOTS_UPSCALE_SIDE, X3_HALF_PIECES, X3_HALF_PIECES_BWD, X3_TWO_PIECES, check, lib, ptr_array)
 
 # indices (state_dict order) of the frozen transposed-conv weights: lr 0 in both reference
 # scripts (train_online.py:84-85, train_parent.py:99-100); their gradients are never formed
-_FROZEN = set(range(8))
-# precision name -> (library dtype, pieces per operand of the f32x3 kernels in the forward, ... in the backward); see OSVOS.set_precision.
-# Pieces: 3 = three bf16 (six products, the default), 2 = two bf16 (three products), 22 = two FP16 under block exponents (three products; csrc/h2split.h)
-# 'bf16w2': the bf16 mode with TWO-PIECE weights in the forward (w_hi + w_lo, two products per product; OSVOS_FLAG_BF16_W2) -- the bf16 dtype with the
-# forward pieces marked 'w2' (the f32x3 piece counts do not apply to it); its backward is the bf16 mode's
-PRECISIONS = {"fp32": (F32, 3, 3), "bf16": (F32_BF16MFMA, 3, 3), "fp32x3": (F32_X3, 3, 3), "fp32x2": (F32_X3, 2, 2), "fp32x3b2": (F32_X3, 3, 2),
-              "fp32h2": (F32_X3, 22, 22), "fp32x3h2": (F32_X3, 3, 22), "bf16w2": (F32_BF16MFMA, "w2", 3)}
-_PIECE_FLAG = {3: 0, 2: X3_TWO_PIECES, 22: X3_HALF_PIECES, "w2": BF16_W2}
+_FROZEN = set(SLOTS_UPSCALE) | set(SLOTS_UPSCALE_SIDE)
+
+
+class Precision(NamedTuple):
+    """(library dtype, pieces per operand of the f32x3 kernels in the forward, ... in the backward); see OSVOS.set_precision.
+    Pieces: 3 = three bf16 (six products, the default), 2 = two bf16 (three products), 22 = two FP16 under block exponents (three products;
+    csrc/h2split.h).  'bf16w2': the bf16 mode with TWO-PIECE weights in the forward (w_hi + w_lo, two products per product; OSVOS_FLAG_BF16_W2) --
+    the bf16 dtype with the forward pieces marked 'w2' (the f32x3 piece counts do not apply to it); its backward is the bf16 mode's.
+    The methods compose the "dtype word" of each library call -- here and nowhere else (csrc/common.h, osvos_dtype_word, decodes it); callers
+    OR in the per-call flags GENERIC_DECONV, INFERENCE and DEFER_JOIN."""
+    dtype: int
+    pieces_fwd: object
+    pieces_bwd: int
+
+    PIECE_FLAG = {3: 0, 2: X3_TWO_PIECES, 22: X3_HALF_PIECES, "w2": BF16_W2}      # (a class constant, not a field)
+
+    def wbuf_word(self):      # of osvos_net_wbuf_bytes: the two-piece forward packs make the buffer larger
+        return self.dtype | (BF16_W2 if self.pieces_fwd == "w2" else 0)
+
+    def pack_word(self):      # of osvos_net_pack: the format of the forward and of the data-gradient packs
+        return self.wbuf_word() | (X3_HALF_PIECES if self.pieces_fwd == 22 else 0) | (X3_HALF_PIECES_BWD if self.pieces_bwd == 22 else 0)
+
+    def fwd_word(self):       # of osvos_net_forward
+        return self.dtype | self.PIECE_FLAG[self.pieces_fwd]
+
+    def bwd_word(self):       # of osvos_net_backward
+        return self.dtype | self.PIECE_FLAG[self.pieces_bwd]
+
+    def pack_format(self):
+        """What the packs in wbuf are: (dtype, forward format, data-gradient format) -- 'w2' two-piece bf16, 'h2' FP16 pairs, '' the dtype's
+        plain packs.  Part of the pack key: a graph recorded under one format must not run its backward on packs of another (the backward raises)."""
+        fwd = "w2" if self.pieces_fwd == "w2" else ("h2" if self.pieces_fwd == 22 else "")
+        return (self.dtype, fwd, "h2" if self.pieces_bwd == 22 else "")
+
+
+PRECISIONS = {"fp32": Precision(F32, 3, 3), "bf16": Precision(F32_BF16MFMA, 3, 3), "fp32x3": Precision(F32_X3, 3, 3), "fp32x2": Precision(F32_X3, 2, 2),
+              "fp32x3b2": Precision(F32_X3, 3, 2), "fp32h2": Precision(F32_X3, 22, 22), "fp32x3h2": Precision(F32_X3, 3, 22),
+              "bf16w2": Precision(F32_BF16MFMA, "w2", 3)}
+TEST_PRECISIONS = ("fp32", "fp32x3", "fp32h2", "bf16", "bf16w2")      # train_online.py --test-precision: forward-only runs
 
 
 class NetRuntime:
@@ -35,7 +67,7 @@ class NetRuntime:
         # 'fp32x3' (default: fp32 tensors and fp32-grade results, the wide 3x3 convolutions on the bf16 matrix pipe with three-way
         # split operands), 'fp32' (the same on the exact fp32 MFMA kernels) or 'bf16' (bf16 MFMA operands and bf16 trunk tensors,
         # fp32 accumulate; head and loss stay fp32).  OSVOS_PRECISION sets the initial value.
-        self.dtype, self.pieces_fwd, self.pieces_bwd = F32_X3, 3, 3
+        self.precision = PRECISIONS["fp32x3"]
         self.set_precision(os.environ.get("OSVOS_PRECISION", "fp32x3").lower() if os.environ.get("OSVOS_PRECISION", "fp32x3").lower() in PRECISIONS else "fp32x3")
         self.aux_stream = None        # second HIP stream: wgrad kernels overlap the dgrad kernels
         self.aux2_stream = None       # third: the slab reduces of the weight gradients
@@ -65,11 +97,7 @@ class NetRuntime:
         key = (device.type, device.index if device.index is not None else torch.cuda.current_device(), name)
         st = cls._shared_streams.get(key)
         if st is None:
-            prio = os.environ.get("OSVOS_AUX_PRIORITY", "")       # tuning: HIP priority of the weight-gradient / reduce streams (lower = more urgent)
-            try:
-                st = torch.cuda.Stream(device=device, priority=int(prio)) if prio and name in ("wgrad", "reduce") else torch.cuda.Stream(device=device)
-            except Exception:
-                st = torch.cuda.Stream(device=device)
+            st = torch.cuda.Stream(device=device)
             cls._shared_streams[key] = st
         return st
 
@@ -101,24 +129,20 @@ class NetRuntime:
         return C.c_void_p(self.aux2_stream.cuda_stream)
 
     def set_precision(self, name):
-        # round 6: the f32x3 kernels can take TWO bf16 pieces per operand (three products instead of six) -- same dtype, packs and workspaces, one flag
-        # on the network calls: 'fp32x2' in both passes, 'fp32x3b2' in the BACKWARD only (forward = 'fp32x3' bit for bit)
-        # 'fp32h2': TWO FP16 pieces under block exponents in both passes (fp32-grade at three products: the packs change format, hence the re-pack);
-        # 'fp32x3h2': the forward of 'fp32x3' bit for bit, the backward on FP16 pairs
-        # 'bf16w2': the bf16 mode's forward on two-piece weight packs (OSVOS_FLAG_BF16_W2) -- a larger buffer, hence re-allocation and re-pack
-        dt, pf, pb = PRECISIONS[name]
-        fmt_before = self.pack_format()
-        self.pieces_fwd, self.pieces_bwd = pf, pb
-        if dt != self.dtype or (pf == "w2") != (fmt_before[1] == "w2"):
-            self.dtype, self.wbuf, self.key = dt, None, None
-        elif self.pack_format() != fmt_before:
+        # another wbuf word (another dtype, 'bf16' <-> 'bf16w2': the lo planes) is another buffer, hence re-allocation and re-pack; another pack format
+        # alone ('fp32h2', 'fp32x3h2': FP16-pair packs in the same buffers) a re-pack; 'fp32x2' / 'fp32x3b2' are 'fp32x3' with one flag on the network
+        # calls -- same packs, nothing to do
+        before, self.precision = self.precision, PRECISIONS[name]
+        if self.precision.wbuf_word() != before.wbuf_word():
+            self.wbuf, self.key = None, None
+        elif self.precision.pack_format() != before.pack_format():
             self.key = None
 
+    dtype = property(lambda self: self.precision.dtype)
+    generic_flag = property(lambda self: GENERIC_DECONV if self.generic_head else 0)
+
     def pack_format(self):
-        """What the packs in wbuf are: (dtype, forward format, data-gradient format) -- 'w2' two-piece bf16, 'h2' FP16 pairs, '' the dtype's plain
-        packs.  Part of the pack key: a graph recorded under one format must not run its backward on packs of another (the backward raises)."""
-        fwd = "w2" if self.pieces_fwd == "w2" else ("h2" if self.pieces_fwd == 22 else "")
-        return (self.dtype, fwd, "h2" if self.pieces_bwd == 22 else "")
+        return self.precision.pack_format()
 
     def ensure_packed(self, params):
         dev = params[0].device
@@ -127,7 +151,7 @@ class NetRuntime:
             return
         l = lib()
         if self.wbuf is None or self.wbuf.device != dev:
-            self.wbuf = torch.empty(l.osvos_net_wbuf_bytes(self.dtype | (BF16_W2 if self.pieces_fwd == "w2" else 0)), device=dev, dtype=torch.uint8)
+            self.wbuf = torch.empty(l.osvos_net_wbuf_bytes(self.precision.wbuf_word()), device=dev, dtype=torch.uint8)
             self.deconv_key = None
         dkey = key[1][:4]
         if dkey != self.deconv_key:
@@ -136,20 +160,18 @@ class NetRuntime:
             self.generic_head = not self._deconv_is_diagonal(params[:4])
             self.deconv_key = dkey
         check(l.osvos_net_pack(ptr_array([p.data_ptr() for p in params]), C.c_void_p(self.wbuf.data_ptr()),
-                               self.cdtype() | (X3_HALF_PIECES if self.pieces_fwd == 22 else 0) | (X3_HALF_PIECES_BWD if self.pieces_bwd == 22 else 0) |
-                               (BF16_W2 if self.pieces_fwd == "w2" else 0),
-                               1, _stream()), "net_pack")
+                               self.precision.pack_word() | self.generic_flag, 1, _stream()), "net_pack")
         self.key = key
 
     def cdtype(self):
         """dtype argument of the osvos_net_* calls: precision, plus the generic-deconvolution flag when the upscale weights need it."""
-        return self.dtype | (GENERIC_DECONV if self.generic_head else 0)
+        return self.dtype | self.generic_flag
 
     def cdtype_fwd(self):
-        return self.cdtype() | _PIECE_FLAG[self.pieces_fwd]
+        return self.precision.fwd_word() | self.generic_flag
 
     def cdtype_bwd(self):
-        return self.cdtype() | _PIECE_FLAG[self.pieces_bwd]
+        return self.precision.bwd_word() | self.generic_flag
 
     @staticmethod
     def _deconv_is_diagonal(ups):
@@ -173,6 +195,38 @@ def wants_backward(x, params):
     return bool(torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)))
 
 
+def _forward_args(x, params):
+    """The argument checks of a forward; returns the input and the parameters as the library takes them: detached, contiguous, float32."""
+    if not x.is_cuda:
+        raise RuntimeError("OSVOS (osvos_pytorch_amd) runs on the GPU only: move the module and the input to "
+                           "'cuda'; there is no CPU fallback")
+    if len(params) != NPARAMS:
+        raise RuntimeError("expected %d parameters, got %d" % (NPARAMS, len(params)))
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError("expected input of shape [N,3,H,W], got %s" % (tuple(x.shape),))
+    xin = x.detach().contiguous().float()
+    ps = [p.detach().contiguous() for p in params]
+    for p in ps:
+        if p.dtype != torch.float32 or p.device != xin.device:
+            raise RuntimeError("parameters must be float32 on the input's device")
+    return xin, ps
+
+
+def _launch_forward(rt, xin, ps, need_bwd):
+    """The forward launch of ``OSVOSNetFunction`` and of ``net_forward_features`` on checked arguments, with xin's device current: packs, the
+    workspace (need_bwd False: the forward-only one, and the inference forward), the five logit maps.  Returns ``(outs, ws, (n, h, w))``."""
+    l = lib()
+    rt.ensure_packed(ps)
+    n, _, h, w = (int(v) for v in xin.shape)
+    nbytes = l.osvos_net_ws_bytes(n, h, w, rt.dtype) if need_bwd else l.osvos_net_ws_bytes_infer(n, h, w, rt.dtype)
+    ws = torch.empty(nbytes, device=xin.device, dtype=torch.uint8)
+    outs = [torch.empty((n, 1, h, w), device=xin.device, dtype=torch.float32) for _ in range(5)]
+    check(l.osvos_net_forward(C.c_void_p(xin.data_ptr()), C.c_void_p(rt.wbuf.data_ptr()), C.c_void_p(ws.data_ptr()),
+                              ptr_array([o.data_ptr() for o in outs]), n, h, w, rt.cdtype_fwd() | (0 if need_bwd else INFERENCE), _stream(),
+                              rt.auxf(xin.device)), "net_forward")
+    return outs, ws, (n, h, w)
+
+
 class OSVOSNetFunction(torch.autograd.Function):
     """(x [N,3,H,W], 52 parameters) -> 5 logit maps [N,1,H,W]   (vgg_osvos.py:59-74)."""
 
@@ -180,34 +234,15 @@ class OSVOSNetFunction(torch.autograd.Function):
     def forward(ctx, rt, need_bwd, x, *params):
         # need_bwd (wants_backward(), decided by the caller): False = the inference forward in the forward-only workspace
         ctx.set_materialize_grads(False)      # unused heads arrive as None, not as zero maps
-        if not x.is_cuda:
-            raise RuntimeError("OSVOS (osvos_pytorch_amd) runs on the GPU only: move the module and the input to "
-                               "'cuda'; there is no CPU fallback")
-        if len(params) != NPARAMS:
-            raise RuntimeError("expected %d parameters, got %d" % (NPARAMS, len(params)))
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise RuntimeError("expected input of shape [N,3,H,W], got %s" % (tuple(x.shape),))
-        l = lib()
-        xin = x.detach().contiguous().float()
-        ps = [p.detach().contiguous() for p in params]
-        for p in ps:
-            if p.dtype != torch.float32 or p.device != xin.device:
-                raise RuntimeError("parameters must be float32 on the input's device")
-        rt.ensure_packed(ps)
-        n, _, h, w = xin.shape
-        nbytes = l.osvos_net_ws_bytes(n, h, w, rt.dtype) if need_bwd else l.osvos_net_ws_bytes_infer(n, h, w, rt.dtype)
+        xin, ps = _forward_args(x, params)
+        outs, ws, shape = _launch_forward(rt, xin, ps, need_bwd)
         ctx.cdtype = rt.cdtype()
         ctx.cdtype_bwd = rt.cdtype_bwd()
-        ws = torch.empty(nbytes, device=xin.device, dtype=torch.uint8)
-        outs = [torch.empty((n, 1, h, w), device=xin.device, dtype=torch.float32) for _ in range(5)]
-        check(l.osvos_net_forward(C.c_void_p(xin.data_ptr()), C.c_void_p(rt.wbuf.data_ptr()), C.c_void_p(ws.data_ptr()),
-                                  ptr_array([o.data_ptr() for o in outs]), n, h, w, rt.cdtype_fwd() | (0 if need_bwd else INFERENCE), _stream(),
-                                  rt.auxf(xin.device)), "net_forward")
         # the activation workspace rides in autograd's saved-tensor slot: released right after a plain backward, kept under
         # retain_graph=True (a second backward recomputes every gradient buffer from the untouched forward half: no buffer of the
         # forward is written by the backward), and a second backward WITHOUT retain_graph raises autograd's own error, like the reference
         ctx.save_for_backward(ws)
-        ctx.rt, ctx.shape = rt, (n, h, w)
+        ctx.rt, ctx.shape = rt, shape
         ctx.param_meta = [(tuple(p.shape), p.device) for p in ps]
         ctx.params = params          # for in-place gradient accumulation in backward
         ctx.pack_key = rt.key
@@ -232,16 +267,16 @@ class OSVOSNetFunction(torch.autograd.Function):
             # the deconv weights (params 0..7): frozen by lr 0 in both reference scripts (train_online.py:84-85) -- the commuted head
             # forms no gradient for them; the generic head (non-diagonal weights = somebody trains them) does
             need = ctx.needs_input_grad[3 + i] and (i not in _FROZEN or bool(ctx.cdtype & GENERIC_DECONV))
-            if need and 4 <= i < 8 and d[i - 4] is None:
+            if need and i in SLOTS_UPSCALE_SIDE and d[i - SLOTS_UPSCALE_SIDE.start] is None:
                 need = False       # upscale_[i] only sees the side head i
-            if need and 42 <= i < 50 and all(g is None for g in d[:4]):
+            if need and i in SLOTS_SCORE_DSN and all(g is None for g in d[:4]):
                 need = False       # score_dsn gets no gradient when only the fused head is used
             wanted.append(need)
         # The weight-gradient kernels produce a layer's weight AND bias gradient in one launch, and the C side launches them
         # when the layer's weight target is non-NULL: a layer with exactly one of (weight, bias) trainable still needs both
         # targets.  The unwanted half goes to a scratch tensor that autograd never sees.
         launch = list(wanted)
-        for wi in range(8, 42, 2):                       # (weight, bias) pairs of the 13 trunk + 4 side_prep convs
+        for wi in SLOTS_CONV[::2]:                       # (weight, bias) pairs of the 13 trunk + 4 side_prep convs
             launch[wi] = launch[wi + 1] = wanted[wi] or wanted[wi + 1]
         # Gradient accumulation (loss /= nAveGrad; backward; ... step every nAveGrad): when every wanted
         # parameter already holds a dense .grad, the slab-reduce kernels add into it directly and autograd
@@ -297,33 +332,18 @@ def net_forward_features(rt, x, params, layer=9):
     its ``osvos_net_ws_format`` (0 fp32, 1 bf16).  The view keeps the workspace alive; nothing is copied."""
     if isinstance(layer, bool) or not isinstance(layer, int) or layer not in FEATURE_LAYERS:
         raise ValueError("forward_features: layer %r is not one of %s (conv2_2, conv3_3, conv4_3, conv5_3)" % (layer, FEATURE_LAYERS))
-    if not x.is_cuda:
-        raise RuntimeError("OSVOS (osvos_pytorch_amd) runs on the GPU only: move the module and the input to 'cuda'; there is no CPU fallback")
-    if len(params) != NPARAMS:
-        raise RuntimeError("expected %d parameters, got %d" % (NPARAMS, len(params)))
-    if x.dim() != 4 or x.shape[1] != 3:
-        raise RuntimeError("expected input of shape [N,3,H,W], got %s" % (tuple(x.shape),))
-    l = lib()
+    # the choice of forward OSVOS.forward makes (wants_backward(), read outside the no_grad block below), and the same launch: same bits
     need_bwd = wants_backward(x, params)
     with torch.no_grad():
-        xin = x.detach().contiguous().float()
-        ps = [p.detach().contiguous() for p in params]
-        for p in ps:
-            if p.dtype != torch.float32 or p.device != xin.device:
-                raise RuntimeError("parameters must be float32 on the input's device")
+        xin, ps = _forward_args(x, params)
         with torch.cuda.device(xin.device):
-            rt.ensure_packed(ps)
-            n, _, h, w = (int(v) for v in xin.shape)
-            # the choice of forward OSVOS.forward makes (wants_backward(), read outside this function's own no_grad block): same call, same bits
-            nbytes = l.osvos_net_ws_bytes(n, h, w, rt.dtype) if need_bwd else l.osvos_net_ws_bytes_infer(n, h, w, rt.dtype)
-            ws = torch.empty(nbytes, device=xin.device, dtype=torch.uint8)
-            outs = [torch.empty((n, 1, h, w), device=xin.device, dtype=torch.float32) for _ in range(5)]
-            check(l.osvos_net_forward(C.c_void_p(xin.data_ptr()), C.c_void_p(rt.wbuf.data_ptr()), C.c_void_p(ws.data_ptr()),
-                                      ptr_array([o.data_ptr() for o in outs]), n, h, w, rt.cdtype_fwd() | (0 if need_bwd else INFERENCE), _stream(),
-                                      rt.auxf(xin.device)), "net_forward")
+            outs, ws, (n, h, w) = _launch_forward(rt, xin, ps, need_bwd)
+        l = lib()
         off, el, ch, hh, ww = C.c_size_t(), C.c_size_t(), C.c_int(), C.c_int(), C.c_int()
         check(l.osvos_net_ws_query(n, h, w, rt.dtype, layer, C.byref(off), C.byref(el), C.byref(ch), C.byref(hh), C.byref(ww)), "net_ws_query")
         fmt = int(l.osvos_net_ws_format(rt.dtype, layer))
+        if fmt < 0:
+            check(fmt, "net_ws_format")
         dt, size = (torch.bfloat16, 2) if fmt == 1 else (torch.float32, 4)
         feat = ws[off.value:off.value + size * el.value].view(dt).view(n, hh.value, ww.value, ch.value)
     return outs, feat, fmt
@@ -403,8 +423,6 @@ _CBCE_SCRATCH = {}
 
 
 def _cbce_scratch(dev, nbytes):
-    if os.environ.get("OSVOS_CBCE_PERSISTENT", "1") == "0":      # A/B switch: a fresh buffer and a memset per call, as rounds 1-5
-        return torch.empty(nbytes, device=dev, dtype=torch.uint8), 0
     if torch.cuda.is_current_stream_capturing():      # a graph gets a buffer of its own, zeroed by a node of the graph (no sharing with eager calls)
         return torch.zeros(nbytes, device=dev, dtype=torch.uint8), 0
     key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream, nbytes)

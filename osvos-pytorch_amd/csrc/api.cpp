@@ -91,39 +91,30 @@ int osvos_nhwc_to_nchw(const void* src, float* dst, int N, int C, int H, int W, 
   return osvos_nhwc_to_nchw_f32((const float*)src, dst, N, C, H, W, cs, (hipStream_t)stream);
 }
 
-// OSVOS_FLAG_BF16_W2 on the op-level pack entries: two-piece forward pack (hi plane, then lo plane), dtype OSVOS_F32_BF16MFMA only
-static bool w2_pack_flag(int& dtype, const char* what, bool* bad) {
-  const bool w2 = (dtype & OSVOS_FLAG_BF16_W2) != 0;
-  dtype &= ~OSVOS_FLAG_BF16_W2;
-  *bad = w2 && dtype != OSVOS_F32_BF16MFMA;
-  if (*bad) osvos_set_error("%s: OSVOS_FLAG_BF16_W2 needs dtype OSVOS_F32_BF16MFMA (got dtype %d)", what, dtype);
-  return w2;
-}
+// the dtype word at op level (common.h): the checks and the message of NEED_F32.  OSVOS_FLAG_BF16_W2 (d->w2) on the two forward-pack entries
+// below: the two-piece pack, hi plane then lo plane
+static bool op_dtype_word(int word, const char* what, DtypeWord* d) { return osvos_dtype_word(word, what, d, " (fp32 tensors only)"); }
 
-size_t osvos_wpack_bytes(int Cout, int Cin, int dtype) {
-  bool bad;
-  const bool w2 = w2_pack_flag(dtype, "wpack_bytes", &bad);
-  if (bad) return 0;
-  if (dtype == OSVOS_F32_BF16MFMA) return (size_t)9 * ((Cin + 31) / 32 * 32) * osvos_cout_pad(Cout) * 2 * (w2 ? 2 : 1);
-  return (size_t)9 * osvos_cin_pad(Cin, dtype) * osvos_cout_pad(Cout) * osvos_elem(dtype);
+size_t osvos_wpack_bytes(int Cout, int Cin, int dtype_) {
+  DtypeWord d;
+  if (!op_dtype_word(dtype_, "wpack_bytes", &d)) return 0;
+  if (d.dtype == OSVOS_F32_BF16MFMA) return (size_t)9 * ((Cin + 31) / 32 * 32) * osvos_cout_pad(Cout) * 2 * (d.w2 ? 2 : 1);
+  return (size_t)9 * osvos_cin_pad(Cin, d.dtype) * osvos_cout_pad(Cout) * osvos_elem(d.dtype);
 }
 size_t osvos_wpack_dgrad_bytes(int Cout, int Cin, int dtype) {
   if (dtype == OSVOS_F32_BF16MFMA) return (size_t)9 * ((Cout + 31) / 32 * 32) * osvos_cout_pad(Cin) * 2;
   return (size_t)9 * osvos_cin_pad(Cout, dtype) * osvos_cout_pad(Cin) * osvos_elem(dtype);
 }
-int osvos_pack_conv3x3_fwd(const float* w, void* wpk, int Cout, int Cin, int dtype, void* stream) {
-  bool bad;
-  if (w2_pack_flag(dtype, "pack_conv3x3_fwd", &bad)) {
-    if (bad) return -1;
+int osvos_pack_conv3x3_fwd(const float* w, void* wpk, int Cout, int Cin, int dtype_, void* stream) {
+  DtypeWord d;
+  if (!op_dtype_word(dtype_, "pack_conv3x3_fwd", &d)) return -1;
+  if (d.w2) {
     OSVOS_ARG_CHECK(w && wpk && Cout > 0 && Cin > 0, "pack_conv3x3_fwd w2: bad arguments");
-    const float* ws[1] = {w};
-    void* dsts[1] = {wpk};
-    void* los[1] = {reinterpret_cast<char*>(wpk) + osvos_wpack_bytes(Cout, Cin, OSVOS_F32_BF16MFMA)};
-    const int co[1] = {Cout}, ci[1] = {Cin}, dg[1] = {0};
-    return osvos_pack_bf16_multi(ws, dsts, co, ci, dg, los, 1, (hipStream_t)stream);
+    PackEntry e;
+    e.w = w; e.dst = wpk; e.lo_dst = reinterpret_cast<char*>(wpk) + osvos_wpack_bytes(Cout, Cin, OSVOS_F32_BF16MFMA); e.Cout = Cout; e.Cin = Cin;
+    return osvos_pack_bf16_multi(&e, 1, (hipStream_t)stream);
   }
-  NEED_F32(dtype, "pack_conv3x3_fwd");
-  if (dtype == OSVOS_F32_BF16MFMA) return osvos_pack_fwd_bf16(w, wpk, Cout, Cin, (hipStream_t)stream);
+  if (d.dtype == OSVOS_F32_BF16MFMA) return osvos_pack_fwd_bf16(w, wpk, Cout, Cin, (hipStream_t)stream);
   return osvos_pack_fwd_f32(w, (float*)wpk, Cout, Cin, (hipStream_t)stream);
 }
 int osvos_pack_conv3x3_dgrad(const float* w, void* wpk, int Cout, int Cin, int dtype, void* stream) {
@@ -161,9 +152,9 @@ int osvos_conv3x3(const void* x, const void* wpk, const float* bias, const void*
 // host only: what osvos_conv3x3_dispatch decides for a call of this shape that carries what `flags` says (launches nothing, reads no tensor)
 int osvos_conv3x3_plan(int N, int H, int W, int Cin, int Cout, int y_cs, int dtype_, int flags, int tile, int ksplit, int sk_grid, int* out) {
   OSVOS_ARG_CHECK(out != nullptr, "conv3x3_plan: null result array");
-  const int dtype = dtype_ & 0xff;
-  NEED_F32(dtype, "conv3x3_plan");
-  OSVOS_ARG_CHECK(!(dtype_ & OSVOS_FLAG_BF16_W2) || dtype == OSVOS_F32_BF16MFMA, "conv3x3_plan: OSVOS_FLAG_BF16_W2 needs dtype OSVOS_F32_BF16MFMA (got dtype %d)", dtype);
+  DtypeWord d;
+  if (!op_dtype_word(dtype_, "conv3x3_plan", &d)) return -1;
+  const int dtype = d.dtype;
   static char here[8];      // any non-null address stands for a tensor the call carries: no launcher's choose() reads through one
   void* const some = here;
   ConvCall c;
@@ -171,8 +162,8 @@ int osvos_conv3x3_plan(int N, int H, int W, int Cin, int Cout, int y_cs, int dty
   c.x = some; c.x_bf16 = (flags & OSVOS_PLAN_X_BF16) != 0;
   c.wpk = some;
   if (flags & OSVOS_PLAN_WPK3) c.wpk3 = some;
-  if (dtype_ & OSVOS_FLAG_BF16_W2) { c.w_pieces = 2; c.w_lo = osvos_wpack_bytes(Cout, Cin, OSVOS_F32_BF16MFMA); }
-  c.pieces = dtype != OSVOS_F32_X3 ? 3 : (dtype_ & OSVOS_FLAG_X3_HALF_PIECES) ? 22 : (dtype_ & OSVOS_FLAG_X3_TWO_PIECES) ? 2 : 3;
+  if (d.w2) { c.w_pieces = 2; c.w_lo = osvos_wpack_bytes(Cout, Cin, OSVOS_F32_BF16MFMA); }
+  c.pieces = d.pieces;
   c.relu = (flags & OSVOS_PLAN_RELU) != 0;
   if (flags & OSVOS_PLAN_Y_F32) c.y = reinterpret_cast<float*>(some);
   if (flags & OSVOS_PLAN_Y_BF16) c.y_bf16 = some;
@@ -306,22 +297,22 @@ int osvos_conv3x3_wgrad(const void* x, const void* dy, void* ws, float* dw, floa
 
 // host only: what osvos_wgrad_dispatch and the family's choose() decide for a call of this shape that carries what `flags` says
 static char g_some[8];      // any non-null address stands for a tensor the call carries: no choose() reads through one
-static WgradCall wgrad_plan_call(int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s, int dtype_, int flags) {
+static WgradCall wgrad_plan_call(int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s, int pieces, int flags) {
   WgradCall c;
   c.x = c.dy = c.ws = g_some; c.dw = reinterpret_cast<float*>(g_some);
   if (!(flags & OSVOS_WGRAD_PLAN_NO_BIAS)) c.db = c.dw;
   c.x_bf16 = (flags & OSVOS_WGRAD_PLAN_X_BF16) != 0; c.dy_bf16 = (flags & OSVOS_WGRAD_PLAN_DY_BF16) != 0;
   c.N = N; c.H = H; c.W = W; c.Cin = Cin; c.Cin_s = Cin_s; c.Cout = Cout; c.Cout_s = Cout_s;
-  c.pieces = (dtype_ & 0xff) != OSVOS_F32_X3 ? 3 : (dtype_ & OSVOS_FLAG_X3_HALF_PIECES) ? 22 : (dtype_ & OSVOS_FLAG_X3_TWO_PIECES) ? 2 : 3;
+  c.pieces = pieces;
   return c;
 }
 int osvos_wgrad_plan(int N, int H, int W, int Cin, int Cin_s, int Cout, int Cout_s, int dtype_, int flags, int* out) {
   OSVOS_ARG_CHECK(out != nullptr, "wgrad_plan: null result array");
   OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "wgrad_plan: bad shape");
-  const int dtype = dtype_ & 0xff;
-  NEED_F32(dtype, "wgrad_plan");
+  DtypeWord d;
+  if (!op_dtype_word(dtype_, "wgrad_plan", &d)) return -1;
   WgradPlan p;
-  if (osvos_wgrad_dispatch_plan(wgrad_plan_call(N, H, W, Cin, Cin_s, Cout, Cout_s, dtype_, flags), dtype, &p)) return -1;
+  if (osvos_wgrad_dispatch_plan(wgrad_plan_call(N, H, W, Cin, Cin_s, Cout, Cout_s, d.pieces, flags), d.dtype, &p)) return -1;
   auto sat = [](size_t v) { return v > 0x7fffffffu ? 0x7fffffff : (int)v; };
   const int v[OSVOS_WGRAD_PLAN_INTS] = {p.family, p.kernel, p.pw, p.ph, p.npx, p.npy, p.npatches, p.per_split, p.nsplit, p.nco_t, p.nci_t,
                                         (int)p.blocks, p.map, p.reduce, sat(p.slab_floats), sat(p.bslab_floats)};
@@ -339,7 +330,7 @@ int osvos_wgrad_c3_plan(int N, int H, int W, int bf16_dy, int* out) {
 int osvos_wgrad_wide_plan(int N, int H, int W, int Cin_s, int Cout, int dtype, int bf16_tensors, int* out) {
   OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0 && Cin_s > 0 && Cout > 0 && out != nullptr, "wgrad_wide_plan: bad arguments");
   OSVOS_ARG_CHECK(!bf16_tensors || dtype == OSVOS_F32_BF16MFMA, "wgrad_wide_plan: bf16 tensors go with dtype OSVOS_F32_BF16MFMA (got %d)", dtype);
-  const WgradCall c = wgrad_plan_call(N, H, W, Cin_s, Cin_s, Cout, Cout, dtype, bf16_tensors ? OSVOS_WGRAD_PLAN_X_BF16 | OSVOS_WGRAD_PLAN_DY_BF16 : 0);
+  const WgradCall c = wgrad_plan_call(N, H, W, Cin_s, Cin_s, Cout, Cout, 3, bf16_tensors ? OSVOS_WGRAD_PLAN_X_BF16 | OSVOS_WGRAD_PLAN_DY_BF16 : 0);
   WgradPlan p;
   if (osvos_wgrad_dispatch_plan(c, dtype, &p)) return -1;
   OSVOS_ARG_CHECK(p.family == WGRAD_F32X3 || p.family == WGRAD_BF16, "wgrad_wide_plan: no wide weight-gradient kernel for dtype %d Cin %d Cout %d", dtype, Cin_s, Cout);

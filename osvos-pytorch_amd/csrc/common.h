@@ -104,3 +104,58 @@ static inline int osvos_cin_pad(int cin, int dtype) { int g2 = 2 * osvos_group(d
 static inline int osvos_cout_pad(int cout) { return (cout + 31) / 32 * 32; }
 static inline size_t osvos_elem(int dtype) { return dtype == OSVOS_BF16 ? 2 : 4; }   // activation element size
 static inline bool osvos_dtype_built(int dtype) { return dtype == OSVOS_F32 || dtype == OSVOS_F32_BF16MFMA || dtype == OSVOS_F32_X3; }
+
+// The "dtype word" of the network calls and of the plan / pack queries (osvos_hip.h): the dtype in the low byte, OSVOS_FLAG_* above it.  Decoded
+// here and nowhere else (composed in one place too: autograd.py, Precision).
+struct DtypeWord {
+  int dtype = OSVOS_F32;
+  bool generic = false;      // OSVOS_FLAG_GENERIC_DECONV
+  bool infer = false;        // OSVOS_FLAG_INFERENCE
+  bool defer_join = false;   // OSVOS_FLAG_DEFER_JOIN
+  bool w2 = false;           // OSVOS_FLAG_BF16_W2: two-piece forward packs (dtype OSVOS_F32_BF16MFMA only)
+  bool half_fwd = false;     // OSVOS_FLAG_X3_HALF_PIECES: FP16 pairs in this call / osvos_net_pack: forward packs in that format
+  bool half_bwd = false;     // OSVOS_FLAG_X3_HALF_PIECES_BWD (osvos_net_pack only): data-gradient packs in that format
+  // Pieces per operand of the f32x3 kernels of the call (ConvCall::pieces, WgradCall::pieces): 3 bf16 (six products), 2 bf16 ('fp32x2',
+  // OSVOS_FLAG_X3_TWO_PIECES: three products) or 22 = two FP16 under block exponents ('fp32h2', OSVOS_FLAG_X3_HALF_PIECES; h2split.h -- the packs
+  // the call reads must be in that format).  3 for every other dtype
+  int pieces = 3;
+};
+// Fills *d from `word` and makes the checks every entry makes: the dtype is built, OSVOS_FLAG_BF16_W2 only with OSVOS_F32_BF16MFMA.  false (and the
+// error set, `what` = the entry's name, `not_built_note` appended to the first message) otherwise
+static inline bool osvos_dtype_word(int word, const char* what, DtypeWord* d, const char* not_built_note = "") {
+  d->dtype = word & 0xff;
+  d->generic = (word & OSVOS_FLAG_GENERIC_DECONV) != 0;
+  d->infer = (word & OSVOS_FLAG_INFERENCE) != 0;
+  d->defer_join = (word & OSVOS_FLAG_DEFER_JOIN) != 0;
+  d->w2 = (word & OSVOS_FLAG_BF16_W2) != 0;
+  d->half_fwd = (word & OSVOS_FLAG_X3_HALF_PIECES) != 0;
+  d->half_bwd = (word & OSVOS_FLAG_X3_HALF_PIECES_BWD) != 0;
+  const bool x3 = d->dtype == OSVOS_F32_X3;
+  d->pieces = x3 && d->half_fwd ? 22 : (x3 && (word & OSVOS_FLAG_X3_TWO_PIECES) ? 2 : 3);
+  if (!osvos_dtype_built(d->dtype)) {
+    osvos_set_error("%s: dtype %d not built%s", what, d->dtype, not_built_note);
+    return false;
+  }
+  if (d->w2 && d->dtype != OSVOS_F32_BF16MFMA) {
+    osvos_set_error("%s: OSVOS_FLAG_BF16_W2 needs dtype OSVOS_F32_BF16MFMA (got dtype %d)", what, d->dtype);
+    return false;
+  }
+  return true;
+}
+
+// Slots of the 52-entry parameter / gradient arrays of osvos_net_pack / osvos_net_backward: state_dict order of networks/vgg_osvos.py.  Named here
+// and nowhere else on the C side (_lib.py names the same groups for the Python side)
+namespace slot {
+constexpr int upscale(int i) { return i; }                 // upscale[i].weight [16][16][k][k], i = 0..3 (the fused head's deconvolutions)
+constexpr int upscale_(int i) { return 4 + i; }            // upscale_[i].weight [1][1][k][k] (the side heads')
+constexpr int conv_w(int l) { return 8 + 2 * l; }          // 3x3 convolution l: 0..12 the trunk (stages.*), 13..16 side_prep[0..3]
+constexpr int conv_b(int l) { return conv_w(l) + 1; }
+constexpr int score_dsn_w(int i) { return 42 + 2 * i; }    // score_dsn[i], i = 0..3
+constexpr int score_dsn_b(int i) { return score_dsn_w(i) + 1; }
+constexpr int fuse_w = 50, fuse_b = 51;
+static_assert(fuse_b + 1 == OSVOS_NPARAMS && conv_w(17) == score_dsn_w(0), "the slots tile the parameter array");
+}  // namespace slot
+// `which` of osvos_net_ws_query: 13 trunk activations, the pooled inputs of stages 1-4, the four side_prep outputs, the NHWC input
+namespace ws_which {
+constexpr int act = 0, pooled = 13, prep = 17, input = 21, count = 22;
+}

@@ -742,38 +742,35 @@ int osvos_conv3x3_bf16mfma_num_tiles(void) { return kNumTilesB; }
 
 int osvos_pack_fwd_bf16(const float* w, void* wpk, int Cout, int Cin, hipStream_t stream) {
   OSVOS_ARG_CHECK(w && wpk && Cout > 0 && Cin > 0, "pack_fwd bf16: bad arguments");
-  const float* ws[1] = {w};
-  void* dsts[1] = {wpk};
-  const int co[1] = {Cout}, ci[1] = {Cin}, dg[1] = {0};
-  return osvos_pack_bf16_multi(ws, dsts, co, ci, dg, nullptr, 1, stream);
+  PackEntry e;
+  e.w = w; e.dst = wpk; e.Cout = Cout; e.Cin = Cin;
+  return osvos_pack_bf16_multi(&e, 1, stream);
 }
 
 int osvos_pack_dgrad_bf16(const float* w, void* wpk, int Cout, int Cin, hipStream_t stream) {
   OSVOS_ARG_CHECK(w && wpk && Cout > 0 && Cin > 0, "pack_dgrad bf16: bad arguments");
-  const float* ws[1] = {w};
-  void* dsts[1] = {wpk};
-  const int co[1] = {Cout}, ci[1] = {Cin}, dg[1] = {1};
-  return osvos_pack_bf16_multi(ws, dsts, co, ci, dg, nullptr, 1, stream);
+  PackEntry e;
+  e.w = w; e.dst = wpk; e.Cout = Cout; e.Cin = Cin; e.dgrad = 1;
+  return osvos_pack_bf16_multi(&e, 1, stream);
 }
 
-int osvos_pack_bf16_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, void* const* lo_dsts, int n,
-                          hipStream_t stream) {
-  OSVOS_ARG_CHECK(ws && dsts && Couts && Cins && dgrads && n >= 0 && n <= OSVOS_PACK_MAX, "pack_bf16_multi: bad table (n = %d)", n);
+int osvos_pack_bf16_multi(const PackEntry* e, int n, hipStream_t stream) {
+  OSVOS_ARG_CHECK(e && n >= 0 && n <= OSVOS_PACK_MAX, "pack_bf16_multi: bad table (n = %d)", n);
   if (n == 0) return 0;
   PackB16Table t;
   t.n = n;
   t.start[0] = 0;
   for (int k = 0; k < n; ++k) {
-    const int K = dgrads[k] ? Couts[k] : Cins[k], M = dgrads[k] ? Cins[k] : Couts[k];
-    OSVOS_ARG_CHECK(ws[k] && dsts[k] && K > 0 && M > 0, "pack_bf16_multi: entry %d (K = %d, M = %d)", k, K, M);
-    t.w[k] = ws[k]; t.dst[k] = reinterpret_cast<bf16_t*>(dsts[k]); t.Cout[k] = Couts[k]; t.Cin[k] = Cins[k]; t.dgrad[k] = dgrads[k] ? 1 : 0;
+    const int K = e[k].dgrad ? e[k].Cout : e[k].Cin, M = e[k].dgrad ? e[k].Cin : e[k].Cout;
+    OSVOS_ARG_CHECK(e[k].w && e[k].dst && K > 0 && M > 0, "pack_bf16_multi: entry %d (K = %d, M = %d)", k, K, M);
+    t.w[k] = e[k].w; t.dst[k] = reinterpret_cast<bf16_t*>(e[k].dst); t.Cout[k] = e[k].Cout; t.Cin[k] = e[k].Cin; t.dgrad[k] = e[k].dgrad ? 1 : 0;
     t.start[k + 1] = t.start[k] + (long)(((K + 31) / 32 * 32) / 8) * (osvos_cout_pad(M) / 32);
     t.pieces[k] = 1;
     t.lo[k] = 0;
-    if (lo_dsts != nullptr && lo_dsts[k] != nullptr) {
-      OSVOS_ARG_CHECK(!dgrads[k], "pack_bf16_multi: entry %d: two-piece packs are forward packs only", k);
-      const long d = reinterpret_cast<const bf16_t*>(lo_dsts[k]) - t.dst[k];
-      OSVOS_ARG_CHECK(reinterpret_cast<const char*>(lo_dsts[k]) == reinterpret_cast<const char*>(t.dst[k] + d), "pack_bf16_multi: entry %d: misaligned lo plane", k);
+    if (e[k].lo_dst != nullptr) {
+      OSVOS_ARG_CHECK(!e[k].dgrad, "pack_bf16_multi: entry %d: two-piece packs are forward packs only", k);
+      const long d = reinterpret_cast<const bf16_t*>(e[k].lo_dst) - t.dst[k];
+      OSVOS_ARG_CHECK(reinterpret_cast<const char*>(e[k].lo_dst) == reinterpret_cast<const char*>(t.dst[k] + d), "pack_bf16_multi: entry %d: misaligned lo plane", k);
       t.pieces[k] = 2;
       t.lo[k] = d;
     }

@@ -1114,20 +1114,19 @@ __global__ __launch_bounds__(256) void pack_x3_multi_kernel(PackX3Table t) {
 
 }  // namespace
 
-int osvos_pack_x3_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, const int* halfs, int n,
-                        hipStream_t stream) {
-  OSVOS_ARG_CHECK(ws && dsts && Couts && Cins && dgrads && halfs && n >= 0 && n <= OSVOS_PACK_MAX, "pack_x3_multi: bad table (n = %d)", n);
+int osvos_pack_x3_multi(const PackEntry* e, int n, hipStream_t stream) {
+  OSVOS_ARG_CHECK(e && n >= 0 && n <= OSVOS_PACK_MAX, "pack_x3_multi: bad table (n = %d)", n);
   if (n == 0) return 0;
   PackX3Table t;
   t.n = n;
   t.start[0] = 0;
   bool any_half = false;
   for (int k = 0; k < n; ++k) {
-    t.half[k] = halfs[k] != 0 ? 1 : 0;
+    t.half[k] = e[k].half != 0 ? 1 : 0;
     any_half = any_half || t.half[k];
-    const int K = dgrads[k] ? Couts[k] : Cins[k], M = dgrads[k] ? Cins[k] : Couts[k];
-    OSVOS_ARG_CHECK(ws[k] && dsts[k] && K % 16 == 0 && M > 0, "pack_x3_multi: entry %d (K = %d, M = %d)", k, K, M);
-    t.w[k] = ws[k]; t.dst[k] = reinterpret_cast<unsigned short*>(dsts[k]); t.Cout[k] = Couts[k]; t.Cin[k] = Cins[k]; t.dgrad[k] = dgrads[k] ? 1 : 0;
+    const int K = e[k].dgrad ? e[k].Cout : e[k].Cin, M = e[k].dgrad ? e[k].Cin : e[k].Cout;
+    OSVOS_ARG_CHECK(e[k].w && e[k].dst && K % 16 == 0 && M > 0, "pack_x3_multi: entry %d (K = %d, M = %d)", k, K, M);
+    t.w[k] = e[k].w; t.dst[k] = reinterpret_cast<unsigned short*>(e[k].dst); t.Cout[k] = e[k].Cout; t.Cin[k] = e[k].Cin; t.dgrad[k] = e[k].dgrad ? 1 : 0;
     t.start[k + 1] = t.start[k] + (long)(K / 8) * (osvos_cout_pad(M) / 32);
   }
   if (any_half) {
@@ -1148,10 +1147,9 @@ int osvos_pack_x3(const float* w, void* wpk3, int Cout, int Cin, int dgrad, int 
   OSVOS_ARG_CHECK(w && wpk3 && Cout > 0 && Cin > 0, "pack_x3: bad arguments");
   const int K = dgrad ? Cout : Cin;
   OSVOS_ARG_CHECK(K % 16 == 0, "pack_x3: %d reduction channels (must be a multiple of 16)", K);
-  const float* ws[1] = {w};
-  void* dsts[1] = {wpk3};
-  const int co[1] = {Cout}, ci[1] = {Cin}, dg[1] = {dgrad}, hf[1] = {half};
-  return osvos_pack_x3_multi(ws, dsts, co, ci, dg, hf, 1, stream);
+  PackEntry e;
+  e.w = w; e.dst = wpk3; e.Cout = Cout; e.Cin = Cin; e.dgrad = dgrad; e.half = half;
+  return osvos_pack_x3_multi(&e, 1, stream);
 }
 
 int osvos_conv3x3_f32x3_num_tiles(void) { return kNumTilesX; }

@@ -175,14 +175,17 @@ int osvos_conv3x3_wgrad_f32x3(const WgradCall& c);
 int osvos_wgrad_f32x3_plan(const WgradCall& c, WgradPlan* p);
 size_t osvos_wpack_x3_bytes(int M, int K);
 #define OSVOS_PACK_MAX 40
-// n packs (n <= OSVOS_PACK_MAX) in one launch: ws[k] OIHW fp32 [Couts[k]][Cins[k]][3][3] -> dsts[k]; dgrads[k] != 0: data-gradient form.
-// bf16: lo_dsts (NULL = none) [k] != NULL also writes the lo plane of a two-piece forward pack there (the hi plane, at dsts[k], is the
-// single-piece pack byte for byte)
-int osvos_pack_bf16_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, void* const* lo_dsts, int n,
-                          hipStream_t stream);
-// pre-split f32x3 packs: halfs[k] / half != 0: the entry in the two-piece FP16 format (h2split.h; three launches instead of one), else three bf16 planes
-int osvos_pack_x3_multi(const float* const* ws, void* const* dsts, const int* Couts, const int* Cins, const int* dgrads, const int* halfs, int n,
-                        hipStream_t stream);
+// One weight pack to write: w OIHW fp32 [Cout][Cin][3][3] -> dst; dgrad != 0: data-gradient form.  The two multi-pack launchers write n of them
+// (n <= OSVOS_PACK_MAX) in one launch
+struct PackEntry {
+  const float* w = nullptr;
+  void* dst = nullptr;
+  void* lo_dst = nullptr;              // bf16 only: also the lo plane of a two-piece forward pack, there (the hi plane, at dst, is the single-piece pack byte for byte)
+  int Cout = 0, Cin = 0, dgrad = 0;
+  int half = 0;                        // f32x3 only: != 0 the two-piece FP16 format (h2split.h; three launches instead of one), else three bf16 planes
+};
+int osvos_pack_bf16_multi(const PackEntry* e, int n, hipStream_t stream);
+int osvos_pack_x3_multi(const PackEntry* e, int n, hipStream_t stream);      // (pre-split f32x3 packs)
 int osvos_pack_x3(const float* w, void* wpk3, int Cout, int Cin, int dgrad, int half, hipStream_t stream);
 bool osvos_dgrad_c3_applicable(int Cin, int Cout);
 int osvos_conv3x3_dgrad_c3_f32(const float* dy, const float* wpk_dgrad, float* dx_nchw, int N, int H, int W, int Cout, hipStream_t stream);

@@ -17,20 +17,31 @@ constexpr int kNumTrunk = 13;
 constexpr int kNumConv = 17;          // 13 trunk + 4 side_prep
 constexpr int kInPad = 8;             // conv1_1 input channels padded 3 -> 8 (one K chunk)
 
+// the 17 3x3 convolutions: 13 of the trunk in order (kStageN[stage] per stage, kStageC[stage] output channels), then side_prep[0..3], which read
+// the last activation of stages 1-4.  cin_s: channel stride of the input tensor (conv1_1's 3 channels are padded to kInPad)
 struct ConvDesc {
   int stage, cin, cin_s, cout, w_param, b_param;
 };
+constexpr ConvDesc conv_row(int l, int stage, int cin, int cout) { return ConvDesc{stage, cin, cin == 3 ? kInPad : cin, cout, slot::conv_w(l), slot::conv_b(l)}; }
+constexpr ConvDesc kConv[kNumConv] = {
+    conv_row(0, 0, 3, 64),     conv_row(1, 0, 64, 64),                                                             // conv1_x
+    conv_row(2, 1, 64, 128),   conv_row(3, 1, 128, 128),                                                           // conv2_x
+    conv_row(4, 2, 128, 256),  conv_row(5, 2, 256, 256),   conv_row(6, 2, 256, 256),                               // conv3_x
+    conv_row(7, 3, 256, 512),  conv_row(8, 3, 512, 512),   conv_row(9, 3, 512, 512),                               // conv4_x
+    conv_row(10, 4, 512, 512), conv_row(11, 4, 512, 512),  conv_row(12, 4, 512, 512),                              // conv5_x
+    conv_row(13, 1, 128, 16),  conv_row(14, 2, 256, 16),   conv_row(15, 3, 512, 16),   conv_row(16, 4, 512, 16)};  // side_prep[0..3]
 
-void conv_table(ConvDesc* d) {
-  int l = 0, cin = 3;
+// (the rows restate kStageN / kStageC, which the stage loops and the layouts still walk: an edit of one without the other does not compile)
+constexpr bool conv_table_agrees() {
+  int l = 0;
   for (int si = 0; si < 5; ++si)
-    for (int j = 0; j < kStageN[si]; ++j) {
-      d[l] = ConvDesc{si, cin, cin == 3 ? kInPad : cin, kStageC[si], 8 + 2 * l, 9 + 2 * l};
-      cin = kStageC[si];
-      ++l;
-    }
-  for (int i = 0; i < 4; ++i) d[kNumTrunk + i] = ConvDesc{i + 1, kStageC[i + 1], kStageC[i + 1], 16, 34 + 2 * i, 35 + 2 * i};
+    for (int j = 0; j < kStageN[si]; ++j, ++l)
+      if (l >= kNumTrunk || kConv[l].stage != si || kConv[l].cout != kStageC[si] || kConv[l].cin != (j > 0 ? kStageC[si] : si > 0 ? kStageC[si - 1] : 3)) return false;
+  for (int i = 0; i < 4; ++i)
+    if (kConv[kNumTrunk + i].stage != i + 1 || kConv[kNumTrunk + i].cin != kStageC[i + 1] || kConv[kNumTrunk + i].cout != 16) return false;
+  return l == kNumTrunk;
 }
+static_assert(conv_table_agrees(), "kConv disagrees with kStageN / kStageC");
 
 int last_of_stage(int si) {
   int l = -1;
@@ -48,23 +59,21 @@ struct WbufLayout {
   size_t total;
 };
 
-// dtype: with OSVOS_FLAG_BF16_W2 the layout is the single-piece one plus the 17 forward lo planes appended in layer order (trunk 0-12, side_prep
-// 13-16): every other offset is unchanged, so the hi planes ARE the bf16 packs and a backward needs no flag to find its packs
-WbufLayout wbuf_layout(int dtype_) {
-  const int dtype = dtype_ & 0xff;
+// With OSVOS_FLAG_BF16_W2 (dw.w2) the layout is the single-piece one plus the 17 forward lo planes appended in layer order (trunk 0-12, side_prep
+// 13-16): every other offset is unchanged, so the hi planes ARE the bf16 packs and a backward finds its packs with or without the flag
+WbufLayout wbuf_layout(const DtypeWord& dw) {
+  const int dtype = dw.dtype;
   WbufLayout L;
-  ConvDesc d[kNumConv];
-  conv_table(d);
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
   for (int l = 0; l < kNumConv; ++l) {
-    L.fwd[l] = take(osvos_wpack_bytes(d[l].cout, d[l].cin_s, dtype));
-    L.dgrad[l] = take(osvos_wpack_dgrad_bytes(d[l].cout, d[l].cin, dtype));
-    L.bias[l] = take(sizeof(float) * d[l].cout);
+    L.fwd[l] = take(osvos_wpack_bytes(kConv[l].cout, kConv[l].cin_s, dtype));
+    L.dgrad[l] = take(osvos_wpack_dgrad_bytes(kConv[l].cout, kConv[l].cin, dtype));
+    L.bias[l] = take(sizeof(float) * kConv[l].cout);
     L.fwd3[l] = L.dgrad3[l] = (size_t)-1;
     if (dtype == OSVOS_F32_X3) {
-      if (d[l].cin_s % 16 == 0 && d[l].cin == d[l].cin_s) L.fwd3[l] = take(osvos_wpack_x3_bytes(d[l].cout, d[l].cin));
-      if (d[l].cout % 16 == 0) L.dgrad3[l] = take(osvos_wpack_x3_bytes(d[l].cin, d[l].cout));
+      if (kConv[l].cin_s % 16 == 0 && kConv[l].cin == kConv[l].cin_s) L.fwd3[l] = take(osvos_wpack_x3_bytes(kConv[l].cout, kConv[l].cin));
+      if (kConv[l].cout % 16 == 0) L.dgrad3[l] = take(osvos_wpack_x3_bytes(kConv[l].cin, kConv[l].cout));
     }
   }
   for (int i = 0; i < 4; ++i) { L.wd[i] = take(16 * sizeof(float)); L.bd[i] = take(sizeof(float)); }
@@ -73,7 +82,7 @@ WbufLayout wbuf_layout(int dtype_) {
   for (int i = 0; i < 4; ++i) { const int k = 4 << i; L.f1[i] = take(sizeof(float) * k * k); L.f16[i] = take(sizeof(float) * k * k); }
   for (int i = 0; i < 4; ++i) { const int k = 4 << i; L.weff[i] = take(sizeof(float) * 16 * k * k); }
   for (int i = 0; i < 4; ++i) { const int k = 4 << i; L.wup[i] = take(sizeof(float) * 256 * k * k); }
-  for (int l = 0; l < kNumConv; ++l) L.fwd_lo[l] = (dtype_ & OSVOS_FLAG_BF16_W2) ? take(osvos_wpack_bytes(d[l].cout, d[l].cin_s, dtype)) : (size_t)-1;
+  for (int l = 0; l < kNumConv; ++l) L.fwd_lo[l] = dw.w2 ? take(osvos_wpack_bytes(kConv[l].cout, kConv[l].cin_s, dtype)) : (size_t)-1;
   L.total = off;
   return L;
 }
@@ -130,9 +139,9 @@ inline bool use_mask_bits(int dtype) {
 // act[l] masks the data gradient of layer l + 1 when both are in the same stage; stage 4's last activation masks its side branch's.
 // f32x3 (fp32 tensors): only where the f32x3 kernel produces the activation in ONE launch -- not conv1_1
 // (exact kernel) and not stage 4, whose forward launches are cut along K (bits would pin them to one K range)
-inline bool act_is_a_mask(const ConvDesc* d, int l, int dtype) {
-  const bool is = (l + 1 < kNumTrunk && d[l + 1].stage == d[l].stage) || l == kNumTrunk - 1;
-  if (dtype == OSVOS_F32_X3) return is && l >= 1 && d[l].stage <= 3;
+inline bool act_is_a_mask(int l, int dtype) {
+  const bool is = (l + 1 < kNumTrunk && kConv[l + 1].stage == kConv[l].stage) || l == kNumTrunk - 1;
+  if (dtype == OSVOS_F32_X3) return is && l >= 1 && kConv[l].stage <= 3;
   return is;
 }
 
@@ -152,17 +161,15 @@ WsLayout ws_layout(int N, int H, int W, int dtype) {
   for (int i = 1; i < 5; ++i) { L.hs[i] = (L.hs[i - 1] + 1) / 2; L.ws[i] = (L.ws[i - 1] + 1) / 2; }
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-  ConvDesc d[kNumConv];
-  conv_table(d);
   const bool store = L.store = use_store(dtype);
   const size_t te = store ? 2 : es;          // element size of the trunk tensors
   L.xin = take(es * N * H * W * kInPad);
   if (store) L.xin_b = take((size_t)2 * N * H * W * kInPad);
   for (int l = 0; l < kNumTrunk; ++l) {
-    const int si = d[l].stage;
-    const size_t e = (size_t)N * L.hs[si] * L.ws[si] * d[l].cout;
+    const int si = kConv[l].stage;
+    const size_t e = (size_t)N * L.hs[si] * L.ws[si] * kConv[l].cout;
     L.act[l] = take(te * e);
-    L.bits[l] = (use_mask_bits(dtype) && act_is_a_mask(d, l, dtype)) ? take(e / 8) : (size_t)-1;
+    L.bits[l] = (use_mask_bits(dtype) && act_is_a_mask(l, dtype)) ? take(e / 8) : (size_t)-1;
   }
   for (int si = 1; si < 5; ++si) {
     const size_t e = (size_t)N * L.hs[si] * L.ws[si] * kStageC[si - 1];
@@ -178,8 +185,8 @@ WsLayout ws_layout(int N, int H, int W, int dtype) {
   {
     size_t mx = 0;
     for (int l = 0; l < kNumTrunk; ++l)
-      if (d[l].cin >= 256) {
-        const size_t b = osvos_conv3x3_splitk_ws_bytes_f32(N, L.hs[d[l].stage], L.ws[d[l].stage], d[l].cout > d[l].cin ? d[l].cout : d[l].cin);
+      if (kConv[l].cin >= 256) {
+        const size_t b = osvos_conv3x3_splitk_ws_bytes_f32(N, L.hs[kConv[l].stage], L.ws[kConv[l].stage], kConv[l].cout > kConv[l].cin ? kConv[l].cout : kConv[l].cin);
         if (b > mx) mx = b;
       }
     L.conv_part = take(mx);
@@ -201,15 +208,15 @@ WsLayout ws_layout(int N, int H, int W, int dtype) {
   // tensor: no buffer is ever rewritten inside one backward, so the weight-gradient stream can trail
   // the data-gradient stream by any number of layers without write-after-read hazards
   for (int l = 0; l < kNumTrunk; ++l) {
-    const size_t e = (size_t)N * L.hs[d[l].stage] * L.ws[d[l].stage] * d[l].cout;
+    const size_t e = (size_t)N * L.hs[kConv[l].stage] * L.ws[kConv[l].stage] * kConv[l].cout;
     L.dy[l] = take(te * e);
   }
   for (int si = 1; si < 5; ++si) L.dpool[si] = take(te * N * L.hs[si] * L.ws[si] * kStageC[si - 1]);
   // one slab workspace per layer: the slab reduce of layer l runs on its own stream while the partial
   // kernel of the next layer already refills another buffer
   for (int l = 0; l < kNumConv; ++l) {
-    const int si = d[l].stage;
-    L.wgrad[l] = take(osvos_wgrad_ws_bytes(N, L.hs[si], L.ws[si], d[l].cin_s, d[l].cout, dtype));
+    const int si = kConv[l].stage;
+    L.wgrad[l] = take(osvos_wgrad_ws_bytes(N, L.hs[si], L.ws[si], kConv[l].cin_s, kConv[l].cout, dtype));
   }
   L.acc = take(sizeof(double) * (5 * OSVOS_HEAD_MAX_BLOCKS * 34));   // head_bwd partials: 4 scales + fuse bias
   L.dxin = take(es * N * H * W * 4);
@@ -303,12 +310,31 @@ inline int dbg_skip() {
 constexpr int dbg_skip() { return 0; }
 #endif
 
-// Pieces per operand of the f32x3 kernels of one network call, from its dtype flags; every ConvCall / WgradCall the call builds carries it.  Precision
-// 'fp32x2' (OSVOS_FLAG_X3_TWO_PIECES): two bf16 pieces (three products) instead of three (six); 'fp32h2' (OSVOS_FLAG_X3_HALF_PIECES): two FP16 pieces
-// under block exponents (h2split.h) -- the packs the call reads must have been written in that format (osvos_net_pack with the matching flag)
-inline int x3_pieces_of(int dtype_) {
-  const bool x3 = (dtype_ & 0xff) == OSVOS_F32_X3;
-  return x3 && (dtype_ & OSVOS_FLAG_X3_HALF_PIECES) ? 22 : (x3 && (dtype_ & OSVOS_FLAG_X3_TWO_PIECES) ? 2 : 3);
+// What the head launchers take per scale i = 0..3 (stage i + 1), typed, gathered once per call: the head's parameters in wbuf and its tensors in ws.
+// The forward touches the first two rows only (the backward's tensors lie behind an inference workspace's end: addresses, never read)
+struct HeadPtrs {
+  const float *wd[4], *bd[4], *f1[4], *f16[4], *weff[4], *wup[4], *wf, *bf;      // score_dsn, the deconvolution filters, (generic) Weff and upscale; fuse
+  float *prep[4], *score[4], *fpart[4];
+  float* dprep[4];
+  void* dprep_b[4];           // (bf16 copy of dprep: store mode, else NULL)
+  double *acc[4], *fb_acc;    // head_bwd partials per scale, then the fuse bias's
+};
+HeadPtrs head_ptrs(const void* wbuf, const WbufLayout& P, void* ws, const WsLayout& L) {
+  HeadPtrs h;
+  auto par = [&](size_t off) { return reinterpret_cast<const float*>(at(wbuf, off)); };
+  auto ten = [&](size_t off) { return reinterpret_cast<float*>(at(ws, off)); };
+  double* const acc = reinterpret_cast<double*>(at(ws, L.acc));
+  for (int i = 0; i < 4; ++i) {
+    h.wd[i] = par(P.wd[i]); h.bd[i] = par(P.bd[i]); h.f1[i] = par(P.f1[i]); h.f16[i] = par(P.f16[i]); h.weff[i] = par(P.weff[i]); h.wup[i] = par(P.wup[i]);
+    h.prep[i] = ten(L.prep[i]); h.score[i] = ten(L.score[i]); h.fpart[i] = ten(L.fpart[i]);
+    const Tensor dprep = L.view(ws, L.dprep[i], L.dprep_b[i]);
+    h.dprep[i] = reinterpret_cast<float*>(dprep.f);
+    h.dprep_b[i] = dprep.b;
+    h.acc[i] = acc + (size_t)i * OSVOS_HEAD_MAX_BLOCKS * 34;
+  }
+  h.wf = par(P.wf); h.bf = par(P.bf);
+  h.fb_acc = acc + (size_t)4 * OSVOS_HEAD_MAX_BLOCKS * 34;
+  return h;
 }
 
 // gradient-ready events armed for the next backward of this host thread (osvos_net_arm_grad_events)
@@ -329,27 +355,31 @@ int osvos_head_grads_finalize(const double* const* part, const int* nblk, const 
 
 extern "C" {
 
-// OSVOS_FLAG_BF16_W2 is defined for dtype OSVOS_F32_BF16MFMA only (osvos_hip.h)
-static bool w2_flag_ok(int dtype_, const char* what) {
-  if (!(dtype_ & OSVOS_FLAG_BF16_W2) || (dtype_ & 0xff) == OSVOS_F32_BF16MFMA) return true;
-  osvos_set_error("%s: OSVOS_FLAG_BF16_W2 needs dtype OSVOS_F32_BF16MFMA (got dtype %d)", what, dtype_ & 0xff);
-  return false;
+// (every entry decodes its dtype word with osvos_dtype_word, common.h: an unbuilt dtype or OSVOS_FLAG_BF16_W2 on another dtype than
+// OSVOS_F32_BF16MFMA is an argument error in all of them -- 0 bytes from the size queries)
+size_t osvos_net_wbuf_bytes(int dtype_) {
+  DtypeWord dw;
+  return osvos_dtype_word(dtype_, "net_wbuf_bytes", &dw) ? wbuf_layout(dw).total : 0;
+}
+size_t osvos_net_ws_bytes(int N, int H, int W, int dtype_) {
+  DtypeWord dw;
+  return osvos_dtype_word(dtype_, "net_ws_bytes", &dw) ? ws_layout(N, H, W, dw.dtype).total : 0;
+}
+size_t osvos_net_ws_bytes_infer(int N, int H, int W, int dtype_) {
+  DtypeWord dw;
+  return osvos_dtype_word(dtype_, "net_ws_bytes_infer", &dw) ? ws_layout(N, H, W, dw.dtype).fwd_total : 0;
 }
 
-size_t osvos_net_wbuf_bytes(int dtype) { return w2_flag_ok(dtype, "net_wbuf_bytes") ? wbuf_layout(dtype).total : 0; }
-size_t osvos_net_ws_bytes(int N, int H, int W, int dtype) { return ws_layout(N, H, W, dtype & 0xff).total; }
-size_t osvos_net_ws_bytes_infer(int N, int H, int W, int dtype) { return ws_layout(N, H, W, dtype & 0xff).fwd_total; }
-
-int osvos_net_ws_query(int N, int H, int W, int dtype, int which, size_t* offset, size_t* elems, int* channels, int* h, int* w) {
-  OSVOS_ARG_CHECK(which >= 0 && which <= 21 && offset && elems && channels && h && w, "ws_query: bad arguments");
-  WsLayout L = ws_layout(N, H, W, dtype & 0xff);
-  ConvDesc d[kNumConv];
-  conv_table(d);
+int osvos_net_ws_query(int N, int H, int W, int dtype_, int which, size_t* offset, size_t* elems, int* channels, int* h, int* w) {
+  OSVOS_ARG_CHECK(which >= 0 && which < ws_which::count && offset && elems && channels && h && w, "ws_query: bad arguments");
+  DtypeWord dw;
+  if (!osvos_dtype_word(dtype_, "ws_query", &dw)) return -1;
+  WsLayout L = ws_layout(N, H, W, dw.dtype);
   int si, c;
   size_t off;
-  if (which < 13) { si = d[which].stage; c = d[which].cout; off = L.act[which]; }
-  else if (which < 17) { si = which - 12; c = kStageC[si - 1]; off = L.pooled[si]; }
-  else if (which < 21) { si = which - 16; c = 16; off = L.prep[which - 17]; }
+  if (which < ws_which::pooled) { si = kConv[which].stage; c = kConv[which].cout; off = L.act[which]; }
+  else if (which < ws_which::prep) { si = which - ws_which::pooled + 1; c = kStageC[si - 1]; off = L.pooled[si]; }
+  else if (which < ws_which::input) { si = which - ws_which::prep + 1; c = 16; off = L.prep[which - ws_which::prep]; }
   else { si = 0; c = kInPad; off = L.xin; }
   *offset = off; *channels = c; *h = L.hs[si]; *w = L.ws[si];
   *elems = (size_t)N * L.hs[si] * L.ws[si] * c;
@@ -357,73 +387,78 @@ int osvos_net_ws_query(int N, int H, int W, int dtype, int which, size_t* offset
 }
 
 // storage format of trunk tensor `which` (osvos_net_ws_query 0..16): 0 fp32 NHWC, 1 bf16 NHWC
-int osvos_net_ws_format(int dtype, int which) {
+int osvos_net_ws_format(int dtype_, int which) {
   (void)which;
-  return use_store(dtype & 0xff) ? 1 : 0;
+  DtypeWord dw;
+  if (!osvos_dtype_word(dtype_, "ws_format", &dw)) return -1;
+  return use_store(dw.dtype) ? 1 : 0;
 }
 
 int osvos_net_pack(const float* const* params, void* wbuf, int dtype_, int with_dgrad, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  const int dtype = dtype_ & 0xff;
-  const bool generic = (dtype_ & OSVOS_FLAG_GENERIC_DECONV) != 0;
   OSVOS_ARG_CHECK(params && wbuf, "net_pack: null pointer");
-  OSVOS_ARG_CHECK(osvos_dtype_built(dtype), "net_pack: dtype %d not built", dtype);
-  if (!w2_flag_ok(dtype_, "net_pack")) return -1;
+  DtypeWord dw;
+  if (!osvos_dtype_word(dtype_, "net_pack", &dw)) return -1;
+  const int dtype = dw.dtype;
   for (int i = 0; i < OSVOS_NPARAMS; ++i) OSVOS_ARG_CHECK(params[i] != nullptr, "net_pack: params[%d] is null", i);
-  WbufLayout L = wbuf_layout(dtype_);
-  ConvDesc d[kNumConv];
-  conv_table(d);
+  WbufLayout L = wbuf_layout(dw);
+  // the small parameters (biases, head weights, deconvolution filters): one gather launch
   const float* srcs[64];
   size_t dsts[64];
   int counts[64];
   int ns = 0;
+  auto small = [&](int param, size_t dst, int count) { srcs[ns] = params[param]; dsts[ns] = dst; counts[ns] = count; ++ns; };
   // f32x3 with pre-split weights: the fp32 packs are read only where no pre-split pack exists (conv1_1 forward: the exact kernel) and by
   // the input-gradient kernel (layer 0's data-gradient pack); all pre-split packs are formed by ONE launch
   const bool x3ps = dtype == OSVOS_F32_X3 && osvos_x3_presplit();
-  const float* xw[OSVOS_PACK_MAX]; void* xd[OSVOS_PACK_MAX]; int xco[OSVOS_PACK_MAX], xci[OSVOS_PACK_MAX], xdg[OSVOS_PACK_MAX], xhalf[OSVOS_PACK_MAX];
-  void* xlo[OSVOS_PACK_MAX];      // precision 'bf16w2': lo planes of the forward packs (NULL: single-piece entry)
-  int nx = 0;
-  // precision 'fp32h2': forward and / or data-gradient packs in the FP16-pair format (h2split.h) -- same buffers, other contents
-  const int half_fwd = (dtype_ & OSVOS_FLAG_X3_HALF_PIECES) ? 1 : 0, half_bwd = (dtype_ & OSVOS_FLAG_X3_HALF_PIECES_BWD) ? 1 : 0;
-  OSVOS_ARG_CHECK(!(half_fwd || half_bwd) || x3ps, "net_pack: the FP16-pair packs exist for dtype OSVOS_F32_X3 with pre-split weights only");
+  // precision 'fp32h2' (dw.half_fwd / half_bwd): forward and / or data-gradient packs in the FP16-pair format (h2split.h) -- same buffers, other contents
+  OSVOS_ARG_CHECK(!(dw.half_fwd || dw.half_bwd) || x3ps, "net_pack: the FP16-pair packs exist for dtype OSVOS_F32_X3 with pre-split weights only");
   const bool b16 = dtype == OSVOS_F32_BF16MFMA;      // all bf16 packs (17 filters x 2 forms) in ONE launch too (round 5 prep)
+  PackEntry packs[OSVOS_PACK_MAX];
+  int nx = 0;
+  // layer l's filter -> wbuf + dst in the multi-pack launch; lo: the lo plane of a two-piece forward pack ('bf16w2'; (size_t)-1: single piece)
+  auto pack = [&](int l, size_t dst, size_t lo, int dgrad, bool half) {
+    PackEntry& e = packs[nx++];
+    e.w = params[kConv[l].w_param]; e.dst = at(wbuf, dst); e.lo_dst = lo != (size_t)-1 ? at(wbuf, lo) : nullptr;
+    e.Cout = kConv[l].cout; e.Cin = kConv[l].cin; e.dgrad = dgrad; e.half = half;
+  };
   for (int l = 0; l < kNumConv; ++l) {
-    int rc;
+    const ConvDesc& c = kConv[l];
+    small(c.b_param, L.bias[l], c.cout);
     if (b16) {
-      xw[nx] = params[d[l].w_param]; xd[nx] = at(wbuf, L.fwd[l]); xco[nx] = d[l].cout; xci[nx] = d[l].cin; xdg[nx] = 0;
-      xlo[nx] = L.fwd_lo[l] != (size_t)-1 ? at(wbuf, L.fwd_lo[l]) : nullptr; ++nx;
-      if (with_dgrad) { xw[nx] = params[d[l].w_param]; xd[nx] = at(wbuf, L.dgrad[l]); xco[nx] = d[l].cout; xci[nx] = d[l].cin; xdg[nx] = 1; xlo[nx] = nullptr; ++nx; }
-      srcs[ns] = params[d[l].b_param]; dsts[ns] = L.bias[l]; counts[ns] = d[l].cout; ++ns;
+      pack(l, L.fwd[l], L.fwd_lo[l], 0, false);
+      if (with_dgrad) pack(l, L.dgrad[l], (size_t)-1, 1, false);
       continue;
     }
-    if (!(x3ps && L.fwd3[l] != (size_t)-1) && (rc = osvos_pack_conv3x3_fwd(params[d[l].w_param], at(wbuf, L.fwd[l]), d[l].cout, d[l].cin, dtype, stream))) return rc;
+    int rc;
+    if (!(x3ps && L.fwd3[l] != (size_t)-1) && (rc = osvos_pack_conv3x3_fwd(params[c.w_param], at(wbuf, L.fwd[l]), c.cout, c.cin, dtype, stream))) return rc;
     if (with_dgrad && !(x3ps && L.dgrad3[l] != (size_t)-1 && l != 0) &&
-        (rc = osvos_pack_conv3x3_dgrad(params[d[l].w_param], at(wbuf, L.dgrad[l]), d[l].cout, d[l].cin, dtype, stream))) return rc;
-    if (L.fwd3[l] != (size_t)-1) { xw[nx] = params[d[l].w_param]; xd[nx] = at(wbuf, L.fwd3[l]); xco[nx] = d[l].cout; xci[nx] = d[l].cin; xdg[nx] = 0; xhalf[nx] = half_fwd; ++nx; }
-    if (with_dgrad && L.dgrad3[l] != (size_t)-1) { xw[nx] = params[d[l].w_param]; xd[nx] = at(wbuf, L.dgrad3[l]); xco[nx] = d[l].cout; xci[nx] = d[l].cin; xdg[nx] = 1; xhalf[nx] = half_bwd; ++nx; }
-    srcs[ns] = params[d[l].b_param]; dsts[ns] = L.bias[l]; counts[ns] = d[l].cout; ++ns;
+        (rc = osvos_pack_conv3x3_dgrad(params[c.w_param], at(wbuf, L.dgrad[l]), c.cout, c.cin, dtype, stream))) return rc;
+    if (L.fwd3[l] != (size_t)-1) pack(l, L.fwd3[l], (size_t)-1, 0, dw.half_fwd);
+    if (with_dgrad && L.dgrad3[l] != (size_t)-1) pack(l, L.dgrad3[l], (size_t)-1, 1, dw.half_bwd);
   }
   if (nx > 0) {
-    const int rc = b16 ? osvos_pack_bf16_multi(xw, xd, xco, xci, xdg, xlo, nx, stream) : osvos_pack_x3_multi(xw, xd, xco, xci, xdg, xhalf, nx, stream);
+    const int rc = b16 ? osvos_pack_bf16_multi(packs, nx, stream) : osvos_pack_x3_multi(packs, nx, stream);
     if (rc) return rc;
   }
 
   for (int i = 0; i < 4; ++i) {
     const int k = 4 << i;
-    srcs[ns] = params[42 + 2 * i]; dsts[ns] = L.wd[i]; counts[ns] = 16; ++ns;
-    srcs[ns] = params[43 + 2 * i]; dsts[ns] = L.bd[i]; counts[ns] = 1; ++ns;
-    srcs[ns] = params[4 + i]; dsts[ns] = L.f1[i]; counts[ns] = k * k; ++ns;     // upscale_[i].weight[0,0]
-    srcs[ns] = params[i]; dsts[ns] = L.f16[i]; counts[ns] = k * k; ++ns;         // upscale[i].weight[0,0]
+    small(slot::score_dsn_w(i), L.wd[i], 16);
+    small(slot::score_dsn_b(i), L.bd[i], 1);
+    small(slot::upscale_(i), L.f1[i], k * k);      // upscale_[i].weight[0,0]
+    small(slot::upscale(i), L.f16[i], k * k);      // upscale[i].weight[0,0]
   }
-  srcs[ns] = params[50]; dsts[ns] = L.wf; counts[ns] = 64; ++ns;
-  srcs[ns] = params[51]; dsts[ns] = L.bf; counts[ns] = 1; ++ns;
+  small(slot::fuse_w, L.wf, 64);
+  small(slot::fuse_b, L.bf, 1);
   int rc = osvos_gather_small(srcs, dsts, counts, ns, wbuf, stream);
-  if (rc || !generic) return rc;
+  if (rc || !dw.generic) return rc;
   for (int i = 0; i < 4; ++i) {      // Weff_i = sum_co wfuse[16 i + co] * upscale[i].weight[:, co]
-    rc = osvos_head_weff(params[i], params[50] + 16 * i, reinterpret_cast<float*>(at(wbuf, L.weff[i])), 4 << i, stream);
+    const float* wup = params[slot::upscale(i)];
+    rc = osvos_head_weff(wup, params[slot::fuse_w] + 16 * i, reinterpret_cast<float*>(at(wbuf, L.weff[i])), 4 << i, stream);
     if (rc) return rc;
     const int k = 4 << i;
-    OSVOS_HIP_CHECK(hipMemcpyAsync(at(wbuf, L.wup[i]), params[i], sizeof(float) * 256 * k * k, hipMemcpyDeviceToDevice, stream));
+    OSVOS_HIP_CHECK(hipMemcpyAsync(at(wbuf, L.wup[i]), wup, sizeof(float) * 256 * k * k, hipMemcpyDeviceToDevice, stream));
   }
   return 0;
 }
@@ -431,22 +466,19 @@ int osvos_net_pack(const float* const* params, void* wbuf, int dtype_, int with_
 int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* const* outs,
                       int N, int H, int W, int dtype_, void* stream_, void* aux_stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  const int dtype = dtype_ & 0xff;
-  const bool generic = (dtype_ & OSVOS_FLAG_GENERIC_DECONV) != 0;
-  const bool infer = (dtype_ & OSVOS_FLAG_INFERENCE) != 0;      // no backward will read the sign bits / pool codes: do not write them
-  const int pieces = x3_pieces_of(dtype_);
   hipStream_t aux_all = aux_stream_ ? (hipStream_t)aux_stream_ : stream;
   const bool two = aux_all != stream;
   OSVOS_ARG_CHECK(x_nchw && wbuf && ws && outs, "net_forward: null pointer");
-  OSVOS_ARG_CHECK(osvos_dtype_built(dtype), "net_forward: dtype %d not built", dtype);
+  DtypeWord dw;
+  if (!osvos_dtype_word(dtype_, "net_forward", &dw)) return -1;
   OSVOS_ARG_CHECK(N > 0 && H > 0 && W > 0, "net_forward: bad shape %dx%dx%d", N, H, W);
   for (int i = 0; i < 5; ++i) OSVOS_ARG_CHECK(outs[i] != nullptr, "net_forward: outs[%d] is null", i);
-  if (!w2_flag_ok(dtype_, "net_forward")) return -1;
-  // precision 'bf16w2': all 17 forward convolutions read two-piece packs (osvos_net_pack with the same flag)
-  const WbufLayout P = wbuf_layout(dtype_);
+  const int dtype = dw.dtype, pieces = dw.pieces;
+  const bool infer = dw.infer;      // no backward will read the sign bits / pool codes: do not write them
+  // precision 'bf16w2' (dw.w2): all 17 forward convolutions read two-piece packs (osvos_net_pack with the same flag)
+  const WbufLayout P = wbuf_layout(dw);
   const WsLayout L = ws_layout(N, H, W, dtype);
-  ConvDesc d[kNumConv];
-  conv_table(d);
+  const HeadPtrs hd = head_ptrs(wbuf, P, ws, L);
   const bool store = L.store;
   Tensor cur = L.view(ws, L.xin, L.xin_b);
   int rc = osvos_nchw_to_nhwc_f32(x_nchw, reinterpret_cast<float*>(cur.f), cur.b, N, 3, H, W, kInPad, stream);
@@ -456,7 +488,6 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
   void* const sk_ws = (L.sk_ws != (size_t)-1 && streamk_mode() >= 1) ? at(ws, L.sk_ws) : nullptr;
   if (sk_ws != nullptr) OSVOS_HIP_CHECK(hipMemsetAsync(sk_ws, 0, osvos_conv3x3_f32x3_streamk_ticket_bytes(), stream));
   int l = 0;
-  const float* score[4]; const float* fpart[4]; const float* f1[4]; const float* f16[4];
   for (int si = 0; si < 5; ++si) {
     const int h = L.hs[si], w = L.ws[si];
     if (si > 0) {
@@ -474,8 +505,8 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
     }
     for (int j = 0; j < kStageN[si]; ++j, ++l) {
       {
-        ProfScope ps(OSVOS_PROF_CONV_FWD, conv_flops(N, h, w, d[l].cin, d[l].cout), stream);
-        ConvCall c = conv_of(d[l], l, false, wbuf, P, pieces, N, h, w, stream);
+        ProfScope ps(OSVOS_PROF_CONV_FWD, conv_flops(N, h, w, kConv[l].cin, kConv[l].cout), stream);
+        ConvCall c = conv_of(kConv[l], l, false, wbuf, P, pieces, N, h, w, stream);
         c.relu = 1;
         const Tensor act = L.view(ws, L.act[l]);
         set_x(c, cur);
@@ -506,33 +537,22 @@ int osvos_net_forward(const float* x_nchw, const void* wbuf, void* ws, float* co
       hipStream_t aux = (si == 4) ? stream : aux_all;
       if (two && aux != stream && (rc = stream_wait(aux, stream))) return rc;
       {
-        ProfScope ps(OSVOS_PROF_OTHER, conv_flops(N, h, w, d[sl].cin, 16), aux);
-        ConvCall c = conv_of(d[sl], sl, false, wbuf, P, pieces, N, h, w, aux);
+        ProfScope ps(OSVOS_PROF_OTHER, conv_flops(N, h, w, kConv[sl].cin, 16), aux);
+        ConvCall c = conv_of(kConv[sl], sl, false, wbuf, P, pieces, N, h, w, aux);
         set_x(c, cur);
-        c.y = reinterpret_cast<float*>(at(ws, L.prep[i]));
+        c.y = hd.prep[i];
         if (L.side_part[i] != (size_t)-1) c.part_ws = at(ws, L.side_part[i]);
         rc = osvos_conv3x3_dispatch(c, dtype);
       }
       if (rc) return rc;
-      float* sc = reinterpret_cast<float*>(at(ws, L.score[i]));
-      float* fp = reinterpret_cast<float*>(at(ws, L.fpart[i]));
-      rc = osvos_head_lowres(at(ws, L.prep[i]), reinterpret_cast<const float*>(at(wbuf, P.wd[i])),
-                             reinterpret_cast<const float*>(at(wbuf, P.bd[i])),
-                             reinterpret_cast<const float*>(at(wbuf, P.wf)) + 16 * i, sc, fp, N, h, w, dtype, aux);
+      rc = osvos_head_lowres(hd.prep[i], hd.wd[i], hd.bd[i], hd.wf + 16 * i, hd.score[i], hd.fpart[i], N, h, w, dtype, aux);
       if (rc) return rc;
-      score[i] = sc; fpart[i] = fp;
-      f1[i] = reinterpret_cast<const float*>(at(wbuf, P.f1[i]));
-      f16[i] = reinterpret_cast<const float*>(at(wbuf, P.f16[i]));
     }
   }
   if (two && (rc = stream_wait(stream, aux_all))) return rc;
-  if (generic) {      // non-diagonal upscale weights: fused head from the 16-channel side_prep outputs and Weff (head_generic.hip)
-    const float* prep[4]; const float* weff[4];
-    for (int i = 0; i < 4; ++i) { prep[i] = reinterpret_cast<const float*>(at(ws, L.prep[i])); weff[i] = reinterpret_cast<const float*>(at(wbuf, P.weff[i])); }
-    return osvos_head_upsample_generic(score, prep, f1, weff, reinterpret_cast<const float*>(at(wbuf, P.bf)), outs, N, H, W, &L.hs[1], &L.ws[1], stream);
-  }
-  return osvos_head_upsample(score, fpart, f1, f16, reinterpret_cast<const float*>(at(wbuf, P.bf)), outs, N, H, W,
-                             &L.hs[1], &L.ws[1], stream);
+  if (dw.generic)      // non-diagonal upscale weights: fused head from the 16-channel side_prep outputs and Weff (head_generic.hip)
+    return osvos_head_upsample_generic(hd.score, hd.prep, hd.f1, hd.weff, hd.bf, outs, N, H, W, &L.hs[1], &L.ws[1], stream);
+  return osvos_head_upsample(hd.score, hd.fpart, hd.f1, hd.f16, hd.bf, outs, N, H, W, &L.hs[1], &L.ws[1], stream);
 }
 
 int osvos_net_join(void* stream_, void* aux_, void* aux2_) {
@@ -556,15 +576,10 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
                        float* dx_nchw, int N, int H, int W, int dtype_, int accumulate, void* stream_, void* aux_stream_,
                        void* aux2_stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  const int dtype = dtype_ & 0xff;
-  const bool generic = (dtype_ & OSVOS_FLAG_GENERIC_DECONV) != 0;
-  const int pieces = x3_pieces_of(dtype_);
   hipStream_t aux = aux_stream_ ? (hipStream_t)aux_stream_ : stream;
   hipStream_t aux2 = aux2_stream_ ? (hipStream_t)aux2_stream_ : aux;
   const GradEvents gev = grad_events();      // armed for this call only
   grad_events().n = 0;
-  // deferred join (OSVOS_FLAG_DEFER_JOIN): not with armed gradient-ready events (their last group is recorded behind the join)
-  const bool defer_join = (dtype_ & OSVOS_FLAG_DEFER_JOIN) != 0 && gev.n == 0 && aux != stream;
   auto ready = [&](int group, hipStream_t st) -> int {      // group's gradients are complete once `st` gets here
     if (group < gev.n && gev.ev[group] != nullptr) OSVOS_HIP_CHECK(hipEventRecord(gev.ev[group], st));
     return 0;
@@ -572,12 +587,15 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
   const bool two = aux != stream;
   const bool three = aux2 != aux;
   OSVOS_ARG_CHECK(wbuf && ws && douts && grads, "net_backward: null pointer");
-  OSVOS_ARG_CHECK(osvos_dtype_built(dtype), "net_backward: dtype %d not built", dtype);
-  if (!w2_flag_ok(dtype_, "net_backward")) return -1;      // (accepted and ignored: the backward of 'bf16w2' is that of 'bf16', on the same packs)
-  const WbufLayout P = wbuf_layout(dtype);
+  DtypeWord dw;
+  if (!osvos_dtype_word(dtype_, "net_backward", &dw)) return -1;      // (OSVOS_FLAG_BF16_W2: the backward of 'bf16w2' is that of 'bf16', on the same packs)
+  const int dtype = dw.dtype, pieces = dw.pieces;
+  const bool generic = dw.generic;
+  // deferred join (OSVOS_FLAG_DEFER_JOIN): not with armed gradient-ready events (their last group is recorded behind the join)
+  const bool defer_join = dw.defer_join && gev.n == 0 && aux != stream;
+  const WbufLayout P = wbuf_layout(dw);
   const WsLayout L = ws_layout(N, H, W, dtype);
-  ConvDesc d[kNumConv];
-  conv_table(d);
+  const HeadPtrs hd = head_ptrs(wbuf, P, ws, L);
   const bool store = L.store;
   // fork: aux waits for everything enqueued on `stream` so far; join: `stream` waits for aux.
   // The weight-gradient kernels run on aux concurrently with the data-gradient kernel of the same
@@ -595,8 +613,8 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
   auto wgrad = [&](const void* xin, const void* g, int l, int h, int w, bool on_main) -> int {
     WgradCall c;
     c.x = xin; c.dy = g; c.x_bf16 = store && l != 0; c.dy_bf16 = store;
-    c.ws = at(ws, L.wgrad[l]); c.dw = grads[d[l].w_param]; c.db = grads[d[l].b_param];
-    c.N = N; c.H = h; c.W = w; c.Cin = d[l].cin; c.Cin_s = d[l].cin_s; c.Cout = c.Cout_s = d[l].cout; c.accumulate = accumulate; c.pieces = pieces;
+    c.ws = at(ws, L.wgrad[l]); c.dw = grads[kConv[l].w_param]; c.db = grads[kConv[l].b_param];
+    c.N = N; c.H = h; c.W = w; c.Cin = kConv[l].cin; c.Cin_s = kConv[l].cin_s; c.Cout = c.Cout_s = kConv[l].cout; c.accumulate = accumulate; c.pieces = pieces;
     const bool split = three && !on_main;
     c.phase = split ? WGRAD_PARTIALS : WGRAD_BOTH; c.stream = on_main ? stream : aux;
     int r = osvos_wgrad_dispatch(c, dtype);
@@ -606,83 +624,62 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
     return osvos_wgrad_dispatch(c, dtype);
   };
   int rc;
-  double* acc = reinterpret_cast<double*>(at(ws, L.acc));
-  const double* part[4];
   int nblk[4], fb_nblk = 0;
   bool have_side = false;
-  for (int i = 0; i < 4; ++i) have_side = have_side || douts[i] != nullptr;
+  for (int i = 0; i < 4; ++i) {
+    have_side = have_side || douts[i] != nullptr;
+    nblk[i] = osvos_head_bwd_blocks(N, L.hs[i + 1], L.ws[i + 1], i);
+  }
   const float* dfused = douts[4];
 
   // ---- head: upstream full-resolution gradients -> dprep[i] (+ score_dsn / fuse gradients) ----
   if (!generic) {        // the four scales in one launch (as four ~20 us launches they sit back to back on the critical path)
-    const float *prep4[4], *f1_4[4], *f16_4[4], *wd4[4];
-    float* dprep4[4];
-    void* dprepb4[4];
-    double* acc4[4];
-    for (int i = 0; i < 4; ++i) {
-      prep4[i] = reinterpret_cast<const float*>(at(ws, L.prep[i]));
-      f1_4[i] = reinterpret_cast<const float*>(at(wbuf, P.f1[i]));
-      f16_4[i] = reinterpret_cast<const float*>(at(wbuf, P.f16[i]));
-      wd4[i] = reinterpret_cast<const float*>(at(wbuf, P.wd[i]));
-      const Tensor dprep = L.view(ws, L.dprep[i], L.dprep_b[i]);
-      dprep4[i] = reinterpret_cast<float*>(dprep.f);
-      dprepb4[i] = dprep.b;
-      acc4[i] = acc + (size_t)i * OSVOS_HEAD_MAX_BLOCKS * 34;
-      part[i] = acc4[i];
-      nblk[i] = osvos_head_bwd_blocks(N, L.hs[i + 1], L.ws[i + 1], i);
-    }
-    rc = osvos_head_bwd4_f32(prep4, douts, dfused, f1_4, f16_4, wd4, reinterpret_cast<const float*>(at(wbuf, P.wf)), dprep4, dprepb4, acc4, N, H, W,
-                             &L.hs[1], &L.ws[1], stream);
+    rc = osvos_head_bwd4_f32(hd.prep, douts, dfused, hd.f1, hd.f16, hd.wd, hd.wf, hd.dprep, hd.dprep_b, hd.acc, N, H, W, &L.hs[1], &L.ws[1], stream);
     if (rc) return rc;
   } else
   for (int i = 0; i < 4; ++i) {
-    const int si = i + 1;
-    const Tensor dprep = L.view(ws, L.dprep[i], L.dprep_b[i]);
-    rc = osvos_head_bwd_generic(reinterpret_cast<const float*>(at(ws, L.prep[i])), douts[i], dfused, reinterpret_cast<const float*>(at(wbuf, P.f1[i])),
-                                reinterpret_cast<const float*>(at(wbuf, P.weff[i])), reinterpret_cast<const float*>(at(wbuf, P.wd[i])),
-                                reinterpret_cast<float*>(dprep.f), dprep.b, acc + (size_t)i * OSVOS_HEAD_MAX_BLOCKS * 34,
-                                N, H, W, L.hs[si], L.ws[si], i, stream);
+    rc = osvos_head_bwd_generic(hd.prep[i], douts[i], dfused, hd.f1[i], hd.weff[i], hd.wd[i], hd.dprep[i], hd.dprep_b[i], hd.acc[i], N, H, W, L.hs[i + 1],
+                                L.ws[i + 1], i, stream);
     if (rc) return rc;
-    part[i] = acc + (size_t)i * OSVOS_HEAD_MAX_BLOCKS * 34;
-    nblk[i] = osvos_head_bwd_blocks(N, L.hs[si], L.ws[si], i);
   }
-  double* fb_part = acc + (size_t)4 * OSVOS_HEAD_MAX_BLOCKS * 34;
   if (dfused != nullptr) {
-    rc = osvos_sum_partials(dfused, (long)N * H * W, fb_part, &fb_nblk, stream);
+    rc = osvos_sum_partials(dfused, (long)N * H * W, hd.fb_acc, &fb_nblk, stream);
     if (rc) return rc;
   }
   // The finalize kernel only feeds PARAMETER gradients (score_dsn, fuse): off the critical path -- on the reduce stream (or the weight-gradient
   // stream) behind an event, so that the data-gradient chain starts one launch earlier (round 6; workspace partials only: nothing of the caller's
-  // is read off `stream`).  The generic head's extra reductions stay on `stream`.
-  OSVOS_ENV_INT(fin_side, "OSVOS_FINALIZE_SIDE", 1);      // A/B switch (0: on `stream`, as rounds 1-5)
-  hipStream_t fin = (!generic && two && fin_side) ? aux2 : stream;
+  // is read off `stream`; on `stream`, as rounds 1-5 had it, the seam is one launch longer and the step level: 232.1 vs 232.2 frames/s).  The generic
+  // head's extra reductions stay on `stream`.
+  hipStream_t fin = (!generic && two) ? aux2 : stream;
   if (fin != stream && (rc = stream_wait(fin, stream))) return rc;
-  rc = osvos_head_grads_finalize(part, nblk, fb_part, fb_nblk, grads, accumulate, have_side ? 1 : 0, fin);
+  rc = osvos_head_grads_finalize(hd.acc, nblk, hd.fb_acc, fb_nblk, grads, accumulate, have_side ? 1 : 0, fin);
   if (rc) return rc;
   if (generic) {
     // fuse.weight / upscale[i].weight gradients from the tap-indexed sums G_i (the partials above carried zeros for fuse.weight);
     // upscale_[i].weight (the 1 -> 1 side deconv) likewise when asked for.  The upscale weights themselves are read from the copy
     // osvos_net_pack left in wbuf.
+    float* const dwf = grads[slot::fuse_w];
     for (int i = 0; i < 4; ++i) {
       const int si = i + 1, k = 4 << i;
       double* G = reinterpret_cast<double*>(at(ws, L.gbuf[i]));
-      if (dfused != nullptr && (grads[50] != nullptr || grads[i] != nullptr)) {
-        rc = osvos_head_tapsum(reinterpret_cast<const float*>(at(ws, L.prep[i])), 16, dfused, G, N, H, W, L.hs[si], L.ws[si], i, stream);
+      float* const dwup = grads[slot::upscale(i)];
+      float* const dwup1 = grads[slot::upscale_(i)];
+      if (dfused != nullptr && (dwf != nullptr || dwup != nullptr)) {
+        rc = osvos_head_tapsum(hd.prep[i], 16, dfused, G, N, H, W, L.hs[si], L.ws[si], i, stream);
         if (rc) return rc;
-        rc = osvos_head_generic_param_grads(reinterpret_cast<const float*>(at(wbuf, P.wup[i])), reinterpret_cast<const float*>(at(wbuf, P.wf)) + 16 * i, G,
-                                            grads[50] ? grads[50] + 16 * i : nullptr, grads[i], k, accumulate, stream);
+        rc = osvos_head_generic_param_grads(hd.wup[i], hd.wf + 16 * i, G, dwf ? dwf + 16 * i : nullptr, dwup, k, accumulate, stream);
         if (rc) return rc;
-      } else if (grads[i] != nullptr && !accumulate) {
-        OSVOS_HIP_CHECK(hipMemsetAsync(grads[i], 0, sizeof(float) * 256 * k * k, stream));
+      } else if (dwup != nullptr && !accumulate) {
+        OSVOS_HIP_CHECK(hipMemsetAsync(dwup, 0, sizeof(float) * 256 * k * k, stream));
       }
-      if (grads[4 + i] != nullptr) {
+      if (dwup1 != nullptr) {
         if (douts[i] != nullptr) {
-          rc = osvos_head_tapsum(reinterpret_cast<const float*>(at(ws, L.score[i])), 1, douts[i], G + 16 * k * k, N, H, W, L.hs[si], L.ws[si], i, stream);
+          rc = osvos_head_tapsum(hd.score[i], 1, douts[i], G + 16 * k * k, N, H, W, L.hs[si], L.ws[si], i, stream);
           if (rc) return rc;
-          rc = osvos_head_dw1(G + 16 * k * k, grads[4 + i], k, accumulate, stream);
+          rc = osvos_head_dw1(G + 16 * k * k, dwup1, k, accumulate, stream);
           if (rc) return rc;
         } else if (!accumulate) {
-          OSVOS_HIP_CHECK(hipMemsetAsync(grads[4 + i], 0, sizeof(float) * k * k, stream));
+          OSVOS_HIP_CHECK(hipMemsetAsync(dwup1, 0, sizeof(float) * k * k, stream));
         }
       }
     }
@@ -692,8 +689,8 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
   // ---- data-gradient chain on `stream`, weight gradients trailing on `aux` ----------------------
   // ready[k]: event recorded on `stream` when the k-th upstream gradient tensor is complete
   double bwd_flops = 0.0;
-  for (int l = 0; l < kNumConv; ++l) bwd_flops += 2.0 * conv_flops(N, L.hs[d[l].stage], L.ws[d[l].stage], d[l].cin, d[l].cout);
-  if (dx_nchw == nullptr) bwd_flops -= conv_flops(N, H, W, 3, d[0].cout);
+  for (int l = 0; l < kNumConv; ++l) bwd_flops += 2.0 * conv_flops(N, L.hs[kConv[l].stage], L.ws[kConv[l].stage], kConv[l].cin, kConv[l].cout);
+  if (dx_nchw == nullptr) bwd_flops -= conv_flops(N, H, W, 3, kConv[0].cout);
   ProfScope ps(OSVOS_PROF_CONV_BWD, bwd_flops, stream);
   auto signal = [&]() -> int { return two ? stream_wait(aux, stream) : 0; };      // aux may consume everything `stream` has produced so far
   if ((rc = signal())) return rc;       // dprep[0..3] ready
@@ -702,31 +699,25 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
   for (int i = 0; i < 4; ++i) {
     const int si = i + 1, sl = kNumTrunk + i, h = L.hs[si], w = L.ws[si];
     const int lx = last_of_stage(si);
-    if (grads[d[sl].w_param] != nullptr && !(dbg_skip() & 16)) {
-      const Tensor dprep = L.view(ws, L.dprep[i], L.dprep_b[i]);
-      rc = wgrad(at(ws, L.act[lx]), dprep.b ? dprep.b : dprep.f, sl, h, w, false);      // (store mode: bf16 x and bf16 dprep)
+    if (grads[kConv[sl].w_param] != nullptr && !(dbg_skip() & 16)) {
+      rc = wgrad(at(ws, L.act[lx]), hd.dprep_b[i] ? hd.dprep_b[i] : hd.dprep[i], sl, h, w, false);      // (store mode: bf16 x and bf16 dprep)
       if (rc) return rc;
     }
   }
   if ((rc = ready(1, aux2))) return rc;        // the four side_prep layers (their slab reduces are the last writers, in order, on aux2)
   // The side branches' data gradients (16 -> C channels: one K chunk, all prologue and epilogue, 13-51 us each at batch 1).  Only stage 4's is needed
   // at once (it IS the upstream gradient of conv5_3); dside of stages 3, 2, 1 is consumed three, six and nine trunk layers later, by the pooling
-  // backward of the stage boundary.  OSVOS_SIDE_DGRAD_ASIDE=1 runs those three on the reduce stream beside the head of the chain instead of in
-  // front of it.  Measured in round 6 and NOT the default: the backward is bound by the chip's throughput over BOTH chains (the weight-gradient
+  // backward of the stage boundary.  All four stay on `stream`, in front of the chain.  Those three on the reduce stream beside the head of the
+  // chain instead were measured in round 6 and are gone: the backward is bound by the chip's throughput over BOTH chains (the weight-gradient
   // stream ends within 3 us of the data-gradient chain), not by the chain's length -- 238.2 vs 237.4 frames/s at batch 1 (noise), 1147 vs 1157 on
-  // configs[2] and 300 vs 306 with the two-piece backward (both slightly worse): same-box alternating rounds, tools/ab_env.sh.
-  OSVOS_ENV_INT(side_aside, "OSVOS_SIDE_DGRAD_ASIDE", 0);
-  hipStream_t sds = (two && side_aside) ? aux2 : stream;
-  hipEvent_t side_ev[3] = {};
-  if (sds != stream && (rc = stream_wait(sds, stream))) return rc;      // dprep[0..3] ready
+  // configs[2] and 300 vs 306 with the two-piece backward (both slightly worse): same-box alternating rounds.
   for (int i = 3; i >= 0; --i) {
     const int si = i + 1, sl = kNumTrunk + i, h = L.hs[si], w = L.ws[si];
     const int lx = last_of_stage(si);
     // stage 4 has no pool after it: its ReLU mask is applied right here and the result is the
     // upstream gradient of conv5_3; stages 1-3 are merged in maxpool2x2_bwd below
     if (dbg_skip() & 8) continue;
-    hipStream_t st = (i == 3) ? stream : sds;
-    ConvCall c = conv_of(d[sl], sl, true, wbuf, P, pieces, N, h, w, st);
+    ConvCall c = conv_of(kConv[sl], sl, true, wbuf, P, pieces, N, h, w, stream);
     set_x(c, L.view(ws, L.dprep[i], L.dprep_b[i]));
     set_y(c, L.view(ws, (i == 3) ? L.dy[lx] : L.dside[i]));
     if (i == 3) {
@@ -735,19 +726,14 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
     }
     rc = osvos_conv3x3_dispatch(c, dtype);
     if (rc) return rc;
-    if (st != stream) {
-      side_ev[i] = event_pool().next();
-      if (!side_ev[i]) return -1;
-      OSVOS_HIP_CHECK(hipEventRecord(side_ev[i], st));
-    }
   }
 
   // trunk, deepest layer first; dy[l] = dLoss/d(conv l output), ReLU mask already applied
   // (stream-K for the data-gradient chain only with OSVOS_X3_STREAMK=2; the workspace's tickets are zero: every launch leaves them so)
   void* const sk_bwd = (L.sk_ws != (size_t)-1 && streamk_mode() >= 2) ? at(ws, L.sk_ws) : nullptr;
   for (int l = kNumTrunk - 1; l >= 0; --l) {
-    const int si = d[l].stage, h = L.hs[si], w = L.ws[si];
-    const bool first_of_stage = (l == 0) || d[l - 1].stage != si;
+    const int si = kConv[l].stage, h = L.hs[si], w = L.ws[si];
+    const bool first_of_stage = (l == 0) || kConv[l - 1].stage != si;
     const void* xin = first_of_stage ? (si == 0 ? at(ws, L.xin) : at(ws, L.pooled[si])) : at(ws, L.act[l - 1]);
     const void* g = at(ws, L.dy[l]);
     const Tensor dy = L.view(ws, L.dy[l]);
@@ -756,7 +742,7 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
     // conv1_1's weight gradient is the LAST piece of work of the step and the weight-gradient stream is the one that finishes last (conv1_2's
     // gradient is still running when the data-gradient chain ends): it goes on the main stream, behind the input gradient, beside conv1_2's
     const bool tail_on_main = l == 0 && two && !defer_join;      // (deferred join: everything gradient-related stays on the side streams)
-    if (grads[d[l].w_param] != nullptr && !tail_on_main) {
+    if (grads[kConv[l].w_param] != nullptr && !tail_on_main) {
       if ((rc = signal())) return rc;   // dy[l] ready -> its weight gradient may start on aux
       rc = wgrad(xin, g, l, h, w, false);
       if (rc) return rc;
@@ -765,16 +751,16 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
     if (l == 0) {
       if (dbg_skip() & 32) {
       } else if (dx_nchw != nullptr && (dtype == OSVOS_F32 || dtype == OSVOS_F32_X3)) {
-        rc = osvos_conv3x3_dgrad_c3_f32(reinterpret_cast<const float*>(g), reinterpret_cast<const float*>(at(wbuf, P.dgrad[0])), dx_nchw, N, h, w, d[0].cout, stream);
+        rc = osvos_conv3x3_dgrad_c3_f32(reinterpret_cast<const float*>(g), reinterpret_cast<const float*>(at(wbuf, P.dgrad[0])), dx_nchw, N, h, w, kConv[0].cout, stream);
         if (rc) return rc;
-      } else if (dx_nchw != nullptr && dy.b != nullptr && d[0].cout == 64) {
+      } else if (dx_nchw != nullptr && dy.b != nullptr && kConv[0].cout == 64) {
         // bf16 trunk tensors: the whole 64-channel halo tile once through LDS, filter rows on the matrix pipe, straight into NCHW (dgrad_c3.hip;
         // same-box A/B at batch 12, two alternating rounds: 1118.7 / 1114.1 frames/s against 1099.1 / 1106.4 with the 32-cout tile + layout
         // kernel below; the fp32-FMA kernel fed with bf16, a first attempt of the round, read 1073-1081 and is gone)
-        rc = osvos_conv3x3_dgrad_c3_bf16mfma(dy.b, at(wbuf, P.dgrad[0]), dx_nchw, N, h, w, d[0].cout, stream);
+        rc = osvos_conv3x3_dgrad_c3_bf16mfma(dy.b, at(wbuf, P.dgrad[0]), dx_nchw, N, h, w, kConv[0].cout, stream);
         if (rc) return rc;
       } else if (dx_nchw != nullptr) {
-        ConvCall c = conv_of(d[0], 0, true, wbuf, P, pieces, N, h, w, stream);
+        ConvCall c = conv_of(kConv[0], 0, true, wbuf, P, pieces, N, h, w, stream);
         set_x(c, dy);
         c.y = reinterpret_cast<float*>(at(ws, L.dxin));
         c.y_cs = 4;
@@ -784,13 +770,13 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
         if (rc) return rc;
       }
       if (tail_on_main) {
-        if (grads[d[0].w_param] != nullptr && !(dbg_skip() & 64) && (rc = wgrad(xin, g, 0, h, w, true))) return rc;
+        if (grads[kConv[0].w_param] != nullptr && !(dbg_skip() & 64) && (rc = wgrad(xin, g, 0, h, w, true))) return rc;
         if ((rc = join())) return rc;
         return ready(2 + 4, stream);      // stage 0 complete: conv1_2's reduce (aux2, joined) and conv1_1's (main)
       }
       break;
     }
-    ConvCall c = conv_of(d[l], l, true, wbuf, P, pieces, N, h, w, stream);      // the data gradient of layer l; below: where it goes and what masks it
+    ConvCall c = conv_of(kConv[l], l, true, wbuf, P, pieces, N, h, w, stream);      // the data gradient of layer l; below: where it goes and what masks it
     set_x(c, dy);
     c.part_ws = at(ws, L.conv_part);
     c.sk_ws = sk_bwd;
@@ -801,7 +787,6 @@ int osvos_net_backward(const void* wbuf, void* ws, const float* const* douts, fl
       const int ps2 = si - 1;
       const void* dside = ps2 >= 1 ? at(ws, L.dside[ps2 - 1]) : nullptr;
       if (dbg_skip() & 2) continue;
-      if (ps2 >= 1 && side_ev[ps2 - 1] != nullptr) OSVOS_HIP_CHECK(hipStreamWaitEvent(stream, side_ev[ps2 - 1], 0));      // dside written on the reduce stream
       if (store && L.pool_code[si] != (size_t)-1)      // one code byte per pooled element instead of the pool's four inputs
         rc = osvos_maxpool2x2_bwd_bf16_code(at(ws, L.pool_code[si]), at(ws, L.dpool[si]), dside, at(ws, L.dy[l - 1]), N, L.hs[ps2], L.ws[ps2],
                                             kStageC[ps2], stream);

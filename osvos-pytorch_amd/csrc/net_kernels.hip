@@ -73,13 +73,13 @@ int osvos_head_grads_finalize(const double* const* part, const int* nblk, const 
   for (int i = 0; i < 4; ++i) {
     a.part[i] = part[i];
     a.nblk[i] = nblk[i];
-    a.dsn_w[i] = have_side ? grads[42 + 2 * i] : nullptr;
-    a.dsn_b[i] = have_side ? grads[43 + 2 * i] : nullptr;
+    a.dsn_w[i] = have_side ? grads[slot::score_dsn_w(i)] : nullptr;
+    a.dsn_b[i] = have_side ? grads[slot::score_dsn_b(i)] : nullptr;
   }
   a.fb_part = fb_part;
   a.fb_nblk = fb_nblk;
-  a.fuse_w = grads[50];
-  a.fuse_b = grads[51];
+  a.fuse_w = grads[slot::fuse_w];
+  a.fuse_b = grads[slot::fuse_b];
   a.accumulate = accumulate;
   hipLaunchKernelGGL(head_grads_finalize_kernel, dim3(133), dim3(64), 0, stream, a);
   OSVOS_LAUNCH_CHECK();

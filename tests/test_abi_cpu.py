@@ -71,6 +71,29 @@ def test_dropin_module_tree_and_state_dict():
         net.forward(torch.zeros(1, 3, 8, 8))          # CPU tensors: fail loudly, no fallback
 
 
+def test_forward_and_forward_features_refuse_bad_arguments_before_anything_touches_a_device():
+    """the three argument errors of the forward launch, with their messages, from both entries that share it; they come before the device guard
+    of forward_features and before the library is asked anything, so a machine without a GPU reports them and nothing else"""
+    import networks.vgg_osvos as vo
+    from osvos_pytorch_amd.autograd import NetRuntime, net_forward_features
+    net = vo.OSVOS(pretrained=0)
+    for call in (net.forward, net.forward_features, lambda x: net.forward_features(x, layer=3)):
+        with pytest.raises(RuntimeError, match=r"runs on the GPU only: move the module and the input to 'cuda'; there is no CPU fallback"):
+            call(torch.zeros(1, 3, 8, 8))
+    with pytest.raises(RuntimeError, match="runs on the GPU only"):
+        net_forward_features(NetRuntime(), torch.zeros(1, 3, 8, 8), [torch.zeros(1)] * 52, 9)
+    with pytest.raises(ValueError, match="layer 5 is not one of"):
+        net.forward_features(torch.zeros(1, 3, 8, 8), layer=5)
+    # the other two messages, past the device check on a machine without one: a tensor that only claims to be on the device
+    class OnDevice(torch.Tensor):
+        is_cuda = True
+    x = torch.zeros(1, 3, 8, 8).as_subclass(OnDevice)
+    with pytest.raises(RuntimeError, match="expected 52 parameters, got 3"):
+        net_forward_features(NetRuntime(), x, [torch.zeros(1)] * 3, 9)
+    with pytest.raises(RuntimeError, match=r"expected input of shape \[N,3,H,W\], got \(1, 4, 8, 8\)"):
+        net_forward_features(NetRuntime(), torch.zeros(1, 4, 8, 8).as_subclass(OnDevice), [torch.zeros(1)] * 52, 9)
+
+
 def test_layer_helpers_match_reference_golden():
     from layers.osvos_layers import (center_crop, class_balanced_cross_entropy_loss, interp_surgery, logit, sigmoid_np,
                                      upsample_filt)

@@ -17,6 +17,12 @@ NET_LAYERS = [(64, 8), (64, 64), (128, 64), (128, 128), (256, 128), (256, 256), 
               (512, 512), (512, 512), (512, 512), (16, 128), (16, 256), (16, 512), (16, 512)]
 
 
+# precision -> the dtype words of (osvos_net_wbuf_bytes, osvos_net_pack, osvos_net_forward, osvos_net_backward), without OSVOS_FLAG_GENERIC_DECONV
+DTYPE_WORDS = {"fp32": (0x0, 0x0, 0x0, 0x0), "bf16": (0x2, 0x2, 0x2, 0x2), "fp32x3": (0x3, 0x3, 0x3, 0x3), "fp32x2": (0x3, 0x3, 0x803, 0x803),
+               "fp32x3b2": (0x3, 0x3, 0x3, 0x803), "fp32h2": (0x3, 0x3003, 0x1003, 0x1003), "fp32x3h2": (0x3, 0x2003, 0x3, 0x1003),
+               "bf16w2": (0x4002, 0x4002, 0x4002, 0x2)}
+
+
 # ---- numpy restatement of the split ------------------------------------------------------------------------------------------------------------
 def rne_bf16(f32):
     """fp32 -> bf16 bits, round to nearest even; NaN stays NaN (quiet bit set); overflow rounds to +-inf -- csrc/common.h f32_to_bf16"""
@@ -171,12 +177,19 @@ def test_op_level_entry_refuses_bad_arguments_without_a_gpu():
 
 def test_pack_format_is_part_of_the_pack_key():
     """the stale-pack hole: a precision switch that changes the pack format must change the key a graph recorded at its forward"""
-    from osvos_pytorch_amd.autograd import NetRuntime
+    from osvos_pytorch_amd.autograd import PRECISIONS, NetRuntime
     rt = NetRuntime()
     fmts = {}
     for name in ("fp32", "fp32x3", "fp32x3b2", "fp32x2", "fp32x3h2", "fp32h2", "bf16", "bf16w2"):
         rt.set_precision(name)
         fmts[name] = rt.pack_format()
+        # the four dtype words of the precision (wbuf, pack, forward, backward), composed in one place: autograd.Precision
+        p = PRECISIONS[name]
+        assert (p.wbuf_word(), p.pack_word(), p.fwd_word(), p.bwd_word()) == DTYPE_WORDS[name], name
+        assert (rt.cdtype_fwd(), rt.cdtype_bwd(), rt.cdtype()) == (p.fwd_word(), p.bwd_word(), p.dtype) and rt.pack_format() == p.pack_format()
+        rt.generic_head = True          # the generic-head flag is OR-ed into the words of the calls
+        assert (rt.cdtype_fwd(), rt.cdtype_bwd(), rt.cdtype()) == (p.fwd_word() | 0x100, p.bwd_word() | 0x100, p.dtype | 0x100)
+        rt.generic_head = False
     assert fmts["fp32x3"] == fmts["fp32x3b2"] == fmts["fp32x2"]        # same packs: no re-pack, a graph may cross these switches
     assert len({fmts[k] for k in ("fp32", "fp32x3", "fp32x3h2", "fp32h2", "bf16", "bf16w2")}) == 6
     # bf16 -> bf16w2 drops the buffer (it grows by the lo planes) and the key; the way back too
@@ -190,10 +203,18 @@ def test_pack_format_is_part_of_the_pack_key():
 
 
 def test_entry_scripts_offer_the_precision():
-    for script, opts in (("train_parent.py", ["--precision"]), ("train_online.py", ["--precision", "--test-precision"])):
+    from osvos_pytorch_amd.autograd import PRECISIONS, TEST_PRECISIONS
+    # the scripts take their choices from the two tables: what the tables offer is pinned here
+    assert sorted(PRECISIONS) == sorted(["fp32", "fp32x3", "fp32x3b2", "fp32x3h2", "fp32h2", "fp32x2", "bf16", "bf16w2"])
+    assert sorted(TEST_PRECISIONS) == sorted(["fp32", "fp32x3", "fp32h2", "bf16", "bf16w2"])
+    for script, opts in (("train_parent.py", {"--precision": "choices=list(PRECISIONS)"}),
+                         ("train_online.py", {"--precision": "choices=list(PRECISIONS)", "--test-precision": "choices=[''] + list(TEST_PRECISIONS)"})):
         src = open(os.path.join(REPO, script)).read()
-        for o in opts:
+        for o, choices in opts.items():
             line = [l for l in src.splitlines() if "add_argument('%s'" % o in l]
-            assert line and "'bf16w2'" in line[0], (script, o)
-    out = subprocess.run([sys.executable, os.path.join(REPO, "train_parent.py"), "--help"], capture_output=True, text=True, timeout=300, cwd=REPO)
-    assert out.returncode == 0 and "bf16w2" in out.stdout, out.stderr[-2000:]
+            assert line and choices in line[0], (script, o)
+        out = subprocess.run([sys.executable, os.path.join(REPO, script), "--help"], capture_output=True, text=True, timeout=300, cwd=REPO)
+        assert out.returncode == 0, out.stderr[-2000:]
+        for o in opts:      # the option's own choice list in the usage text names the precision
+            usage = out.stdout.split("[" + o + " {", 1)
+            assert len(usage) == 2 and "bf16w2" in usage[1].split("}", 1)[0].split(","), (script, o, out.stdout[:2000])

@@ -75,6 +75,7 @@ import torch
 import networks.vgg_osvos as vo
 from layers.osvos_layers import sigmoid_np  # noqa: F401  (kept importable like the reference)
 from osvos_pytorch_amd import sequence
+from osvos_pytorch_amd.autograd import PRECISIONS, TEST_PRECISIONS
 from osvos_pytorch_amd.results import ComponentTracker, SequenceEvaluator, save_masks
 from mypath import Path
 from osvos_pytorch_amd.parallel import shard_indices
@@ -539,9 +540,9 @@ def parse_args(argv=None):
                     help='input pipeline on the GPU: Pillow decode -> pinned uint8 -> osvos_augment_frame (flip, scale+rotate, mean, CHW); '
                          'the first frame is decoded ONCE and re-augmented on the device every iteration')
     ap.add_argument('--prefetch', type=int, default=3, help='--device-augment: test frames decoded / copied ahead of the forward')
-    ap.add_argument('--precision', default=os.environ.get('OSVOS_PRECISION', 'fp32x3'), choices=['fp32', 'fp32x3', 'fp32x3b2', 'fp32x3h2', 'fp32h2', 'fp32x2', 'bf16', 'bf16w2'])
-    ap.add_argument('--test-precision', default=os.environ.get('OSVOS_TEST_PRECISION', ''), choices=['', 'fp32', 'fp32x3', 'fp32h2', 'bf16', 'bf16w2'],
-                    help="precision of the TEST forwards (train_online.py:172-189 of the reference; default: the training precision).  'fp32h2' -- the f32x3 "
+    ap.add_argument('--precision', default=os.environ.get('OSVOS_PRECISION', 'fp32x3'), choices=list(PRECISIONS), help="arithmetic of the network calls (OSVOS.set_precision): 'fp32x3' fp32-grade results on the bf16 matrix pipe, 'fp32' the exact fp32 kernels, 'fp32x3b2' / 'fp32x3h2' / 'fp32h2' / 'fp32x2' two pieces per operand, 'bf16' bf16 operands and trunk tensors, 'bf16w2' the same with two-piece forward weights")
+    ap.add_argument('--test-precision', default=os.environ.get('OSVOS_TEST_PRECISION', ''), choices=[''] + list(TEST_PRECISIONS), help="precision of the TEST forwards, e.g. 'fp32h2' or 'bf16w2' "
+                    "(train_online.py:172-189 of the reference; default: the training precision).  'fp32h2' -- the f32x3 "
                          "convolutions on two FP16 pieces under block exponents -- runs a forward 1.5x as fast as 'fp32x3' with logits closer to float64 "
                          "(DESIGN.md 3.1a); the masks are the same up to pixels within 1e-5 std of the threshold")
     ap.add_argument('--window-fused', action='store_true',
