@@ -799,9 +799,34 @@ int osvos_lucid_compose_ex(const unsigned char* bgr, const unsigned char* mask, 
  *   walk the window in ascending row with the 4-byte integer dot instruction.
  *   The local map a caller forms from it is max(sim_fg, -1) - max(sim_bg, -1), three fp32 operations: an empty class counts as the smallest
  *   possible cosine.
- * Limits: C a multiple of 64 in 64..1024, Pq and Pr 1..2^20, P 1..2^30, N 1..65535, sides 1..16384, stride a power of two 1..64.  q, Q and R
- *   are 16-byte aligned.  Outputs (and ws) must not overlap inputs or each other.  Every argument error returns < 0 before any device
- *   call, with a text that names the bad parameter. */
+ * Memory bank (osvos_match_bank_update; the bank of STM and its successors, kept by age): a bank has cap rows -- R int8 [cap][C], rinv_r fp32
+ *   [cap], label_r uint8 [cap] -- and is searched by nearest / topk as it is (Pr <= cap; an unused row carries label 255, so it is in
+ *   neither class).  Rows [0, protected_rows) are the first frame's and are never written by an update; rows [protected_rows, cap) form a
+ *   ring of ring = cap - protected_rows rows.  state int32 [4] in device memory = {cursor, filled, calls, added_last}, all zero for a new
+ *   bank; a state that is neither that nor written by this function is outside the contract (the kernel reduces cursor mod ring before it
+ *   uses it, so even then nothing outside the ring is written).
+ *   The call takes the rows of ONE frame that has already been searched against THIS bank: q int8 [P][C] with rinv_q fp32 [P], label_q uint8
+ *   [P] (osvos_match_cell_labels of that frame's mask) and sim fp32 [2][P], that search's output, foreground first.
+ *   Selection: row a is selected iff all four hold -- label_q[a] is 0 or 1;  rinv_q[a] > 0;  own < tau (the row is novel), where
+ *     own = sim[label_q[a] == 1 ? 0 : 1][a] and other is the other class's value;  fl32(own - other) >= margin (the bank as it stands does not
+ *     contradict the mask's label: the guard against drift).  Each comparison is one fp32 comparison, so a NaN selects nothing.
+ *   Subsampling: n = the number of selected rows, m = min(n, max_new, ring).  The selected rows are ranked r = 0 .. n - 1 in ascending row
+ *     order; rank r is kept iff floor((r + 1) m / n) > floor(r m / n), in 64-bit integers, and is then kept row j = floor(r m / n): an even
+ *     subsample in which every j in 0 .. m - 1 occurs exactly once.
+ *   Write: kept row j goes to slot protected_rows + (cursor + j) mod ring -- its C bytes, its rinv_q and its label.  No other byte of the
+ *     bank changes.  m <= ring, so one call writes no slot twice; the oldest rows are overwritten first.
+ *   State after the call: cursor = (cursor + m) mod ring, filled = min(filled + m, ring), calls += 1, added_last = m.  With ring == 0 or
+ *     n == 0, m = 0 and only calls and added_last change.
+ *   N frames each update their own bank: every array above, state included, carries a leading [N].  Three launches on the stream: flags and
+ *   per-workgroup counts;  one workgroup per bank that scans the counts, reads state, leaves n, m and the old cursor in ws and writes the
+ *   new state;  the ranks (wave ballots and population counts) and the copies (16-byte vector loads and stores).  No atomics, no workgroup
+ *   waits on another, no read-back; identical calls give identical bytes.
+ *   ws: osvos_match_bank_ws_bytes(N, P) bytes, 8-byte aligned, contents irrelevant on entry; 0 for arguments the call refuses.
+ *   tau and margin are finite, max_new >= 0, 0 <= protected_rows <= cap, cap in 1..2^20; the bank, state and ws overlap neither the frame's
+ *   arrays nor each other.
+ * Limits: C a multiple of 64 in 64..1024, Pq and Pr 1..2^20, P 1..2^30 (1..2^20 for the bank update), N 1..65535, sides 1..16384, stride a
+ *   power of two 1..64.  q, Q and R are 16-byte aligned.  Outputs (and ws) must not overlap inputs or each other.  Every argument error
+ *   returns < 0 before any device call, with a text that names the bad parameter. */
 int osvos_match_quantize(const void* feat, int format, signed char* q, float* rinv, long P, int C, void* stream);
 int osvos_match_cell_labels(const unsigned char* mask, unsigned char* label, int N, int H, int W, int h, int w, int stride, void* stream);
 size_t osvos_match_ws_bytes(int N, int Pq, int Pr, int C);
@@ -814,6 +839,10 @@ int osvos_match_topk(const signed char* Q, const float* rinv_q, const signed cha
                      void* ws, int N, int NR, int Pq, int Pr, int C, int K, void* stream);
 int osvos_match_local(const signed char* Q, const float* rinv_q, const signed char* R, const float* rinv_r, const unsigned char* label_r, float* sim,
                       int* idx /* may be NULL */, int N, int NR, int h, int w, int C, int radius, void* stream);
+size_t osvos_match_bank_ws_bytes(int N, int P);
+int osvos_match_bank_update(const signed char* q, const float* rinv_q, const unsigned char* label_q, const float* sim, signed char* R,
+                            float* rinv_r, unsigned char* label_r, int* state, void* ws, int N, int P, int C, int cap, int protected_rows,
+                            int max_new, float tau, float margin, void* stream);
 
 /* ---- fused SGD (torch.optim.SGD semantics, train_online.py:79-88,147) ----------------------
  * for each i: d = g + wd*p; buf = first ? d : momentum*buf + d; p -= lr*buf      (flat tensors) */

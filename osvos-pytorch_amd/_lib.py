@@ -173,6 +173,8 @@ PROTOTYPES = {
     "osvos_match_topk_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "osvos_match_topk": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "osvos_match_local": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "osvos_match_bank_ws_bytes": (_sz, [_i, _i]),
+    "osvos_match_bank_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp]),
     "osvos_lucid_inpaint_ws_bytes": (_sz, [_i, _i, _i]),
     "osvos_lucid_inpaint": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "osvos_lucid_compose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -10,6 +10,9 @@ csrc/match.hip; the rule: include/osvos_hip.h).
     topk:     in place of the nearest row, the mean cosine to the k best rows of the class (``osvos_match_topk``, csrc/match_ext.hip)
     local:    nearest over the reference cells within ``radius`` cells of the query cell on the same grid (``osvos_match_local``); its map
               counts a class the window does not hold as cosine -1
+    memory:   a fixed-capacity bank behind the first frame's rows that collects, frame after frame, the rows the bank does not hold yet and the
+              mask confirms (``osvos_match_bank_update``, csrc/match_bank.hip; ``MemoryBank``): the oldest rows are overwritten first, the first
+              frame's never
 
 The network's logits are the only evidence every other stage has; when the network fires on a distractor that merely looks like the object
 to its classifier, the map is a second opinion from the features themselves.  ``AppearanceMatcher`` adds ``gain * map`` to the fused logits
@@ -173,6 +176,114 @@ def check_match_options(topk, local_radius, local_gain):
     g.check_number("local_gain", local_gain, 0, None, "match")
 
 
+def check_memory(memory, memory_tau=0.9, memory_new=512, memory_margin=0.0):
+    """ValueError unless ``memory`` is an integer in 0..2^20 - 1 (rows of the ring; 0 = off), ``memory_new`` an integer >= 0 and ``memory_tau`` and
+    ``memory_margin`` finite numbers (host only)"""
+    g.check_int("memory", memory, 0, MATCH_MAX_P - 1, "match")
+    g.check_number("memory_tau", memory_tau, -float(1 << 30), float(1 << 30), "match")
+    g.check_int("memory_new", memory_new, 0, 1 << 30, "match")
+    g.check_number("memory_margin", memory_margin, -float(1 << 30), float(1 << 30), "match")
+
+
+def bank_workspace(n, p, device, ws=None):
+    """a uint8 CUDA tensor of at least osvos_match_bank_ws_bytes: ``ws`` when it is large enough, 8-byte aligned and on ``device``, else a new one"""
+    return g.workspace(lib().osvos_match_bank_ws_bytes(n, p), device, ws, "N %d P %d" % (n, p), "match", align=8)
+
+
+def bank_update(q, rinv_q, label_q, sim, r, rinv_r, label_r, state, max_new, tau, margin, protected, ws=None):
+    """one ``osvos_match_bank_update``: the rows of N frames -- q int8 [N,P,C], rinv_q float32 [N,P], label_q uint8 [N,P] (``cell_labels`` of the
+    frame's mask) and sim float32 [N,2,P], the search of these rows against the banks -- are added IN PLACE to the N banks r int8 [N,cap,C],
+    rinv_r float32 [N,cap], label_r uint8 [N,cap] with state int32 [N,4], whose rows below ``protected`` are never written (the rule:
+    include/osvos_hip.h).  Enqueued only; -> the workspace it used."""
+    for t, what in ((q, "q"), (rinv_q, "rinv_q"), (label_q, "label_q"), (sim, "sim"), (r, "r"), (rinv_r, "rinv_r"), (label_r, "label_r"), (state, "state")):
+        g.need_cuda(t, what, "match")
+    check_memory(0, tau, max_new, margin)
+    if q.dtype != torch.int8 or r.dtype != torch.int8 or q.dim() != 3 or r.dim() != 3 or q.shape[2] != r.shape[2] or q.shape[0] != r.shape[0]:
+        raise ValueError("q and r must be int8 [N,P,C] and [N,cap,C] tensors with the same N and C, got %s %s and %s %s"
+                         % (q.dtype, tuple(q.shape), r.dtype, tuple(r.shape)))
+    n, p, c = (int(v) for v in q.shape)
+    cap = int(r.shape[1])
+    if not _channels_ok(c) or n < 1 or not (1 <= p <= MATCH_MAX_P and 1 <= cap <= MATCH_MAX_P):
+        raise ValueError("match: N %d P %d cap %d C %d: rows 1..%d, C a multiple of 64 in 64..%d" % (n, p, cap, c, MATCH_MAX_P, MATCH_MAX_C))
+    g.check_int("protected", protected, 0, cap, "match")
+    want = ((rinv_q, "rinv_q", torch.float32, (n, p)), (label_q, "label_q", torch.uint8, (n, p)), (sim, "sim", torch.float32, (n, 2, p)),
+            (rinv_r, "rinv_r", torch.float32, (n, cap)), (label_r, "label_r", torch.uint8, (n, cap)), (state, "state", torch.int32, (n, 4)))
+    for t, what, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != q.device:
+            raise ValueError("%s must be a %s %s tensor on the device of q, got %s %s" % (what, str(dtype).replace("torch.", ""), list(shape), t.dtype,
+                                                                                          tuple(t.shape)))
+    for t, what in ((r, "r"), (rinv_r, "rinv_r"), (label_r, "label_r"), (state, "state")):      # written in place: no copy may stand in for them
+        if not t.is_contiguous():
+            raise ValueError("match: %s is written in place and must be contiguous" % what)
+    q, rinv_q, label_q, sim = (t.contiguous() for t in (q, rinv_q, label_q, sim))
+    ws = bank_workspace(n, p, q.device, ws)
+    g.call("match_bank_update", q.device, g.ptr(q), g.ptr(rinv_q), g.ptr(label_q), g.ptr(sim), g.ptr(r), g.ptr(rinv_r), g.ptr(label_r), g.ptr(state),
+           g.ptr(ws), n, p, c, cap, int(protected), int(max_new), float(tau), float(margin))
+    return ws
+
+
+class MemoryBank(object):
+    """The first frame's rows and, behind them, a ring of ``capacity_rows`` rows that ``update`` fills over the sequence, all on the device.
+
+    ``seed(r0, rinv0, label0)`` -- int8 [1,P0,C], float32 [1,P0], uint8 [1,P0] -- allocates [1, P0 + capacity_rows, C]: the first frame's rows
+    with their labels as they are (protected: no update writes them), the ring void (label 255, everything else zero), ``state`` zero.
+    ``update(q, rinv_q, label_q, sim)`` admits at most ``max_new`` rows of a frame that was searched against this bank: those with a 0 / 1 label
+    whose own-class cosine is below ``tau`` (the bank does not hold them yet) and at least ``margin`` above the other class's (the bank does not
+    contradict the label), evenly subsampled, over the oldest ring rows.  One library call, no read-back.
+    ``rows`` is the host's bound on the rows written so far, protected + min(ring, calls * min(max_new, ring)); ``operands()`` the three bank
+    tensors narrowed to it.  Rows past what was really written are void, so the bound costs time when it is loose and never a bit.
+
+    The defaults are starting values, NOT tuned on DAVIS."""
+
+    def __init__(self, capacity_rows, tau=0.9, max_new=512, margin=0.0):
+        check_memory(capacity_rows, tau, max_new, margin)
+        if capacity_rows < 1:
+            raise ValueError("match: MemoryBank of %d rows (1..%d)" % (capacity_rows, MATCH_MAX_P - 1))
+        self.capacity_rows, self.tau, self.max_new, self.margin = int(capacity_rows), float(tau), int(max_new), float(margin)
+        self.protected = self.host_calls = 0
+        self.r = self.rinv_r = self.label_r = self.state = self._ws = None
+
+    @property
+    def ring(self):
+        return self.capacity_rows
+
+    @property
+    def rows(self):
+        return self.protected + min(self.ring, self.host_calls * min(self.max_new, self.ring))
+
+    def seed(self, r0, rinv0, label0):
+        for t, what in ((r0, "r0"), (rinv0, "rinv0"), (label0, "label0")):
+            g.need_cuda(t, what, "match")
+        if r0.dtype != torch.int8 or r0.dim() != 3 or r0.shape[0] != 1 or not _channels_ok(int(r0.shape[2])):
+            raise ValueError("r0 must be an int8 [1,P0,C] tensor, C a multiple of 64 in 64..%d, got %s %s" % (MATCH_MAX_C, r0.dtype, tuple(r0.shape)))
+        p0, c = int(r0.shape[1]), int(r0.shape[2])
+        if not 1 <= p0 <= MATCH_MAX_P - self.capacity_rows:
+            raise ValueError("match: %d first-frame rows and %d memory rows (together 2..%d)" % (p0, self.capacity_rows, MATCH_MAX_P))
+        if rinv0.dtype != torch.float32 or tuple(rinv0.shape) != (1, p0) or label0.dtype != torch.uint8 or tuple(label0.shape) != (1, p0):
+            raise ValueError("rinv0 and label0 must be float32 and uint8 [1,%d] tensors" % p0)
+        cap, dev = p0 + self.capacity_rows, r0.device
+        self.r = torch.zeros((1, cap, c), device=dev, dtype=torch.int8)
+        self.rinv_r = torch.zeros((1, cap), device=dev, dtype=torch.float32)
+        self.label_r = torch.full((1, cap), 255, device=dev, dtype=torch.uint8)
+        self.state = torch.zeros((1, 4), device=dev, dtype=torch.int32)
+        self.r[:, :p0].copy_(r0)
+        self.rinv_r[:, :p0].copy_(rinv0)
+        self.label_r[:, :p0].copy_(label0)
+        self.protected, self.host_calls = p0, 0
+        return self
+
+    def update(self, q, rinv_q, label_q, sim):
+        if self.r is None:
+            raise RuntimeError("MemoryBank: seed(first frame's rows) comes first")
+        self._ws = bank_update(q, rinv_q, label_q, sim, self.r, self.rinv_r, self.label_r, self.state, self.max_new, self.tau, self.margin,
+                               self.protected, ws=self._ws)
+        self.host_calls += 1
+
+    def operands(self):
+        rows = self.rows
+        return self.r[:, :rows], self.rinv_r[:, :rows], self.label_r[:, :rows]
+
+
 class AppearanceMatcher(object):
     """A second opinion on the fused logits from the trunk features themselves, on the device.
 
@@ -192,17 +303,27 @@ class AppearanceMatcher(object):
     ``previous``; on the first matched frame, or without ``prev_mask``, there is no local view.  ``topk=1, local_gain=0`` is the matcher
     without these options: the same calls, the same bytes.
 
+    ``memory`` > 0 searches a ``MemoryBank(memory, memory_tau, memory_new, memory_margin)`` in place of the first-frame bank: the first frame's
+    rows and a ring of ``memory`` rows behind them.  When ``prev_mask`` arrives, the previous call's rows, that call's search result against
+    the bank (taken before the previous-frame bank was combined in) and the cell labels of ``prev_mask`` update the bank, on the device,
+    before the new frame is searched; frames come one at a time then (N = 1).  ``memory=0`` is the matcher without it: the same calls, the
+    same bytes.
+
     The defaults are starting values, NOT tuned on DAVIS."""
 
-    def __init__(self, net, layer=9, gain=4.0, previous=False, topk=1, local_radius=0, local_gain=0.0):
+    def __init__(self, net, layer=9, gain=4.0, previous=False, topk=1, local_radius=0, local_gain=0.0, memory=0, memory_tau=0.9, memory_new=512,
+                 memory_margin=0.0):
         check_match(layer, gain)
         check_match_options(topk, local_radius, local_gain)
+        check_memory(memory, memory_tau, memory_new, memory_margin)
+        self.memory, self.memory_tau, self.memory_new, self.memory_margin = int(memory), float(memory_tau), int(memory_new), float(memory_margin)
+        self._memory = None          # the MemoryBank (memory > 0), seeded by set_reference
         self.net, self.layer, self.gain, self.previous = net, int(layer), float(gain), bool(previous)
         self.topk, self.local_radius, self.local_gain = int(topk), int(local_radius), float(local_gain)
         self.stride = stride_of(layer)
         self.inert = False
         self._bank = None            # (r [1,P,C], rinv_r [1,P], label [1,P]) of the first frame
-        self._last = None            # (q, rinv_q) of the previous call
+        self._last = None            # (q, rinv_q) of the previous call; with memory also its sim against the memory bank
         self._ws = self._ws_prev = None
 
     @property
@@ -212,17 +333,18 @@ class AppearanceMatcher(object):
 
     @property
     def needs_previous(self):
-        """True when the next call wants this call's features and mask: the previous-frame bank, the local view, or both"""
-        return self.previous or self.local_gain > 0
+        """True when the next call wants this call's features and mask: the previous-frame bank, the local view, the memory bank, or several"""
+        return self.previous or self.local_gain > 0 or self.memory > 0
 
     def _search(self, q, rinv_q, r, rinv_r, label, which):
         """one bank: ``nearest``, or ``topk`` when topk > 1; ``which`` names the bank's workspace attribute"""
         n, p, c = (int(v) for v in q.shape)
+        pr = int(r.shape[1])
         if self.topk > 1:
-            ws = topk_workspace(n, p, p, c, self.topk, q.device, getattr(self, which))
+            ws = topk_workspace(n, p, pr, c, self.topk, q.device, getattr(self, which))
             setattr(self, which, ws)
             return topk(q, rinv_q, r, rinv_r, label, self.topk, ws=ws)
-        ws = nearest_workspace(n, p, p, c, q.device, getattr(self, which))
+        ws = nearest_workspace(n, p, pr, c, q.device, getattr(self, which))
         setattr(self, which, ws)
         return nearest(q, rinv_q, r, rinv_r, label, ws=ws)
 
@@ -248,6 +370,7 @@ class AppearanceMatcher(object):
             print("AppearanceMatcher: the first frame gives %d foreground and %d background cells at layer %d (stride %d): no matching, plain forwards"
                   % (n_fg, n_bg, self.layer, self.stride), file=sys.stderr)
         self._bank, self._last = (r, rinv_r, label), None
+        self._memory = MemoryBank(self.memory, self.memory_tau, self.memory_new, self.memory_margin).seed(r, rinv_r, label) if self.memory > 0 else None
         return self
 
     def __call__(self, x, prev_mask=None):
@@ -263,18 +386,36 @@ class AppearanceMatcher(object):
         r, rinv_r, label = self._bank
         if int(r.shape[1]) != p:
             raise ValueError("AppearanceMatcher: the frame's %d x %d feature grid is not the first frame's" % (h, w))
-        sim = self._search(q, rinv_q, r, rinv_r, label, "_ws")
+        if self._memory is not None and n != 1:
+            raise ValueError("AppearanceMatcher: with memory the frames come one at a time, got %d" % n)
+
+        def prev_labels():
+            """the cell labels of prev_mask, or None without a previous frame of this shape: computed once for the memory bank, the
+            previous-frame bank and the local view"""
+            if prev_mask is None or self._last is None or self._last[0].shape != q.shape:
+                return None
+            plabel = cell_labels(prev_mask, self.stride)
+            if tuple(plabel.shape) != (n, h, w):
+                raise ValueError("prev_mask of %s does not belong to frames of %s" % (tuple(prev_mask.shape), tuple(x.shape)))
+            return plabel
+
+        plabel = None
+        if self._memory is not None:                                         # the bank takes the previous frame in BEFORE this one is searched
+            plabel = prev_labels()
+            if plabel is not None:
+                self._memory.update(self._last[0], self._last[1], plabel.view(n, p), self._last[2])
+            r, rinv_r, label = self._memory.operands()
+        sim = first = self._search(q, rinv_q, r, rinv_r, label, "_ws")
         local_mp = None
         if self.needs_previous:
-            if prev_mask is not None and self._last is not None and self._last[0].shape == q.shape:
-                plabel = cell_labels(prev_mask, self.stride)
-                if tuple(plabel.shape) != (n, h, w):
-                    raise ValueError("prev_mask of %s does not belong to frames of %s" % (tuple(prev_mask.shape), tuple(x.shape)))
+            if self._memory is None:
+                plabel = prev_labels()
+            if plabel is not None:
                 if self.previous:
                     sim = torch.maximum(sim, self._search(q, rinv_q, self._last[0], self._last[1], plabel.view(n, p), "_ws_prev"))
                 if self.local_gain > 0:
                     local_mp = local_map(local(q, rinv_q, self._last[0], self._last[1], plabel.view(n, p), (h, w), self.local_radius)).view(n, h, w)
-            self._last = (q, rinv_q)
+            self._last = (q, rinv_q, first) if self._memory is not None else (q, rinv_q)
         views, weights = [outs[-1], (sim[:, 0] - sim[:, 1]).view(n, h, w)], [1.0, self.gain]
         if local_mp is not None:
             views, weights = views + [local_mp], weights + [self.local_gain]

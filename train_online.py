@@ -33,6 +33,10 @@ running on the MI355X-native OSVOS path.  Differences by design:
     (osvos_pytorch_amd.match.AppearanceMatcher), in the test forward itself.  ``--match-previous`` also searches the previous frame's features under its final mask.  Not with --tta-*.
     ``--match-topk K`` scores a class by the mean cosine to its K best bank rows (VideoMatch), ``--match-local R[,GAIN]`` adds GAIN times a
     map searched only within R feature cells of each pixel in the previous frame (FEELVOS); both need --match-gain, off they change no byte.
+    ``--match-memory ROWS[,TAU[,NEW[,MARGIN]]]`` searches a memory bank in place of the first frame's alone: the first frame's rows plus a ring
+    of ROWS rows into which every frame writes, on the device, at most NEW of its rows that the bank does not hold yet (own-class cosine
+    below TAU) and that the bank does not contradict (own minus other at least MARGIN), oldest rows first (osvos_pytorch_amd.match.MemoryBank);
+    needs --match-gain, not with --adapt-steps, 0 = off changes no byte; TAU 0.9, NEW 512, MARGIN 0 are starting values, not tuned on DAVIS.
     Starting values, not tuned on DAVIS; with G = 0 nothing is built and not one byte changes
   * ``--lucid P``: lucid first-frame synthesis -- with probability P a training sample is not the flipped / rotated / scaled frame but a
     re-composition of it: the object cut out, the hole inpainted once per sequence, object and background moved by affines of their own,
@@ -386,11 +390,19 @@ def check_match_args(args):
             local_radius, local_gain = (parse_numbers(args.match_local, (int, float) if ',' in args.match_local else (int,), '--match-local',
                                                       expect='R or R,GAIN', finite=True) + (args.match_gain,))[:2]
         match.check_match_options(args.match_topk, local_radius, local_gain)
+        memory = (0, 0.9, 512, 0.0)
+        if args.match_memory:
+            parts = args.match_memory.count(',') + 1
+            memory = parse_numbers(args.match_memory, (int, float, int, float)[:parts] if parts <= 4 else (), '--match-memory',
+                                   expect='ROWS[,TAU[,NEW[,MARGIN]]]', finite=True) + memory[parts:]
+        match.check_memory(*memory)
     except ValueError as e:
         raise SystemExit('--match-*: %s' % e)
     if not args.match_gain:
         if args.match_topk != 1 or args.match_local:
             raise SystemExit('--match-topk / --match-local need --match-gain: they are options of the appearance matcher')
+        if memory[0] > 0:
+            raise SystemExit('--match-memory needs --match-gain: it is an option of the appearance matcher')
         return
     if args.tta:
         raise SystemExit('--match-gain is not run together with --tta-scales / --tta-flip: matching under test-time augmentation is not built')
@@ -399,11 +411,16 @@ def check_match_args(args):
         raise SystemExit('--match-previous is not run together with --adapt-steps: the adapter forwards every frame twice')
     if local_gain > 0 and args.adapt_steps:
         raise SystemExit('--match-local is not run together with --adapt-steps: the adapter forwards every frame twice')
+    if memory[0] > 0 and args.adapt_steps:
+        raise SystemExit('--match-memory is not run together with --adapt-steps: the adapter forwards every frame twice, and the network '
+                         'changes under the bank')
     args.match = dict(layer=args.match_layer, gain=args.match_gain, previous=args.match_previous)
     if args.match_topk > 1:          # (an option that is off adds nothing: AppearanceMatcher is built exactly as before)
         args.match.update(topk=args.match_topk)
     if local_gain > 0:
         args.match.update(local_radius=local_radius, local_gain=local_gain)
+    if memory[0] > 0:
+        args.match.update(zip(('memory', 'memory_tau', 'memory_new', 'memory_margin'), memory))
 
 
 def check_lucid_args(args):
@@ -627,6 +644,14 @@ def parse_args(argv=None):
                          'of the previous frame\'s features under its final mask that looks only R feature cells (0..15) around each '
                          'pixel; a class the window does not hold counts as cosine -1.  Independent of --match-previous.  Not with '
                          '--adapt-steps')
+    ap.add_argument('--match-memory', default='', metavar='ROWS[,TAU[,NEW[,MARGIN]]]',
+                    help='--match-gain: a memory bank of ROWS rows behind the first frame\'s (0 = off; as in STM and its successors) that '
+                         'collects features over the sequence, on the device: after every frame at most NEW (default 512) of its rows are '
+                         'written over the oldest memory rows, evenly subsampled from those the frame\'s mask labels object or background, '
+                         'whose cosine to their own class in the bank is below TAU (default 0.9: the bank does not hold them yet) and at '
+                         'least MARGIN (default 0) above the cosine to the other class (the bank does not contradict the mask).  The first '
+                         'frame\'s rows are never overwritten.  The mask is the final one, with --multi-object each network\'s raw output.  '
+                         'Not with --adapt-steps.  The defaults are starting values, not tuned on DAVIS')
     ap.add_argument('--lucid', dest='lucid_p', type=float, default=0.0, metavar='P',
                     help='lucid first-frame synthesis (0 = off): with probability P (0..1) a training sample is a re-composition of the '
                          'annotated frame -- the object cut out, the hole inpainted once per sequence, object and background moved by affines '
