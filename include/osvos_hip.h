@@ -824,6 +824,28 @@ int osvos_lucid_compose_ex(const unsigned char* bgr, const unsigned char* mask, 
  *   ws: osvos_match_bank_ws_bytes(N, P) bytes, 8-byte aligned, contents irrelevant on entry; 0 for arguments the call refuses.
  *   tau and margin are finite, max_new >= 0, 0 <= protected_rows <= cap, cap in 1..2^20; the bank, state and ws overlap neither the frame's
  *   arrays nor each other.
+ * Softmax readout (osvos_match_soft; the memory read of STM, STCN and XMem): the operands, limits, alignment, aliasing rules and the NR = N
+ *   or 1 rule of nearest; beta, the temperature, a finite float in OSVOS_MATCH_MIN_BETA..OSVOS_MATCH_MAX_BETA.  Every row of a class votes
+ *   with weight exp(beta (cosine - 1)), and the class's evidence is the mass of its votes.  For query row a and reference row b:
+ *     t_ab = (float) dot(Q_a, R_b) * rinv_r[b], exactly as in nearest;   cos_ab = fl32(t_ab * rinv_q[a]);
+ *     k = (float) ((double) beta * log2(e)), formed once on the host;     e_ab = fl32(fl32(cos_ab - 1.0f) * k)
+ *   -- single fp32 operations, no fused multiply-add -- and w_ab = 2^e_ab, for which the hardware exponential is allowed (so lse is compared
+ *   within a bar, not bit for bit).  beta <= 40 keeps e >= -116: no weight is denormal or zero; Pr <= 2^20 keeps every sum finite.
+ *     S_c[a] = the sum of w_ab over the b with label_r[b] == c, in fp32, in an order the sizes alone fix;
+ *     lse_c[a] = (float) (1.0 + log((double) S_c[a]) / (double) beta), formed in double by the finish kernel.
+ *   Rows with any other label contribute nothing, and neither do the rows past Pr that a tile loads as zeros: they are masked by their
+ *   label, not relied on to be small (a zero row has cosine 0 and weight exp(-beta)).  max_b cos <= lse <= max_b cos + ln(n_c) / beta, n_c
+ *   the rows of the class; the attention log-odds of the object are beta (lse_fg - lse_bg).  A class without a row gives -2.0f.
+ *   best_c[a], when requested, is nearest's sim BIT FOR BIT, the -2.0f of an empty class included: a caller that feeds the memory bank's
+ *   novelty and margin tests with it keeps their meaning under the soft readout.
+ *   Out: lse fp32 [N][2][Pq] (foreground first), best fp32 [N][2][Pq] (may be NULL).  Two launches: nearest's tile kernel with, per lane,
+ *   the query's rinv_q and a running sum (and, with best, a running maximum) per class in place of the (value, index) pairs -- the two lane
+ *   halves merged with one shuffle, low half plus high half; per-slice partial sums and maxima go to ws -- and a kernel with one lane per
+ *   (frame, class, query) that adds the slices in ascending order and forms lse.  No atomics, no workgroup waits on another; identical
+ *   calls give identical bytes whatever ws held on entry.
+ *   ws: osvos_match_soft_ws_bytes(N, Pq, Pr, C) bytes, 8-byte aligned, contents irrelevant on entry; 0 for arguments the call refuses.
+ *   Left out: a softmax over the top k rows only; a value read-out richer than the label; a soft readout inside the local window; a
+ *   learned temperature.
  * Limits: C a multiple of 64 in 64..1024, Pq and Pr 1..2^20, P 1..2^30 (1..2^20 for the bank update), N 1..65535, sides 1..16384, stride a
  *   power of two 1..64.  q, Q and R are 16-byte aligned.  Outputs (and ws) must not overlap inputs or each other.  Every argument error
  *   returns < 0 before any device call, with a text that names the bad parameter. */
@@ -843,6 +865,11 @@ size_t osvos_match_bank_ws_bytes(int N, int P);
 int osvos_match_bank_update(const signed char* q, const float* rinv_q, const unsigned char* label_q, const float* sim, signed char* R,
                             float* rinv_r, unsigned char* label_r, int* state, void* ws, int N, int P, int C, int cap, int protected_rows,
                             int max_new, float tau, float margin, void* stream);
+#define OSVOS_MATCH_MIN_BETA 0.0625f
+#define OSVOS_MATCH_MAX_BETA 40.0f
+size_t osvos_match_soft_ws_bytes(int N, int Pq, int Pr, int C);
+int osvos_match_soft(const signed char* Q, const float* rinv_q, const signed char* R, const float* rinv_r, const unsigned char* label_r,
+                     float* lse, float* best /* may be NULL */, void* ws, int N, int NR, int Pq, int Pr, int C, float beta, void* stream);
 
 /* ---- fused SGD (torch.optim.SGD semantics, train_online.py:79-88,147) ----------------------
  * for each i: d = g + wd*p; buf = first ? d : momentum*buf + d; p -= lr*buf      (flat tensors) */

@@ -46,6 +46,8 @@ MATCH_MAX_C = 1024          # osvos_match_*: most channels (a multiple of 64, fr
 MATCH_MAX_P = 1 << 20       # osvos_match_nearest: most query / reference rows per frame
 MATCH_MAX_K = 16            # OSVOS_MATCH_MAX_K: most rows osvos_match_topk averages per class
 MATCH_MAX_RADIUS = 15       # OSVOS_MATCH_MAX_RADIUS: largest window radius of osvos_match_local, in cells
+MATCH_MIN_BETA = 0.0625     # OSVOS_MATCH_MIN_BETA: smallest temperature of osvos_match_soft
+MATCH_MAX_BETA = 40.0       # OSVOS_MATCH_MAX_BETA: largest (no weight exp(beta (cos - 1)) is denormal)
 SQDIST_NONE = 2147483647    # OSVOS_SQDIST_NONE: osvos_mask_sqdist's value in an image without a source pixel
 SQDIST_MAX_SIDE = 4096      # OSVOS_SQDIST_MAX_SIDE: largest H / W of osvos_mask_sqdist and osvos_adapt_targets
 LUCID_MAX_BATCH = 16        # OSVOS_LUCID_MAX_BATCH: samples per osvos_lucid_compose launch
@@ -175,6 +177,8 @@ PROTOTYPES = {
     "osvos_match_local": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "osvos_match_bank_ws_bytes": (_sz, [_i, _i]),
     "osvos_match_bank_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp]),
+    "osvos_match_soft_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "osvos_match_soft": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "osvos_lucid_inpaint_ws_bytes": (_sz, [_i, _i, _i]),
     "osvos_lucid_inpaint": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "osvos_lucid_compose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -13,10 +13,14 @@ csrc/match.hip; the rule: include/osvos_hip.h).
     memory:   a fixed-capacity bank behind the first frame's rows that collects, frame after frame, the rows the bank does not hold yet and the
               mask confirms (``osvos_match_bank_update``, csrc/match_bank.hip; ``MemoryBank``): the oldest rows are overwritten first, the first
               frame's never
+    soft:     in place of one row per class, every row of the class votes with weight exp(beta (cosine - 1)) and the class's score is
+              1 + ln(sum of its weights) / beta, between its largest cosine and that plus ln(rows) / beta (``osvos_match_soft``,
+              csrc/match_soft.hip): the softmax read of STM, STCN and XMem over the labels; one mislabelled or drifted row is outvoted
 
 The network's logits are the only evidence every other stage has; when the network fires on a distractor that merely looks like the object
 to its classifier, the map is a second opinion from the features themselves.  ``AppearanceMatcher`` adds ``gain * map`` to the fused logits
-with ``tta.fuse_views`` (bilinear, on the device).  Integer dot products: the result is exact and repeats bit for bit.
+with ``tta.fuse_views`` (bilinear, on the device).  Integer dot products: the result is exact and repeats bit for bit (the soft readout
+repeats bit for bit too, and agrees with its restatement within the error of the hardware exponential and of a float32 sum).
 
 The default parameters are STARTING VALUES, NOT TUNED ON DAVIS (no dataset was at hand when this was written), and no accuracy claim is
 made for them: tune them on a validation split before quoting a score.
@@ -27,7 +31,7 @@ import torch
 
 from . import _glue as g
 from . import tta
-from ._lib import MATCH_MAX_C, MATCH_MAX_K, MATCH_MAX_P, MATCH_MAX_RADIUS, lib
+from ._lib import MATCH_MAX_BETA, MATCH_MAX_C, MATCH_MAX_K, MATCH_MAX_P, MATCH_MAX_RADIUS, MATCH_MIN_BETA, lib
 from .autograd import FEATURE_LAYERS
 
 _STRIDE = {3: 2, 6: 4, 9: 8, 12: 16}      # conv2_2, conv3_3, conv4_3, conv5_3: 2^stage under ceil-mode pooling
@@ -167,6 +171,58 @@ def local_map(sim):
     """sim [N,2,P] of ``local`` -> max(sim_fg, -1) - max(sim_bg, -1), float32 [N,P]: a class the window does not hold counts as the smallest
     possible cosine, so "no object was near here a frame ago" is evidence against the object"""
     return torch.clamp_min(sim[:, 0], -1.0) - torch.clamp_min(sim[:, 1], -1.0)
+
+
+def check_soft(beta, balance=False):
+    """ValueError unless ``beta`` is 0 (off) or a finite number in 1/16..40 and ``balance`` a bool (host only)"""
+    g.check_number("soft_beta", beta, 0, MATCH_MAX_BETA, "match")
+    if 0 < beta < MATCH_MIN_BETA:
+        raise ValueError("match: soft_beta %r (0 = off, or a finite number in %g..%g)" % (beta, MATCH_MIN_BETA, MATCH_MAX_BETA))
+    if not isinstance(balance, bool):
+        raise ValueError("match: soft_balance must be True or False, got %r" % (balance,))
+
+
+def soft_workspace(n, pq, pr, c, device, ws=None):
+    """a uint8 CUDA tensor of at least osvos_match_soft_ws_bytes: ``ws`` when it is large enough, 8-byte aligned and on ``device``, else a new one"""
+    return g.workspace(lib().osvos_match_soft_ws_bytes(n, pq, pr, c), device, ws, "N %d Pq %d Pr %d C %d" % (n, pq, pr, c), "match", align=8)
+
+
+def soft(q, rinv_q, r, rinv_r, label_r, beta, ws=None, with_best=False):
+    """the operands of ``nearest`` and a temperature ``beta`` (1/16..40) -> lse float32 [N,2,Pq]: per query row and class
+    1 + ln(sum over the class's rows of exp(beta (cosine - 1))) / beta -- the class's largest cosine when one row dominates, up to
+    ln(rows) / beta more when many rows are as near; -2 for a class the bank does not hold.  beta (lse_fg - lse_bg) is the log-odds of the
+    object under a softmax over every row of the bank (STM's read with the label as the value).  ``with_best``: also best float32 [N,2,Pq],
+    ``nearest``'s sim bit for bit, from the same pass.  Enqueued only."""
+    check_soft(beta)
+    if not beta > 0:
+        raise ValueError("match: soft takes a temperature in %g..%g, got %r" % (MATCH_MIN_BETA, MATCH_MAX_BETA, beta))
+    (q, rinv_q, r, rinv_r, label_r), n, nr, pq, pr, c = _operands(q, rinv_q, r, rinv_r, label_r)
+    lse = torch.empty((n, 2, pq), device=q.device, dtype=torch.float32)
+    best = torch.empty((n, 2, pq), device=q.device, dtype=torch.float32) if with_best else None
+    ws = soft_workspace(n, pq, pr, c, q.device, ws)
+    g.call("match_soft", q.device, g.ptr(q), g.ptr(rinv_q), g.ptr(r), g.ptr(rinv_r), g.ptr(label_r), g.ptr(lse), g.ptr(best), g.ptr(ws), n, nr, pq, pr,
+           c, float(beta))
+    return (lse, best) if with_best else lse
+
+
+def soft_rows(label_r):
+    """label_r uint8 [NR,Pr] -> float32 [NR,2,1]: the rows of the foreground and of the background, counted on the device (no read-back)"""
+    return torch.stack([(label_r == 1).sum(dim=1), (label_r == 0).sum(dim=1)], dim=1).to(torch.float32)[:, :, None]
+
+
+def soft_union(a, b, beta):
+    """lse [N,2,Pq] of two banks -> that of their union, logaddexp(beta a, beta b) / beta: the softmax over both banks' rows.  A class a
+    bank does not hold (-2) counts as minus infinity; -2 when neither holds it"""
+    inf = float("inf")
+    x, y = (torch.where(t == -2.0, torch.full_like(t, -inf), t * beta) for t in (a, b))
+    u = torch.logaddexp(x, y) / beta
+    return torch.where((a == -2.0) & (b == -2.0), torch.full_like(u, -2.0), u)
+
+
+def soft_balanced(lse, rows, beta):
+    """lse [N,2,Pq] minus ln(rows) / beta per class (``rows`` of ``soft_rows``): the MEAN of the weights in place of their sum, so that a bank
+    with ten times more background rows carries no prior.  An empty class stays -2"""
+    return torch.where(rows > 0, lse - torch.log(torch.clamp_min(rows, 1.0)) / beta, lse)
 
 
 def check_match_options(topk, local_radius, local_gain):
@@ -309,13 +365,26 @@ class AppearanceMatcher(object):
     before the new frame is searched; frames come one at a time then (N = 1).  ``memory=0`` is the matcher without it: the same calls, the
     same bytes.
 
+    ``soft_beta`` > 0 reads every bank with ``soft`` in place of ``nearest``: the map is lse_fg - lse_bg, 1 / beta times the log-odds of the
+    object under a softmax over all rows of the bank.  With ``previous=True`` the two banks combine as the softmax over their union
+    (``soft_union``).  ``soft_balance=True`` subtracts ln(rows of the class) / beta per class -- the rows actually searched, both banks',
+    counted on the device -- so that the larger class carries no prior.  With ``memory`` > 0 the search also returns ``nearest``'s sim from
+    the same pass and THAT is what ``MemoryBank.update`` receives: the bank evolves exactly as without the soft readout.  Not with
+    ``topk`` > 1 (a softmax over the top k rows is not built); the local view is unchanged.  ``soft_beta=0`` is the matcher without it: the
+    same calls, the same bytes.  Beta 10 is a starting value.
+
     The defaults are starting values, NOT tuned on DAVIS."""
 
     def __init__(self, net, layer=9, gain=4.0, previous=False, topk=1, local_radius=0, local_gain=0.0, memory=0, memory_tau=0.9, memory_new=512,
-                 memory_margin=0.0):
+                 memory_margin=0.0, soft_beta=0.0, soft_balance=False):
         check_match(layer, gain)
         check_match_options(topk, local_radius, local_gain)
         check_memory(memory, memory_tau, memory_new, memory_margin)
+        check_soft(soft_beta, soft_balance)
+        if soft_beta > 0 and topk > 1:
+            raise ValueError("match: soft_beta %g with topk %d: the soft readout sums over every row of a class; a softmax over the top k is not built"
+                             % (soft_beta, topk))
+        self.soft_beta, self.soft_balance = float(soft_beta), bool(soft_balance)
         self.memory, self.memory_tau, self.memory_new, self.memory_margin = int(memory), float(memory_tau), int(memory_new), float(memory_margin)
         self._memory = None          # the MemoryBank (memory > 0), seeded by set_reference
         self.net, self.layer, self.gain, self.previous = net, int(layer), float(gain), bool(previous)
@@ -347,6 +416,15 @@ class AppearanceMatcher(object):
         ws = nearest_workspace(n, p, pr, c, q.device, getattr(self, which))
         setattr(self, which, ws)
         return nearest(q, rinv_q, r, rinv_r, label, ws=ws)
+
+    def _search_soft(self, q, rinv_q, r, rinv_r, label, which, with_best=False):
+        """one bank under the soft readout -> (lse, ``nearest``'s sim or None, the bank's rows per class)"""
+        n, p, c = (int(v) for v in q.shape)
+        ws = soft_workspace(n, p, int(r.shape[1]), c, q.device, getattr(self, which))
+        setattr(self, which, ws)
+        out = soft(q, rinv_q, r, rinv_r, label, self.soft_beta, ws=ws, with_best=with_best)
+        lse, best = out if with_best else (out, None)
+        return lse, best, soft_rows(label) if self.soft_balance else None
 
     def _features(self, x):
         outs, feat, _ = self.net.forward_features(x, self.layer)
@@ -405,17 +483,26 @@ class AppearanceMatcher(object):
             if plabel is not None:
                 self._memory.update(self._last[0], self._last[1], plabel.view(n, p), self._last[2])
             r, rinv_r, label = self._memory.operands()
-        sim = first = self._search(q, rinv_q, r, rinv_r, label, "_ws")
+        soft_on, rows = self.soft_beta > 0, None
+        if soft_on:                                                          # (first: nearest's sim from the same pass, for the memory bank)
+            sim, first, rows = self._search_soft(q, rinv_q, r, rinv_r, label, "_ws", with_best=self._memory is not None)
+        else:
+            sim = first = self._search(q, rinv_q, r, rinv_r, label, "_ws")
         local_mp = None
         if self.needs_previous:
             if self._memory is None:
                 plabel = prev_labels()
             if plabel is not None:
-                if self.previous:
+                if self.previous and soft_on:                                # the softmax over the union of the two banks
+                    other, _, prows = self._search_soft(q, rinv_q, self._last[0], self._last[1], plabel.view(n, p), "_ws_prev")
+                    sim, rows = soft_union(sim, other, self.soft_beta), rows + prows if self.soft_balance else None
+                elif self.previous:
                     sim = torch.maximum(sim, self._search(q, rinv_q, self._last[0], self._last[1], plabel.view(n, p), "_ws_prev"))
                 if self.local_gain > 0:
                     local_mp = local_map(local(q, rinv_q, self._last[0], self._last[1], plabel.view(n, p), (h, w), self.local_radius)).view(n, h, w)
             self._last = (q, rinv_q, first) if self._memory is not None else (q, rinv_q)
+        if rows is not None:
+            sim = soft_balanced(sim, rows, self.soft_beta)
         views, weights = [outs[-1], (sim[:, 0] - sim[:, 1]).view(n, h, w)], [1.0, self.gain]
         if local_mp is not None:
             views, weights = views + [local_mp], weights + [self.local_gain]

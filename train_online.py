@@ -37,6 +37,10 @@ running on the MI355X-native OSVOS path.  Differences by design:
     of ROWS rows into which every frame writes, on the device, at most NEW of its rows that the bank does not hold yet (own-class cosine
     below TAU) and that the bank does not contradict (own minus other at least MARGIN), oldest rows first (osvos_pytorch_amd.match.MemoryBank);
     needs --match-gain, not with --adapt-steps, 0 = off changes no byte; TAU 0.9, NEW 512, MARGIN 0 are starting values, not tuned on DAVIS.
+    ``--match-soft BETA[,balance]`` reads the bank with a softmax over all its rows (STM, STCN, XMem): a class scores 1 + ln(sum over its
+    rows of exp(BETA (cosine - 1))) / BETA in place of its largest cosine (osvos_pytorch_amd.match.soft), ``balance`` subtracts
+    ln(rows) / BETA per class; needs --match-gain, not with --match-topk above 1, off it changes no byte; BETA 10 is a starting value, not
+    tuned on DAVIS.
     Starting values, not tuned on DAVIS; with G = 0 nothing is built and not one byte changes
   * ``--lucid P``: lucid first-frame synthesis -- with probability P a training sample is not the flipped / rotated / scaled frame but a
     re-composition of it: the object cut out, the hole inpainted once per sequence, object and background moved by affines of their own,
@@ -396,9 +400,20 @@ def check_match_args(args):
             memory = parse_numbers(args.match_memory, (int, float, int, float)[:parts] if parts <= 4 else (), '--match-memory',
                                    expect='ROWS[,TAU[,NEW[,MARGIN]]]', finite=True) + memory[parts:]
         match.check_memory(*memory)
+        soft_beta, soft_balance = 0.0, False
+        if args.match_soft:
+            beta_text, comma, word = args.match_soft.partition(',')
+            if comma and word.strip().lower() != 'balance':
+                raise ValueError('--match-soft takes BETA or BETA,balance, got %r' % args.match_soft)
+            soft_beta, soft_balance = parse_numbers(beta_text, (float,), '--match-soft', expect='BETA or BETA,balance', finite=True)[0], bool(comma)
+            match.check_soft(soft_beta, soft_balance)
+            if soft_beta > 0 and args.match_topk > 1:
+                raise ValueError('--match-soft is not run together with --match-topk above 1: a softmax over the top k rows is not built')
     except ValueError as e:
         raise SystemExit('--match-*: %s' % e)
     if not args.match_gain:
+        if soft_beta > 0:
+            raise SystemExit('--match-soft needs --match-gain: it is an option of the appearance matcher')
         if args.match_topk != 1 or args.match_local:
             raise SystemExit('--match-topk / --match-local need --match-gain: they are options of the appearance matcher')
         if memory[0] > 0:
@@ -421,6 +436,8 @@ def check_match_args(args):
         args.match.update(local_radius=local_radius, local_gain=local_gain)
     if memory[0] > 0:
         args.match.update(zip(('memory', 'memory_tau', 'memory_new', 'memory_margin'), memory))
+    if soft_beta > 0:
+        args.match.update(soft_beta=soft_beta, soft_balance=soft_balance)
 
 
 def check_lucid_args(args):
@@ -652,6 +669,15 @@ def parse_args(argv=None):
                          'least MARGIN (default 0) above the cosine to the other class (the bank does not contradict the mask).  The first '
                          'frame\'s rows are never overwritten.  The mask is the final one, with --multi-object each network\'s raw output.  '
                          'Not with --adapt-steps.  The defaults are starting values, not tuned on DAVIS')
+    ap.add_argument('--match-soft', default='', metavar='BETA[,balance]',
+                    help='--match-gain: the softmax readout of the bank (off by default; as STM, STCN and XMem read their memory) -- every '
+                         'row of a class votes with weight exp(BETA (cosine - 1)) and the class scores 1 + ln(sum of its weights) / BETA in '
+                         'place of its largest cosine, so that a few mislabelled or drifted rows are outvoted by the rows that look the same; '
+                         'BETA in 0.0625..40.  With --match-previous the two banks combine as the softmax over their union; with '
+                         '--match-memory the bank is still updated from the largest cosines and evolves exactly as without this option.  '
+                         '",balance" subtracts ln(rows of the class) / BETA: the mean weight, so that the larger class carries no prior.  '
+                         'Not with --match-topk above 1; --match-local is unchanged; runs with --adapt-steps wherever --match-gain alone '
+                         'does.  BETA 10 is a starting value, not tuned on DAVIS')
     ap.add_argument('--lucid', dest='lucid_p', type=float, default=0.0, metavar='P',
                     help='lucid first-frame synthesis (0 = off): with probability P (0..1) a training sample is a re-composition of the '
                          'annotated frame -- the object cut out, the hole inpainted once per sequence, object and background moved by affines '
