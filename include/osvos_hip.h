@@ -882,6 +882,37 @@ int osvos_sgd_step(float* p, const float* g, float* buf, long count, float lr, f
 int osvos_sgd_step_multi(float* const* params, const float* const* grads, float* const* bufs, const long* counts,
                          const float* lrs, const float* wds, int n, float momentum, int first, void* stream);
 
+/* ---- interactive scribbles: strokes to a label map, an error region to a stroke (its skeleton) ----
+ * The raster call: segs int32 [M][6] on the device, a row = (x0, y0, x1, y1, value, frame) -> out uint8 [N][H][W], every byte written.  A
+ *   row with frame < 0 (or >= N) is padding.  out[n][y][x] = 255 when no row of frame n covers the pixel p = (x, y), else the `value` of the
+ *   covering row with the HIGHEST index.  Coverage of p by the segment a -> b with radius r, exact in signed 64-bit integers:
+ *     d = b - a, L = d.d, w = p - a, t = w.d;   L == 0 or t <= 0: w.w <= r^2;   t >= L: |p - b|^2 <= r^2;   else (w x d)^2 <= r^2 L.
+ *   The caller keeps coordinates in [0, 16384) and value in 0..254 (the kernel does not check them; with such coordinates nothing
+ *   overflows: (w x d)^2 < 2^58, r^2 L < 2^42).  M 0..OSVOS_SCRIBBLE_MAX_SEGMENTS (segs may be null when M is 0), radius
+ *   0..OSVOS_SCRIBBLE_MAX_RADIUS.  One launch, no atomics, no workspace: a workgroup per 64 x 16 tile and frame gathers the rows that can
+ *   touch its tile into an LDS list of OSVOS_SCRIBBLE_LIST_CAP rows, highest index first, and empties the list in as many passes as it takes.
+ * The thinning call: mask bytes [N][H][W] (non-zero = set) -> out bytes in {0, 1}: the Guo-Hall skeleton; info int32 [N][2] on the device =
+ *   (iterations run, 1 if the last of them deleted nothing else 0).  Neighbours of a pixel clockwise from north: P2 N, P3 NE, P4 E, P5 SE,
+ *   P6 S, P7 SW, P8 W, P9 NW; pixels outside the frame are 0.
+ *     C  = (!P2 & (P3 | P4)) + (!P4 & (P5 | P6)) + (!P6 & (P7 | P8)) + (!P8 & (P9 | P2))
+ *     N1 = (P9 | P2) + (P3 | P4) + (P5 | P6) + (P7 | P8),  N2 = (P2 | P3) + (P4 | P5) + (P6 | P7) + (P8 | P9),  Nm = min(N1, N2)
+ *   Sub-step 0 deletes every set pixel with C == 1, 2 <= Nm <= 3 and ((P2 | P3 | !P5) & P4) == 0; sub-step 1 likewise with
+ *   ((P6 | P7 | !P9) & P8) == 0; each sub-step is evaluated for all pixels on the plane as it was before it.  An iteration is sub-step 0
+ *   then sub-step 1; a frame stops after its first iteration that deletes nothing or after max_iters (1..OSVOS_THIN_MAX_ITERS), and never
+ *   changes again whatever the other frames do.  path: 1 = one workgroup per frame keeps the frame's 1-bit plane in LDS and iterates behind
+ *   barriers (H * ceil(W / 64) <= OSVOS_THIN_RESIDENT_WORDS, an argument error otherwise), 2 = two planes ping-pong in ws, one launch per
+ *   iteration, max_iters launches enqueued whatever the masks hold, 0 = path 1 when the plane fits, else path 2.  Both paths write the same
+ *   bytes.  Nothing is read back.  out may be mask.  ws: the size query's bytes for (N, H, W), 8-byte aligned, contents irrelevant on entry;
+ *   0 for sizes the call refuses.  Sides 1..16384, N 1..65535. */
+#define OSVOS_SCRIBBLE_MAX_SEGMENTS 65535
+#define OSVOS_SCRIBBLE_MAX_RADIUS 64
+#define OSVOS_SCRIBBLE_LIST_CAP 512
+#define OSVOS_THIN_MAX_ITERS 512
+#define OSVOS_THIN_RESIDENT_WORDS 8000
+int osvos_scribble_raster(const int* segs, int M, unsigned char* out, int N, int H, int W, int radius, void* stream);
+size_t osvos_mask_thin_ws_bytes(int N, int H, int W);
+int osvos_mask_thin(const unsigned char* mask, unsigned char* out, int* info, int N, int H, int W, int max_iters, int path, void* ws, void* stream);
+
 /* ---- opt-in launch profiler (bench.py only): hipEvent pairs around every kernel family that
  * osvos_net_forward/backward launches, recorded on the caller's stream.  Families: 0 conv3x3
  * forward launches, 1 backward conv regions (data-gradient kernel || weight-gradient kernel +

@@ -60,6 +60,11 @@ LUCID_MIN_CELL = 8          # OSVOS_LUCID_MIN_CELL: smallest lattice cell of the
 LUCID_MAX_CELL = 256        # OSVOS_LUCID_MAX_CELL: largest lattice cell
 LUCID_MAX_OCC_RADIUS = 4096  # OSVOS_LUCID_MAX_OCC_RADIUS: largest occluder semi-axis
 LUCID_MAX_OCC_OFFSET = 8192  # OSVOS_LUCID_MAX_OCC_OFFSET: largest |centre| and |source offset| of an occluder
+SCRIBBLE_MAX_SEGMENTS = 65535  # OSVOS_SCRIBBLE_MAX_SEGMENTS: most rows of osvos_scribble_raster's segment table
+SCRIBBLE_MAX_RADIUS = 64    # OSVOS_SCRIBBLE_MAX_RADIUS: largest stroke radius
+SCRIBBLE_LIST_CAP = 512     # OSVOS_SCRIBBLE_LIST_CAP: rows of a tile's LDS list; more survivors take more passes
+THIN_MAX_ITERS = 512        # OSVOS_THIN_MAX_ITERS: most iterations of osvos_mask_thin
+THIN_RESIDENT_WORDS = 8000  # OSVOS_THIN_RESIDENT_WORDS: largest 1-bit plane, in 64-bit words, that path 1 keeps in LDS
 GENERIC_DECONV = 0x100    # OSVOS_FLAG_GENERIC_DECONV: OR-ed into the dtype of the osvos_net_* calls
 NPARAMS = 52
 # the slot groups of the 52 parameters / gradients in state_dict order (csrc/common.h, namespace slot, names them for the C side)
@@ -188,6 +193,9 @@ PROTOTYPES = {
     "osvos_mask_sqdist": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "osvos_adapt_ws_bytes": (_sz, [_i, _i, _i]),
     "osvos_adapt_targets": (_i, [_vp, _vp, _f, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "osvos_scribble_raster": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "osvos_mask_thin_ws_bytes": (_sz, [_i, _i, _i]),
+    "osvos_mask_thin": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "osvos_sgd_step": (_i, [_vp, _vp, _vp, _l, _f, _f, _f, _i, _vp]),
     "osvos_sgd_step_multi": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp]),
     "osvos_prof_start": (_i, [_i]),

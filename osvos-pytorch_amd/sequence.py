@@ -9,6 +9,8 @@ None for an option that is off.  THE ORDER OF THE STAGES LIVES HERE, and tests/t
                             state of the next frame (SingleObjectSequence.step)
   ``multi_object_sequence`` per object: fine-tuning (the caller's) and FrameForward over every frame into a [K,F,H,W] stack; then post_chain
                             stage by stage over chunks of frames; ``score_objects`` merges, scores and writes
+  ``interactive_sequence``  per round: annotate (the first interaction, then the simulated annotator on the worst frame of the previous
+                            round's prediction), fit, FrameForward and post_chain over every frame, score
 
 The two recipes differ in ONE rule.  The mask that --match-previous (and --match-local) hands to the next frame (FrameForward.remember) is the FINAL mask in
 the single-object recipe -- after crf, snap and tracker -- and the RAW output of the matched forward in the multi-object recipe, whose post
@@ -191,3 +193,63 @@ def score_objects(logits, gts, paths):
         evaluator.add(labels[at], torch.stack([gts[f] for f in at]))      # (enqueued: nothing is read back here)
     save_label_maps(labels, paths)
     return evaluator.summary()
+
+
+def interactive_sequence(session, forward, post, rounds, steps0, steps, gts, robot, first=None, make_evaluator=None, on_round=None):
+    """The interactive loop (Scribble-OSVOS) over one sequence.  session: scribble.InteractiveSession (the strokes, the training, the decoded
+    frames); forward: the network's FrameForward; post: the keyword arguments of ``post_chain`` (crf, snap); gts: the uint8 annotation
+    [H,W] of EVERY frame (the annotator needs the truth of the frame it looks at; the object is ``session.object_id``); robot:
+    ``robot(None, gt)`` -> the first interaction's map, ``robot(pred_labels, gt)`` -> the strokes through the errors of a prediction
+    (scribble.Robot).  first: [(frame, map), ..] to open with in place of the robot's first interaction (a person's strokes).  on_round:
+    ``on_round(r, dict)`` is called as each round's report is complete.
+
+    Round 0 annotates with the first interaction on frame 0 and fits ``steps0`` optimizer steps.  Every later round takes the annotated-truth
+    frame with the lowest J of the previous round's prediction (the first of several), runs the robot on it, adds the result and fits
+    ``steps`` steps.  Every round then predicts all frames (``forward``, then ``post_chain``) and scores them (``make_evaluator()``, default
+    results.SequenceEvaluator).  The network keeps training from round to round.  A round's annotation comes from the round before, so
+    nothing is trained after the last prediction: that prediction is the result.
+
+    -> (per round a dict: 'frame' annotated (a list in round 0 with ``first``), 'labelled' pixels of all strokes so far, 'J', 'F' means,
+    'fit_s', 'predict_s' seconds; the fused logits of the last round, a list of [1,1,H,W])"""
+    if rounds < 1 or steps0 < 0 or steps < 0:
+        raise ValueError("interactive_sequence: rounds >= 1 and steps >= 0, got %r, %r, %r" % (rounds, steps0, steps))
+    n = len(session.frames_u8)
+    if len(gts) != n or any(gt is None for gt in gts):
+        raise ValueError("interactive_sequence: the annotator needs the annotation of every one of the %d frames" % n)
+    if make_evaluator is None:
+        from .results import SequenceEvaluator as make_evaluator
+    sync = torch.cuda.synchronize if session.frames_u8[0].is_cuda else (lambda: None)
+    report, fused, js = [], None, None
+    for r in range(rounds):
+        if r == 0 and first is not None:
+            frame = [f for f, _ in first]
+            for f, m in first:
+                session.add(f, m)
+        elif r == 0:
+            frame = 0
+            session.add(0, robot(None, gts[0]))
+        else:
+            frame = min(range(n), key=lambda f: js[f])
+            pred = (fused[frame][0, 0] > 0).to(torch.uint8) * session.object_id
+            session.add(frame, robot(pred, gts[frame]))
+        sync()
+        t0 = timeit.default_timer()
+        session.fit(steps0 if r == 0 else steps)
+        sync()
+        t1 = timeit.default_timer()
+        evaluator, fused = make_evaluator(), []
+        with torch.no_grad():
+            for f in range(n):
+                out = forward(session.frames_u8[f], session.image(f) if forward.needs_image else None)
+                out = post_chain(out, session.frames_u8[f], **post)
+                forward.remember(out)
+                evaluator.add(out, (gts[f] == session.object_id).float()[None, None])
+                fused.append(out)
+        session.set_previous([o[0, 0] > 0 for o in fused])
+        js, fs = evaluator.per_frame()          # (the round's one read-back of scores)
+        t2 = timeit.default_timer()
+        report.append({'frame': frame, 'labelled': session.labelled_pixels(), 'J': sum(js) / len(js), 'F': sum(fs) / len(fs), 'fit_s': t1 - t0,
+                       'predict_s': t2 - t1})
+        if on_round is not None:
+            on_round(r, report[-1])
+    return report, fused

@@ -55,6 +55,12 @@ running on the MI355X-native OSVOS path.  Differences by design:
     ``--zoom-outside`` around them (osvos_pytorch_amd.roi.RoiZoom); frame 0 runs on the full frame.  Before --crf-iters, --snap-cell and
     --track-components, which keep running on the frame's grid.  Not with --tta-*, --match-gain or --adapt-steps.  ``--zoom-margin PCT,PX``.
     Starting values, not tuned on DAVIS; with MAXZOOM = 0 nothing is built and not one byte changes
+  * ``--interactive ROUNDS[,STEPS0[,STEPS]]``: interactive segmentation from scribbles (Scribble-OSVOS, the baseline of the DAVIS interactive
+    track) in place of the first-frame fine-tune -- strokes are rastered into a label map on the device, the network trains on the labelled
+    pixels only (the rest void), a simulated annotator draws the skeleton of the largest error regions of the worst frame, and the rounds
+    repeat (osvos_pytorch_amd.scribble, sequence.interactive_sequence); ``--scribbles FILE`` runs one round on a person's strokes in the
+    DAVIS interactive JSON layout; --scribble-radius, --scribble-min-area, --scribble-prior.  Starting values, not tuned on DAVIS; without
+    either option the script makes the calls it made and writes the bytes it wrote
   * the test phase -- which stage runs when, and what is carried from frame to frame -- is osvos_pytorch_amd.sequence for both recipes: the
     order is stated there, once, and asserted by tests/test_sequence_cpu.py; this file parses the options, fine-tunes, builds the stages
     (build_forward, build_post) and prints
@@ -477,6 +483,103 @@ def check_lucid_args(args):
         args.lucid_void = True
 
 
+def check_scribble_args(args):
+    """the --interactive / --scribbles rules; SystemExit on values or combinations the interactive loop does not run -- checked before any GPU
+    work.  Sets args.interactive to dict(rounds, steps0, steps, file), or None without either option"""
+    from osvos_pytorch_amd import scribble
+    from osvos_pytorch_amd._glue import parse_numbers
+    args.interactive = None
+    try:
+        scribble.check_radius(args.scribble_radius)
+        if args.scribble_min_area < 0:
+            raise ValueError('--scribble-min-area takes a pixel count >= 0, got %d' % args.scribble_min_area)
+        if not 0 <= args.scribble_prior <= 8192:
+            raise ValueError('--scribble-prior takes a distance of 0..8192 pixels (0 = off), got %d' % args.scribble_prior)
+        rounds, steps0, steps = 1, 200, 100          # starting values, not tuned on DAVIS
+        if args.interactive_rounds:
+            parts = args.interactive_rounds.count(',') + 1
+            got = parse_numbers(args.interactive_rounds, (int, int, int)[:parts] if parts <= 3 else (), '--interactive', expect='ROUNDS[,STEPS0[,STEPS]]')
+            rounds, steps0, steps = got + (rounds, steps0, steps)[parts:]
+            if rounds < 1 or steps0 < 1 or steps < 1:
+                raise ValueError('--interactive takes ROUNDS >= 1 and step counts >= 1, got %r' % args.interactive_rounds)
+    except ValueError as e:
+        raise SystemExit('--interactive / --scribble*: %s' % e)
+    if not args.interactive_rounds and not args.scribbles:
+        return
+    if args.scribbles and args.interactive_rounds and rounds != 1:
+        raise SystemExit('--scribbles runs ONE round on the strokes of the file in place of the simulated annotator: --interactive 1[,STEPS0] or none')
+    refused = (('--multi-object', args.multi_object, 'the interactive loop trains one network on one object'),
+               ('--window-fused', args.window_fused, 'window_batch has no void rule, and strokes label few pixels'),
+               ('--lucid', args.lucid_p, 'the synthesis needs a complete first-frame mask'),
+               ('--adapt-steps', args.adapt_steps, 'the adapter starts from a complete first-frame mask'),
+               ('--match-*', args.match_gain or args.match_previous or args.match_topk != 1 or args.match_local or args.match_memory or args.match_soft,
+                'the first-frame bank needs a complete first-frame mask'),
+               ('--track-components', args.track_components is not None, 'the tracker is seeded with a complete first-frame mask'),
+               ('--zoom', args.zoom, 'out of scope of the interactive loop'),
+               ('--flow-search', args.flow_search, 'it moves the state of --adapt-steps and --track-components, which do not run here'),
+               ('--test-precision', args.test_precision, 'the network keeps training between the predictions: one precision serves both'))
+    for name, on, why in refused:
+        if on:
+            raise SystemExit('--interactive / --scribbles is not run together with %s: %s' % (name, why))
+    if not args.device_augment:
+        raise SystemExit('--interactive / --scribbles needs --device-augment: strokes are rastered, and the samples made, from the decoded frames on the device')
+    if os.environ.get('OSVOS_FUSED_LOSS_STEP', '1') == '0':
+        raise SystemExit('--interactive / --scribbles needs the fused loss step (OSVOS_FUSED_LOSS_STEP is 0): the void rule lives in the HIP loss kernel')
+    args.interactive = dict(rounds=rounds, steps0=steps0, steps=steps, file=args.scribbles)
+
+
+def interactive_sequence(args, seq_name, device, seed, save_dir, parentEpoch, nAveGrad):
+    """Scribble-OSVOS on one sequence in place of the first-frame fine-tune: rounds of strokes (the simulated annotator's, or with --scribbles
+    one round of a person's), training on the labelled pixels only, prediction and scoring of every frame (sequence.interactive_sequence);
+    one line per round, one final line, the masks of the last round"""
+    from osvos_pytorch_amd import scribble
+    from osvos_pytorch_amd.augment import DeviceAugment
+    from osvos_pytorch_amd.davis_io import DevicePrefetcher
+    net, optimizer = load_parent(args, save_dir, parentEpoch, device)
+    _, testloader = device_loaders(args, seq_name, device, seed)          # (seeds Python's random: the augmentation draws)
+    frames, gts, names = [], [], []
+    for idx, img, lab in DevicePrefetcher(testloader.frames, range(len(testloader.frames)), device, depth=args.prefetch):
+        if lab is None:
+            raise SystemExit('--interactive / --scribbles: frame %d of %s has no annotation; the annotator and the scores need the truth of every '
+                             'frame (--synthetic-frames K, or a DAVIS sequence with all annotations)' % (idx, seq_name))
+        frames.append(img)
+        gts.append((lab > 127).to(torch.uint8))                           # the label map: object id 1
+        names.append(os.path.basename(testloader.frames.fname(idx)))
+    h, w = int(frames[0].shape[0]), int(frames[0].shape[1])
+    it = args.interactive
+    first = None
+    if it['file']:
+        try:
+            paths, _ = scribble.load_davis_json(it['file'], (h, w))
+            maps = scribble.rasterize(paths, (h, w), args.scribble_radius, len(frames), device)
+        except (OSError, ValueError) as e:
+            raise SystemExit('--scribbles: %s' % e)
+        first = [(f, maps[f]) for f in sorted(set(p[0] for p in paths))]
+        if not first:
+            raise SystemExit('--scribbles: %s holds no stroke' % it['file'])
+    print('Start of Interactive Training, sequence: ' + seq_name)
+    session = scribble.InteractiveSession(net, optimizer, frames, 1, nAveGrad, DeviceAugment(rots=(-30, 30), scales=(.75, 1.25)), args.scribble_prior)
+    robot = scribble.Robot(args.scribble_radius, args.scribble_min_area)
+    post = build_post(args)
+    assert post.pop('flow') is None and post.pop('make_tracker') is None      # (parse_args refuses both with --interactive)
+
+    def round_line(r, rep):
+        print('Interactive round %d on %s: frame %s annotated, %d labelled pixels, J %.4f F %.4f, fit %.3f s, predict %.3f s'
+              % (r, seq_name, rep['frame'], rep['labelled'], rep['J'], rep['F'], rep['fit_s'], rep['predict_s']))
+
+    report, fused = sequence.interactive_sequence(session, build_forward(args, net), post, it['rounds'], it['steps0'], it['steps'], gts, robot,
+                                                  first=first, on_round=round_line)
+    jf = [0.5 * (rep['J'] + rep['F']) for rep in report]
+    print('Interactive J&F on %s per round: %s mean %.4f' % (seq_name, ' '.join('%.4f' % v for v in jf), sum(jf) / len(jf)))
+    c = session.summary()
+    print('Interactive strokes on %s: %d frames annotated, %d in the training rotation, %d left out (one class), %d micro-batches'
+          % (seq_name, c['annotated'], c['training'], c['left_out'], c['micro_batches']))
+    save_dir_res = os.path.join(save_dir, 'Results', seq_name)
+    os.makedirs(save_dir_res, exist_ok=True)
+    for out, name in zip(fused, names):
+        save_masks(out, [os.path.join(save_dir_res, name + '.png')])
+
+
 def build_forward(args, net, trainloader=None):
     """the sequence.FrameForward of a fine-tuned network: the --test-precision re-pack, then the stages that belong to one network, each None
     when its option is off -- test-time augmentation, the online adapter (with ``trainloader``: the single-object recipe) on a FRESH optimizer
@@ -713,7 +816,25 @@ def parse_args(argv=None):
     ap.add_argument('--zoom-canvas', default='', metavar='HxW', help='--zoom: the size of the network\'s input (default: the frame\'s size)')
     ap.add_argument('--zoom-outside', type=float, default=-20.0, metavar='V',
                     help='--zoom: the logit of every pixel outside the box (finite, so that --crf-iters and --snap-cell keep working on it)')
+    ap.add_argument('--interactive', dest='interactive_rounds', default='', metavar='ROUNDS[,STEPS0[,STEPS]]',
+                    help='interactive segmentation from scribbles (Scribble-OSVOS) in place of the first-frame fine-tune: round 0 trains STEPS0 '
+                         '(default 200) optimizer steps on strokes through the first annotation\'s object and background, every later round '
+                         'STEPS (default 100) more after a simulated annotator has drawn strokes through the largest errors of the worst frame; '
+                         'unlabelled pixels are void.  Every round predicts and scores all frames; the masks of the last round are written.  '
+                         'Needs --device-augment, the single-object loop and the truth of every frame (--synthetic-frames K, or a DAVIS '
+                         'sequence with all annotations).  With --tta-*, --crf-iters, --snap-cell; not with --multi-object, --window-fused, '
+                         '--lucid, --adapt-steps, --match-*, --track-components, --zoom, --flow-search, --test-precision.  The defaults are '
+                         'starting values, not tuned on DAVIS')
+    ap.add_argument('--scribbles', default='', metavar='FILE',
+                    help='one interactive round on a person\'s strokes in place of the simulated annotator\'s: a JSON file in the DAVIS '
+                         'interactive layout {"scribbles": [per frame: [{"path": [[x, y], ..], "object_id": k}, ..]]}, x and y in 0..1')
+    ap.add_argument('--scribble-radius', type=int, default=3, help='--interactive / --scribbles: half the width of a stroke, 0..64 pixels')
+    ap.add_argument('--scribble-min-area', type=int, default=64, help='--interactive: error regions below this many pixels get no stroke')
+    ap.add_argument('--scribble-prior', type=int, default=0, metavar='D',
+                    help='--interactive: from the second round on, unlabelled pixels farther than D pixels from every stroke are trained towards '
+                         'the previous round\'s mask instead of being void (0 = off)')
     args = ap.parse_args(argv)
+    check_scribble_args(args)
     args.tta = tta_scales(args)
     check_adapt_args(args)
     check_zoom_args(args)
@@ -746,6 +867,9 @@ def main():
         seq_name = seqs[si]
         if args.multi_object:
             multi_object_sequence(args, seq_name, device, seed + si, save_dir, parentEpoch, nEpochs, nAveGrad)
+            continue
+        if args.interactive:
+            interactive_sequence(args, seq_name, device, seed + si, save_dir, parentEpoch, nAveGrad)
             continue
         net, optimizer = load_parent(args, save_dir, parentEpoch, device)
         if args.device_augment:
